@@ -12,9 +12,17 @@ ranks (strong scaling): frame pairs for detect/match, points for BA, one RCCL al
 per trust-region iteration.
 
 One JSON line on rank 0.  `value` = descriptor-match pairs/s over the match stage of the timed steps (first quantity of
-the metric); `ba_residuals_per_s`, `frames_per_s` and `stage_ms` are reported beside it; `roofline` describes the kernel
-with the largest share of device time inside the timed steps (per-launch HIP events on the launch stream, see
-mm_profile_* in include/meatmodeler.h); `cpu_baseline` times the CPU oracle on a bounded sample.
+the metric); `ms_per_step` = wall time of one timed step; `ba_residuals_per_s`, `frames_per_s` and `stage_ms` are
+reported beside it.  A plain run does only that: set-up, warm-up, the timed steps and the line.
+
+--full adds what takes work of its own: one untimed step with HIP events on every launch (per-kernel table), events
+around the dominant kernel inside the timed steps, `roofline` for the kernel with the largest share of device time (see
+mm_profile_* in include/meatmodeler.h), `bf_knn2` roof figures and `cpu_baseline` (the CPU oracle timed on a bounded
+sample).
+
+--dump-outputs DIR writes what the last timed step returned (key points, descriptors, match counts, tracks, triangulated
+and adjusted points, cameras) as DIR/<name>.npy in float32 / float64, at most 64 MB in all: an array above its share is
+replaced by a fixed seeded sample of its rows.  The inputs are seeded, so two builds can be compared array for array.
 """
 import argparse
 import json
@@ -48,7 +56,12 @@ def parse():
                     help="frames per ORB launch set (the pyramid workspace is ~4.5 MB per frame; one set per clip avoids "
                          "16 x 14 launch tails: detect 34.6 -> 28.7 ms)")
     ap.add_argument("--arc", type=float, default=None, help="orbit arc in degrees (default 0.72 deg/frame)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel tables, the roofline of the dominant kernel and the CPU baseline (extra work "
+                         "outside the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-ba", action="store_true")
     ap.add_argument("--ba-window", type=int, default=0,
                     help="sliding-window BA instead of the global one (SURVEY 8(f)-2): keyframes per window (1 GPU only)")
@@ -67,12 +80,16 @@ def parse():
                          "per window on --ba-streams streams (default: at the C5 window shape -- 75 k points per window -- both are "
                          "bound by the same total kernel work, 912 vs 927 ms; the lock-step solve wins on smaller problems)")
     ap.add_argument("--verbose", type=int, default=0)
-    ap.add_argument("--no-profile", action="store_true", help="no per-launch HIP events at all (no kernel table, no roofline)")
+    ap.add_argument("--no-profile", action="store_true",
+                    help="--full without per-launch HIP events (no kernel table, no roofline)")
     ap.add_argument("--profile-timed", choices=("dominant", "big"), default="dominant",
-                    help="HIP events inside the TIMED steps: around the launches of the dominant kernel only (default; every "
-                         "bracketed launch costs the stream a bubble) or around every launch of >= 64 workgroups (rounds 1-3: "
-                         "inflates a BA iteration by ~10 %%)")
-    return ap.parse_args()
+                    help="--full: HIP events inside the TIMED steps: around the launches of the dominant kernel only (default; "
+                         "every bracketed launch costs the stream a bubble) or around every launch of >= 64 workgroups (rounds "
+                         "1-3: inflates a BA iteration by ~10 %%)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def algorithmic_work(name, cfg):
@@ -187,7 +204,7 @@ def main():
         else:
             dist.init_process_group(backend)
 
-    from meatmodeler_amd import synth, ops
+    from meatmodeler_amd import synth
     from meatmodeler_amd._lib import default_context
     from meatmodeler_amd.pipeline import ClipPipeline
 
@@ -211,11 +228,12 @@ def main():
     def step(timers=None):
         if a.ba_window > 0:
             o = pipe.run(frames, K, ext, ba=False, dist=d, timers=timers)
-            o["windows"] = pipe.adjust_windows(o, K, ext, window=a.ba_window, stride=a.ba_stride or max(1, a.ba_window // 2),
-                                               ftol=1e-4, timers=timers, dist=d,
-                                               order=a.ba_order or "wavefront",
-                                               streams=a.ba_streams, batched=bool(a.ba_batched),
-                                               max_nfev=a.ba_window_max_nfev or None)["windows"]
+            w = pipe.adjust_windows(o, K, ext, window=a.ba_window, stride=a.ba_stride or max(1, a.ba_window // 2),
+                                    ftol=1e-4, timers=timers, dist=d,
+                                    order=a.ba_order or "wavefront",
+                                    streams=a.ba_streams, batched=bool(a.ba_batched),
+                                    max_nfev=a.ba_window_max_nfev or None)
+            o["windows"], o["window_cams"], o["window_points"] = w["windows"], w["cams"], w["points"]
             return o
         return pipe.run(frames, K, ext, ba=not a.no_ba, ftol=1e-4, verbose=a.verbose, dist=d, timers=timers)
 
@@ -227,9 +245,10 @@ def main():
     # One extra, untimed step with events on EVERY launch gives the complete per-kernel table and names the dominant kernel
     # (largest share of device time).  Inside the timed steps only THAT kernel's launches are bracketed by events (level 3):
     # every bracketed launch costs the stream a bubble, and bracketing all launches of >= 64 workgroups (level 2, what
-    # rounds 1-3 did; --profile-timed big) made a BA iteration 1.36 ms where it is 1.24 ms unobserved.
+    # rounds 1-3 did; --profile-timed big) made a BA iteration 1.36 ms where it is 1.24 ms unobserved.  A plain run (no
+    # --full) records no events at all.
     prof_full = {}
-    if not a.no_profile:
+    if a.full and not a.no_profile:
         ctx.profile(1)
         step()
         prof_full = ctx.profile_report()
@@ -271,6 +290,119 @@ def main():
     value = pair_evals / (stage_ms["match"] * 1e-3) if stage_ms["match"] > 0 else 0.0
     ba_rps = n_obs * nfev / (stage_ms["ba"] * 1e-3) if stage_ms["ba"] > 0 else 0.0
 
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, out)
+
+    if a.full:
+        roofline, bf, kernels, kernels_full = kernel_report(a, pipe, out, prof, prof_full, rank, world)
+
+    cpu = None
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
+        cpu = cpu_baseline(frames, N, F, nfev)
+
+    if rank == 0:
+        line = {
+            "metric": "descriptor-match pairs/sec + BA residuals/sec, 500×1080p frames, 1/2/4/8 GPU",
+            "value": value, "unit": "descriptor pairs/s (match stage)",
+            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / a.steps,
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "u8/int32 (match), f64 (BA)",
+            "data": "synthetic",
+            "config": {"workload": f"{F} frames {W}x{H}, {N} ORB kpts/frame, BF Hamming 2-NN + ratio, track linking, "
+                                   "2-view DLT, full BA (TRF, Schur, f64 MFMA Cholesky)" + (" [BA off]" if a.no_ba else ""),
+                       "frames": F, "height": H, "width": W, "nfeatures": N, "parallelism": f"pairs/points x{world}"},
+            "ba_residuals_per_s": ba_rps, "frames_per_s": F / (elapsed / a.steps), "stage_ms": stage_ms,
+            # the trust-region path on this outlier-laden clip is chaotic (the iteration count moves with rounding-level
+            # changes), so the per-iteration time is the figure to compare between builds, not ms_per_step
+            "ba": None if res is None else {
+                "nfev": nfev, "njev": res.njev, "iterations": getattr(res, "iterations", None),
+                "ms_per_iteration": stage_ms["ba_solve"] / max(getattr(res, "iterations", 0) or 1, 1),
+                "host_segments_ms_last_step": getattr(res, "host_segments_ms", None),
+                # N > 1: the same library loop (mm_ba_trf_dist); its exchange points call back into torch.distributed
+                "driver": "mm_ba_trf_dist" if world > 1 and getattr(res, "collectives", 0) else
+                          ("mm_ba_trf" if getattr(res, "host_segments_ms", {}).get("library") is not None else "python"),
+                "collectives": getattr(res, "collectives", None),
+                "collectives_per_evaluation": (getattr(res, "collectives", 0) or 0) / max(nfev, 1),
+                "chol_fallbacks": getattr(res, "chol_fallbacks", None)},
+            "problem": {"keypoints": int(kp_count.sum()), "descriptor_pairs": pair_evals,
+                        "matches": int(out["match_count"].sum()), "tracks": out["n_tracks"], "observations": n_obs,
+                        "ba_nfev": nfev, "ba_status": res.status if res is not None else None,
+                        "ba_cost": res.cost if res is not None else None, "cam_span": out.get("cam_span"),
+                        "schur_pairs": out.get("n_pairs"), "render_s": t_render},
+            "sliding_window_ba": None if "windows" not in out else {
+                "window": a.ba_window, "stride": a.ba_stride or max(1, a.ba_window // 2), "windows": len(out["windows"]),
+                "order": a.ba_order or "wavefront", "streams": a.ba_streams, "max_nfev_per_window": a.ba_window_max_nfev or None,
+                "batched": bool(a.ba_batched) and (a.ba_order or "wavefront") == "wavefront",
+                "ms": stage_ms["ba_windows"], "nfev_total": int(sum(w["nfev"] for w in out["windows"])),
+                "observations_total": int(sum(w["observations"] for w in out["windows"])),
+                "residual_evals_per_s": sum(w["observations"] * w["nfev"] for w in out["windows"]) /
+                                        max(stage_ms["ba_windows"] * 1e-3, 1e-9),
+                "status_counts": {str(k): int(sum(1 for w in out["windows"] if w["status"] == k))
+                                  for k in sorted({w["status"] for w in out["windows"]})},
+                "per_window": [[w["lo"], w["hi"], w["points"], w["observations"], w["nfev"], w["status"],
+                                float(f"{w['cost']:.6g}")] for w in out["windows"]],
+                "per_window_columns": ["lo", "hi", "points", "observations", "nfev", "status", "cost"]},
+        }
+        if a.full:
+            line.update({
+                "roofline": roofline,
+                "bf_knn2": bf,
+                "kernels": kernels[:12],
+                "kernels_all_launches_extra_step": kernels_full[:16],
+                "cpu_baseline": cpu,
+            })
+        print(json.dumps(line))
+    if use_dist:
+        dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(dirname, out):
+    """The arrays the last timed step handed back, as DIR/<name>.npy.  Only the valid rows of the per-frame key point
+    tables are kept (the rest is workspace).  Integers are stored as float32 when that is exact, else float64.  Every
+    array gets an equal share of DUMP_BUDGET_BYTES; one above its share is replaced by the rows of a fixed seeded sample
+    (same rows for arrays of the same length), in their original order.  With several ranks: rank 0's view (its own
+    frames' descriptors, its own share of the adjusted points)."""
+    import torch
+
+    def valid_rows(table, counts):       # rows table[i, :counts[i]] of a per-frame table, frame after frame
+        counts = torch.as_tensor(counts, device=table.device)
+        return table[torch.arange(table.shape[1], device=table.device)[None, :] < counts[:, None]]
+
+    arrays = dict(keypoints_xy=valid_rows(out["xy_dev"], out["kp_count"]), keypoint_count=out["kp_count"])
+    if out["det"] is not None:
+        arrays["descriptors"] = valid_rows(out["det"]["desc"], out["det"]["n"])
+    arrays.update(match_count=out["match_count"], track_ptr=out["track_ptr_dev"], track_obs_frame=out["obs_frame_dev"],
+                  track_obs_kp=out["obs_kp_dev"], points_triangulated=out["points0"])
+    res = out.get("ba")
+    if res is not None:
+        arrays.update(ba_cams=res.cams, ba_points=res.pts, ba_cost=np.array([res.cost], np.float64))
+    if "window_cams" in out:
+        arrays.update(window_cams=out["window_cams"], window_points=out["window_points"])
+    share = DUMP_BUDGET_BYTES // len(arrays) - 128          # (128: the .npy header)
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in arrays.items():
+        v = v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        if v.dtype.kind in "iub":
+            v = v.astype(np.float32 if v.size == 0 or np.abs(v).max() < (1 << 24) else np.float64)
+        elif v.dtype not in (np.float32, np.float64):
+            v = v.astype(np.float64)
+        rows = v.shape[0] if v.ndim else 1
+        row_bytes = max(v.nbytes // max(rows, 1), 1)
+        if v.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(rows, share // row_bytes, replace=False))
+            v = v[keep]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(v))
+
+
+def kernel_report(a, pipe, out, prof, prof_full, rank, world):
+    """--full: per-kernel tables of the extra step (`prof_full`) and of the timed steps (`prof`), the roofline of the
+    dominant kernel and the roof figures of the matching kernel.  -> (roofline, bf_knn2, kernels, kernels_full)."""
+    from meatmodeler_amd import ops
+    F, H, W, N = a.frames, a.height, a.width, a.nfeatures
+    kp_count, n_obs, res = out["kp_count"], out["n_obs"], out.get("ba")
+    nfev = res.nfev if res is not None else 0
     # ---- roofline of the dominant kernel (this rank's launches; rank 0 reports) ----
     lv_w, lv_h, _, _ = ops.orb_level_sizes(H, W, pipe.prm)
     (p_lo, p_hi), (f_lo, f_hi) = __import__("meatmodeler_amd.parallel", fromlist=["x"]).pair_block(F, rank, world)
@@ -395,60 +527,7 @@ def main():
         for k_ in ("valu_Tlops",):
             bf.pop(k_, None)
 
-    cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
-        cpu = cpu_baseline(frames, N, F, nfev)
-
-    if rank == 0:
-        line = {
-            "metric": "descriptor-match pairs/sec + BA residuals/sec, 500×1080p frames, 1/2/4/8 GPU",
-            "value": value, "unit": "descriptor pairs/s (match stage)",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / a.steps,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "u8/int32 (match), f64 (BA)",
-            "data": "synthetic",
-            "config": {"workload": f"{F} frames {W}x{H}, {N} ORB kpts/frame, BF Hamming 2-NN + ratio, track linking, "
-                                   "2-view DLT, full BA (TRF, Schur, f64 MFMA Cholesky)" + (" [BA off]" if a.no_ba else ""),
-                       "frames": F, "height": H, "width": W, "nfeatures": N, "parallelism": f"pairs/points x{world}"},
-            "ba_residuals_per_s": ba_rps, "frames_per_s": F / (elapsed / a.steps), "stage_ms": stage_ms,
-            # the trust-region path on this outlier-laden clip is chaotic (the iteration count moves with rounding-level
-            # changes), so the per-iteration time is the figure to compare between builds, not ms_per_step
-            "ba": None if res is None else {
-                "nfev": nfev, "njev": res.njev, "iterations": getattr(res, "iterations", None),
-                "ms_per_iteration": stage_ms["ba_solve"] / max(getattr(res, "iterations", 0) or 1, 1),
-                "host_segments_ms_last_step": getattr(res, "host_segments_ms", None),
-                # N > 1: the same library loop (mm_ba_trf_dist); its exchange points call back into torch.distributed
-                "driver": "mm_ba_trf_dist" if world > 1 and getattr(res, "collectives", 0) else
-                          ("mm_ba_trf" if getattr(res, "host_segments_ms", {}).get("library") is not None else "python"),
-                "collectives": getattr(res, "collectives", None),
-                "collectives_per_evaluation": (getattr(res, "collectives", 0) or 0) / max(nfev, 1),
-                "chol_fallbacks": getattr(res, "chol_fallbacks", None)},
-            "problem": {"keypoints": int(kp_count.sum()), "descriptor_pairs": pair_evals,
-                        "matches": int(out["match_count"].sum()), "tracks": out["n_tracks"], "observations": n_obs,
-                        "ba_nfev": nfev, "ba_status": res.status if res is not None else None,
-                        "ba_cost": res.cost if res is not None else None, "cam_span": out.get("cam_span"),
-                        "schur_pairs": out.get("n_pairs"), "render_s": t_render},
-            "sliding_window_ba": None if "windows" not in out else {
-                "window": a.ba_window, "stride": a.ba_stride or max(1, a.ba_window // 2), "windows": len(out["windows"]),
-                "order": a.ba_order or "wavefront", "streams": a.ba_streams, "max_nfev_per_window": a.ba_window_max_nfev or None,
-                "batched": bool(a.ba_batched) and (a.ba_order or "wavefront") == "wavefront",
-                "ms": stage_ms["ba_windows"], "nfev_total": int(sum(w["nfev"] for w in out["windows"])),
-                "observations_total": int(sum(w["observations"] for w in out["windows"])),
-                "residual_evals_per_s": sum(w["observations"] * w["nfev"] for w in out["windows"]) /
-                                        max(stage_ms["ba_windows"] * 1e-3, 1e-9),
-                "status_counts": {str(k): int(sum(1 for w in out["windows"] if w["status"] == k))
-                                  for k in sorted({w["status"] for w in out["windows"]})},
-                "per_window": [[w["lo"], w["hi"], w["points"], w["observations"], w["nfev"], w["status"],
-                                float(f"{w['cost']:.6g}")] for w in out["windows"]],
-                "per_window_columns": ["lo", "hi", "points", "observations", "nfev", "status", "cost"]},
-            "roofline": roofline,
-            "bf_knn2": bf,
-            "kernels": kernels[:12],
-            "kernels_all_launches_extra_step": kernels_full[:16],
-            "cpu_baseline": cpu,
-        }
-        print(json.dumps(line))
-    if use_dist:
-        dist.destroy_process_group()
+    return roofline, bf, kernels, kernels_full
 
 
 def cpu_baseline(frames, nfeatures, n_frames, gpu_nfev):

@@ -1909,6 +1909,39 @@ def test_bench_refuses_more_ranks_than_gpus():
     assert b"GPU(s) visible" in p.stderr and not any(ln.startswith(b"{") for ln in p.stdout.splitlines())
 
 
+def test_bench_plain_and_full_runs_and_output_dump(tmp_path):
+    """A plain run times exactly --steps steps, reports ms_per_step and leaves the --full fields out; --dump-outputs writes
+    the last step's outputs as float32 / float64 .npy files, 64 MB at most, and two runs with the same arguments see the
+    same seeded inputs, hence the same key points, descriptors, matches and tracks.  --full adds the kernel tables and
+    the roofline."""
+    args = ["--gpus", "1", "--frames", "12", "--steps", "2", "--warmup", "1"]
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        p = _run_bench(args + ["--dump-outputs", str(d)], {}, timeout=300)
+        assert p.returncode == 0, p.stderr.decode(errors="replace")[-4000:]
+        lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout.decode()[-2000:]
+        line = json.loads(lines[0])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert not {"roofline", "kernels", "kernels_all_launches_extra_step", "cpu_baseline"} & set(line)
+        files = sorted(d.glob("*.npy"))
+        assert sum(f.stat().st_size for f in files) <= 64e6
+        arrays = {f.stem: np.load(f) for f in files}
+        assert {"keypoints_xy", "descriptors", "match_count", "track_ptr", "points_triangulated", "ba_cams",
+                "ba_points"} <= set(arrays)
+        assert all(v.dtype in (np.float32, np.float64) for v in arrays.values())
+        assert arrays["keypoints_xy"].shape[0] == arrays["keypoint_count"].sum() > 0
+        dumps.append(arrays)
+    for name in ("keypoint_count", "keypoints_xy", "descriptors", "match_count", "track_ptr", "track_obs_frame",
+                 "track_obs_kp"):
+        np.testing.assert_array_equal(dumps[0][name], dumps[1][name])
+    p = _run_bench(args + ["--full", "--no-cpu-baseline"], {}, timeout=300)
+    assert p.returncode == 0, p.stderr.decode(errors="replace")[-4000:]
+    line = json.loads([ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")][-1])
+    assert line["kernels"] and line["kernels_all_launches_extra_step"] and line["roofline"]["kernel"]
+
+
 def test_library_dist_loop_over_rccl_one_rank(tmp_path):
     """backend "nccl" (RCCL) under the sharded library loop, as far as one GPU allows: one rank whose all-reduce always goes
     through torch.distributed.  The sums are trivial, the path is the real one (ProcessGroupNCCL on views of the library's

@@ -342,6 +342,17 @@ def test_frame_oracle_definitions():
     assert (out == out[0, 0]).all()
 
 
+def test_bench_options():
+    """bench.py has --full and --dump-outputs, and refuses --steps 0 before it touches a device."""
+    import subprocess
+    import sys
+    bench = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")
+    p = subprocess.run([sys.executable, bench, "--help"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=60)
+    assert p.returncode == 0 and b"--full" in p.stdout and b"--dump-outputs" in p.stdout
+    p = subprocess.run([sys.executable, bench, "--steps", "0"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=60)
+    assert p.returncode == 2 and b"--steps must be >= 1" in p.stderr
+
+
 def test_bench_launcher_refuses_without_enough_gpus():
     """`python bench.py --gpus N` with no launcher around it starts its own ranks -- and says so loudly when the box has
     fewer than N GPUs instead of reporting a one-GPU run as N.  On this CPU-only container: no GPU at

@@ -1,4 +1,8 @@
-run() { tag=$1; shift; env "$@" timeout -k 10 300 python bench.py --frames 400 --nfeatures 8000 --ba-window 50 --ba-stride 25 --steps 1 --warmup 1 --no-cpu-baseline $EXTRA > gpurun_out/win_$tag.log 2>&1; grep "^{" gpurun_out/win_$tag.log | tail -1 | python -c "
+# (logs go to $OUT, default: out/ in the repository)
+ROOT=$(cd "$(dirname "$0")/../.." && pwd)
+OUT=$(realpath -m "${OUT:-$ROOT/out}")
+mkdir -p "$OUT" && cd "$ROOT" || exit 1
+run() { tag=$1; shift; env "$@" timeout -k 10 300 python bench.py --full --frames 400 --nfeatures 8000 --ba-window 50 --ba-stride 25 --steps 1 --warmup 1 --no-cpu-baseline $EXTRA > $OUT/win_$tag.log 2>&1; grep "^{" $OUT/win_$tag.log | tail -1 | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); s=j['sliding_window_ba']
 print('$tag', round(s['ms'],1), s['nfev_total'], round(s['ms']/s['nfev_total'],4), s['streams'])
