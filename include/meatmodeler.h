@@ -386,6 +386,34 @@ size_t mm_ba_trf_batched_workspace_bytes(const mm_ba_problem *pb);
 int mm_ba_trf_batched(mm_ctx *ctx, int n_prob, const mm_ba_problem *const *pbs, double *const *cams /*dev, in/out*/,
                       double *const *pts /*dev, in/out*/, const mm_trf_params *prm, mm_trf_report *reports /*host [n_prob]*/,
                       void *const *ws /*dev*/, const size_t *ws_bytes, int32_t *solved_alone /*host [n_prob] | NULL*/);
+/* FIXED CAMERAS (the anchored sliding window; hook at reference processor.py:395-408: the cameras
+ * older than the window are observed but not optimised).  A side descriptor to an unchanged mm_ba_problem: observations with
+ * fi in [pb->F, pb->F + F_fixed) use fixed camera fi - pb->F, whose 6 parameters (rvec, t) are read-only inputs.  The
+ * residual is bundleAdjuster.py:81-102 on [free cams | fixed cams | points]; the solve is the one of mm_ba_trf
+ * (bundleAdjuster.py:180-192) over the FREE parameters [free cams | points] only: n = 6F + 3P, and every norm, scale and
+ * termination test (|x| of the xtol test included) is over those n entries.  Fixed-camera observations enter the residual,
+ * the cost, the point blocks C / g_p and the point half of J v -- not B, g_c, the pair list, S or cam_span.  So the CSR by
+ * camera (cam_ptr / cam_obs) covers the F free cameras and the pair list (mm_ba_pairs_count / _emit on the free
+ * observations) holds free-free pairs only.  The caller guarantees fi < F + F_fixed.
+ * fx == NULL or F_fixed == 0: exactly the call without _fixed. */
+typedef struct mm_ba_fixed {
+    int32_t F_fixed;        /* observations with fi in [pb->F, pb->F + F_fixed) use these cameras */
+    int32_t reserved;
+    const double *cams;     /* dev [F_fixed, 6], read only */
+} mm_ba_fixed;
+/* mm_ba_residual / mm_ba_normal_eq with fixed cameras (parity surface): B / gc cover the free cameras. */
+int mm_ba_residual_fixed(mm_ctx *ctx, const mm_ba_problem *pb, const mm_ba_fixed *fx, const double *cams /*dev [F,6]*/,
+                         const double *pts /*dev [P,3]*/, double *res /*dev|NULL*/, double *cost2 /*dev [1]*/, void *ws,
+                         size_t ws_bytes);
+int mm_ba_normal_eq_fixed(mm_ctx *ctx, const mm_ba_problem *pb, const mm_ba_fixed *fx, const double *cams, const double *pts,
+                          double *B, double *gc, double *C, double *gp);
+/* mm_ba_trf with fixed cameras: the same loop, the same launches per trust-region iteration (the fixed cameras' rotation
+ * coefficients are computed once per solve), the same fall-back to the launch-per-column factorisation.  cams [F,6] are the
+ * free cameras (in/out), fx->cams are never written.  Needs the co-observation pair list (MM_ERR_ARG without one). */
+size_t mm_ba_trf_fixed_workspace_bytes(const mm_ba_problem *pb, const mm_ba_fixed *fx);
+int mm_ba_trf_fixed(mm_ctx *ctx, const mm_ba_problem *pb, const mm_ba_fixed *fx, double *cams /*dev, in/out*/,
+                    double *pts /*dev, in/out*/, const mm_trf_params *prm, mm_trf_report *report /*host*/,
+                    mm_trf_row *log /*host|NULL*/, int log_cap, void *ws /*dev, 256-byte aligned*/, size_t ws_bytes);
 /* SPD solve A x = b by blocked Cholesky (f64 MFMA trailing updates).  A [n,n] row-major, lower triangle is
  * overwritten by L; b [nrhs,n] is overwritten by x.  half_bandwidth: A[i][j] == 0 whenever i - j > half_bandwidth
  * (pass n for a dense matrix); the factorisation and the substitutions skip blocks outside the band.

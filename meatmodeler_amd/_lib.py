@@ -36,6 +36,11 @@ class BAProblem(C.Structure):
                 ("chunk_end", vp), ("pair_o", vp), ("pair_o2", vp), ("pair_p", vp)]
 
 
+class BAFixed(C.Structure):
+    """mm_ba_fixed: observations with fi in [F, F + F_fixed) use these read-only cameras (dev [F_fixed, 6])."""
+    _fields_ = [("F_fixed", C.c_int32), ("reserved", C.c_int32), ("cams", vp)]
+
+
 class TrfParams(C.Structure):
     _fields_ = [("ftol", C.c_double), ("xtol", C.c_double), ("gtol", C.c_double), ("min_damping", C.c_double),
                 ("max_nfev", C.c_int64)]
@@ -136,6 +141,11 @@ SIGNATURES = {
     "mm_ba_trf_batched_workspace_bytes": (C.c_size_t, [C.POINTER(BAProblem)]),
     "mm_ba_trf_batched": (C.c_int, [vp, C.c_int, C.POINTER(C.POINTER(BAProblem)), C.POINTER(vp), C.POINTER(vp),
                                     C.POINTER(TrfParams), C.POINTER(TrfReport), C.POINTER(vp), C.POINTER(C.c_size_t), c_i32p]),
+    "mm_ba_residual_fixed": (C.c_int, [vp, C.POINTER(BAProblem), C.POINTER(BAFixed), vp, vp, vp, vp, vp, C.c_size_t]),
+    "mm_ba_normal_eq_fixed": (C.c_int, [vp, C.POINTER(BAProblem), C.POINTER(BAFixed), vp, vp, vp, vp, vp, vp]),
+    "mm_ba_trf_fixed_workspace_bytes": (C.c_size_t, [C.POINTER(BAProblem), C.POINTER(BAFixed)]),
+    "mm_ba_trf_fixed": (C.c_int, [vp, C.POINTER(BAProblem), C.POINTER(BAFixed), vp, vp, C.POINTER(TrfParams),
+                                  C.POINTER(TrfReport), C.POINTER(TrfRow), C.c_int, vp, C.c_size_t]),
     "mm_ba_trf_dist_workspace_bytes": (C.c_size_t, [C.POINTER(BAProblem), C.c_int]),
     "mm_ba_trf_dist": (C.c_int, [vp, C.POINTER(BAProblem), vp, vp, C.POINTER(TrfParams), C.POINTER(TrfReport),
                                  C.POINTER(TrfRow), C.c_int, vp, C.c_size_t, C.POINTER(Dist)]),

@@ -338,6 +338,10 @@ class SchurTRF:
             self._Bd, self._Cd = torch.empty((F, 6, 6), **f64), torch.empty((P, 6), **f64)
             self._si = torch.empty(n, **f64)
 
+        if getattr(pb, "F_fixed", 0):      # fixed cameras: the library loop only (mm_ba_trf_fixed)
+            if self.driver != "library" or self.allreduce is not None:
+                raise NotImplementedError("fixed cameras: only the library driver on one GPU (mm_ba_trf_fixed)")
+            return self._solve_library(x, ftol, xtol, gtol, max_nfev, verbose)
         if (self.driver == "library" and self.allreduce is None and hasattr(pb, "trf_solve")
                 and not getattr(pb, "overlap", False)):
             return self._solve_library(x, ftol, xtol, gtol, max_nfev, verbose)
@@ -802,9 +806,34 @@ def reformatPoseResult(result, n_frames):
     return [np.hstack((_rodrigues_matrix(r), t.reshape(3, 1))) for r, t in zip(fp[:, :3], fp[:, 3:6])]
 
 
+def fixed_frame_order(fixed_frames, n_frames):
+    """Mask or index list of fixed frames -> (order, new_index): the free frames in their original order, then the fixed
+    ones (order [F] = original index of each new camera index); new_index [F] is its inverse.  The free frames become
+    cameras 0..F_free-1, fixed frame order[F_free + k] becomes fixed camera k (mm_ba_fixed)."""
+    fx = np.asarray(fixed_frames)
+    if fx.dtype == bool:
+        if fx.shape != (n_frames,):
+            raise ValueError(f"fixed_frames: a boolean mask needs {n_frames} entries")
+        mask = fx.copy()
+    else:
+        idx = fx.astype(np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= n_frames):
+            raise ValueError("fixed_frames: frame index out of range")
+        mask = np.zeros(n_frames, bool)
+        mask[idx] = True
+    order = np.concatenate([np.flatnonzero(~mask), np.flatnonzero(mask)])
+    new_index = np.empty(n_frames, np.int64)
+    new_index[order] = np.arange(n_frames)
+    return order, new_index, int((~mask).sum())
+
+
 def solvePoints(frame_extrinsic_matrices, camera_intrinsic_matrix, points_3D, points_2D, frame_indices, point_indices,
-                ftol=1e-4, xtol=1e-8, gtol=1e-8, max_nfev=None, verbose=2):
-    """adjustPoints with the optimiser settings exposed; returns the full result object (x, cost, nfev, ...)."""
+                ftol=1e-4, xtol=1e-8, gtol=1e-8, max_nfev=None, verbose=2, *, fixed_frames=None):
+    """adjustPoints with the optimiser settings exposed; returns the full result object (x, cost, nfev, ...).
+
+    fixed_frames (keyword only): boolean mask or index list over the frames whose extrinsics are observed but not
+    adjusted (mm_ba_trf_fixed).  The solve runs over the free frames and all points; res.x and
+    res.cams come back in the caller's frame order, the rows of the fixed frames equal to their input parameters."""
     ctx = default_context()
     dev = ctx.device
     ext = np.asarray(frame_extrinsic_matrices, float)
@@ -813,6 +842,9 @@ def solvePoints(frame_extrinsic_matrices, camera_intrinsic_matrix, points_3D, po
     P = len(pts0)
     with np.errstate(all="ignore"):
         cams0 = frameParameters(ext).reshape(F, 6)
+    if fixed_frames is not None:
+        return _solve_points_fixed(ctx, cams0, pts0, camera_intrinsic_matrix, points_2D, frame_indices, point_indices,
+                                   fixed_frames, ftol, xtol, gtol, max_nfev, verbose)
     pb = ops.BADevice(camera_intrinsic_matrix, frame_indices, point_indices, points_2D, F, P, dev, ctx)
     solver = SchurTRF(pb)
     cams_d, pts_d = _dev(cams0, dev), _dev(pts0, dev)
@@ -826,11 +858,41 @@ def solvePoints(frame_extrinsic_matrices, camera_intrinsic_matrix, points_3D, po
     return res
 
 
-def adjustPoints(frame_extrinsic_matrices, camera_intrinsic_matrix, points_3D, points_2D, frame_indices, point_indices):
+def _solve_points_fixed(ctx, cams0, pts0, K, points_2D, frame_indices, point_indices, fixed_frames, ftol, xtol, gtol,
+                        max_nfev, verbose):
+    dev = ctx.device
+    F, P = len(cams0), len(pts0)
+    order, new_index, F_free = fixed_frame_order(fixed_frames, F)
+    if F_free == 0:
+        raise ValueError("fixed_frames: every frame is fixed (points-only refinement is not supported)")
+    fi = new_index[np.asarray(frame_indices, np.int64).reshape(-1)]
+    if not (fi < F_free).any():
+        raise ValueError("fixed_frames: no point is observed by a free frame")
+    cams_r = cams0[order]
+    fixed_d = _dev(np.ascontiguousarray(cams_r[F_free:]), dev)
+    pb = ops.BADevice(K, fi.astype(np.int32), point_indices, points_2D, F_free, P, dev, ctx, fixed_cams=fixed_d)
+    solver = SchurTRF(pb)
+    cams_d, pts_d = _dev(np.ascontiguousarray(cams_r[:F_free]), dev), _dev(pts0, dev)
+    cost0 = None
+    if verbose >= 1:
+        cost0 = solver._cost(cams_d, pts_d)
+    res = solver.solve(cams_d, pts_d, ftol=ftol, xtol=xtol, gtol=gtol, max_nfev=max_nfev, verbose=verbose)
+    cams = cams0.copy()
+    cams[order[:F_free]] = res.cams.cpu().numpy()
+    res.cams = torch.as_tensor(cams).to(dev)
+    res.x = np.concatenate([cams.reshape(-1), res.pts.cpu().numpy().reshape(-1)])
+    if verbose >= 1:
+        _finish_verbose(res, cost0, verbose)
+    return res
+
+
+def adjustPoints(frame_extrinsic_matrices, camera_intrinsic_matrix, points_3D, points_2D, frame_indices, point_indices,
+                 *, fixed_frames=None):
     """Full bundle adjustment over all cameras and points (bundleAdjuster.py:160-194) with the reference's settings
-    (x_scale='jac', ftol=1e-4, verbose=2 progress table).  -> (points [P,3], list of F 4x4 extrinsics)."""
+    (x_scale='jac', ftol=1e-4, verbose=2 progress table).  -> (points [P,3], list of F 4x4 extrinsics).
+    fixed_frames: frames kept fixed (see solvePoints); their extrinsics come back as given."""
     res = solvePoints(frame_extrinsic_matrices, camera_intrinsic_matrix, points_3D, points_2D, frame_indices,
-                      point_indices, ftol=1e-4, verbose=2)
+                      point_indices, ftol=1e-4, verbose=2, fixed_frames=fixed_frames)
     F = len(frame_extrinsic_matrices)
     return reformatPointResult(res, F, len(np.asarray(points_3D).reshape(-1, 3)))
 

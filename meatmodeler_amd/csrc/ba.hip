@@ -26,8 +26,19 @@
 
 namespace {
 
+// Parameters of the camera of an observation.  FIXED (mm_ba_fixed): indices f >= F are fixed camera f - F of `fxc` -- an
+// address select, not a branch.  The sweeps below are templates on FIXED; FIXED = false is the code they always had.
+template <bool FIXED>
+__device__ __forceinline__ const double *cam_at(const double *__restrict__ cams, const double *__restrict__ fxc, int F, int f) {
+    if constexpr (FIXED)
+        return f < F ? cams + (size_t)f * 6 : fxc + (size_t)(f - F) * 6;
+    else
+        return cams + (size_t)f * 6;
+}
+
 // ---- residual + cost ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void ba_residual_body(mm_ba_problem pb, const double *__restrict__ cams,
+template <bool FIXED>
+__device__ __forceinline__ void ba_residual_body(mm_ba_problem pb, const double *__restrict__ cams, const double *__restrict__ fxc,
                                                           const double *__restrict__ pts, const CamCoef *__restrict__ ctab, double *__restrict__ res,
                                                           double *__restrict__ partial, const unsigned bx, const unsigned gx) {
     __shared__ double sm[4];
@@ -38,7 +49,7 @@ __device__ __forceinline__ void ba_residual_body(mm_ba_problem pb, const double 
     for (int64_t o = (int64_t)bx * 256 + threadIdx.x; o < pb.O; o += (int64_t)gx * 256) {
         Proj pr;
         const int f = pb.fi[o];
-        ba_eval_cc<false, false>(cams + (size_t)f * 6, ctab[f],
+        ba_eval_cc<false, false>(cam_at<FIXED>(cams, fxc, pb.F, f), ctab[f],
                                  pts + (size_t)pb.pi[o] * 3, Ks, pb.obs[2 * o], pb.obs[2 * o + 1], pr);
         if (res) {
             res[2 * o] = pr.r0;
@@ -51,7 +62,10 @@ __device__ __forceinline__ void ba_residual_body(mm_ba_problem pb, const double 
 }
 __global__ __launch_bounds__(256) void ba_residual_kernel(mm_ba_problem pb, const double *__restrict__ cams,
                                                           const double *__restrict__ pts, const CamCoef *__restrict__ ctab, double *__restrict__ res,
-                                                          double *__restrict__ partial) { ba_residual_body(pb, cams, pts, ctab, res, partial, blockIdx.x, gridDim.x); }
+                                                          double *__restrict__ partial) { ba_residual_body<false>(pb, cams, nullptr, pts, ctab, res, partial, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256) void ba_residual_fixed_kernel(mm_ba_problem pb, const double *__restrict__ cams, const double *__restrict__ fxc,
+                                                                const double *__restrict__ pts, const CamCoef *__restrict__ ctab, double *__restrict__ res,
+                                                                double *__restrict__ partial) { ba_residual_body<true>(pb, cams, fxc, pts, ctab, res, partial, blockIdx.x, gridDim.x); }
 
 __global__ __launch_bounds__(256) void sum_partials_kernel(const double *__restrict__ partial, int n,
                                                            double *__restrict__ out) {
@@ -122,7 +136,8 @@ __global__ __launch_bounds__(256) void ba_jacobian_kernel(mm_ba_problem pb, cons
 #define MM_PB_LANES 4
 #endif
 constexpr int PB_LANES = MM_PB_LANES;      // lanes per point in the point-block sweeps (normal equations 84.3 / 81.6 / 98.0 us with 2 / 4 / 8: round 4)
-__device__ __forceinline__ void ba_point_blocks_body(mm_ba_problem pb, const double *__restrict__ cams,
+template <bool FIXED>
+__device__ __forceinline__ void ba_point_blocks_body(mm_ba_problem pb, const double *__restrict__ cams, const double *__restrict__ fxc,
                                                               const double *__restrict__ pts, const CamCoef *__restrict__ ctab, double *__restrict__ C,
                                                               double *__restrict__ gp, const unsigned bx, const unsigned gx) {
     __shared__ double Ks[9];
@@ -139,7 +154,7 @@ __device__ __forceinline__ void ba_point_blocks_body(mm_ba_problem pb, const dou
             const int o = pb.pt_obs[e];
             Proj pr;
             const int f = pb.fi[o];
-            ba_eval_cc<false, true>(cams + (size_t)f * 6, ctab[f], Xp, Ks, pb.obs[2 * (size_t)o], pb.obs[2 * (size_t)o + 1], pr);
+            ba_eval_cc<false, true>(cam_at<FIXED>(cams, fxc, pb.F, f), ctab[f], Xp, Ks, pb.obs[2 * (size_t)o], pb.obs[2 * (size_t)o + 1], pr);
 #pragma unroll
             for (int m = 0; m < 2; ++m) {
                 const double j0 = pr.Jp[m][0], j1 = pr.Jp[m][1], j2 = pr.Jp[m][2];
@@ -167,7 +182,10 @@ __device__ __forceinline__ void ba_point_blocks_body(mm_ba_problem pb, const dou
 }
 __global__ __launch_bounds__(256) void ba_point_blocks_kernel(mm_ba_problem pb, const double *__restrict__ cams,
                                                               const double *__restrict__ pts, const CamCoef *__restrict__ ctab, double *__restrict__ C,
-                                                              double *__restrict__ gp) { ba_point_blocks_body(pb, cams, pts, ctab, C, gp, blockIdx.x, gridDim.x); }
+                                                              double *__restrict__ gp) { ba_point_blocks_body<false>(pb, cams, nullptr, pts, ctab, C, gp, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256) void ba_point_blocks_fixed_kernel(mm_ba_problem pb, const double *__restrict__ cams, const double *__restrict__ fxc,
+                                                                    const double *__restrict__ pts, const CamCoef *__restrict__ ctab, double *__restrict__ C,
+                                                                    double *__restrict__ gp) { ba_point_blocks_body<true>(pb, cams, fxc, pts, ctab, C, gp, blockIdx.x, gridDim.x); }
 
 // ---- camera blocks: B[F,6,6] and gc[F,6]; one workgroup per camera over its (gathered) observations -----------------
 __device__ __forceinline__ void ba_camera_blocks_body(mm_ba_problem pb, const double *__restrict__ cams,
@@ -227,7 +245,14 @@ __global__ __launch_bounds__(256) void ba_normal_eq_kernel(mm_ba_problem pb, con
                                                            const CamCoef *__restrict__ ctab, double *__restrict__ B, double *__restrict__ gc,
                                                            double *__restrict__ C, double *__restrict__ gp) {
     if ((int)blockIdx.x < pb.F) ba_camera_blocks_body(pb, cams, pts, B, gc, blockIdx.x, (unsigned)pb.F);
-    else ba_point_blocks_body(pb, cams, pts, ctab, C, gp, blockIdx.x - (unsigned)pb.F, gridDim.x - (unsigned)pb.F);
+    else ba_point_blocks_body<false>(pb, cams, nullptr, pts, ctab, C, gp, blockIdx.x - (unsigned)pb.F, gridDim.x - (unsigned)pb.F);
+}
+// (fixed cameras: the CSR by camera covers the free ones only, so the camera blocks are the same body)
+__global__ __launch_bounds__(256) void ba_normal_eq_fixed_kernel(mm_ba_problem pb, const double *__restrict__ cams, const double *__restrict__ fxc,
+                                                                 const double *__restrict__ pts, const CamCoef *__restrict__ ctab, double *__restrict__ B,
+                                                                 double *__restrict__ gc, double *__restrict__ C, double *__restrict__ gp) {
+    if ((int)blockIdx.x < pb.F) ba_camera_blocks_body(pb, cams, pts, B, gc, blockIdx.x, (unsigned)pb.F);
+    else ba_point_blocks_body<true>(pb, cams, fxc, pts, ctab, C, gp, blockIdx.x - (unsigned)pb.F, gridDim.x - (unsigned)pb.F);
 }
 
 // ---- out = Jc wc[fi] + Jp wp[pi] ----------------------------------------------------------------------------------
@@ -269,7 +294,8 @@ __global__ __launch_bounds__(256) void ba_jvp_kernel(mm_ba_problem pb, const dou
 // needs exactly these sums right after each of its two Jacobian products (|J d g_h|^2; <J s2, J d g_h>, |J s2|^2):
 // two vector passes less per iteration.  Deterministic: fixed tree per workgroup, then one small launch adds the
 // per-workgroup partials in index order.
-__device__ __forceinline__ void ba_jvp_dots_body(mm_ba_problem pb, const double *__restrict__ cams,
+template <bool FIXED>
+__device__ __forceinline__ void ba_jvp_dots_body(mm_ba_problem pb, const double *__restrict__ cams, const double *__restrict__ fxc,
                                                           const double *__restrict__ pts, const CamCoef *__restrict__ ctab, const double *__restrict__ wc,
                                                           const double *__restrict__ wp, double *__restrict__ out,
                                                           const double *__restrict__ other, double *__restrict__ partial, const unsigned bx, const unsigned gx) {
@@ -282,10 +308,10 @@ __device__ __forceinline__ void ba_jvp_dots_body(mm_ba_problem pb, const double 
     for (int64_t o = (int64_t)bx * 256 + threadIdx.x; o < pb.O; o += (int64_t)gx * 256) {
         const int f = pb.fi[o], p = pb.pi[o];
         Proj pr;
-        ba_eval_cc<true, true>(cams + (size_t)f * 6, ctab[f],
+        ba_eval_cc<true, true>(cam_at<FIXED>(cams, fxc, pb.F, f), ctab[f],
                                pts + (size_t)p * 3, Ks, pb.obs[2 * o], pb.obs[2 * o + 1], pr);
         double y0 = 0, y1 = 0;
-        if (wc) {
+        if (wc && (!FIXED || f < pb.F)) {      // (a fixed camera has no parameter step)
 #pragma unroll
             for (int k = 0; k < 6; ++k) {
                 const double w = wc[(size_t)f * 6 + k];
@@ -316,7 +342,11 @@ __device__ __forceinline__ void ba_jvp_dots_body(mm_ba_problem pb, const double 
 __global__ __launch_bounds__(256) void ba_jvp_dots_kernel(mm_ba_problem pb, const double *__restrict__ cams,
                                                           const double *__restrict__ pts, const CamCoef *__restrict__ ctab, const double *__restrict__ wc,
                                                           const double *__restrict__ wp, double *__restrict__ out,
-                                                          const double *__restrict__ other, double *__restrict__ partial) { ba_jvp_dots_body(pb, cams, pts, ctab, wc, wp, out, other, partial, blockIdx.x, gridDim.x); }
+                                                          const double *__restrict__ other, double *__restrict__ partial) { ba_jvp_dots_body<false>(pb, cams, nullptr, pts, ctab, wc, wp, out, other, partial, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256) void ba_jvp_dots_fixed_kernel(mm_ba_problem pb, const double *__restrict__ cams, const double *__restrict__ fxc,
+                                                                const double *__restrict__ pts, const CamCoef *__restrict__ ctab, const double *__restrict__ wc,
+                                                                const double *__restrict__ wp, double *__restrict__ out,
+                                                                const double *__restrict__ other, double *__restrict__ partial) { ba_jvp_dots_body<true>(pb, cams, fxc, pts, ctab, wc, wp, out, other, partial, blockIdx.x, gridDim.x); }
 
 __global__ __launch_bounds__(256) void jvp_rows_kernel(const double *__restrict__ partial, unsigned n_wg, double *__restrict__ rows) { (void)jvp_rows_body(partial, n_wg, rows, blockIdx.x, gridDim.x); }
 
@@ -360,7 +390,8 @@ __global__ __launch_bounds__(256) void ba_backsub_kernel(mm_ba_problem pb, const
 // (85 us at C3 against 25 us for the Jacobian product over the same observations).  Pass 1 writes every observation's
 // 3-vector Jp^T (Jc dc) into a scratch array in CSR-by-point order, pass 2 adds each point's rows in that order (a fixed
 // order: deterministic) and applies Cinv.
-__device__ __forceinline__ void ba_backsub_obs_body(mm_ba_problem pb, const double *__restrict__ cams,
+template <bool FIXED>
+__device__ __forceinline__ void ba_backsub_obs_body(mm_ba_problem pb, const double *__restrict__ cams, const double *__restrict__ fxc,
                                                              const double *__restrict__ pts, const CamCoef *__restrict__ ctab,
                                                              const double *__restrict__ dc, double *__restrict__ T, const unsigned bx, const unsigned gx) {
     __shared__ double Ks[9];
@@ -371,14 +402,16 @@ __device__ __forceinline__ void ba_backsub_obs_body(mm_ba_problem pb, const doub
     const int o = pb.pt_obs[e];
     const int f = pb.fi[o], p = pb.pi[o];
     Proj pr;
-    ba_eval_cc<true, true>(cams + (size_t)f * 6, ctab[f], pts + (size_t)p * 3, Ks, pb.obs[2 * (size_t)o],
+    ba_eval_cc<true, true>(cam_at<FIXED>(cams, fxc, pb.F, f), ctab[f], pts + (size_t)p * 3, Ks, pb.obs[2 * (size_t)o],
                            pb.obs[2 * (size_t)o + 1], pr);
     double s0 = 0, s1 = 0;
+    if (!FIXED || f < pb.F) {      // (a fixed camera has no step: its row of T is zero)
 #pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const double d = dc[(size_t)f * 6 + k];
-        s0 += pr.Jc[0][k] * d;
-        s1 += pr.Jc[1][k] * d;
+        for (int k = 0; k < 6; ++k) {
+            const double d = dc[(size_t)f * 6 + k];
+            s0 += pr.Jc[0][k] * d;
+            s1 += pr.Jc[1][k] * d;
+        }
     }
     T[3 * e] = pr.Jp[0][0] * s0 + pr.Jp[1][0] * s1;
     T[3 * e + 1] = pr.Jp[0][1] * s0 + pr.Jp[1][1] * s1;
@@ -386,7 +419,10 @@ __device__ __forceinline__ void ba_backsub_obs_body(mm_ba_problem pb, const doub
 }
 __global__ __launch_bounds__(256) void ba_backsub_obs_kernel(mm_ba_problem pb, const double *__restrict__ cams,
                                                              const double *__restrict__ pts, const CamCoef *__restrict__ ctab,
-                                                             const double *__restrict__ dc, double *__restrict__ T) { ba_backsub_obs_body(pb, cams, pts, ctab, dc, T, blockIdx.x, gridDim.x); }
+                                                             const double *__restrict__ dc, double *__restrict__ T) { ba_backsub_obs_body<false>(pb, cams, nullptr, pts, ctab, dc, T, blockIdx.x, gridDim.x); }
+__global__ __launch_bounds__(256) void ba_backsub_obs_fixed_kernel(mm_ba_problem pb, const double *__restrict__ cams, const double *__restrict__ fxc,
+                                                                   const double *__restrict__ pts, const CamCoef *__restrict__ ctab,
+                                                                   const double *__restrict__ dc, double *__restrict__ T) { ba_backsub_obs_body<true>(pb, cams, fxc, pts, ctab, dc, T, blockIdx.x, gridDim.x); }
 
 // (four lanes per point like the point blocks: rows of T that belong to one point are read by neighbouring lanes, and the
 // launch no longer waits for the threads that own the longest tracks; fixed butterfly: deterministic)
@@ -489,7 +525,7 @@ __global__ __launch_bounds__(256) void cam_coef_batch_kernel(const mm_batch_prob
 }
 __global__ __launch_bounds__(256) void ba_residual_batch_kernel(const mm_batch_prob *__restrict__ tab, const int32_t *__restrict__ list) {
     MM_BATCH_PROB(g_res);
-    ba_residual_body(bp.pb, bp.x_new, bp.x_new + bp.nc, (const CamCoef *)bp.ctab_new, nullptr, bp.res_partial, blockIdx.x, bp.g_res);
+    ba_residual_body<false>(bp.pb, bp.x_new, nullptr, bp.x_new + bp.nc, (const CamCoef *)bp.ctab_new, nullptr, bp.res_partial, blockIdx.x, bp.g_res);
 }
 __global__ __launch_bounds__(256) void sum_partials_publish_batch_kernel(const mm_batch_prob *__restrict__ tab, const int32_t *__restrict__ list,
                                                                          const mm_batch_dyn *__restrict__ dyn) {
@@ -512,7 +548,7 @@ __global__ __launch_bounds__(256) void ba_jvp_dots_batch_kernel(const mm_batch_p
     MM_BATCH_PROB(g_jvp);
     // first product of an iteration: u1 = J (d g_h); second: Jq2 = J s2 with <Jq2, u1>
     const double *w = second ? bp.s2 : bp.ghs;
-    ba_jvp_dots_body(bp.pb, bp.x, bp.x + bp.nc, (const CamCoef *)bp.ctab_x, w, w + bp.nc, second ? bp.Jq2 : bp.u1,
+    ba_jvp_dots_body<false>(bp.pb, bp.x, nullptr, bp.x + bp.nc, (const CamCoef *)bp.ctab_x, w, w + bp.nc, second ? bp.Jq2 : bp.u1,
                      second ? bp.u1 : nullptr, bp.jvp_partial, blockIdx.x, bp.g_jvp);
 }
 __global__ __launch_bounds__(256) void jvp_rows_batch_kernel(const mm_batch_prob *__restrict__ tab, const int32_t *__restrict__ list, int second) {
@@ -533,7 +569,7 @@ __global__ void set_reg_batch_kernel(const mm_batch_prob *__restrict__ tab, cons
 }
 __global__ __launch_bounds__(256) void ba_backsub_obs_batch_kernel(const mm_batch_prob *__restrict__ tab, const int32_t *__restrict__ list) {
     MM_BATCH_PROB(g_obs);
-    ba_backsub_obs_body(bp.pb, bp.x, bp.x + bp.nc, (const CamCoef *)bp.ctab_x, bp.v, bp.backsub_T, blockIdx.x, bp.g_obs);
+    ba_backsub_obs_body<false>(bp.pb, bp.x, nullptr, bp.x + bp.nc, (const CamCoef *)bp.ctab_x, bp.v, bp.backsub_T, blockIdx.x, bp.g_obs);
 }
 __global__ __launch_bounds__(256) void ba_backsub_points_batch_kernel(const mm_batch_prob *__restrict__ tab, const int32_t *__restrict__ list) {
     MM_BATCH_PROB(g_pts);
@@ -544,7 +580,7 @@ __global__ __launch_bounds__(256) void ba_normal_eq_batch_kernel(const mm_batch_
     const unsigned F = (unsigned)bp.pb.F;
     if (blockIdx.x < F) ba_camera_blocks_body(bp.pb, bp.x, bp.x + bp.nc, bp.B, bp.g, blockIdx.x, F);
     else if (blockIdx.x - F < bp.g_pblk)
-        ba_point_blocks_body(bp.pb, bp.x, bp.x + bp.nc, (const CamCoef *)bp.ctab_x, bp.C, bp.g + bp.nc, blockIdx.x - F, bp.g_pblk);
+        ba_point_blocks_body<false>(bp.pb, bp.x, nullptr, bp.x + bp.nc, (const CamCoef *)bp.ctab_x, bp.C, bp.g + bp.nc, blockIdx.x - F, bp.g_pblk);
 }
 
 }  // namespace
@@ -552,15 +588,19 @@ __global__ __launch_bounds__(256) void ba_normal_eq_batch_kernel(const mm_batch_
 // The table lives in the context.  `cam_tab_for` remembers which camera vector it was computed from; a caller that
 // knows the vector has not changed since (the library's own trust-region loop, trf.hip) keeps it valid with
 // mm_cam_table_hold() and the sweeps then skip the launch.  Everybody else gets a fresh table per call.
+// With fixed cameras (mm_fixed_scope) the table has F + fx_F rows: rows F.. hold the fixed cameras, computed once per
+// _fixed call (they never change), rows 0..F-1 as above.
 int mm_cam_coef_table(mm_ctx *ctx, const double *cams, int F, const void **tab_out) {
-    if (F > ctx->cam_tab_cap) {
+    const int rows = F + ctx->fx_F;
+    if (rows > ctx->cam_tab_cap) {
         if (ctx->cam_tab) (void)hipFree(ctx->cam_tab);
         ctx->cam_tab = nullptr;
         ctx->cam_tab_cap = 0;
-        const int cap = F < 1024 ? 1024 : F + F / 2;
+        const int cap = rows < 1024 ? 1024 : rows + rows / 2;
         MM_HIP(ctx, hipMalloc(&ctx->cam_tab, (size_t)cap * sizeof(CamCoef)));
         ctx->cam_tab_cap = cap;
         ctx->cam_tab_for = nullptr;
+        ctx->fx_tab_ok = false;
     }
     if (!(ctx->cam_tab_hold && ctx->cam_tab_for == cams && ctx->cam_tab_F == F)) {
         if (F > 0)
@@ -568,17 +608,24 @@ int mm_cam_coef_table(mm_ctx *ctx, const double *cams, int F, const void **tab_o
         ctx->cam_tab_for = cams;
         ctx->cam_tab_F = F;
     }
+    if (ctx->fx_F > 0 && !ctx->fx_tab_ok) {
+        MM_LAUNCH(ctx, "cam_coef_kernel", cam_coef_kernel, dim3((ctx->fx_F + 255) / 256), dim3(256), 0, ctx->fx_cams, ctx->fx_F,
+                  (CamCoef *)ctx->cam_tab + F);
+        ctx->fx_tab_ok = true;
+    }
     *tab_out = ctx->cam_tab;
     return MM_OK;
 }
 int mm_cam_table_adopt(mm_ctx *ctx, const double *cams, int F, void **tab_out) {
-    if (F > ctx->cam_tab_cap) {
+    const int rows = F + ctx->fx_F;
+    if (rows > ctx->cam_tab_cap) {
         if (ctx->cam_tab) (void)hipFree(ctx->cam_tab);
         ctx->cam_tab = nullptr;
         ctx->cam_tab_cap = 0;
-        const int cap = F < 1024 ? 1024 : F + F / 2;
+        const int cap = rows < 1024 ? 1024 : rows + rows / 2;
         MM_HIP(ctx, hipMalloc(&ctx->cam_tab, (size_t)cap * sizeof(CamCoef)));
         ctx->cam_tab_cap = cap;
+        ctx->fx_tab_ok = false;      // (the next mm_cam_coef_table refills the fixed rows)
     }
     ctx->cam_tab_for = cams;
     ctx->cam_tab_F = F;
@@ -615,7 +662,11 @@ int mm_ba_residual(mm_ctx *ctx, const mm_ba_problem *pb, const double *cams, con
     int64_t nb = (pb->O + 255) / 256;
     int blocks = (int)(nb < 1 ? 1 : (nb > res_wg_cap() ? res_wg_cap() : nb));
     MM_CAM_TABLE(ctx, pb, cams);
-    MM_LAUNCH(ctx, "ba_residual_kernel", ba_residual_kernel, dim3(blocks), dim3(256), 0, *pb, cams, pts, ctab, res, (double *)ws);
+    if (ctx->fx_F > 0)
+        MM_LAUNCH(ctx, "ba_residual_fixed_kernel", ba_residual_fixed_kernel, dim3(blocks), dim3(256), 0, *pb, cams, ctx->fx_cams, pts, ctab, res,
+                  (double *)ws);
+    else
+        MM_LAUNCH(ctx, "ba_residual_kernel", ba_residual_kernel, dim3(blocks), dim3(256), 0, *pb, cams, pts, ctab, res, (double *)ws);
     MM_LAUNCH(ctx, "sum_partials_kernel", sum_partials_kernel, dim3(1), dim3(256), 0, (const double *)ws, blocks, cost2);
     return MM_OK;
 }
@@ -624,6 +675,7 @@ int mm_ba_jacobian(mm_ctx *ctx, const mm_ba_problem *pb, const double *cams, con
     int rc = check_pb(ctx, pb, "mm_ba_jacobian");
     if (rc) return rc;
     if (!cams || !pts || !Jc || !Jp) return mm_fail(ctx, MM_ERR_ARG, "mm_ba_jacobian: null pointer");
+    if (ctx->fx_F > 0) return mm_fail(ctx, MM_ERR_ARG, "mm_ba_jacobian: no fixed-camera form");
     if (pb->O == 0) return MM_OK;
     MM_CAM_TABLE(ctx, pb, cams);
     MM_LAUNCH(ctx, "ba_jacobian_kernel", ba_jacobian_kernel, dim3((unsigned)((pb->O + 255) / 256)), dim3(256), 0, *pb, cams, pts, ctab, Jc, Jp);
@@ -641,15 +693,23 @@ int mm_ba_normal_eq(mm_ctx *ctx, const mm_ba_problem *pb, const double *cams, co
         if (!pb->pt_ptr || !pb->pt_obs || !pb->cam_ptr || !pb->cam_obs) return mm_fail(ctx, MM_ERR_ARG, "mm_ba_normal_eq: CSR missing");
         MM_CAM_TABLE(ctx, pb, cams);
         const unsigned g_pblk = (unsigned)((pb->P + 256 / PB_LANES - 1) / (256 / PB_LANES));
-        MM_LAUNCH(ctx, "ba_normal_eq_kernel", ba_normal_eq_kernel, dim3((unsigned)pb->F + g_pblk), dim3(256), 0, *pb, cams, pts, ctab, B, gc, C, gp);
+        if (ctx->fx_F > 0)
+            MM_LAUNCH(ctx, "ba_normal_eq_fixed_kernel", ba_normal_eq_fixed_kernel, dim3((unsigned)pb->F + g_pblk), dim3(256), 0, *pb, cams,
+                      ctx->fx_cams, pts, ctab, B, gc, C, gp);
+        else
+            MM_LAUNCH(ctx, "ba_normal_eq_kernel", ba_normal_eq_kernel, dim3((unsigned)pb->F + g_pblk), dim3(256), 0, *pb, cams, pts, ctab, B, gc, C, gp);
         return MM_OK;
     }
     if (C) {
         if (!pb->pt_ptr || !pb->pt_obs) return mm_fail(ctx, MM_ERR_ARG, "mm_ba_normal_eq: point CSR missing");
         if (pb->P > 0) {
             MM_CAM_TABLE(ctx, pb, cams);
-            MM_LAUNCH(ctx, "ba_point_blocks_kernel", ba_point_blocks_kernel, dim3((pb->P + 256 / PB_LANES - 1) / (256 / PB_LANES)), dim3(256), 0,
-                      *pb, cams, pts, ctab, C, gp);
+            if (ctx->fx_F > 0)
+                MM_LAUNCH(ctx, "ba_point_blocks_fixed_kernel", ba_point_blocks_fixed_kernel, dim3((pb->P + 256 / PB_LANES - 1) / (256 / PB_LANES)),
+                          dim3(256), 0, *pb, cams, ctx->fx_cams, pts, ctab, C, gp);
+            else
+                MM_LAUNCH(ctx, "ba_point_blocks_kernel", ba_point_blocks_kernel, dim3((pb->P + 256 / PB_LANES - 1) / (256 / PB_LANES)), dim3(256), 0,
+                          *pb, cams, pts, ctab, C, gp);
         }
     }
     if (B) {
@@ -666,6 +726,7 @@ int mm_ba_jvp(mm_ctx *ctx, const mm_ba_problem *pb, const double *cams, const do
     int rc = check_pb(ctx, pb, "mm_ba_jvp");
     if (rc) return rc;
     if (!cams || !pts || !out) return mm_fail(ctx, MM_ERR_ARG, "mm_ba_jvp: null pointer");
+    if (ctx->fx_F > 0) return mm_fail(ctx, MM_ERR_ARG, "mm_ba_jvp: no fixed-camera form");
     if (pb->O == 0) return MM_OK;
     MM_CAM_TABLE(ctx, pb, cams);
     MM_LAUNCH(ctx, "ba_jvp_kernel", ba_jvp_kernel, dim3((unsigned)((pb->O + 255) / 256)), dim3(256), 0, *pb, cams, pts, ctab, wc, wp, out);
@@ -691,8 +752,12 @@ int mm_ba_jvp_dots(mm_ctx *ctx, const mm_ba_problem *pb, const double *cams, con
     const int64_t n_all = (pb->O + 255) / 256;
     const unsigned n_wg = (unsigned)(n_all < jvp_wg_cap() ? n_all : jvp_wg_cap());
     MM_CAM_TABLE(ctx, pb, cams);
-    MM_LAUNCH(ctx, "ba_jvp_kernel", ba_jvp_dots_kernel, dim3(n_wg), dim3(256), 0, *pb, cams, pts, ctab, wc, wp, out, other,
-              (double *)((char *)ws + 256));
+    if (ctx->fx_F > 0)
+        MM_LAUNCH(ctx, "ba_jvp_fixed_kernel", ba_jvp_dots_fixed_kernel, dim3(n_wg), dim3(256), 0, *pb, cams, ctx->fx_cams, pts, ctab, wc, wp,
+                  out, other, (double *)((char *)ws + 256));
+    else
+        MM_LAUNCH(ctx, "ba_jvp_kernel", ba_jvp_dots_kernel, dim3(n_wg), dim3(256), 0, *pb, cams, pts, ctab, wc, wp, out, other,
+                  (double *)((char *)ws + 256));
     if (ctx->jvp_rows_deferred) {      // (mm_ba_trf: the consumer's own kernel adds the partials -- mm_trf_rows_step2d)
         ctx->jvp_partial = (const double *)((char *)ws + 256);
         ctx->jvp_n_wg = n_wg;
@@ -715,16 +780,46 @@ int mm_ba_backsub(mm_ctx *ctx, const mm_ba_problem *pb, const double *cams, cons
         return mm_fail(ctx, MM_ERR_ARG, "mm_ba_backsub: null pointer");
     if (ws && ws_bytes < mm_ba_backsub_workspace_bytes(pb)) return mm_fail(ctx, MM_ERR_WORKSPACE, "mm_ba_backsub: workspace too small");
     if (pb->P == 0) return MM_OK;
+    if (ctx->fx_F > 0 && !ws) return mm_fail(ctx, MM_ERR_WORKSPACE, "mm_ba_backsub: fixed cameras need the workspace");
     MM_CAM_TABLE(ctx, pb, cams);
     if (ws && pb->O > 0) {
-        MM_LAUNCH(ctx, "ba_backsub_kernel", ba_backsub_obs_kernel, dim3((unsigned)((pb->O + 255) / 256)), dim3(256), 0, *pb, cams, pts,
-                  ctab, dc, (double *)ws);
+        if (ctx->fx_F > 0)
+            MM_LAUNCH(ctx, "ba_backsub_fixed_kernel", ba_backsub_obs_fixed_kernel, dim3((unsigned)((pb->O + 255) / 256)), dim3(256), 0, *pb,
+                      cams, ctx->fx_cams, pts, ctab, dc, (double *)ws);
+        else
+            MM_LAUNCH(ctx, "ba_backsub_kernel", ba_backsub_obs_kernel, dim3((unsigned)((pb->O + 255) / 256)), dim3(256), 0, *pb, cams, pts,
+                      ctab, dc, (double *)ws);
         MM_LAUNCH(ctx, "ba_backsub_points_kernel", ba_backsub_points_kernel, dim3((pb->P + 256 / PB_LANES - 1) / (256 / PB_LANES)), dim3(256), 0,
                   *pb, (const double *)ws, Cinv, gp, dp);
         return MM_OK;
     }
     MM_LAUNCH(ctx, "ba_backsub_kernel", ba_backsub_kernel, dim3((pb->P + 255) / 256), dim3(256), 0, *pb, cams, pts, ctab, Cinv, gp, dc, dp);
     return MM_OK;
+}
+
+static int mm_ba_fixed_check(mm_ctx *ctx, const mm_ba_fixed *fx, const char *who) {
+    if (fx->F_fixed < 0 || (fx->F_fixed > 0 && !fx->cams)) return mm_fail(ctx, MM_ERR_ARG, "%s: bad fixed-camera descriptor", who);
+    return MM_OK;
+}
+
+int mm_ba_residual_fixed(mm_ctx *ctx, const mm_ba_problem *pb, const mm_ba_fixed *fx, const double *cams, const double *pts,
+                         double *res, double *cost2, void *ws, size_t ws_bytes) {
+    if (!ctx) return MM_ERR_ARG;
+    if (!fx || fx->F_fixed == 0) return mm_ba_residual(ctx, pb, cams, pts, res, cost2, ws, ws_bytes);
+    int rc = mm_ba_fixed_check(ctx, fx, "mm_ba_residual_fixed");
+    if (rc) return rc;
+    mm_fixed_scope scope(ctx, fx);
+    return mm_ba_residual(ctx, pb, cams, pts, res, cost2, ws, ws_bytes);
+}
+
+int mm_ba_normal_eq_fixed(mm_ctx *ctx, const mm_ba_problem *pb, const mm_ba_fixed *fx, const double *cams, const double *pts,
+                          double *B, double *gc, double *C, double *gp) {
+    if (!ctx) return MM_ERR_ARG;
+    if (!fx || fx->F_fixed == 0) return mm_ba_normal_eq(ctx, pb, cams, pts, B, gc, C, gp);
+    int rc = mm_ba_fixed_check(ctx, fx, "mm_ba_normal_eq_fixed");
+    if (rc) return rc;
+    mm_fixed_scope scope(ctx, fx);
+    return mm_ba_normal_eq(ctx, pb, cams, pts, B, gc, C, gp);
 }
 
 int mm_trf_damping(mm_ctx *ctx, const double *gh2, const double *d11, double Delta, double min_damping, double *out) {
@@ -745,7 +840,11 @@ int mm_ba_residual_publish(mm_ctx *ctx, const mm_ba_problem *pb, const double *c
     int64_t nb = (pb->O + 255) / 256;
     int blocks = (int)(nb < 1 ? 1 : (nb > res_wg_cap() ? res_wg_cap() : nb));
     MM_CAM_TABLE(ctx, pb, cams);
-    MM_LAUNCH(ctx, "ba_residual_kernel", ba_residual_kernel, dim3(blocks), dim3(256), 0, *pb, cams, pts, ctab, (double *)nullptr, (double *)ws);
+    if (ctx->fx_F > 0)
+        MM_LAUNCH(ctx, "ba_residual_fixed_kernel", ba_residual_fixed_kernel, dim3(blocks), dim3(256), 0, *pb, cams, ctx->fx_cams, pts, ctab,
+                  (double *)nullptr, (double *)ws);
+    else
+        MM_LAUNCH(ctx, "ba_residual_kernel", ba_residual_kernel, dim3(blocks), dim3(256), 0, *pb, cams, pts, ctab, (double *)nullptr, (double *)ws);
     MM_LAUNCH(ctx, "sum_partials_kernel", sum_partials_publish_kernel, dim3(1), dim3(256), 0, (const double *)ws, blocks, board,
               cost_slot, count, (MMHostBoard *)host_board, seq);
     return MM_OK;

@@ -53,6 +53,12 @@ struct mm_ctx {
     int cam_tab_cap = 0, cam_tab_F = 0;
     const double *cam_tab_for = nullptr;
     bool cam_tab_hold = false;
+    // fixed cameras of the *_fixed entry points, set for the duration of one such call (mm_fixed_scope): observations with
+    // fi in [F, F + fx_F) read camera fi - F from fx_cams; the coefficient table then has F + fx_F rows, the fixed ones
+    // filled once per call (fx_tab_ok) -- they do not change during a solve
+    const double *fx_cams = nullptr;
+    int fx_F = 0;
+    bool fx_tab_ok = false;
     // pinned, device-visible host mailbox of mm_ba_trf (trf.hip): the trial-step scalars are written into it by a kernel
     // and the host spins on its sequence number instead of paying a copy + stream synchronisation per trial step
     void *host_board = nullptr;
@@ -74,6 +80,21 @@ struct mm_stream_swap {
     hipStream_t saved;
     mm_stream_swap(mm_ctx *ctx, hipStream_t s) : c(ctx), saved(ctx->stream) { ctx->stream = s; }
     ~mm_stream_swap() { c->stream = saved; }
+};
+
+// the fixed cameras of one *_fixed call (mm_ba_fixed, include/meatmodeler.h) are visible to the sweeps of the enclosed scope
+struct mm_fixed_scope {
+    mm_ctx *c;
+    mm_fixed_scope(mm_ctx *ctx, const mm_ba_fixed *fx) : c(ctx) {
+        ctx->fx_cams = fx->cams;
+        ctx->fx_F = fx->F_fixed;
+        ctx->fx_tab_ok = false;
+    }
+    ~mm_fixed_scope() {
+        c->fx_cams = nullptr;
+        c->fx_F = 0;
+        c->fx_tab_ok = false;
+    }
 };
 
 // ba.hip: per-camera rotation coefficients shared by the sweeps (see there)

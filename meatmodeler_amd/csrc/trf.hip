@@ -649,6 +649,26 @@ extern "C" int mm_ba_trf_dist(mm_ctx *ctx, const mm_ba_problem *pb, double *cams
     return trf_run(ctx, pb, cams, pts, prm, rep, log, log_cap, ws, ws_bytes, dist);
 }
 
+// ---- fixed cameras (the anchored sliding window; hook at reference processor.py:395-408) ----------
+// The loop above, unchanged, with the context's fixed-camera scope around it: the sweeps that read a camera per observation
+// take their FIXED twins (ba.hip), the coefficient table gains the fixed rows once per solve, and everything that works on
+// the unknowns -- pair list, reduced system, factorisation, vector passes, norms, termination -- sees the 6F + 3P free
+// parameters only.  No launch per trust-region iteration is added.
+extern "C" size_t mm_ba_trf_fixed_workspace_bytes(const mm_ba_problem *pb, const mm_ba_fixed *fx) {
+    (void)fx;      // (the fixed rows of the coefficient table live in the context)
+    return mm_ba_trf_workspace_bytes(pb);
+}
+
+extern "C" int mm_ba_trf_fixed(mm_ctx *ctx, const mm_ba_problem *pb, const mm_ba_fixed *fx, double *cams, double *pts,
+                               const mm_trf_params *prm, mm_trf_report *rep, mm_trf_row *log, int log_cap, void *ws, size_t ws_bytes) {
+    if (!ctx) return MM_ERR_ARG;
+    if (!fx || fx->F_fixed == 0) return trf_run(ctx, pb, cams, pts, prm, rep, log, log_cap, ws, ws_bytes, nullptr);
+    if (fx->F_fixed < 0 || !fx->cams) return mm_fail(ctx, MM_ERR_ARG, "mm_ba_trf_fixed: bad fixed-camera descriptor");
+    // (the general Schur kernel walks every observation of a point, fixed cameras included: the pair list keeps to free ones)
+    if (pb && pb->O > 0 && pb->n_chunks <= 0) return mm_fail(ctx, MM_ERR_ARG, "mm_ba_trf_fixed: the problem needs its co-observation pair list");
+    mm_fixed_scope scope(ctx, fx);
+    return trf_run(ctx, pb, cams, pts, prm, rep, log, log_cap, ws, ws_bytes, nullptr);
+}
 
 // ---- several independent problems in lock-step: mm_ba_trf_batched -------------------------------------------------------------
 // The sliding-window adjustment (hook processor.py:395-408) solves dozens of small problems -- 50

@@ -222,10 +222,15 @@ def ba_build_index(F, P, fi, pi):
 class BADevice:
     """Device-resident BA problem: observation arrays, CSR indices and the mm_ba_problem descriptor."""
 
-    def __init__(self, K, fi, pi, obs, F, P, device, ctx=None, pairs=True, max_band_span=192):
+    def __init__(self, K, fi, pi, obs, F, P, device, ctx=None, pairs=True, max_band_span=192, fixed_cams=None):
         """fi, pi: int [O] (numpy or device tensors), obs [O,2] f64 (numpy or device tensor).  All index structures
         (CSR by point, CSR by camera, co-observation pair list and its chunk table) are built on the device: torch
-        provides the sorts / scans (index plumbing), two HIP kernels enumerate the pairs."""
+        provides the sorts / scans (index plumbing), two HIP kernels enumerate the pairs.
+
+        fixed_cams: [F_fixed, 6] f64 device tensor of cameras that are observed but not optimised (mm_ba_fixed):
+        fi in [F, F + F_fixed) is fixed camera fi - F.  The CSR by camera and the pair list then cover the F free
+        cameras only, and residual / normal_eq / trf_solve run the *_fixed entry points; the other sweeps have no
+        fixed-camera form and raise NotImplementedError."""
         self.ctx = ctx or default_context()
         self._mdot = None
         dev = device
@@ -242,11 +247,20 @@ class BADevice:
         self.fi = to_dev(fi, torch.int32).reshape(-1)
         self.pi = to_dev(pi, torch.int32).reshape(-1)
         self.obs = to_dev(obs, torch.float64).reshape(-1, 2)
+        self.fixed_cams, self.F_fixed, self.fx = None, 0, None
+        if fixed_cams is not None:
+            assert (isinstance(fixed_cams, torch.Tensor) and fixed_cams.dtype == torch.float64 and fixed_cams.device == dev
+                    and fixed_cams.dim() == 2 and fixed_cams.shape[1] == 6), "fixed_cams: [F_fixed, 6] f64 device tensor"
+            self.F_fixed = int(fixed_cams.shape[0])
+            if self.F_fixed:
+                self.fixed_cams = fixed_cams.contiguous()
+                self.fx = _lib.BAFixed(self.F_fixed, 0, ptr(self.fixed_cams))
+        F_all = F + self.F_fixed
         i64 = dict(dtype=torch.int64, device=dev)
         if O:
             lim = torch.stack([self.fi.min(), self.fi.max(), self.pi.min(), self.pi.max(),
                                (self.pi[1:] >= self.pi[:-1]).all().to(torch.int32)]).tolist()
-            if lim[0] < 0 or lim[1] >= F or lim[2] < 0 or lim[3] >= P:
+            if lim[0] < 0 or lim[1] >= F_all or lim[2] < 0 or lim[3] >= P:
                 raise ValueError("frame / point index out of range")
             point_major = bool(lim[4])
         else:
@@ -258,7 +272,12 @@ class BADevice:
             self.pt_obs = torch.sort(self.pi, stable=True)[1].to(torch.int32)
         self.pt_ptr = torch.zeros(P + 1, dtype=torch.int32, device=dev)
         self.cam_ptr = torch.zeros(F + 1, dtype=torch.int32, device=dev)
-        if O:
+        if O and self.F_fixed:      # (the observations of fixed cameras sort behind those of the free ones)
+            self.pt_ptr[1:] = torch.cumsum(torch.bincount(self.pi, minlength=P), 0).to(torch.int32)
+            self.cam_ptr[1:] = torch.cumsum(torch.bincount(self.fi, minlength=F_all)[:F], 0).to(torch.int32)
+            n_free = int(self.cam_ptr[-1].item())
+            self.cam_obs = torch.sort(self.fi, stable=True)[1][:n_free].to(torch.int32).contiguous()
+        elif O:
             self.pt_ptr[1:] = torch.cumsum(torch.bincount(self.pi, minlength=P), 0).to(torch.int32)
             self.cam_ptr[1:] = torch.cumsum(torch.bincount(self.fi, minlength=F), 0).to(torch.int32)
             self.cam_obs = torch.sort(self.fi, stable=True)[1].to(torch.int32)      # stable: observation order kept
@@ -278,12 +297,27 @@ class BADevice:
                             ptr(self.pt_ptr), ptr(self.pt_obs), ptr(self.cam_ptr), ptr(self.cam_obs),
                             0, 0, 0, None, None, 0, None, None, None, None, None, None)
         self.n_pairs = 0
-        if O:
+        # the pair list and cam_span are over the free cameras: with fixed ones the two pair kernels see the free
+        # observations only (a problem of its own, same order), and the pairs are mapped back to observation indices
+        pair_pb, free_idx, O_pairs = self.pb, None, O
+        if O and self.F_fixed:
+            free_idx = torch.nonzero(self.fi < F).reshape(-1)
+            O_pairs = int(free_idx.numel())
+            fi_f, pi_f = self.fi[free_idx].contiguous(), self.pi[free_idx].contiguous()
+            pt_ptr_f = torch.zeros(P + 1, dtype=torch.int32, device=dev)
+            pt_ptr_f[1:] = torch.cumsum(torch.bincount(pi_f, minlength=P), 0).to(torch.int32)
+            pt_obs_f = (torch.arange(O_pairs, dtype=torch.int32, device=dev) if point_major
+                        else torch.sort(pi_f, stable=True)[1].to(torch.int32))
+            self._pair_src = (fi_f, pi_f, pt_ptr_f, pt_obs_f)      # (kept alive while the descriptor points at them)
+            pair_pb = BAProblem(F, P, O_pairs, ptr(self.K), ptr(fi_f), ptr(pi_f), ptr(self.obs), ptr(pt_ptr_f),
+                                ptr(pt_obs_f), ptr(self.cam_ptr), ptr(self.cam_obs),
+                                0, 0, 0, None, None, 0, None, None, None, None, None, None)
+        if O_pairs:
             # widest camera span of any point: cameras further apart never share a point, so the reduced camera system
             # is block banded with this half-width (tracks from consecutive-keyframe matching span a few frames only)
-            cnt = torch.empty(O, dtype=torch.int32, device=dev)
+            cnt = torch.empty(O_pairs, dtype=torch.int32, device=dev)
             span_t = torch.zeros(1, dtype=torch.int32, device=dev)
-            self.ctx.check(lib.mm_ba_pairs_count(self.ctx.h, C.byref(self.pb), ptr(cnt), ptr(span_t)),
+            self.ctx.check(lib.mm_ba_pairs_count(self.ctx.h, C.byref(pair_pb), ptr(cnt), ptr(span_t)),
                            "mm_ba_pairs_count")
             offs = torch.cumsum(cnt, 0, dtype=torch.int64)
             span, n = torch.stack([span_t[0].to(torch.int64), offs[-1]]).tolist()
@@ -296,10 +330,13 @@ class BADevice:
                 po = torch.empty(n, dtype=torch.int32, device=dev)
                 po2 = torch.empty(n, dtype=torch.int32, device=dev)
                 offs_ex = (offs - cnt).contiguous()
-                self.ctx.check(lib.mm_ba_pairs_emit(self.ctx.h, C.byref(self.pb), ptr(offs_ex), self.cam_span, ptr(key),
+                self.ctx.check(lib.mm_ba_pairs_emit(self.ctx.h, C.byref(pair_pb), ptr(offs_ex), self.cam_span, ptr(key),
                                                     ptr(po), ptr(po2)), "mm_ba_pairs_emit")
                 key_s, perm = torch.sort(key, stable=True)          # fixed order inside every segment
                 self.pair_o, self.pair_o2 = po[perm].contiguous(), po2[perm].contiguous()
+                if free_idx is not None:
+                    self.pair_o = free_idx[self.pair_o.long()].to(torch.int32).contiguous()
+                    self.pair_o2 = free_idx[self.pair_o2.long()].to(torch.int32).contiguous()
                 seg_ids, counts = torch.unique_consecutive(key_s, return_counts=True)
                 seg_hi = torch.cumsum(counts, 0)
                 seg_lo = seg_hi - counts
@@ -346,11 +383,21 @@ class BADevice:
         sum (a 1-element f64 device tensor, e.g. a slot of the trust-region driver's scalar board)."""
         res = torch.empty((self.O, 2), dtype=torch.float64, device=self.device) if want_res else None
         cost2 = cost_out if cost_out is not None else torch.empty(1, dtype=torch.float64, device=self.device)
+        if self.fx is not None:
+            self.ctx.check(lib.mm_ba_residual_fixed(self.ctx.h, C.byref(self.pb), C.byref(self.fx), ptr(cams), ptr(pts),
+                                                    ptr(res), ptr(cost2), ptr(self._ws), self._ws.numel()),
+                           "mm_ba_residual_fixed")
+            return cost2, res
         self.ctx.check(lib.mm_ba_residual(self.ctx.h, C.byref(self.pb), ptr(cams), ptr(pts), ptr(res), ptr(cost2),
                                           ptr(self._ws), self._ws.numel()), "mm_ba_residual")
         return cost2, res
 
+    def _no_fixed(self, what):
+        if self.fx is not None:
+            raise NotImplementedError(f"BADevice.{what}: no fixed-camera form (residual, normal_eq and trf_solve have one)")
+
     def jacobian(self, cams, pts):
+        self._no_fixed("jacobian")
         Jc = torch.empty((self.O, 2, 6), dtype=torch.float64, device=self.device)
         Jp = torch.empty((self.O, 2, 3), dtype=torch.float64, device=self.device)
         self.ctx.check(lib.mm_ba_jacobian(self.ctx.h, C.byref(self.pb), ptr(cams), ptr(pts), ptr(Jc), ptr(Jp)),
@@ -370,11 +417,16 @@ class BADevice:
             gc = torch.empty((self.F, 6), dtype=torch.float64, device=d) if want_cams else None
             Cb = torch.empty((self.P, 6), dtype=torch.float64, device=d) if want_pts else None
             gp = torch.empty((self.P, 3), dtype=torch.float64, device=d) if want_pts else None
+        if self.fx is not None:
+            self.ctx.check(lib.mm_ba_normal_eq_fixed(self.ctx.h, C.byref(self.pb), C.byref(self.fx), ptr(cams), ptr(pts),
+                                                     ptr(B), ptr(gc), ptr(Cb), ptr(gp)), "mm_ba_normal_eq_fixed")
+            return B, gc, Cb, gp
         self.ctx.check(lib.mm_ba_normal_eq(self.ctx.h, C.byref(self.pb), ptr(cams), ptr(pts), ptr(B), ptr(gc), ptr(Cb),
                                            ptr(gp)), "mm_ba_normal_eq")
         return B, gc, Cb, gp
 
     def jvp(self, cams, pts, wc, wp):
+        self._no_fixed("jvp")
         out = torch.empty((self.O, 2), dtype=torch.float64, device=self.device)
         self.ctx.check(lib.mm_ba_jvp(self.ctx.h, C.byref(self.pb), ptr(cams), ptr(pts), ptr(wc), ptr(wp), ptr(out)),
                        "mm_ba_jvp")
@@ -383,6 +435,7 @@ class BADevice:
     def jvp_dots(self, cams, pts, wc, wp, other=None):
         """jvp with its inner products fused in (mm_ba_jvp_dots): -> (out [O,2], rows [2,3]) with rows[0] = <out, other>
         (other None: <out, out>) and rows[1] = <out, out>, each as {0, total, total}."""
+        self._no_fixed("jvp_dots")
         out = torch.empty((self.O, 2), dtype=torch.float64, device=self.device)
         rows = torch.empty((2, 3), dtype=torch.float64, device=self.device)
         if getattr(self, "_jvp_ws", None) is None:
@@ -395,6 +448,7 @@ class BADevice:
     def schur(self, cams, pts, Bd, Cd, gc, gp):
         """Reduced camera system.  With a pair list (banded problems) only the LOWER block band of S is produced
         (deterministically) and the rest of S is zero; otherwise all of S is filled."""
+        self._no_fixed("schur")
         n = 6 * self.F
         if self._S is None:
             self._alloc_S(n)
@@ -424,6 +478,7 @@ class BADevice:
     def schur_solve(self, cams, pts, Bd, Cd, gc, gp, half_bandwidth):
         """Reduced camera system built and solved in one overlapped call (mm_ba_schur_solve): -> (info, dc [6F], Cinv).
         dc is the solution of S dc = v (the camera part of the damped Gauss-Newton step)."""
+        self._no_fixed("schur_solve")
         n = 6 * self.F
         if self._S is None:
             self._alloc_S(n)
@@ -512,16 +567,23 @@ class BADevice:
         for t in (cams, pts):
             assert t.dtype == torch.float64 and t.is_contiguous() and t.device == self.device
         if getattr(self, "_trf_ws", None) is None:
-            self._trf_ws = torch.empty(lib.mm_ba_trf_workspace_bytes(C.byref(self.pb)), dtype=torch.uint8,
-                                       device=self.device)
+            nb = (lib.mm_ba_trf_fixed_workspace_bytes(C.byref(self.pb), C.byref(self.fx)) if self.fx is not None
+                  else lib.mm_ba_trf_workspace_bytes(C.byref(self.pb)))
+            self._trf_ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
         prm = _lib.TrfParams(ftol, xtol, gtol, min_damping, int(max_nfev) if max_nfev else 0)
         rep = _lib.TrfReport()
         log = (_lib.TrfRow * max(log_cap, 1))()
-        rc = lib.mm_ba_trf(self.ctx.h, C.byref(self.pb), ptr(cams), ptr(pts), C.byref(prm), C.byref(rep), log,
-                           int(log_cap), ptr(self._trf_ws), self._trf_ws.numel())
+        if self.fx is not None:      # (fixed cameras: mm_ba_trf_fixed, the same loop over the free parameters)
+            name = "mm_ba_trf_fixed"
+            rc = lib.mm_ba_trf_fixed(self.ctx.h, C.byref(self.pb), C.byref(self.fx), ptr(cams), ptr(pts), C.byref(prm),
+                                     C.byref(rep), log, int(log_cap), ptr(self._trf_ws), self._trf_ws.numel())
+        else:
+            name = "mm_ba_trf"
+            rc = lib.mm_ba_trf(self.ctx.h, C.byref(self.pb), ptr(cams), ptr(pts), C.byref(prm), C.byref(rep), log,
+                               int(log_cap), ptr(self._trf_ws), self._trf_ws.numel())
         if rc and rep.status == -2:
             raise ValueError("Residuals are not finite in the initial point.")      # (as scipy's least_squares does)
-        self.ctx.check(rc, "mm_ba_trf")
+        self.ctx.check(rc, name)
         rows = [(r.iteration, r.nfev, r.cost, r.reduction, r.step_norm, r.optimality)
                 for r in log[:min(rep.log_rows, log_cap)]]
         return rep, rows
@@ -534,6 +596,7 @@ class BADevice:
         An exception raised by `allreduce` -- or any error on this rank -- is FATAL FOR THE WHOLE GROUP: this rank leaves
         the loop while its peers wait inside their next collective (include/meatmodeler.h); it is re-raised here and the
         caller is expected to tear the process group down (its timeout bounds the peers' wait otherwise)."""
+        self._no_fixed("trf_solve_dist")
         for t in (cams, pts):
             assert t.dtype == torch.float64 and t.is_contiguous() and t.device == self.device
         need = lib.mm_ba_trf_dist_workspace_bytes(C.byref(self.pb), int(half_bandwidth))
@@ -570,6 +633,7 @@ class BADevice:
         return rep, rows
 
     def backsub(self, cams, pts, Cinv, gp, dc):
+        self._no_fixed("backsub")
         dp = torch.empty((self.P, 3), dtype=torch.float64, device=self.device)
         if getattr(self, "_backsub_ws", None) is None:
             self._backsub_ws = torch.empty(lib.mm_ba_backsub_workspace_bytes(C.byref(self.pb)), dtype=torch.uint8,

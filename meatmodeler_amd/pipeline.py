@@ -133,8 +133,20 @@ class ClipPipeline:
             return inside
         return inside & (last_frame <= hi - 2)
 
+    @staticmethod
+    def window_selection_anchored(first_frame, last_frame, lo, hi, n_frames):
+        """Tracks adjusted by the ANCHORED window [lo, hi): finished by keyframe hi - 1 or the clip's end (as in
+        `window_selection`) and last observed at or after keyframe lo -- a track may begin before the window (a boundary
+        track); its older observations then pull against the fixed cameras.  For lo = 0 this is `window_selection`.
+        (first_frame is not needed; it is taken for the same call shape.)  Works on numpy arrays and on tensors alike."""
+        del first_frame
+        sel = (last_frame >= lo) & (last_frame < hi)
+        if hi >= n_frames:
+            return sel
+        return sel & (last_frame <= hi - 2)
+
     def adjust_windows(self, out, K, extrinsics, window=50, stride=25, ftol=1e-4, verbose=0, timers=None, dist=None,
-                       order="sequential", streams=1, batched=False, max_nfev=None):
+                       order="sequential", streams=1, batched=False, max_nfev=None, boundary="inside"):
         """Incremental bundle adjustment over a sliding window of keyframes: the reference keeps this step as a
         commented hook (processor.py:395-408: after a keyframe whose tracks were popped, `managePoints(popped_tracks)`
         + `adjustPoints` over everything so far); bounding it to the last `window` keyframes is what makes the
@@ -166,13 +178,30 @@ class ClipPipeline:
         them, so a pass costs about as many evaluations as its slowest window needs instead of the sum over its windows.
         Bit-identical to solving the windows one at a time.
 
+        boundary = "inside" (default): the window adjusts the tracks that lie entirely inside it, with all its cameras free
+        (above).  boundary = "anchored": the local bundle adjustment of SLAM / incremental SfM that SURVEY.md 8(f)-2
+        specifies.  The points are the finished tracks (same rule) last observed at or after lo
+        (`window_selection_anchored`), so a track that crosses the window's left edge is adjusted with ALL its
+        observations; the cameras lo .. hi - 1 are free, the cameras 0 .. lo - 1 -- as earlier windows left them -- are
+        fixed (mm_ba_trf_fixed: observed, not optimised, never written), so the gauge stays pinned to the settled
+        trajectory instead of re-floating in every window.  The first window (lo = 0) is the same as with "inside".  Each
+        window's stats gain `fixed_cameras`, the number of distinct fixed cameras its tracks observe.  Sequential, one rank,
+        one stream only: windows solved side by side would read each other's free cameras as fixed (ValueError otherwise).
+
         `out` is the result of `run(..., ba=False)`.  -> dict(cams [F,6] device, points [T,3] device, windows=[...])."""
         d = self.device
         world = dist.get_world_size() if dist is not None else 1
         rank = dist.get_rank() if dist is not None else 0
-        allreduce = parallel.AllReduce() if world > 1 else None
         if order not in ("sequential", "wavefront"):
             raise ValueError("order must be 'sequential' or 'wavefront'")
+        if boundary not in ("inside", "anchored"):
+            raise ValueError("boundary must be 'inside' or 'anchored'")
+        if boundary == "anchored":
+            if order != "sequential" or batched or int(streams) > 1 or dist is not None:
+                raise ValueError("boundary='anchored' needs order='sequential' on one rank and one stream (no batched): "
+                                 "its windows read the cameras earlier windows settled")
+            return self._adjust_windows_anchored(out, K, extrinsics, window, stride, ftol, verbose, timers, max_nfev)
+        allreduce = parallel.AllReduce() if world > 1 else None
         if order == "wavefront":
             return self._adjust_windows_wavefront(out, K, extrinsics, window, stride, ftol, verbose, timers, allreduce,
                                                   world, rank, streams, batched, max_nfev)
@@ -228,6 +257,54 @@ class ClipPipeline:
             else:
                 pts[sel] = res.pts
             stats.append(dict(lo=lo, hi=hi, points=P_all, observations=O, nfev=res.nfev, cost=res.cost,
+                              status=res.status))
+        self.ctx.sync()
+        if timers is not None:
+            timers["ba_windows"] = timers.get("ba_windows", 0.0) + (time.perf_counter() - t0) * 1e3
+        return dict(cams=cams, points=pts, windows=stats)
+
+    def _adjust_windows_anchored(self, out, K, extrinsics, window, stride, ftol, verbose, timers, max_nfev):
+        """adjust_windows(boundary="anchored"): free cameras lo .. hi - 1 (indices f - lo), fixed cameras 0 .. lo - 1
+        (indices W + f, the current values), the finished tracks last observed at or after lo."""
+        d = self.device
+        F = int(np.asarray(extrinsics).shape[0])
+        tp, of_, ok = out["track_ptr_dev"], out["obs_frame_dev"], out["obs_kp_dev"]
+        xy = out["xy_dev"]
+        T = tp.shape[0] - 1
+        with np.errstate(all="ignore"):
+            cams = torch.as_tensor(frameParameters(np.asarray(extrinsics, float)[:, :3, :]).reshape(F, 6)).to(d)
+        pts = out["points0"].clone()
+        stats = []
+        if T == 0:
+            return dict(cams=cams, points=pts, windows=stats)
+        tp64 = tp.long()
+        first_f, last_f = of_[tp64[:-1]], of_[tp64[1:] - 1]
+        window = max(2, min(int(window), F))
+        his = list(range(window, F, max(1, int(stride)))) + [F]
+        t0 = time.perf_counter()
+        for hi in his:
+            lo = max(0, hi - window)
+            W = hi - lo
+            sel = torch.nonzero(self.window_selection_anchored(first_f, last_f, lo, hi, F)).reshape(-1)
+            P = int(sel.numel())
+            if P == 0:
+                continue
+            # managePoints order; frame indices come back as obs_frame - lo: the cameras before the window (negative)
+            # become fixed camera W + f
+            coords, fi, pi = ops.flatten_tracks(tp, of_, ok, xy, sel=sel, frame_offset=lo, ctx=self.ctx)
+            O = int(fi.numel())
+            n_fixed = 0
+            if lo > 0:
+                fi = torch.where(fi < 0, fi + (lo + W), fi).contiguous()
+                n_fixed = int(torch.unique(fi[fi >= W]).numel())
+                pb = ops.BADevice(K, fi, pi, coords, W, P, d, self.ctx, fixed_cams=cams[:lo].clone())
+            else:
+                pb = ops.BADevice(K, fi, pi, coords, W, P, d, self.ctx)
+            res = SchurTRF(pb).solve(cams[lo:hi].contiguous(), pts[sel].contiguous(), ftol=ftol, max_nfev=max_nfev,
+                                     verbose=verbose)
+            cams[lo:hi] = res.cams
+            pts[sel] = res.pts
+            stats.append(dict(lo=lo, hi=hi, points=P, observations=O, fixed_cameras=n_fixed, nfev=res.nfev, cost=res.cost,
                               status=res.status))
         self.ctx.sync()
         if timers is not None:
