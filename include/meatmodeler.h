@@ -430,7 +430,10 @@ size_t mm_chol_workspace_bytes(int n);
  * unspecified).  both_triangles != 0: both triangles of the band hold A on input; 0: only the lower one (the band of the
  * upper triangle is then filled from it first).  This freedom lets a narrow band be eliminated from BOTH ends at once
  * (chain of ~(nblk + bwb) / 2 dependent block columns instead of nblk): what the bundle adjustment calls per
- * trust-region iteration.  MM_CHOL_TWISTED=0 in the environment forces the one-ended elimination. */
+ * trust-region iteration.  MM_CHOL_TWISTED=0 in the environment forces the one-ended elimination.
+ * info: as for mm_chol_solve while the elimination is one-ended.  The two-ended elimination runs in another order than
+ * LAPACK's, and on the reversed side a failure spreads towards SMALLER columns: a matrix that is not positive definite (or
+ * holds a NaN) then gives 1 <= info <= n, some column at which a pivot was not positive, not necessarily the first. */
 int mm_chol_solve_sym(mm_ctx *ctx, double *A /*dev*/, int n, double *b /*dev [n]*/, int half_bandwidth, int both_triangles,
                       int32_t *info /*dev*/, void *ws, size_t ws_bytes);
 int mm_chol_solve(mm_ctx *ctx, double *A /*dev*/, int n, double *b /*dev*/, int nrhs, int half_bandwidth,

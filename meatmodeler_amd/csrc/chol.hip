@@ -2288,6 +2288,42 @@ __global__ __launch_bounds__(256) void fwd_step_kernel(const double *__restrict_
     if (row < row_end && part == 0) b[row] -= s;
 }
 
+// forward substitution of block row r for a right-hand side that did NOT ride along with the single-launch
+// factorisation (the second and later ones), the way that kernel does it for the one that did -- left-looking, the same
+// products summed in the same order (tile_matvec: 4 lanes per row, 16 terms each; offsets 1, 2, .. bwb), so that a
+// right-hand side gets the same bits wherever it stands in b:
+//   y_r = Linv_rr (b_r - sum_{d = 1..min(bwb, r)} L_{r,r-d} y_{r-d});  b is left alone.  ONE workgroup.
+__global__ __launch_bounds__(256) void fwd_row_kernel(const double *__restrict__ A, const double *__restrict__ Linv,
+                                                      const double *__restrict__ b, double *__restrict__ y, int n, int r,
+                                                      int bwb) {
+    __shared__ double rhs[NB], ys[NB];
+    const int row = threadIdx.x >> 2, part = threadIdx.x & 3;
+    const int r0 = r * NB;
+    if (threadIdx.x < NB) rhs[threadIdx.x] = r0 + threadIdx.x < n ? b[r0 + threadIdx.x] : 0.0;
+    for (int d = 1; d <= bwb && d <= r; ++d) {
+        const int c0 = (r - d) * NB;      // (a whole block: c0 + 63 < r0 < n)
+        __syncthreads();
+        if (threadIdx.x < NB) ys[threadIdx.x] = y[c0 + threadIdx.x];
+        __syncthreads();
+        double s = 0.0;
+        if (r0 + row < n) {
+            const double *Lr = A + (size_t)(r0 + row) * n + c0 + part * 16;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) s += Lr[q] * ys[part * 16 + q];
+        }
+        s += __shfl_down(s, 2, 4);
+        s += __shfl_down(s, 1, 4);
+        if (part == 0) rhs[row] -= s;
+    }
+    __syncthreads();
+    double s = 0.0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) s += Linv[row * NB + part * 16 + q] * rhs[part * 16 + q];
+    s += __shfl_down(s, 2, 4);
+    s += __shfl_down(s, 1, 4);
+    if (part == 0 && r0 + row < n) y[r0 + row] = s;
+}
+
 // backward step k: x_k = Linv_kk^T y_k (redundantly); workgroup 0 publishes x_k into `x`; columns left of the block
 // (inside the band) get y_j -= L_kj^T x_k, one column per thread.
 __global__ __launch_bounds__(256) void bwd_step_kernel(const double *__restrict__ A, const double *__restrict__ Linv,
@@ -2537,6 +2573,11 @@ int mm_chol_solve_gated(mm_ctx *ctx, double *A, int n, double *b, int nrhs, int 
         double *bc = b + (size_t)c * n;
         for (int k = 0; k < nblk && !(c == 0 && fwd_done); ++k) {  // L y = b
             const int k0 = k * NB;
+            if (fused && c > 0) {      // the first right-hand side's bits for every other one (see fwd_row_kernel)
+                MM_LAUNCH(ctx, "fwd_row_kernel", fwd_row_kernel, dim3(1), dim3(256), 0, (const double *)A,
+                          (const double *)(Linv + (size_t)k * NB * NB), (const double *)bc, ytmp, n, k, bwb);
+                continue;
+            }
             long re = (long)k0 + NB + (long)bwb * NB;
             const int row_end = re > n ? n : (int)re;
             const int below = row_end - (k0 + NB);
