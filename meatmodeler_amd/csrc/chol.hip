@@ -655,13 +655,8 @@ __global__ __launch_bounds__(256) void chol_update_kernel(double *__restrict__ A
 // identity rows -- the same trick as the partial last block of the one-ended scheme.
 constexpr long SPIN_LIMIT = 1L << 23;
 constexpr int FUSED_MAX_BWB = 15;  // 16 + 105 = 121 resident workgroups per side at most
+constexpr int FUSED_MAX_W = FUSED_MAX_BWB + 1;      // offsets 0 .. bwb of a block row
 constexpr size_t FUSED_LDS_BYTES = (size_t)(4 * NB * LDT + 4 * 16 * 17 + 3 * NB) * sizeof(double);   // 146 KB of the CU's 160
-
-struct TwGeom {
-    int n, nblk, bwb;
-    int a, m, b;  // block columns eliminated by side 0 first (T), last (M), and by side 1 (Bt); b == 0: one-ended
-    int pad;      // 64 nblk - n virtual identity rows behind the matrix
-};
 
 // Element (row, col) of a 64 x 64 tile in either coordinate system: p + row sr + col sc, valid inside [r_lo, r_hi) x
 // [c_lo, c_hi) (outside: structural zero / identity padding, never dereferenced).
@@ -674,7 +669,7 @@ struct TileRef {
     __device__ __forceinline__ bool cv(int col) const { return col >= c_lo && col < c_hi; }
 };
 
-__device__ __forceinline__ TileRef tile_ref(double *A, const TwGeom &g, int side, int rb, int cb) {
+__device__ __forceinline__ TileRef tile_ref(double *A, const mm_chol_geom &g, int side, int rb, int cb) {
     TileRef t;
     const long ld = g.n;
     if (side == 0) {
@@ -699,7 +694,7 @@ __device__ __forceinline__ TileRef tile_ref(double *A, const TwGeom &g, int side
 }
 
 // position of element i of block `blk` of a vector (right-hand side, y, x) in natural order; valid iff 0 <= . < n
-__device__ __forceinline__ long vec_index(const TwGeom &g, int side, int blk, int i) {
+__device__ __forceinline__ long vec_index(const mm_chol_geom &g, int side, int blk, int i) {
     return side == 0 ? (long)NB * blk + i : (long)NB * g.nblk - 1 - (long)NB * blk - i;
 }
 
@@ -707,17 +702,11 @@ __device__ __forceinline__ long vec_index(const TwGeom &g, int side, int blk, in
 // and read with agent-scope relaxed atomics (write-through stores, cache-bypassing loads: `global_* ... sc1`), the
 // writer drains its stores (s_waitcnt) before raising the flag: no cache maintenance.  (Plain accesses bracketed by
 // agent-scope release / acquire fences measured +4 % per factorisation.)
-template <int MODE>
 __device__ __forceinline__ double ld_shared(const double *p) {
-    if (MODE == 2) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return *p;
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-template <int MODE>
 __device__ __forceinline__ void st_shared(double *p, double v) {
-    if (MODE == 2)
-        __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else
-        *p = v;
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // Two doubles in ONE 16-byte write-through store (p 16-byte aligned).  An 8-byte sc1 store is one fabric write per LANE:
@@ -730,14 +719,13 @@ __device__ __forceinline__ void st_shared16(double *p, double v0, double v1) {
 
 // 64 x 64 tile of a published block -> LDS (zero outside the valid range); 16 coalesced 8-byte loads per thread, all
 // in flight
-template <int MODE>
 __device__ __forceinline__ void load_tile_shared(double (*T)[LDT], const TileRef &t) {
     double v[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
         const int e = thread_id() + 256 * q;
         const int r = e / NB, c = e % NB;
-        v[q] = (t.rv(r) && t.cv(c)) ? ld_shared<MODE>(t.at(r, c)) : 0.0;
+        v[q] = (t.rv(r) && t.cv(c)) ? ld_shared(t.at(r, c)) : 0.0;
     }
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
@@ -762,14 +750,13 @@ __device__ __forceinline__ void store_tile_shared16(const double (*T)[LDT], cons
 }
 
 // the same in two halves: request into registers (several tiles may be in flight), commit later (tile_commit)
-template <int MODE>
 __device__ __forceinline__ void tile_prefetch_shared(double (&pre)[16], const TileRef &t) {
     const int tid = thread_id();
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
         const int e = tid + 256 * q;
         const int r = e / NB, c = e % NB;
-        pre[q] = (t.rv(r) && t.cv(c)) ? ld_shared<MODE>(t.at(r, c)) : 0.0;
+        pre[q] = (t.rv(r) && t.cv(c)) ? ld_shared(t.at(r, c)) : 0.0;
     }
 }
 
@@ -792,25 +779,17 @@ __device__ __forceinline__ bool spin_until_set(const int32_t *flag, int32_t *abo
 }
 
 // all 256 threads; returns false (uniformly) when the grid is being abandoned
-template <int MODE>
 __device__ __forceinline__ bool wg_wait(const int32_t *f1, const int32_t *f2, int32_t *abort_flag, int *s_ok) {
     if (threadIdx.x == 0) *s_ok = spin_until_set(f1, abort_flag) && (f2 == nullptr || spin_until_set(f2, abort_flag));
     __syncthreads();
     const bool ok = *s_ok != 0;
     __syncthreads();
-    if (MODE == 1)
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // drop stale cache lines before reading the published block
-    else
-        asm volatile("" ::: "memory");
+    asm volatile("" ::: "memory");      // (the published block is read with cache-bypassing loads: no fence)
     return ok;
 }
 
-template <int MODE>
 __device__ __forceinline__ void wg_publish(int32_t *flag) {
-    if (MODE == 1)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    else
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // this wave's write-through stores have landed
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // this wave's write-through stores have landed
     __syncthreads();
     if (threadIdx.x == 0) __hip_atomic_store(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -855,23 +834,6 @@ __device__ __forceinline__ double tile_matvec(const double (*Tm)[LD], const doub
 // counters itself and fetches the pieces it needs (all four waves store identical values into Bs / Xd).  When the last
 // stage arrives, four MFMAs and a 2 KB load are all that is left; the owner of the diagonal block (r, r) also adds
 // P_k P_k^T to its accumulator stage by stage, so the rank-64 update is off the chain as well.
-template <int MODE>
-__device__ __forceinline__ bool wave_wait_ge(const int32_t *flag, int want, int32_t *abort_flag) {
-    for (long it = 0; it < SPIN_LIMIT; ++it) {
-        if (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= want) {
-            if (MODE == 1)
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            else
-                asm volatile("" ::: "memory");
-            return true;
-        }
-        if ((it & 255) == 255 && __hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return false;
-        __builtin_amdgcn_s_sleep(1);
-    }
-    __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return false;
-}
-
 // s = sum_{k in [K0, K1)} P_k L_jk^T for this wave's 16 rows, subtracted from block j of As
 template <int J, int K0, int K1>
 __device__ __forceinline__ void trsm_update(double (*As)[LDT], const double (*Bs)[LDT], int row0, int lr, int lk) {
@@ -892,7 +854,7 @@ __device__ __forceinline__ void trsm_update(double (*As)[LDT], const double (*Bs
 }
 
 // P_j = W_j X_jj^T: block j of As in place, and to global memory
-template <int MODE, int J>
+template <int J>
 __device__ __forceinline__ void trsm_finish(double (*As)[LDT], const double (*Xd)[16][17], const TileRef &t, int row0,
                                             int lr, int lk, double *spub_blk) {
     double4_t pj = {0, 0, 0, 0};
@@ -951,38 +913,22 @@ __device__ __forceinline__ bool poll_words_pipelined(const double *p, unsigned l
     auto there = [&](double v) {
         return !(__builtin_amdgcn_ballot_w64((unsigned long long)__double_as_longlong(v) == STAGE_SENTINEL) & watch);
     };
-#ifndef MM_CHOL_POLL_DEPTH
-#define MM_CHOL_POLL_DEPTH 4
-#endif
     double c0 = ld();
-    double c1 = 0.0, c2 = 0.0, c3 = 0.0;
-    if (MM_CHOL_POLL_DEPTH >= 2) {
-        __builtin_amdgcn_s_sleep(2);
-        c1 = ld();
-    }
-    if (MM_CHOL_POLL_DEPTH >= 3) {
-        __builtin_amdgcn_s_sleep(2);
-        c2 = ld();
-    }
-    if (MM_CHOL_POLL_DEPTH >= 4) {
-        __builtin_amdgcn_s_sleep(2);
-        c3 = ld();
-    }
+    __builtin_amdgcn_s_sleep(2);
+    double c1 = ld();
+    __builtin_amdgcn_s_sleep(2);
+    double c2 = ld();
+    __builtin_amdgcn_s_sleep(2);
+    double c3 = ld();
     for (long it = 0; it < SPIN_LIMIT; ++it) {
         if (there(c0)) return true;
         c0 = ld();
-        if (MM_CHOL_POLL_DEPTH >= 2) {
-            if (there(c1)) return true;
-            c1 = ld();
-        }
-        if (MM_CHOL_POLL_DEPTH >= 3) {
-            if (there(c2)) return true;
-            c2 = ld();
-        }
-        if (MM_CHOL_POLL_DEPTH >= 4) {
-            if (there(c3)) return true;
-            c3 = ld();
-        }
+        if (there(c1)) return true;
+        c1 = ld();
+        if (there(c2)) return true;
+        c2 = ld();
+        if (there(c3)) return true;
+        c3 = ld();
         if ((it & 63) == 63 && __hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return false;
     }
     __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1038,12 +984,9 @@ __device__ __forceinline__ bool stage_wait(StageRegs<K> &g, const double *lpub_c
     __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return false;
 }
-// The row head's LAST stage sits on the chain  factorisation of L_{r-1,r-1} -> this solve -> factorisation of L_rr: it may
+// The row head's stages sit on the chain  factorisation of L_{r-1,r-1} -> this solve -> factorisation of L_rr: it may
 // poll the stage's own words (four per lane) instead of a canary followed by the load -- one trip
-// to memory less per block column (only this one consumer per diagonal block: see stage_wait on flooding).
-#ifndef MM_CHOL_DIRECT_LAST
-#define MM_CHOL_DIRECT_LAST 2
-#endif
+// to memory less per stage (only this one consumer per diagonal block: see stage_wait on flooding).
 template <int K>
 __device__ __forceinline__ bool stage_wait_direct(StageRegs<K> &g, const double *lpub_c, const double *Linv_c, int lane,
                                                   int32_t *abort_flag) {
@@ -1058,7 +1001,7 @@ __device__ __forceinline__ bool stage_wait_direct(StageRegs<K> &g, const double 
     return false;
 }
 // stage K of the solve on this wave's 16 rows, its operands in registers
-template <int MODE, int K>
+template <int K>
 __device__ __forceinline__ void stage_compute(const StageRegs<K> &g, double (*As)[LDT], double (*Bs)[LDT], double (*Xd)[16][17],
                                               const TileRef &t, double *spub_blk, int lane, int row0) {
     const int lr = lane & 15, lk = lane >> 4;
@@ -1073,7 +1016,7 @@ __device__ __forceinline__ void stage_compute(const StageRegs<K> &g, double (*As
         Xd[K][e >> 4][e & 15] = g.xv[q];
     }
     wave_lds_sync();
-    trsm_finish<MODE, K>(As, Xd, t, row0, lr, lk, spub_blk);
+    trsm_finish<K>(As, Xd, t, row0, lr, lk, spub_blk);
     if constexpr (K < 1) trsm_update<1, K, K + 1>(As, Bs, row0, lr, lk);
     if constexpr (K < 2) trsm_update<2, K, K + 1>(As, Bs, row0, lr, lk);
     if constexpr (K < 3) trsm_update<3, K, K + 1>(As, Bs, row0, lr, lk);
@@ -1102,7 +1045,7 @@ __device__ __forceinline__ void syrk_slice(const double (*As)[LDT], double4_t (&
 // SYRK (the owner of the diagonal block of the same row): also acc += P P^T -- the first three 16-column slices while the
 // last stage is awaited, so that only 16 MFMAs of it follow the last stage.  spub_blk: see trsm_finish.  Returns false
 // (uniformly) if a wait was abandoned.
-template <int MODE, bool SYRK>
+template <bool SYRK>
 __device__ __forceinline__ bool finish_off_block_streamed(double (*As)[LDT], double (*Bs)[LDT], double (*Xd)[16][17],
                                                           const double *lpub_c, const double *Linv_c, int32_t *abort_flag,
                                                           const TileRef &t, double4_t (&acc)[2][2], double *spub_blk,
@@ -1112,12 +1055,12 @@ __device__ __forceinline__ bool finish_off_block_streamed(double (*As)[LDT], dou
     StageRegs<1> g1;
     StageRegs<2> g2;
     StageRegs<3> g3;
-    // (MM_CHOL_DIRECT_LAST: 1 = the row head polls the words of its LAST stage directly, 2 = of every stage -- its early
-    // loads usually come back as the sentinel, and canary + reload is two trips to memory per stage on a consumer that delay
-    // injection shows running BEHIND the producer's panels)
+    // (the row head polls the words of EVERY stage directly, not only of its last one: its early loads usually come back as
+    // the sentinel, and canary + reload is two trips to memory per stage on a consumer that delay injection shows running
+    // BEHIND the producer's panels)
     auto wait_stage = [&](auto &gk, auto ktag) __attribute__((always_inline)) -> bool {
         constexpr int K = decltype(ktag)::value;
-        if constexpr (SYRK && (MM_CHOL_DIRECT_LAST >= 2 || (MM_CHOL_DIRECT_LAST == 1 && K == 3)))
+        if constexpr (SYRK)
             return stage_wait_direct<K>(gk, lpub_c, Linv_c, lane, abort_flag);
         else
             return stage_wait<K>(gk, lpub_c, Linv_c, lane, abort_flag);
@@ -1126,15 +1069,15 @@ __device__ __forceinline__ bool finish_off_block_streamed(double (*As)[LDT], dou
     bool ok = wait_stage(g0, std::integral_constant<int, 0>{});
     stage_issue<1>(g1, lpub_c, Linv_c, lane);
     if constexpr (SYRK) MM_DELAY(12);
-    stage_compute<MODE, 0>(g0, As, Bs, Xd, t, spub_blk, lane, row0);
+    stage_compute<0>(g0, As, Bs, Xd, t, spub_blk, lane, row0);
     ok = wait_stage(g1, std::integral_constant<int, 1>{}) && ok;
     stage_issue<2>(g2, lpub_c, Linv_c, lane);
     if constexpr (SYRK) MM_DELAY(13);
-    stage_compute<MODE, 1>(g1, As, Bs, Xd, t, spub_blk, lane, row0);
+    stage_compute<1>(g1, As, Bs, Xd, t, spub_blk, lane, row0);
     ok = wait_stage(g2, std::integral_constant<int, 2>{}) && ok;
     stage_issue<3>(g3, lpub_c, Linv_c, lane);
     if constexpr (SYRK) MM_DELAY(14);
-    stage_compute<MODE, 2>(g2, As, Bs, Xd, t, spub_blk, lane, row0);
+    stage_compute<2>(g2, As, Bs, Xd, t, spub_blk, lane, row0);
     if constexpr (SYRK) {
         __syncthreads();      // P_0 .. P_2 of all four waves
         syrk_slice<0>(As, acc);
@@ -1152,7 +1095,7 @@ __device__ __forceinline__ bool finish_off_block_streamed(double (*As)[LDT], dou
 #ifdef MM_CHOL_DELAY_SITE
     MM_DELAY_IF(MM_CHOL_DELAY_SITE, MM_CHOL_DELAY_SITE >= 52 && MM_CHOL_DELAY_SITE < 70 && (delay_tag >> 4) == MM_CHOL_DELAY_SITE - 50);      // offset d = site - 50
 #endif
-    stage_compute<MODE, 3>(g3, As, Bs, Xd, t, spub_blk, lane, row0);
+    stage_compute<3>(g3, As, Bs, Xd, t, spub_blk, lane, row0);
     MM_TRACE_ROW(trace_row, 3);
     const bool all_ok = !__syncthreads_or(!ok);
     if constexpr (SYRK) syrk_slice<3>(As, acc);
@@ -1273,7 +1216,6 @@ __device__ __forceinline__ void gemm_slice(const double (*As)[LDT], const double
 
 // producer side of the streamed hand-over (factor_block_lds calls l(k) on wave 2, x(k) on the wave that inverted
 // diagonal block k): write-through stores and nothing else -- the consumers poll the values
-template <int MODE>
 struct StagePub {
     const double (*M)[NB + 1];
     const double (*X)[NB + 1];
@@ -1330,19 +1272,19 @@ struct StagePub {
 // flags (int32): [0] abort, then per side: flag[nblk][W] block (r, d) published (d >= 1; the diagonal blocks are handed
 // over piecewise through polled data, see trsm_stage) | yflag[nblk] | cflag[nblk][W] forward contribution of block (r, d)
 // written | [nblk] unused
-__device__ __forceinline__ size_t tw_side_flags(int nblk, int W) { return 2 * (size_t)nblk * W + 2 * (size_t)nblk; }
+__host__ __device__ __forceinline__ size_t tw_side_flags(int nblk, int W) { return 2 * (size_t)nblk * W + 2 * (size_t)nblk; }
 
 // Forward substitution L y = b rides along (b_fwd != nullptr): the owner of block (r, c) multiplies it with y_c as
 // soon as that exists and hands the 64-vector to the owner of the diagonal block r, which adds the contributions in
 // a fixed order (deterministic), applies L_rr^-1 and publishes y_r.  The y chain trails the factorisation by a hop or
 // two.  NOT for free, as this comment claimed until round 4: y_c leaves its row head ~12 us after L_cc, and an owner that
-// waits for it between two blocks is late for the next one -- with MM_CHOL_NO_FWD=1 the kernel took 506 instead of 531 us.
+// waits for it between two blocks is late for the next one -- launched without a right-hand side (the forward substitution
+// left to the launch-per-column kernels) the kernel took 506 instead of 531 us.
 // The owners of the two farthest offsets therefore take the product after their next block (defer_fwd below); what is
 // left of the difference is the tail of the y chain behind the last column.  (Two-ended: the rows of M receive
 // contributions from both sides.)
 
-template <int MODE>
-__device__ __forceinline__ void chol_band_fused_body(double *A, TwGeom g, double *Linv,
+__device__ __forceinline__ void chol_band_fused_body(double *A, mm_chol_geom g, double *Linv,
                                                               int32_t *__restrict__ flags, int32_t *__restrict__ info,
                                                               const double *b_fwd, double *y,
                                                               double *contrib, double *lpub, double *spub,
@@ -1394,7 +1336,7 @@ __device__ __forceinline__ void chol_band_fused_body(double *A, TwGeom g, double
     auto rows_ready = [&](int q) -> bool {
         if (!slab_ready) return true;
         const int s_lo = (NB * q / 6) / cams_per_slab, s_hi = min(n_cams - 1, (NB * q + NB - 1) / 6) / cams_per_slab;
-        return wg_wait<MODE>(slab_ready + s_lo, s_hi != s_lo ? slab_ready + s_hi : nullptr, abort_flag, &s_ok);
+        return wg_wait(slab_ready + s_lo, s_hi != s_lo ? slab_ready + s_hi : nullptr, abort_flag, &s_ok);
     };
     double4_t acc[2][2];
     if (side == 2) {
@@ -1416,18 +1358,18 @@ __device__ __forceinline__ void chol_band_fused_body(double *A, TwGeom g, double
         // its own entries: requested now, parked in Ds before they are needed (not when the matrix is still being produced)
         double own[16];
         const bool early = !slab_ready;
-        if (early) tile_prefetch_shared<MODE>(own, t);
+        if (early) tile_prefetch_shared(own, t);
         // the other end's blocks sit at their natural positions (upper triangle): read with side 0's addressing
         const int rr = nblk - 1 - r, rc = nblk - 1 - c;  // the two rows in side 1's numbering (rr <= rc)
         bool ok_ = true;
         auto product0 = [&](int k) __attribute__((always_inline)) {      // with column k of T
             if (r == c && k == r - 1) return;  // (the head of row r adds L_{r,r-1} L_{r,r-1}^T itself, from its LDS copy)
-            if (!wg_wait<MODE>(flag(fb0(), r, r - k), r != c ? flag(fb0(), c, c - k) : nullptr, abort_flag, &s_ok)) {
+            if (!wg_wait(flag(fb0(), r, r - k), r != c ? flag(fb0(), c, c - k) : nullptr, abort_flag, &s_ok)) {
                 ok_ = false;
                 return;
             }
-            load_tile_shared<MODE>(As, tile_ref(A, g, 0, r, k));
-            if (r != c) load_tile_shared<MODE>(Bs, tile_ref(A, g, 0, c, k));
+            load_tile_shared(As, tile_ref(A, g, 0, r, k));
+            if (r != c) load_tile_shared(Bs, tile_ref(A, g, 0, c, k));
             __syncthreads();
             if (r != c)
                 tile_gemm_nt(As, Bs, acc);
@@ -1435,12 +1377,12 @@ __device__ __forceinline__ void chol_band_fused_body(double *A, TwGeom g, double
                 tile_gemm_nt(As, As, acc);
         };
         auto product1 = [&](int kt) __attribute__((always_inline)) {     // with column kt of the other end
-            if (!wg_wait<MODE>(flag(fb1(), rr, rr - kt), r != c ? flag(fb1(), rc, rc - kt) : nullptr, abort_flag, &s_ok)) {
+            if (!wg_wait(flag(fb1(), rr, rr - kt), r != c ? flag(fb1(), rc, rc - kt) : nullptr, abort_flag, &s_ok)) {
                 ok_ = false;
                 return;
             }
-            load_tile_shared<MODE>(As, tile_ref(A, g, 0, r, nblk - 1 - kt));
-            if (r != c) load_tile_shared<MODE>(Bs, tile_ref(A, g, 0, c, nblk - 1 - kt));
+            load_tile_shared(As, tile_ref(A, g, 0, r, nblk - 1 - kt));
+            if (r != c) load_tile_shared(Bs, tile_ref(A, g, 0, c, nblk - 1 - kt));
             __syncthreads();
             if (r != c)
                 tile_gemm_nt(As, Bs, acc);
@@ -1464,12 +1406,12 @@ __device__ __forceinline__ void chol_band_fused_body(double *A, TwGeom g, double
         if (early) {
             MM_ACC_FOREACH(As[row][col] = Ds[row][col] - acc[a][b][i];)
         } else {
-            MM_ACC_FOREACH(As[row][col] = ((t.rv(row) && t.cv(col)) ? ld_shared<MODE>(t.at(row, col)) : 0.0) - acc[a][b][i];)
+            MM_ACC_FOREACH(As[row][col] = ((t.rv(row) && t.cv(col)) ? ld_shared(t.at(row, col)) : 0.0) - acc[a][b][i];)
         }
         __syncthreads();
         MM_DELAY(9);
         store_tile_shared16(As, t);
-        wg_publish<MODE>(pflag(i, jj));
+        wg_publish(pflag(i, jj));
         return;
     }
     // role of this workgroup: offset d (0 = row head: blocks (r, r-1) and (r, r)), first column / row j, period
@@ -1491,24 +1433,22 @@ __device__ __forceinline__ void chol_band_fused_body(double *A, TwGeom g, double
         // anti-diagonal of owners below waits for (measured by delay injection, tools/dev/chol_delay.sh: the row heads
         // have slack, the owners of the far offsets do not).  Those owners take the product of block (r, c) with y_c AFTER
         // their next block is out, from its copy in A; the head of row r needs it bwb - 1 columns later at the earliest.
-#ifndef MM_CHOL_DEFER_MAXP
-#define MM_CHOL_DEFER_MAXP 2
-#endif
-        const bool defer_fwd = period <= MM_CHOL_DEFER_MAXP && d >= period + 2;
+        constexpr int DEFER_MAX_PERIOD = 2;      // the owners of the two farthest offsets (period 1 and 2)
+        const bool defer_fwd = period <= DEFER_MAX_PERIOD && d >= period + 2;
         int pend_c = -1;
         auto fwd_part = [&](int rr, int cc, bool reload) -> bool {
-            if (!wg_wait<MODE>(yflag(fb, cc), nullptr, abort_flag, &s_ok)) return false;
-            if (reload) load_tile_shared<MODE>(As, tile_ref(A, g, side, rr, cc));      // (the barrier of wg_wait covers the last use of As)
+            if (!wg_wait(yflag(fb, cc), nullptr, abort_flag, &s_ok)) return false;
+            if (reload) load_tile_shared(As, tile_ref(A, g, side, rr, cc));      // (the barrier of wg_wait covers the last use of As)
             if (threadIdx.x < NB) {
                 const long vi = vec_index(g, side, cc, threadIdx.x);
-                ys[threadIdx.x] = (vi >= 0 && vi < n) ? ld_shared<MODE>(y + vi) : 0.0;
+                ys[threadIdx.x] = (vi >= 0 && vi < n) ? ld_shared(y + vi) : 0.0;
             }
             __syncthreads();
             const double tv = tile_matvec<LDT>(As, ys);
             // a row of M is finished by side 0: hand the vector over in ITS element order
             const int row = threadIdx.x >> 2, at = (side == 1 && rr >= ncols) ? NB - 1 - row : row;
-            if ((threadIdx.x & 3) == 0) st_shared<MODE>(cslot(side, rr, d) + at, tv);
-            wg_publish<MODE>(cflag(fb, rr, d));
+            if ((threadIdx.x & 3) == 0) st_shared(cslot(side, rr, d) + at, tv);
+            wg_publish(cflag(fb, rr, d));
             return true;
         };
         // The block's own entries of A: requested a whole block ahead (into registers, before the previous block's solve) and
@@ -1517,7 +1457,7 @@ __device__ __forceinline__ void chol_band_fused_body(double *A, TwGeom g, double
         // entries come out of a pre-accumulator at the last moment.
         double own[16];
         auto own_early = [&](int c_) { return !slab_ready && !(tw && side == 0 && c_ >= g.a) && c_ + d < nrows && c_ < ncols; };
-        if (own_early(j)) tile_prefetch_shared<MODE>(own, tile_ref(A, g, side, j + d, j));
+        if (own_early(j)) tile_prefetch_shared(own, tile_ref(A, g, side, j + d, j));
         for (int c = j; c + d < nrows && c < ncols; c += period) {
             const int r = c + d;
             const TileRef t = tile_ref(A, g, side, r, c);
@@ -1555,10 +1495,10 @@ __device__ __forceinline__ void chol_band_fused_body(double *A, TwGeom g, double
                     if (!col_ok) MM_FUSED_ABANDON;
                     continue;
                 }
-                if (!wg_wait<MODE>(flag(fb, r, r - k), c - k > 1 ? flag(fb, c, c - k) : nullptr, abort_flag, &s_ok)) MM_FUSED_ABANDON;
-                load_tile_shared<MODE>(As, tile_ref(A, g, side, r, k));
+                if (!wg_wait(flag(fb, r, r - k), c - k > 1 ? flag(fb, c, c - k) : nullptr, abort_flag, &s_ok)) MM_FUSED_ABANDON;
+                load_tile_shared(As, tile_ref(A, g, side, r, k));
                 if (c - k > 1) {
-                    load_tile_shared<MODE>(Bs, tile_ref(A, g, side, c, k));
+                    load_tile_shared(Bs, tile_ref(A, g, side, c, k));
                     __syncthreads();
                 } else if (!load_tile_polled(Bs, spubp(side, c), abort_flag)) {
                     MM_FUSED_ABANDON;
@@ -1568,7 +1508,7 @@ __device__ __forceinline__ void chol_band_fused_body(double *A, TwGeom g, double
             // the block's own entries are fetched as late as possible (their latency hides behind the wait for L_cc):
             // when the matrix is still being produced by a concurrent launch, this owner needs them only now
             if (in_m) {
-                if (!wg_wait<MODE>(pflag(r - g.a, c - g.a), nullptr, abort_flag, &s_ok)) MM_FUSED_ABANDON;
+                if (!wg_wait(pflag(r - g.a, c - g.a), nullptr, abort_flag, &s_ok)) MM_FUSED_ABANDON;
             } else if (!rows_ready(side == 0 ? r : nat(1, c))) {
                 MM_FUSED_ABANDON;
             }
@@ -1577,18 +1517,18 @@ __device__ __forceinline__ void chol_band_fused_body(double *A, TwGeom g, double
             if (early) {
                 MM_ACC_FOREACH(As[row][col] = Ds[row][col] - acc[a][b][i];)
             } else {
-                MM_ACC_FOREACH(As[row][col] = ((t.rv(row) && t.cv(col)) ? ld_shared<MODE>(t.at(row, col)) : 0.0) - acc[a][b][i];)
+                MM_ACC_FOREACH(As[row][col] = ((t.rv(row) && t.cv(col)) ? ld_shared(t.at(row, col)) : 0.0) - acc[a][b][i];)
             }
             __syncthreads();
-            if (own_early(c + period)) tile_prefetch_shared<MODE>(own, tile_ref(A, g, side, c + period + d, c + period));
+            if (own_early(c + period)) tile_prefetch_shared(own, tile_ref(A, g, side, c + period + d, c + period));
             // (d = 2: the block also goes out panel by panel for the head of its row, whose last column it is)
             MM_DELAY(8);      // (d >= 2 owner, products done, before its solve)
-            if (!finish_off_block_streamed<MODE, false>(As, Bs, T, lpubp(side, c), linv(side, c), abort_flag, t, acc,
+            if (!finish_off_block_streamed<false>(As, Bs, T, lpubp(side, c), linv(side, c), abort_flag, t, acc,
                                                         d == 2 ? (r < ncols ? spub2p(side, r) : nullptr) : opubp(side, r, d), -1,
                                                         (d == 2 ? 1 : 2) | (in_m ? 4 : 0) | (d << 4)))
                 MM_FUSED_ABANDON;
             if (d > 2 || r < ncols) store_tile_shared16(As, t);      // (its copy in A: see trsm_finish)
-            wg_publish<MODE>(flag(fb, r, d));
+            wg_publish(flag(fb, r, d));
             MM_DELAY(11);      // (d >= 2 owner, block published)
             if (b_fwd) {
                 if (pend_c >= 0) {      // the previous block's product: its y has long been published
@@ -1631,13 +1571,13 @@ __device__ __forceinline__ void chol_band_fused_body(double *A, TwGeom g, double
         auto fetch_own = [&]() __attribute__((always_inline)) {
             fetched = true;
             if (diag_pre && !defer_diag &&
-                !wg_wait<MODE>(pflag(r - g.a, r - g.a), sub_pre ? pflag(r - g.a, r - 1 - g.a) : nullptr, abort_flag, &s_ok))
+                !wg_wait(pflag(r - g.a, r - g.a), sub_pre ? pflag(r - g.a, r - 1 - g.a) : nullptr, abort_flag, &s_ok))
                 fetch_ok = false;
             if (fetch_ok && diag_here && !rows_ready(nat(side, r))) fetch_ok = false;
             if (fetch_ok && side == 1 && has_sub && !rows_ready(nat(1, r - 1))) fetch_ok = false;
             if (!fetch_ok) return;
-            if (diag_here && !defer_diag) load_tile_shared<MODE>(Ds, dt);      // (the upper triangle is masked where the tile is used)
-            if (has_sub) load_tile_shared<MODE>(Ss, st);
+            if (diag_here && !defer_diag) load_tile_shared(Ds, dt);      // (the upper triangle is masked where the tile is used)
+            if (has_sub) load_tile_shared(Ss, st);
         };
         if (!diag_pre || r >= g.a + 2 || defer_diag) {
             fetch_own();
@@ -1703,11 +1643,11 @@ __device__ __forceinline__ void chol_band_fused_body(double *A, TwGeom g, double
                 continue;
             }
             // both blocks of the column are waited for and fetched together (one trip to memory, one barrier)
-            if (!wg_wait<MODE>(flag(fb, r, r - k), do_sub ? flag(fb, r - 1, r - 1 - k) : nullptr, abort_flag, &s_ok)) MM_FUSED_ABANDON;
+            if (!wg_wait(flag(fb, r, r - k), do_sub ? flag(fb, r - 1, r - 1 - k) : nullptr, abort_flag, &s_ok)) MM_FUSED_ABANDON;
             {
                 double pa[16], pb[16];
-                tile_prefetch_shared<MODE>(pa, tile_ref(A, g, side, r, k));
-                if (do_sub) tile_prefetch_shared<MODE>(pb, tile_ref(A, g, side, r - 1, k));
+                tile_prefetch_shared(pa, tile_ref(A, g, side, r, k));
+                if (do_sub) tile_prefetch_shared(pb, tile_ref(A, g, side, r - 1, k));
                 tile_commit(As, pa);
                 if (do_sub) tile_commit(Bs, pb);
             }
@@ -1729,9 +1669,9 @@ __device__ __forceinline__ void chol_band_fused_body(double *A, TwGeom g, double
             MM_ACC_FOREACH(Ss[row][col] -= acc1[a][b][i];)
             __syncthreads();
             // the solve streams behind the factorisation of L_{r-1,r-1}; acc += L_{r,r-1} L_{r,r-1}^T rides along
-            const bool ok = diag_here ? finish_off_block_streamed<MODE, true>(Ss, Bs, T, lpubp(side, r - 1), linv(side, r - 1), abort_flag,
+            const bool ok = diag_here ? finish_off_block_streamed<true>(Ss, Bs, T, lpubp(side, r - 1), linv(side, r - 1), abort_flag,
                                                                               st, acc, spubp(side, r), side == 0 ? r : -1)
-                                      : finish_off_block_streamed<MODE, false>(Ss, Bs, T, lpubp(side, r - 1), linv(side, r - 1),
+                                      : finish_off_block_streamed<false>(Ss, Bs, T, lpubp(side, r - 1), linv(side, r - 1),
                                                                                abort_flag, st, acc, nullptr);
             if (!ok) MM_FUSED_ABANDON;
             MM_TRACE(r, 4);
@@ -1742,28 +1682,28 @@ __device__ __forceinline__ void chol_band_fused_body(double *A, TwGeom g, double
             // once (a few microseconds on the chain, once per factorisation).
             if (diag_pre && r == g.a) {
                 store_tile_shared16(Ss, st);
-                wg_publish<MODE>(flag(fb, r, 1));
+                wg_publish(flag(fb, r, 1));
             }
         }
         if (!diag_here) {  // side 1, block (b, b - 1): its row belongs to M, side 0 finishes it
-            wg_publish<MODE>(flag(fb, r, 1));
+            wg_publish(flag(fb, r, 1));
             if (b_fwd) {
-                if (!wg_wait<MODE>(yflag(fb, r - 1), nullptr, abort_flag, &s_ok)) MM_FUSED_ABANDON;
+                if (!wg_wait(yflag(fb, r - 1), nullptr, abort_flag, &s_ok)) MM_FUSED_ABANDON;
                 if (threadIdx.x < NB) {
                     const long vi = vec_index(g, side, r - 1, threadIdx.x);
-                    ys[threadIdx.x] = (vi >= 0 && vi < n) ? ld_shared<MODE>(y + vi) : 0.0;
+                    ys[threadIdx.x] = (vi >= 0 && vi < n) ? ld_shared(y + vi) : 0.0;
                 }
                 __syncthreads();
                 const double tv = tile_matvec<LDT>(Ss, ys);
-                if ((threadIdx.x & 3) == 0) st_shared<MODE>(cslot(side, r, 1) + (NB - 1 - (threadIdx.x >> 2)), tv);
-                wg_publish<MODE>(cflag(fb, r, 1));
+                if ((threadIdx.x & 3) == 0) st_shared(cslot(side, r, 1) + (NB - 1 - (threadIdx.x >> 2)), tv);
+                wg_publish(cflag(fb, r, 1));
             }
             __syncthreads();
             continue;
         }
         if (defer_diag) {      // (see above: the first row of M takes its pre-accumulated diagonal tile only now)
-            if (!wg_wait<MODE>(pflag(0, 0), nullptr, abort_flag, &s_ok)) MM_FUSED_ABANDON;
-            load_tile_shared<MODE>(Ds, dt);
+            if (!wg_wait(pflag(0, 0), nullptr, abort_flag, &s_ok)) MM_FUSED_ABANDON;
+            load_tile_shared(Ds, dt);
         }
         __syncthreads();  // As / Bs are reused as M / X from here
         MM_DELAY(3);
@@ -1787,7 +1727,7 @@ __device__ __forceinline__ void chol_band_fused_body(double *A, TwGeom g, double
         double *Lr = linv(side, r);
         MM_TRACE(r, 6);
         // the block streams out while it is factored: column panel k's sub-diagonal blocks, then X_kk (see trsm_stage)
-        factor_block_lds(M, X, R, 0, bad, StagePub<MODE>{M, X, dt, Lr, lpubp(side, r), has_sub && !(diag_pre && r == g.a) ? flag(fb, r, 1) : nullptr, Ss, st},
+        factor_block_lds(M, X, R, 0, bad, StagePub{M, X, dt, Lr, lpubp(side, r), has_sub && !(diag_pre && r == g.a) ? flag(fb, r, 1) : nullptr, Ss, st},
                          side == 0 ? r : -1);
         MM_TRACE(r, 7);
         if (bad && threadIdx.x == 64) {  // `bad` = 1-based position inside the block; report the natural column
@@ -1808,51 +1748,47 @@ __device__ __forceinline__ void chol_band_fused_body(double *A, TwGeom g, double
         if (b_fwd) {  // y_r = L_rr^-1 (b_r - sum_d L_{r,r-d} y_{r-d})
             if (threadIdx.x < NB) {
                 const long vi = vec_index(g, side, r, threadIdx.x);
-                rhs[threadIdx.x] = (vi >= 0 && vi < n) ? ld_shared<MODE>(b_fwd + vi) : 0.0;
+                rhs[threadIdx.x] = (vi >= 0 && vi < n) ? ld_shared(b_fwd + vi) : 0.0;
             }
             if (has_sub) {  // this workgroup owns (r, r-1): still in Ss
-                if (!wg_wait<MODE>(yflag(fb, r - 1), nullptr, abort_flag, &s_ok)) MM_FUSED_ABANDON;
+                if (!wg_wait(yflag(fb, r - 1), nullptr, abort_flag, &s_ok)) MM_FUSED_ABANDON;
                 if (threadIdx.x < NB) {
                     const long vi = vec_index(g, side, r - 1, threadIdx.x);
-                    ys[threadIdx.x] = (vi >= 0 && vi < n) ? ld_shared<MODE>(y + vi) : 0.0;
+                    ys[threadIdx.x] = (vi >= 0 && vi < n) ? ld_shared(y + vi) : 0.0;
                 }
                 __syncthreads();
                 const double tv = tile_matvec<LDT>(Ss, ys);
                 if ((threadIdx.x & 3) == 0) rhs[threadIdx.x >> 2] -= tv;
             }
             for (int dd = 2; dd <= bwb && dd <= r; ++dd) {
-                if (!wg_wait<MODE>(cflag(fb, r, dd), nullptr, abort_flag, &s_ok)) MM_FUSED_ABANDON;
-                if (threadIdx.x < NB) rhs[threadIdx.x] -= ld_shared<MODE>(cslot(side, r, dd) + threadIdx.x);
+                if (!wg_wait(cflag(fb, r, dd), nullptr, abort_flag, &s_ok)) MM_FUSED_ABANDON;
+                if (threadIdx.x < NB) rhs[threadIdx.x] -= ld_shared(cslot(side, r, dd) + threadIdx.x);
             }
             if (tw && side == 0 && r >= g.a) {  // a row of M: what the other end's columns contribute (fixed order)
                 const int rr = nblk - 1 - r;
                 for (int dd = max(1, rr - g.b + 1); dd <= bwb && dd <= rr; ++dd) {
-                    if (!wg_wait<MODE>(cflag(fb1(), rr, dd), nullptr, abort_flag, &s_ok)) MM_FUSED_ABANDON;
-                    if (threadIdx.x < NB) rhs[threadIdx.x] -= ld_shared<MODE>(cslot(1, rr, dd) + threadIdx.x);
+                    if (!wg_wait(cflag(fb1(), rr, dd), nullptr, abort_flag, &s_ok)) MM_FUSED_ABANDON;
+                    if (threadIdx.x < NB) rhs[threadIdx.x] -= ld_shared(cslot(1, rr, dd) + threadIdx.x);
                 }
             }
             __syncthreads();
             const double yr = tile_matvec<NB + 1>(X, rhs);
             if ((threadIdx.x & 3) == 0) {
                 const long vi = vec_index(g, side, r, threadIdx.x >> 2);
-                if (vi >= 0 && vi < n) st_shared<MODE>(y + vi, yr);
+                if (vi >= 0 && vi < n) st_shared(y + vi, yr);
             }
-            wg_publish<MODE>(yflag(fb, r));
+            wg_publish(yflag(fb, r));
         }
         MM_TRACE(r, 9);
         __syncthreads();  // M / X are overwritten by the next row's tiles
     }
 }
-template <int MODE>
-__global__ __launch_bounds__(256) void chol_band_fused_kernel(double *A, TwGeom g, double *Linv,
+__global__ __launch_bounds__(256) void chol_band_fused_kernel(double *A, mm_chol_geom g, double *Linv,
                                                               int32_t *__restrict__ flags, int32_t *__restrict__ info,
                                                               const double *b_fwd, double *y,
                                                               double *contrib, double *lpub, double *spub,
                                                               const int32_t *slab_ready, int cams_per_slab, int n_cams) {
-    chol_band_fused_body<MODE>(A, g, Linv, flags, info, b_fwd, y, contrib, lpub, spub, slab_ready, cams_per_slab, n_cams, blockIdx.x);
-}
-__device__ __forceinline__ TwGeom batch_geom(const mm_batch_prob &bp) {
-    return TwGeom{bp.chol_n, bp.chol_nblk, bp.chol_bwb, bp.chol_a, bp.chol_m, bp.chol_b, bp.chol_pad};
+    chol_band_fused_body(A, g, Linv, flags, info, b_fwd, y, contrib, lpub, spub, slab_ready, cams_per_slab, n_cams, blockIdx.x);
 }
 // batched (mm_ba_trf_batched): blockIdx.y picks the problem.  Workgroups are dispatched in order of their linear index, x
 // fastest: all workgroups of the problems listed earlier are resident (or done) before a later problem's, and a workgroup
@@ -1861,8 +1797,8 @@ __device__ __forceinline__ TwGeom batch_geom(const mm_batch_prob &bp) {
 __global__ __launch_bounds__(256) void chol_band_fused_batch_kernel(const mm_batch_prob *__restrict__ tab, const int32_t *__restrict__ list) {
     const mm_batch_prob &bp = tab[list[blockIdx.y]];
     if (blockIdx.x >= bp.g_chol) return;
-    chol_band_fused_body<2>(bp.S, batch_geom(bp), bp.chol_Linv, bp.chol_flags, bp.info, bp.v, bp.chol_ytmp, bp.chol_contrib, bp.chol_lpub,
-                            bp.chol_spub, nullptr, 1, 0, blockIdx.x);
+    chol_band_fused_body(bp.S, bp.chol.g, bp.chol.Linv, bp.chol.flags, bp.info, bp.v, bp.chol.ytmp, bp.chol.contrib, bp.chol.lpub,
+                         bp.chol.spub, nullptr, 1, 0, blockIdx.x);
 }
 
 
@@ -1895,10 +1831,6 @@ __device__ __forceinline__ void tile_prefetch(double (&pre)[16], const TileRef &
         pre[q] = (t.rv(r) && t.cv(c)) ? *t.at(r, c) : 0.0;
     }
 }
-__device__ __forceinline__ void tile_prefetch_dense(double (&pre)[16], const double *__restrict__ src) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) pre[q] = src[threadIdx.x + 256 * q];
-}
 // out[c] = sum_r T[r][c] v[r] for c = threadIdx.x & 63 (valid in the first 64 threads after the call); 256 threads
 __device__ __forceinline__ double tile_matvec_t(const double (*T)[LDT], const double *v, double (*part)[NB]) {
     const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
@@ -1909,7 +1841,7 @@ __device__ __forceinline__ double tile_matvec_t(const double (*T)[LDT], const do
     __syncthreads();
     return (part[0][c] + part[1][c]) + (part[2][c] + part[3][c]);
 }
-// The same product straight from the registers a tile was prefetched into (tile_prefetch / tile_prefetch_dense: element
+// The same product straight from the registers a tile was prefetched into (tile_prefetch: element
 // threadIdx.x + 256 q = row (threadIdx.x >> 6) + 4 q, column threadIdx.x & 63): thread (g, c) adds the rows g, g + 4, ... of
 // column c -- the tile never goes through LDS (16 stores + 16 loads per thread and a barrier less per product; round 4).
 __device__ __forceinline__ double reg_matvec_t(const double (&pre)[16], const double *v, double (*part)[NB]) {
@@ -1934,13 +1866,12 @@ __device__ __forceinline__ double poll_value(const double *p, int32_t *abort_fla
     return 0.0;
 }
 
-__device__ __forceinline__ void chol_band_bwd_body(double *A, TwGeom g, const double *__restrict__ Linv,
+__device__ __forceinline__ void chol_band_bwd_body(double *A, mm_chol_geom g, const double *__restrict__ Linv,
                                                             const double *__restrict__ y, double *x, double *contrib,
                                                             int32_t *__restrict__ abort_flag, int32_t *__restrict__ info, const unsigned bx) {
     extern __shared__ double smem[];
-    double (*T1)[LDT] = reinterpret_cast<double (*)[LDT]>(smem + NB * LDT);      // (side 1's prologue only)
     double (*part)[NB] = reinterpret_cast<double (*)[NB]>(smem + 2 * NB * LDT);
-    double *vec = smem + 2 * NB * LDT + 4 * NB, *vec2 = vec + NB;
+    double *vec = smem + 2 * NB * LDT + 4 * NB;
     const int bwb = g.bwb, W = bwb + 1, nblk = g.nblk, n = g.n;
     const int GB = bwb >= 2 ? bwb : 1;  // workgroups per side
     const int side = (int)bx / GB, lid = (int)bx % GB;
@@ -1959,10 +1890,7 @@ __device__ __forceinline__ void chol_band_bwd_body(double *A, TwGeom g, const do
         return vi >= 0 && vi < n;
     };
     int failed = 0;
-#ifndef MM_CHOL_BWD_CHAIN_WAVE
-#define MM_CHOL_BWD_CHAIN_WAVE 1
-#endif
-    if (lid == 0 && MM_CHOL_BWD_CHAIN_WAVE) {
+    if (lid == 0) {
         // The chain  x_k = L_kk^-T (y_k - L_{k+1,k}^T x_{k+1} - contributions)  on ONE wave (round 4).  Delay injection showed
         // the chain workgroup itself pacing this kernel (its helpers have slack): four waves sharing each product paid five
         // workgroup barriers and as many LDS round trips per step (3.1 us).  Here wave 0 walks the chain alone -- lane c owns
@@ -2033,7 +1961,7 @@ __device__ __forceinline__ void chol_band_bwd_body(double *A, TwGeom g, const do
         }
         // ---- wave 0: the chain ----
         const int lane = lane_id();
-        double cv[FUSED_MAX_BWB + 1], yk = 0.0;
+        double cv[FUSED_MAX_W], yk = 0.0;
         auto vposl = [&](int blk, long &vi) -> bool {
             vi = vec_index(g, side, blk, lane);
             return vi >= 0 && vi < n;
@@ -2084,7 +2012,7 @@ __device__ __forceinline__ void chol_band_bwd_body(double *A, TwGeom g, const do
             long vi;
             const bool okv = vposl(k, vi);
             if (okv) {
-                st_shared<2>(xpoll(vi), xk);
+                st_shared(xpoll(vi), xk);
                 x[vi] = xk;
             }
             cvec2[lane] = okv ? xk : 0.0;
@@ -2097,87 +2025,6 @@ __device__ __forceinline__ void chol_band_bwd_body(double *A, TwGeom g, const do
         return;
     }
     // tiles are fetched two steps ahead (a step is shorter than a trip to memory): two register slots, loop unrolled by 2
-    if (lid == 0) {
-        double p0a[16], p1a[16], p0b[16], p1b[16];
-        auto fetch = [&](int k, double (&p0)[16], double (&p1)[16]) {  // tiles of step k: L_kk^-1 and L_{k,k-1}
-            if (k < 0) return;
-            tile_prefetch_dense(p0, Linv + (size_t)nat(k) * NB * NB);
-            if (k > 0) tile_prefetch(p1, tile_ref(A, g, side, k, k - 1));
-        };
-        double local = 0.0;  // L_{k+1,k}^T x_{k+1}, element threadIdx.x (first 64 threads)
-        bool dead = false;
-        // y_k and the contributions of step k are requested during step k + 1 (right after x_{k+1} went out), so their
-        // memory latency overlaps the local matrix-vector work; what is still the sentinel then gets polled
-        double cv[FUSED_MAX_BWB + 1], yk = 0.0;
-        auto request = [&](int k) {
-            if (k < 0 || threadIdx.x >= NB) return;
-            long vi;
-            yk = vpos(k, vi) ? y[vi] : 0.0;
-#pragma unroll
-            for (int dd = 2; dd <= FUSED_MAX_BWB; ++dd)
-                if (dd <= bwb && k + dd < nrows)
-                    cv[dd] = __hip_atomic_load(cslot(k, dd) + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        };
-        auto step = [&](int k, double (&p0)[16], double (&p1)[16]) {
-            MM_DELAY(21);      // (backward chain, top of a step)
-            if (threadIdx.x < NB) {
-                double rhs = yk - local;
-#pragma unroll
-                for (int dd = 2; dd <= FUSED_MAX_BWB; ++dd)  // fixed summation order
-                    if (dd <= bwb && k + dd < nrows) {
-                        if ((unsigned long long)__double_as_longlong(cv[dd]) == BWD_SENTINEL)
-                            cv[dd] = poll_value(cslot(k, dd) + threadIdx.x, abort_flag, failed);
-                        rhs -= cv[dd];
-                    }
-                vec[threadIdx.x] = rhs;
-            }
-            if (__syncthreads_or(failed)) {
-                dead = true;
-                return;
-            }
-            const double xk = reg_matvec_t(p0, vec, part);
-            if (threadIdx.x < NB) {
-                long vi;
-                const bool ok = vpos(k, vi);
-                if (ok) {
-                    st_shared<2>(xpoll(vi), xk);
-                    x[vi] = xk;
-                }
-                vec2[threadIdx.x] = ok ? xk : 0.0;
-            }
-            request(k - 1);
-            MM_DELAY(22);      // (backward chain, x_k is out)
-            __syncthreads();
-            if (k > 0) local = reg_matvec_t(p1, vec2, part);
-            fetch(k - 2, p0, p1);      // (both register sets of this step are spent)
-            __syncthreads();  // vec / vec2 / part are rewritten by the next step
-        };
-        const int ktop = ncols - 1;  // first block this chain solves for
-        if (ktop < 0) return;
-        if (side == 1 && ktop + 1 < nrows && bwb >= 1) {
-            // the row above the chain's first block belongs to M: x of that row comes from side 0, the block
-            // (ktop + 1, ktop) is this side's -> `local` for the first step
-            double pt[16];
-            tile_prefetch(pt, tile_ref(A, g, side, ktop + 1, ktop));
-            tile_commit(T1, pt);
-            if (threadIdx.x < NB) {
-                long vi;
-                vec2[threadIdx.x] = vpos(ktop + 1, vi) ? poll_value(xpoll(vi), abort_flag, failed) : 0.0;
-            }
-            if (__syncthreads_or(failed)) MM_FUSED_ABANDON;
-            local = tile_matvec_t(T1, vec2, part);
-            __syncthreads();
-        }
-        request(ktop);
-        fetch(ktop, p0a, p1a);
-        fetch(ktop - 1, p0b, p1b);
-        for (int k = ktop; k >= 0 && !dead; k -= 2) {
-            step(k, p0a, p1a);
-            if (k - 1 >= 0 && !dead) step(k - 1, p0b, p1b);
-        }
-        if (dead) MM_FUSED_ABANDON;
-        return;
-    }
     const int d = lid + 1;  // 2 .. bwb
     const int kfirst = min(nrows - 1 - d, ncols - 1);
     if (kfirst < 0) return;
@@ -2197,7 +2044,7 @@ __device__ __forceinline__ void chol_band_bwd_body(double *A, TwGeom g, const do
         }
         MM_DELAY(23);      // (backward helpers, x_{k+d} seen)
         const double t = reg_matvec_t(pp, vec, part);
-        if (threadIdx.x < NB) st_shared<2>(cslot(k, d) + threadIdx.x, t);
+        if (threadIdx.x < NB) st_shared(cslot(k, d) + threadIdx.x, t);
         fetch(k - 2, pp);
         __syncthreads();
     };
@@ -2209,7 +2056,7 @@ __device__ __forceinline__ void chol_band_bwd_body(double *A, TwGeom g, const do
     }
     if (dead) MM_FUSED_ABANDON;
 }
-__global__ __launch_bounds__(256) void chol_band_bwd_kernel(double *A, TwGeom g, const double *__restrict__ Linv,
+__global__ __launch_bounds__(256) void chol_band_bwd_kernel(double *A, mm_chol_geom g, const double *__restrict__ Linv,
                                                             const double *__restrict__ y, double *x, double *contrib,
                                                             int32_t *__restrict__ abort_flag, int32_t *__restrict__ info) {
     chol_band_bwd_body(A, g, Linv, y, x, contrib, abort_flag, info, blockIdx.x);
@@ -2217,7 +2064,7 @@ __global__ __launch_bounds__(256) void chol_band_bwd_kernel(double *A, TwGeom g,
 __global__ __launch_bounds__(256) void chol_band_bwd_batch_kernel(const mm_batch_prob *__restrict__ tab, const int32_t *__restrict__ list) {
     const mm_batch_prob &bp = tab[list[blockIdx.y]];
     if (blockIdx.x >= bp.g_bwd) return;
-    chol_band_bwd_body(bp.S, batch_geom(bp), bp.chol_Linv, bp.chol_ytmp, bp.v, bp.chol_contrib_bwd, bp.chol_flags, bp.info, blockIdx.x);
+    chol_band_bwd_body(bp.S, bp.chol.g, bp.chol.Linv, bp.chol.ytmp, bp.v, bp.chol.contrib_bwd, bp.chol.flags, bp.info, blockIdx.x);
 }
 
 
@@ -2229,9 +2076,7 @@ __global__ __launch_bounds__(256) void chol_init_kernel(mm_chol_init_args a) { m
 constexpr unsigned CHOL_INIT_GRID = 128;
 __global__ __launch_bounds__(256) void chol_init_batch_kernel(const mm_batch_prob *__restrict__ tab, const int32_t *__restrict__ list) {
     const mm_batch_prob &bp = tab[list[blockIdx.y]];
-    const mm_chol_init_args a = {bp.info, bp.chol_flags, (size_t)bp.chol_nflags, (unsigned long long *)bp.chol_contrib_bwd, (size_t)bp.chol_nsent,
-                                 (unsigned long long *)bp.chol_lpub, (size_t)bp.chol_nlpub, (unsigned long long *)bp.chol_Linv, (size_t)bp.chol_nblk};
-    mm_chol_init_body(a, blockIdx.x, CHOL_INIT_GRID);
+    mm_chol_init_body(mm_chol_init_args_of(bp.info, bp.chol), blockIdx.x, CHOL_INIT_GRID);
 }
 // copy the band of the lower triangle into the upper triangle for the columns side 1 eliminates: (j, i) <- (i, j) for
 // i >= row0, 0 < i - j <= hb (callers of the two-ended path that only filled the lower triangle)
@@ -2357,14 +2202,6 @@ __global__ __launch_bounds__(256) void bwd_step_kernel(const double *__restrict_
 
 extern "C" {
 
-size_t mm_chol_workspace_bytes(int n) {
-    size_t nblk = (size_t)(n + NB - 1) / NB;
-    return mm_align_up(nblk * NB * NB * sizeof(double), 256) + mm_align_up((size_t)(n + NB) * sizeof(double), 256) +
-           mm_align_up((2 * (2 * nblk * (FUSED_MAX_BWB + 1) + 2 * nblk) + 64 + FUSED_MAX_BWB * FUSED_MAX_BWB) * sizeof(int32_t), 256) +
-           2 * mm_align_up(2 * nblk * (FUSED_MAX_BWB + 1) * NB * sizeof(double), 256) +  // forward + backward contributions
-           mm_align_up(nblk * (LPUB_BLOCK + (size_t)(2 + 2 * (FUSED_MAX_BWB - 2)) * NB * NB) * sizeof(double), 256);   // hand-over buffers of the streamed blocks
-}
-
 int mm_chol_solve(mm_ctx *ctx, double *A, int n, double *b, int nrhs, int half_bandwidth, int32_t *info, void *ws,
                   size_t ws_bytes) {
     return mm_chol_solve_gated(ctx, A, n, b, nrhs, half_bandwidth, info, ws, ws_bytes, nullptr, 1, 0, 0);
@@ -2448,12 +2285,12 @@ static bool chol_reserve_budget(mm_ctx *ctx, int grid) {
     return true;
 }
 
-static int chol_fused_mode() {
-    static const int mode = [] {
+static bool chol_fused_enabled() {
+    static const bool on = [] {
         const char *e = getenv("MM_CHOL_FUSED");
-        return e ? atoi(e) : 2;
+        return !e || atoi(e) != 0;
     }();
-    return mode;
+    return on;
 }
 
 static bool chol_twisted_enabled() {
@@ -2464,12 +2301,75 @@ static bool chol_twisted_enabled() {
     return on;
 }
 
-bool mm_chol_fused_eligible(int n, int half_bandwidth) {
-    const int nblk = (n + NB - 1) / NB;
-    long bwb_l = ((long)half_bandwidth + NB - 1) / NB;
-    const int bwb = bwb_l > nblk ? nblk : (int)bwb_l;
-    return chol_fused_mode() > 0 && nblk >= 2 && bwb >= 1 && bwb <= FUSED_MAX_BWB && !(n & 1);
+// ---- the plan of one solve ---------------------------------------------------------------------------------------------------
+// ONE walk over the workspace, Linv | ytmp | flags | contrib | contrib_bwd | lpub | spub: every region 256-byte aligned and
+// sized for the widest band of the single launch, so that one workspace serves every half_bandwidth.  Returns the end of the
+// walk (= mm_chol_workspace_bytes); ws == nullptr: only that.
+static_assert(LPUB_BLOCK * sizeof(double) % 256 == 0 && NB * NB * sizeof(double) % 256 == 0,
+              "lpub and spub are filled as one buffer (chol_nlpub): no alignment gap between them");
+static size_t chol_carve(void *ws, int n, mm_chol_layout *lay) {
+    const size_t nblk = (size_t)(n + NB - 1) / NB;
+    size_t end = 0;
+    auto take = [&](size_t count, size_t elem) -> void * {
+        void *p = ws ? (char *)ws + end : nullptr;
+        end += mm_align_up(count * elem, 256);
+        return p;
+    };
+    double *Linv = (double *)take(nblk * NB * NB, sizeof(double));      // L_kk^-1 of every diagonal block
+    double *ytmp = (double *)take((size_t)n + NB, sizeof(double));
+    int32_t *flags = (int32_t *)take(2 * tw_side_flags((int)nblk, FUSED_MAX_W) + 64 + FUSED_MAX_BWB * FUSED_MAX_BWB, sizeof(int32_t));
+    double *contrib = (double *)take(2 * nblk * FUSED_MAX_W * NB, sizeof(double));          // forward contributions, per side
+    double *contrib_bwd = (double *)take(2 * nblk * FUSED_MAX_W * NB, sizeof(double));      // backward ones + the words x is polled on
+    double *lpub = (double *)take(nblk * LPUB_BLOCK, sizeof(double));                       // hand-over buffers of the streamed blocks
+    double *spub = (double *)take(nblk * (size_t)(2 + 2 * (FUSED_MAX_BWB - 2)) * NB * NB, sizeof(double));
+    if (lay) {
+        lay->Linv = Linv; lay->ytmp = ytmp; lay->flags = flags; lay->contrib = contrib; lay->contrib_bwd = contrib_bwd;
+        lay->lpub = lpub; lay->spub = spub;
+    }
+    return end;
 }
+
+// Everything mm_chol_solve_gated(n, half_bandwidth, sym_mode, nrhs, gated) decides before its first launch; ws may be null
+// (no pointers then).  mm_chol_init_plan and mm_batch_chol_setup plan the solve they stand in for: sym_mode 2, nrhs 1, not gated.
+//   * single launch: the switch is on, 2 <= nblk, 1 <= bwb <= FUSED_MAX_BWB, n even (16-byte stores of element pairs) and
+//     64 nblk n < 2^31 (TileRef's 32-bit offsets); a context that had to abandon one (chol_avoid_fused, mm_ba_trf) keeps off it --
+//     but never a gated solve, which has no other path: for that one a plan without `fused` is an argument error;
+//   * two-ended: single launch, layout of the factor free (sym_mode > 0), one right-hand side, at least four block columns
+//     outside the separator;
+//   * no_room (the budget of resident workgroups is spent, chol_reserve_budget): the launch-per-column plan of the same solve.
+static mm_chol_plan chol_plan(const mm_ctx *ctx, int n, int half_bandwidth, int sym_mode, int nrhs, bool gated, void *ws,
+                              bool no_room = false) {
+    mm_chol_plan p = {};
+    const int nblk = (n + NB - 1) / NB;
+    // block (bi, bj) can be non-zero iff 64 (bi - bj) - 63 <= half_bandwidth
+    const long bwb_l = ((long)half_bandwidth + NB - 1) / NB;
+    const int bwb = bwb_l > nblk ? nblk : (int)bwb_l;
+    const bool eligible = chol_fused_enabled() && nblk >= 2 && bwb >= 1 && bwb <= FUSED_MAX_BWB && !(n & 1) &&
+                          (long)NB * nblk * n < (1L << 31);
+    p.fused = eligible && !no_room && (gated || !ctx->chol_avoid_fused);
+    mm_chol_geom &g = p.lay.g;
+    g = mm_chol_geom{n, nblk, bwb, nblk, 0, 0, nblk * NB - n};
+    if (p.fused && sym_mode > 0 && nrhs == 1 && chol_twisted_enabled() && nblk - bwb >= 4) {
+        g.m = bwb;                       // the separator: no coupling across 64 m + 1 > half_bandwidth
+        g.a = (nblk - g.m + 1) / 2;
+        g.b = nblk - g.m - g.a;
+    }
+    p.sides = g.b > 0 ? 2 : 1;
+    chol_carve(ws, n, &p.lay);
+    if (!p.fused) return p;
+    const int G_side = (bwb + 1) + bwb * (bwb - 1) / 2;
+    // two-ended: a third group of workgroups, one per block of M x M (fewer than G: m = bwb), pre-accumulates
+    p.grid_fused = (unsigned)(g.b > 0 ? 2 * G_side + g.m * (g.m + 1) / 2 : G_side);
+    p.grid_bwd = (unsigned)(p.sides * (bwb >= 2 ? bwb : 1));
+    p.lay.nflags = 1 + 2 * tw_side_flags(nblk, bwb + 1) + (size_t)g.m * g.m;      // abort | both sides' | the pre-accumulators'
+    p.lay.nsent = (size_t)p.sides * nblk * (bwb + 1) * NB;
+    p.lay.nlpub = chol_nlpub(nblk, bwb);
+    return p;
+}
+
+extern "C" size_t mm_chol_workspace_bytes(int n) { return chol_carve(nullptr, n, nullptr); }
+
+bool mm_chol_fused_eligible(int n, int half_bandwidth) { return chol_plan(nullptr, n, half_bandwidth, 2, 1, true, nullptr).fused; }
 
 // mm_chol_solve with the rows of A / b gated by slab flags (slab_ready == nullptr: everything is there already).
 // sym_mode 0: only the lower triangle is valid and it must come back as the plain Cholesky factor (mm_chol_solve);
@@ -2483,51 +2383,32 @@ int mm_chol_solve_gated(mm_ctx *ctx, double *A, int n, double *b, int nrhs, int 
         return mm_fail(ctx, MM_ERR_ARG, "mm_chol_solve: bad argument");
     if (!ws || ws_bytes < mm_chol_workspace_bytes(n)) return mm_fail(ctx, MM_ERR_WORKSPACE, "mm_chol_solve: workspace too small");
     if (((uintptr_t)A & 15) || (n & 1)) return mm_fail(ctx, MM_ERR_ARG, "mm_chol_solve: A must be 16-byte aligned and n even");
-    const int nblk = (n + NB - 1) / NB;
-    double *Linv = (double *)ws;
-    double *ytmp = (double *)((char *)ws + mm_align_up((size_t)nblk * NB * NB * sizeof(double), 256));
-    // block (bi, bj) can be non-zero iff 64 (bi - bj) - 63 <= half_bandwidth
-    long bwb_l = ((long)half_bandwidth + NB - 1) / NB;
-    const int bwb = bwb_l > nblk ? nblk : (int)bwb_l;
-    bool fwd_done = false;  // forward substitution of right-hand side 0 already done by the fused kernel
-    const int fused_mode = chol_fused_mode();
-    if (slab_ready && !mm_chol_fused_eligible(n, half_bandwidth))
-        return mm_fail(ctx, MM_ERR_ARG, "mm_chol_solve_gated: gating needs the single-launch factorisation");
-    bool fused = fused_mode > 0 && nblk >= 2 && bwb >= 1 && bwb <= FUSED_MAX_BWB && (long)NB * nblk * n < (1L << 31);
-    if (fused && ctx->chol_avoid_fused && !slab_ready) fused = false;      // (after an abandoned attempt: mm_ba_trf)
-    TwGeom g = {n, nblk, bwb, nblk, 0, 0, nblk * NB - n};
-    if (fused && sym_mode > 0 && nrhs == 1 && chol_twisted_enabled() && nblk - bwb >= 4) {
-        g.m = bwb;                       // the separator: no coupling across 64 m + 1 > half_bandwidth
-        g.a = (nblk - g.m + 1) / 2;
-        g.b = nblk - g.m - g.a;
-    }
-    const int G_side = (bwb + 1) + bwb * (bwb - 1) / 2;
-    // two-ended: a third group of workgroups, one per block of M x M (fewer than G: m = bwb), pre-accumulates
-    const int fused_grid = g.b > 0 ? 2 * G_side + g.m * (g.m + 1) / 2 : G_side;
-    if (fused && !chol_reserve_budget(ctx, fused_grid)) {
-        if (slab_ready) return mm_fail(ctx, MM_ERR_HIP, "mm_chol_solve_gated: no room for the single-launch factorisation");
+    const bool gated = slab_ready != nullptr;
+    mm_chol_plan p = chol_plan(ctx, n, half_bandwidth, sym_mode, nrhs, gated, ws);
+    if (gated && !p.fused) return mm_fail(ctx, MM_ERR_ARG, "mm_chol_solve_gated: gating needs the single-launch factorisation");
+    if (p.fused && !chol_reserve_budget(ctx, (int)p.grid_fused)) {
+        if (gated) return mm_fail(ctx, MM_ERR_HIP, "mm_chol_solve_gated: no room for the single-launch factorisation");
         if (ctx->chol_strict_budget) {      // sharded solve: say so instead of diverging from the other ranks' path
             ctx->chol_last_path = -1;
             MM_HIP(ctx, hipMemsetAsync(info, 0xFF, sizeof(int32_t), ctx->stream));      // info = -1
             return MM_OK;
         }
-        fused = false;
-        g = TwGeom{n, nblk, bwb, nblk, 0, 0, nblk * NB - n};
+        p = chol_plan(ctx, n, half_bandwidth, sym_mode, nrhs, gated, ws, /*no_room=*/true);
     }
+    const mm_chol_layout &lay = p.lay;
+    const mm_chol_geom &g = lay.g;
+    const bool fused = p.fused;
+    const int nblk = g.nblk, bwb = g.bwb;
+    bool fwd_done = false;  // forward substitution of right-hand side 0 already done by the fused kernel
     ctx->chol_last_path = fused ? 1 : 0;
     struct InitTokenReset {      // a pre-initialisation is good for exactly one solve
         mm_ctx *c;
         ~InitTokenReset() { c->chol_init_done = nullptr; }
     } token_reset{ctx};
-    int32_t *flags = (int32_t *)((char *)ytmp + mm_align_up((size_t)(n + NB) * sizeof(double), 256));
-    double *contrib = (double *)((char *)flags + mm_align_up((2 * (2 * (size_t)nblk * (FUSED_MAX_BWB + 1) + 2 * nblk) + 64 + FUSED_MAX_BWB * FUSED_MAX_BWB) * sizeof(int32_t), 256));
-    const int sides = g.b > 0 ? 2 : 1;
-    double *contrib_bwd = (double *)((char *)contrib + mm_align_up(2 * (size_t)nblk * (FUSED_MAX_BWB + 1) * NB * sizeof(double), 256));
-    double *lpub = (double *)((char *)contrib_bwd + mm_align_up(2 * (size_t)nblk * (FUSED_MAX_BWB + 1) * NB * sizeof(double), 256));
     if (!fused) MM_HIP(ctx, hipMemsetAsync(info, 0, sizeof(int32_t), ctx->stream));
     if (fused) {
         if (!ctx->attr_chol_fused) {
-            MM_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(chol_band_fused_kernel<2>),
+            MM_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(chol_band_fused_kernel),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUSED_LDS_BYTES));
             ctx->attr_chol_fused = true;
         }
@@ -2536,30 +2417,24 @@ int mm_chol_solve_gated(mm_ctx *ctx, double *A, int n, double *b, int nrhs, int 
             MM_LAUNCH(ctx, "chol_mirror_kernel", chol_mirror_kernel, dim3(n - (g.a + g.m) * NB), dim3(256), 0, A, n,
                       (g.a + g.m) * NB, (int)(reach < n - 1 ? reach : n - 1));
         }
-        const size_t nflags = 1 + 2 * (2 * (size_t)nblk * (bwb + 1) + 2 * nblk) + (size_t)g.m * g.m;
-        static const bool no_fwd = getenv("MM_CHOL_NO_FWD") && atoi(getenv("MM_CHOL_NO_FWD")) > 0;      // (diagnostic: the forward substitution by the launch-per-column kernels)
-        const double *b_fwd = nrhs >= 1 && !no_fwd ? b : nullptr;  // the first right-hand side rides along
-        double *spub = lpub + (size_t)nblk * LPUB_BLOCK;
-        const mm_chol_init_args ia = {info, flags, nflags, (unsigned long long *)contrib_bwd, (size_t)sides * nblk * (bwb + 1) * NB,
-                                      (unsigned long long *)lpub, chol_nlpub(nblk, bwb), (unsigned long long *)Linv,
-                                      (size_t)nblk};
-        if (ctx->chol_init_done == ws && ctx->chol_init_sides == sides) {
+        const double *b_fwd = nrhs >= 1 ? b : nullptr;  // the first right-hand side rides along
+        if (ctx->chol_init_done == ws && ctx->chol_init_sides == p.sides) {
             // (the caller's own kernel ran mm_chol_init_body with mm_chol_init_plan's arguments for this workspace)
         } else {
-            MM_LAUNCH(ctx, "chol_init_kernel", chol_init_kernel, dim3(128), dim3(256), 0, ia);
+            MM_LAUNCH(ctx, "chol_init_kernel", chol_init_kernel, dim3(CHOL_INIT_GRID), dim3(256), 0, mm_chol_init_args_of(info, lay));
         }
         if (ctx->debug_abandon > 0) {      // test hook (mm_ctx_control): behave as if a workgroup had given up waiting
             --ctx->debug_abandon;
             const int32_t one = 1;
-            MM_HIP(ctx, hipMemcpyAsync(flags, &one, sizeof(one), hipMemcpyHostToDevice, ctx->stream));
+            MM_HIP(ctx, hipMemcpyAsync(lay.flags, &one, sizeof(one), hipMemcpyHostToDevice, ctx->stream));
         }
-        MM_LAUNCH(ctx, "chol_band_fused_kernel", chol_band_fused_kernel<2>, dim3(fused_grid), dim3(256), FUSED_LDS_BYTES, A, g, Linv,
-                  flags, info, b_fwd, ytmp, contrib, lpub, spub, slab_ready, cams_per_slab, n_cams);
+        MM_LAUNCH(ctx, "chol_band_fused_kernel", chol_band_fused_kernel, dim3(p.grid_fused), dim3(256), FUSED_LDS_BYTES, A, g, lay.Linv,
+                  lay.flags, info, b_fwd, lay.ytmp, lay.contrib, lay.lpub, lay.spub, slab_ready, cams_per_slab, n_cams);
         fwd_done = b_fwd != nullptr;
     } else {
         for (int k = 0; k < nblk; ++k) {
             const int k0 = k * NB;
-            double *Lk = Linv + (size_t)k * NB * NB;
+            double *Lk = lay.Linv + (size_t)k * NB * NB;
             MM_LAUNCH(ctx, "chol_diag_kernel", chol_diag_kernel, dim3(1), dim3(256), 0, A, n, k0, Lk, info);
             int m = nblk - k - 1;
             if (m > bwb) m = bwb;
@@ -2575,7 +2450,7 @@ int mm_chol_solve_gated(mm_ctx *ctx, double *A, int n, double *b, int nrhs, int 
             const int k0 = k * NB;
             if (fused && c > 0) {      // the first right-hand side's bits for every other one (see fwd_row_kernel)
                 MM_LAUNCH(ctx, "fwd_row_kernel", fwd_row_kernel, dim3(1), dim3(256), 0, (const double *)A,
-                          (const double *)(Linv + (size_t)k * NB * NB), (const double *)bc, ytmp, n, k, bwb);
+                          (const double *)(lay.Linv + (size_t)k * NB * NB), (const double *)bc, lay.ytmp, n, k, bwb);
                 continue;
             }
             long re = (long)k0 + NB + (long)bwb * NB;
@@ -2583,7 +2458,7 @@ int mm_chol_solve_gated(mm_ctx *ctx, double *A, int n, double *b, int nrhs, int 
             const int below = row_end - (k0 + NB);
             const int grid = below > 0 ? (below + 31) / 32 : 1;
             MM_LAUNCH(ctx, "fwd_step_kernel", fwd_step_kernel, dim3(grid), dim3(256), 0, (const double *)A,
-                      (const double *)(Linv + (size_t)k * NB * NB), bc, ytmp, n, k0, row_end);
+                      (const double *)(lay.Linv + (size_t)k * NB * NB), bc, lay.ytmp, n, k0, row_end);
         }
         if (fused) {  // L^T x = y in one launch
             if (!ctx->attr_chol_bwd) {
@@ -2595,11 +2470,11 @@ int mm_chol_solve_gated(mm_ctx *ctx, double *A, int n, double *b, int nrhs, int 
             // right-hand side chol_init_kernel prepared it; an abort flag left by the factorisation makes the kernel
             // leave at once -- info is -1 then anyway)
             if (c > 0) {
-                MM_HIP(ctx, hipMemsetAsync(flags, 0, sizeof(int32_t), ctx->stream));
-                MM_HIP(ctx, hipMemsetAsync(contrib_bwd, 0xFF, (size_t)sides * nblk * (bwb + 1) * NB * sizeof(double), ctx->stream));
+                MM_HIP(ctx, hipMemsetAsync(lay.flags, 0, sizeof(int32_t), ctx->stream));
+                MM_HIP(ctx, hipMemsetAsync(lay.contrib_bwd, 0xFF, lay.nsent * sizeof(double), ctx->stream));
             }
-            MM_LAUNCH(ctx, "chol_band_bwd_kernel", chol_band_bwd_kernel, dim3(sides * (bwb >= 2 ? bwb : 1)), dim3(256),
-                      BWD_LDS_BYTES, A, g, (const double *)Linv, (const double *)ytmp, bc, contrib_bwd, flags, info);
+            MM_LAUNCH(ctx, "chol_band_bwd_kernel", chol_band_bwd_kernel, dim3(p.grid_bwd), dim3(256), BWD_LDS_BYTES, A, g,
+                      (const double *)lay.Linv, (const double *)lay.ytmp, bc, lay.contrib_bwd, lay.flags, info);
             continue;
         }
         for (int k = nblk - 1; k >= 0; --k) {  // L^T x = y
@@ -2609,40 +2484,21 @@ int mm_chol_solve_gated(mm_ctx *ctx, double *A, int n, double *b, int nrhs, int 
             const int left = k0 - col_begin;
             const int grid = left > 0 ? (left + NB - 1) / NB : 1;
             MM_LAUNCH(ctx, "bwd_step_kernel", bwd_step_kernel, dim3(grid), dim3(256), 0, (const double *)A,
-                      (const double *)(Linv + (size_t)k * NB * NB), ytmp, bc, n, k0, col_begin);
+                      (const double *)(lay.Linv + (size_t)k * NB * NB), lay.ytmp, bc, n, k0, col_begin);
         }
     }
     if (fused) chol_budget_mark(ctx);
     return MM_OK;
 }
 
-// see mm_common.h: the same geometry / layout lines as mm_chol_solve_gated(sym_mode 2, one right-hand side, not gated)
+// see mm_common.h: the fills of the plan of mm_chol_solve_sym(both triangles) on this workspace
 bool mm_chol_init_plan(mm_ctx *ctx, int n, int half_bandwidth, int32_t *info, void *ws, size_t ws_bytes, mm_chol_init_args *out, int *sides_out, int *bwb_out) {
     if (!ctx || !ws || !info || !out || n <= 0 || (n & 1) || half_bandwidth < 0 || ws_bytes < mm_chol_workspace_bytes(n)) return false;
-    const int nblk = (n + NB - 1) / NB;
-    long bwb_l = ((long)half_bandwidth + NB - 1) / NB;
-    const int bwb = bwb_l > nblk ? nblk : (int)bwb_l;
-    const bool fused = chol_fused_mode() > 0 && nblk >= 2 && bwb >= 1 && bwb <= FUSED_MAX_BWB && (long)NB * nblk * n < (1L << 31) &&
-                       !ctx->chol_avoid_fused;
-    if (!fused) return false;
-    TwGeom g = {n, nblk, bwb, nblk, 0, 0, nblk * NB - n};
-    if (chol_twisted_enabled() && nblk - bwb >= 4) {
-        g.m = bwb;
-        g.a = (nblk - g.m + 1) / 2;
-        g.b = nblk - g.m - g.a;
-    }
-    const int sides = g.b > 0 ? 2 : 1;
-    double *Linv = (double *)ws;
-    double *ytmp = (double *)((char *)ws + mm_align_up((size_t)nblk * NB * NB * sizeof(double), 256));
-    int32_t *flags = (int32_t *)((char *)ytmp + mm_align_up((size_t)(n + NB) * sizeof(double), 256));
-    double *contrib = (double *)((char *)flags + mm_align_up((2 * (2 * (size_t)nblk * (FUSED_MAX_BWB + 1) + 2 * nblk) + 64 + FUSED_MAX_BWB * FUSED_MAX_BWB) * sizeof(int32_t), 256));
-    double *contrib_bwd = (double *)((char *)contrib + mm_align_up(2 * (size_t)nblk * (FUSED_MAX_BWB + 1) * NB * sizeof(double), 256));
-    double *lpub = (double *)((char *)contrib_bwd + mm_align_up(2 * (size_t)nblk * (FUSED_MAX_BWB + 1) * NB * sizeof(double), 256));
-    *out = mm_chol_init_args{info, flags, 1 + 2 * (2 * (size_t)nblk * (bwb + 1) + 2 * nblk) + (size_t)g.m * g.m,
-                             (unsigned long long *)contrib_bwd, (size_t)sides * nblk * (bwb + 1) * NB, (unsigned long long *)lpub,
-                             chol_nlpub(nblk, bwb), (unsigned long long *)Linv, (size_t)nblk};
-    if (sides_out) *sides_out = sides;
-    if (bwb_out) *bwb_out = bwb;
+    const mm_chol_plan p = chol_plan(ctx, n, half_bandwidth, 2, 1, false, ws);
+    if (!p.fused) return false;
+    *out = mm_chol_init_args_of(info, p.lay);
+    if (sides_out) *sides_out = p.sides;
+    if (bwb_out) *bwb_out = p.lay.g.bwb;
     return true;
 }
 void mm_chol_init_done(mm_ctx *ctx, const void *ws, int sides) {
@@ -2651,44 +2507,16 @@ void mm_chol_init_done(mm_ctx *ctx, const void *ws, int sides) {
 }
 
 // ---- batched factorisation + substitutions (mm_ba_trf_batched, trf.hip) --------------------------------------------------------
-// The geometry and workspace layout mm_chol_solve_sym(both triangles) would use for this problem alone; fails (the caller
-// then solves the batch one problem at a time) when that would not be the single-launch path.
+// The plan mm_chol_solve_sym(both triangles) would make for this problem alone; fails (the caller then solves the batch one
+// problem at a time) when that would not be the single-launch path.
 int mm_batch_chol_setup(mm_ctx *ctx, mm_batch_prob *bp, void *ws, size_t ws_bytes) {
-    const int n = (int)bp->nc, hb = bp->half_bw;
+    const int n = (int)bp->nc;
     if (!ws || ws_bytes < mm_chol_workspace_bytes(n) || (n & 1)) return mm_fail(ctx, MM_ERR_WORKSPACE, "mm_ba_trf_batched: Cholesky workspace");
-    const int nblk = (n + NB - 1) / NB;
-    long bwb_l = ((long)hb + NB - 1) / NB;
-    const int bwb = bwb_l > nblk ? nblk : (int)bwb_l;
-    const bool fused = chol_fused_mode() > 0 && nblk >= 2 && bwb >= 1 && bwb <= FUSED_MAX_BWB && (long)NB * nblk * n < (1L << 31) &&
-                       !ctx->chol_avoid_fused;
-    if (!fused) return mm_fail(ctx, MM_ERR_ARG, "mm_ba_trf_batched: a reduced system outside the single-launch factorisation");
-    TwGeom g = {n, nblk, bwb, nblk, 0, 0, nblk * NB - n};
-    if (chol_twisted_enabled() && nblk - bwb >= 4) {
-        g.m = bwb;
-        g.a = (nblk - g.m + 1) / 2;
-        g.b = nblk - g.m - g.a;
-    }
-    const int G_side = (bwb + 1) + bwb * (bwb - 1) / 2;
-    const int sides = g.b > 0 ? 2 : 1;
-    bp->g_chol = (uint32_t)(g.b > 0 ? 2 * G_side + g.m * (g.m + 1) / 2 : G_side);
-    bp->g_bwd = (uint32_t)(sides * (bwb >= 2 ? bwb : 1));
-    bp->chol_n = g.n; bp->chol_nblk = g.nblk; bp->chol_bwb = g.bwb; bp->chol_a = g.a; bp->chol_m = g.m; bp->chol_b = g.b; bp->chol_pad = g.pad;
-    double *Linv = (double *)ws;
-    double *ytmp = (double *)((char *)ws + mm_align_up((size_t)nblk * NB * NB * sizeof(double), 256));
-    int32_t *flags = (int32_t *)((char *)ytmp + mm_align_up((size_t)(n + NB) * sizeof(double), 256));
-    double *contrib = (double *)((char *)flags + mm_align_up((2 * (2 * (size_t)nblk * (FUSED_MAX_BWB + 1) + 2 * nblk) + 64 + FUSED_MAX_BWB * FUSED_MAX_BWB) * sizeof(int32_t), 256));
-    double *contrib_bwd = (double *)((char *)contrib + mm_align_up(2 * (size_t)nblk * (FUSED_MAX_BWB + 1) * NB * sizeof(double), 256));
-    double *lpub = (double *)((char *)contrib_bwd + mm_align_up(2 * (size_t)nblk * (FUSED_MAX_BWB + 1) * NB * sizeof(double), 256));
-    bp->chol_Linv = Linv;
-    bp->chol_ytmp = ytmp;
-    bp->chol_flags = flags;
-    bp->chol_contrib = contrib;
-    bp->chol_contrib_bwd = contrib_bwd;
-    bp->chol_lpub = lpub;
-    bp->chol_spub = lpub + (size_t)nblk * LPUB_BLOCK;
-    bp->chol_nflags = 1 + 2 * (2 * (size_t)nblk * (bwb + 1) + 2 * nblk) + (size_t)g.m * g.m;
-    bp->chol_nsent = (size_t)sides * nblk * (bwb + 1) * NB;
-    bp->chol_nlpub = chol_nlpub(nblk, bwb);
+    const mm_chol_plan p = chol_plan(ctx, n, bp->half_bw, 2, 1, false, ws);
+    if (!p.fused) return mm_fail(ctx, MM_ERR_ARG, "mm_ba_trf_batched: a reduced system outside the single-launch factorisation");
+    bp->chol = p.lay;
+    bp->g_chol = p.grid_fused;
+    bp->g_bwd = p.grid_bwd;
     return MM_OK;
 }
 int mm_batch_chol(mm_ctx *ctx, const mm_batch_prob *tab, const int32_t *list, int n_list, unsigned max_g_chol, unsigned max_g_bwd) {

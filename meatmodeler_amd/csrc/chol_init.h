@@ -7,6 +7,12 @@
 constexpr int MM_CHOL_NB = 64;                            // block size of the factorisation (chol.hip's NB)
 constexpr unsigned long long MM_CHOL_SENTINEL = ~0ull;    // the NaN every polled word starts as
 
+// the fills a planned solve needs (host: mm_chol_solve_gated, mm_chol_init_plan; device: chol_init_batch_kernel)
+__host__ __device__ inline mm_chol_init_args mm_chol_init_args_of(int32_t *info, const mm_chol_layout &l) {
+    return mm_chol_init_args{info, l.flags, (size_t)l.nflags, (unsigned long long *)l.contrib_bwd, (size_t)l.nsent,
+                             (unsigned long long *)l.lpub, (size_t)l.nlpub, (unsigned long long *)l.Linv, (size_t)l.g.nblk};
+}
+
 __device__ __forceinline__ void mm_chol_init_body(const mm_chol_init_args &a, const unsigned bx, const unsigned gx) {
     // (lpub covers both hand-over buffers: the streamed pieces of the diagonal blocks and the sub-diagonal blocks)
     const size_t i = (size_t)bx * 256 + threadIdx.x, stride = (size_t)gx * 256;

@@ -125,8 +125,29 @@ int mm_ba_damp_damping(mm_ctx *ctx, int F, int P, const double *B, const double 
                        const double *d11, double Delta, double min_damping, double *damp_out, double *Bd, double *Cd);
 // chol.hip: give back the workgroups a context has reserved for a single-launch factorisation (call after a host sync)
 void mm_chol_release_budget(mm_ctx *ctx);
-// chol.hip internals used by the overlapped Schur + solve entry point (schur.hip)
+// chol.hip internals used by the overlapped Schur + solve entry point (schur.hip): would a gated solve of this system take
+// the single-launch path (the only one that honours the gating)?
 bool mm_chol_fused_eligible(int n, int half_bandwidth);
+// chol.hip: block geometry of one banded solve (what its single-launch kernels are given)
+struct mm_chol_geom {
+    int n, nblk, bwb;
+    int a, m, b;  // block columns eliminated by side 0 first (T), last (M), and by side 1 (Bt); b == 0: one-ended
+    int pad;      // 64 nblk - n virtual identity rows behind the matrix
+};
+// where the buffers of that solve sit in its workspace, and how much of them is filled before a single launch (chol_init.h)
+struct mm_chol_layout {
+    double *Linv, *ytmp, *contrib, *contrib_bwd, *lpub, *spub;
+    int32_t *flags;
+    mm_chol_geom g;
+    uint64_t nflags, nsent, nlpub;      // flag words to clear | sentinel words in contrib_bwd | in lpub and spub (contiguous)
+};
+// everything that is decided once per solve (chol.hip: chol_plan is the only place that computes any of it)
+struct mm_chol_plan {
+    mm_chol_layout lay;
+    bool fused;                        // single launch (else: three launches per block column, one-ended, no fills)
+    int sides;                         // 2: eliminated from both ends (lay.g.b > 0)
+    unsigned grid_fused, grid_bwd;     // workgroups of chol_band_fused_kernel / chol_band_bwd_kernel
+};
 // what chol_init_kernel fills before a single-launch factorisation (chol_init.h has the device function)
 struct mm_chol_init_args {
     int32_t *info, *flags;
@@ -189,10 +210,7 @@ struct mm_batch_prob {
     // reduced camera system (schur.hip) and its factorisation (chol.hip)
     double *schur_partial, *schur_camtab;
     int32_t *schur_seg_done, *schur_desc;
-    double *chol_Linv, *chol_ytmp, *chol_contrib, *chol_contrib_bwd, *chol_lpub, *chol_spub;
-    int32_t *chol_flags;
-    int32_t chol_n, chol_nblk, chol_bwb, chol_a, chol_m, chol_b, chol_pad;      // (TwGeom of chol.hip)
-    uint64_t chol_nflags, chol_nsent, chol_nlpub;
+    mm_chol_layout chol;          // (of the plan mm_batch_chol_setup made; its grids are g_chol and g_bwd below)
     int32_t half_bw, chol_sym_mirror;
     // per-kernel grids (what the single-problem launch would use)
     uint32_t g_vec, g_res, g_jvp, g_pblk, g_obs, g_pts, g_scale, g_damp, g_prep, g_pairs, g_chol, g_bwd, g_coef, g_zero;

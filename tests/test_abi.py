@@ -29,6 +29,10 @@ def test_abi_version_and_sizes_without_gpu():
     assert _lib.lib.mm_abi_version() == 3
     assert _lib.lib.mm_bf_workspace_bytes(1, 4000, 4000) > 0
     assert _lib.lib.mm_chol_workspace_bytes(3000) >= 47 * 64 * 64 * 8
+    # the workspace is one walk over seven regions sized for the widest single-launch band: its end at the block boundaries
+    # (values of the formula before the walk and the size were made one function)
+    sizes = {2: 997632, 64: 997888, 66: 1993728, 130: 2989824, 322: 5978112, 446: 6974464, 3000: 46819072}
+    assert {n: _lib.lib.mm_chol_workspace_bytes(n) for n in sizes} == sizes
     p = _lib.OrbParams(4000, 8, 31, 20, 1.2, 0)
     assert _lib.lib.mm_orb_workspace_bytes(2, 1080, 1920, ctypes.byref(p)) > 2 * 1920 * 1080
     assert ctypes.sizeof(_lib.BAProblem) == 16 + 8 * 8 + 16 + 2 * 8 + 8 + 6 * 8   # matches sizeof(mm_ba_problem)

@@ -1,5 +1,5 @@
 """Time mm_chol_solve on the reduced-camera-system shape of the 500-frame clip (n = 3000, half bandwidth 528).
-usage: MM_CHOL_FUSED={0,1,2} MM_CHOL_TWISTED={0,1} python tools/bench_chol.py [n] [hb] [reps] [sym]
+usage: MM_CHOL_FUSED={0,1} MM_CHOL_TWISTED={0,1} python tools/bench_chol.py [n] [hb] [reps] [sym]
 sym = 1 (default): mm_chol_solve_sym (solution only; narrow bands are eliminated from both ends); 0: mm_chol_solve."""
 import os
 import sys
