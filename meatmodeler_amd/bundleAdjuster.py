@@ -16,6 +16,7 @@ Jacobian; see DESIGN.md §BA for what "parity" means on this gauge-free problem.
 Host Python only sequences launches and does the 2x2 / scalar algebra of the trust region; torch is used for
 device buffers and a handful of axpy / dot reductions on the parameter vector.
 """
+import math
 import os
 import time
 import warnings
@@ -191,6 +192,98 @@ def _check_termination(dF, F, dx_norm, x_norm, ratio, ftol, xtol):
     return None
 
 
+class _TrfDecide:
+    """The host's decisions of the trust-region solve -- accept / reject / try again / terminate as SciPy's trf_no_bounds
+    takes them, plus the rule for raising the damping when the reduced camera system is not positive definite -- stated
+    once for the two loops sequenced from Python.  The Python statement of csrc/trf_decide.h, method for method and field
+    for field (tests/test_trf_decisions_cpu.py replays the same boards through both); see there for a driver's iteration.
+    `log` (a list, optional) receives the rows of the verbose=2 table, NaN where SciPy prints nothing."""
+
+    # what the machine answers (the numbers of csrc/trf_decide.h)
+    BODY, TRIAL, FINAL, DONE, RETRY, USABLE, ABANDONED, INDEFINITE = range(8)
+
+    def __init__(self, cost, xx_scaled, n, ftol, xtol, gtol, max_nfev=None, min_damping=0.0, log=None):
+        self.Delta = math.sqrt(xx_scaled)      # Delta0 = |x * scale_inv|  (trf.py:428)
+        if self.Delta == 0:
+            self.Delta = 1.0
+        self.cost = self.cost0 = cost
+        self.x_norm = 0.0
+        self.step_norm = self.actual = self.g_norm = float("nan")
+        self.min_damping = min_damping if min_damping > 0 else 1e-9
+        self.reg = 0.0
+        self.nfev = self.njev = 1
+        self.iteration = self.attempt = 0
+        self.termination = None
+        self.max_nfev = max_nfev if max_nfev is not None and max_nfev > 0 else 100 * n
+        self.accepted = False
+        self.ftol, self.xtol, self.gtol = ftol, xtol, gtol
+        self.log, self.n_log = log, 0
+
+    def begin(self):
+        return self.FINAL if self.termination is not None or self.nfev == self.max_nfev else self.BODY
+
+    def on_solve(self, info, reg_used, g_norm, xx):
+        """The board of an iteration's first trial step: info of the factorisation, the damping it ran with, |g|_inf, |x|^2."""
+        if info < 0:
+            return self.ABANDONED      # (nothing noted: the driver may issue the same attempt again)
+        if info > 0:
+            if reg_used <= self.min_damping * (1.0 + 1e-12):      # failed AT the floor: the floor was too low
+                self.min_damping *= 100.0
+            self.reg = reg_used * 100.0
+            self.attempt += 1
+            return self.INDEFINITE if self.attempt >= 6 else self.RETRY
+        self.attempt = 0
+        self.g_norm = g_norm
+        if g_norm < self.gtol:      # (checked before the step is used, as trf.py:443 does)
+            self.termination = 1
+        self._emit_row()
+        if self.termination is not None:
+            return self.DONE
+        self.x_norm = math.sqrt(xx)
+        self.actual = -1.0
+        return self.USABLE
+
+    def on_trial(self, predicted, step_h_norm, step_norm, cost2_new):
+        """A trial step: predicted reduction, |p| in the scaled variables, the unscaled step norm, twice the cost there."""
+        cost_new = 0.5 * cost2_new
+        self.nfev += 1
+        if not math.isfinite(cost_new):
+            self.Delta = 0.25 * step_h_norm
+        else:
+            self.actual = self.cost - cost_new
+            Delta_new, ratio = _update_tr_radius(self.Delta, self.actual, predicted, step_h_norm,
+                                                 step_h_norm > 0.95 * self.Delta)
+            self.step_norm = step_norm
+            self.termination = _check_termination(self.actual, self.cost, step_norm, self.x_norm, ratio, self.ftol, self.xtol)
+            if self.termination is None:
+                self.Delta = Delta_new
+        if self.termination is None and self.actual <= 0 and self.nfev < self.max_nfev:
+            return self.TRIAL
+        self.accepted = self.actual > 0
+        if self.accepted:
+            self.cost = cost_new
+            self.njev += 1
+        else:
+            self.step_norm = 0.0
+            self.actual = 0.0
+        self.iteration += 1
+        return self.begin()
+
+    def on_final(self, g_norm):
+        self.g_norm = g_norm
+        self._emit_row()
+        return self.DONE
+
+    @property
+    def status(self):
+        return 0 if self.termination is None else self.termination
+
+    def _emit_row(self):
+        if self.log is not None:
+            self.log.append((self.iteration, self.nfev, self.cost, self.actual, self.step_norm, self.g_norm))
+        self.n_log += 1
+
+
 _MESSAGES = {-1: "Improper input parameters status returned from `leastsq`",
              0: "The maximum number of function evaluations is exceeded.",
              1: "`gtol` termination condition is satisfied.", 2: "`ftol` termination condition is satisfied.",
@@ -204,8 +297,9 @@ def _print_header():
 
 
 def _print_iteration(it, nfev, cost, red, step, opt):
-    red = " " * 15 if red is None else f"{red:^15.2e}"
-    step = " " * 15 if step is None else f"{step:^15.2e}"
+    """One row of the table; None (solvePose) or NaN (the rows of the decision machines) where SciPy prints nothing."""
+    red = " " * 15 if red is None or np.isnan(red) else f"{red:^15.2e}"
+    step = " " * 15 if step is None or np.isnan(step) else f"{step:^15.2e}"
     print(f"{it:^15}{nfev:^15}{cost:^15.4e}{red}{step}{opt:^15.2e}")
 
 
@@ -362,7 +456,6 @@ class SchurTRF:
         # so the packed band [n, half_bw + 1] carries everything the factorisation reads.
         band_exchange = (self.allreduce is not None and hasattr(pb, "band_view")
                          and span_all <= getattr(pb, "max_band_span", 192) and half_bw < nc)
-        nfev, njev = 1, 1
         if (self.driver == "library" and self.allreduce is not None and hasattr(pb, "trf_solve_dist")
                 and getattr(self.allreduce, "world_size", 1) <= 16):
             # sharded: the same library loop, with this process group's all-reduce as its callback (mm_ba_trf_dist)
@@ -372,23 +465,16 @@ class SchurTRF:
         B, C = self._normal(x, g)
         si = self._scale_inv(B, C)
         xs = x * si
-        Delta = float(torch.sqrt(self._dots([(xs, xs)])[0]).item())
-        if Delta == 0:
-            Delta = 1.0
-        if max_nfev is None:
-            max_nfev = n * 100
-        alpha = 0.0
-        termination = None
-        iteration = 0
-        step_norm = None
-        actual = None
+        # every decision from here on is the machine's; this loop does the device work its answers ask for
+        td = _TrfDecide(cost, float(self._dots([(xs, xs)])[0].item()), n, ftol, xtol, gtol, max_nfev, self.min_damping,
+                        log=[] if verbose == 2 else None)
         if verbose == 2:
             _print_header()
         # wall time between the host synchronisation points of an iteration (the syncs drain the stream, so these are
         # real intervals): normal equations, damping, Schur, Cholesky, subspace .. sync A | trial steps .. accept
         seg = {"to_syncA": 0.0, "syncA_to_accept": 0.0}
         t_mark = time.perf_counter()
-        g_norm = None
+        state = td.begin()
         while True:
             # g_h = d * g (d = 1 / scale_inv) and d * g_h in one pass that also yields |g_h|^2 and |g|_inf
             gh, ghs = torch.empty_like(g), torch.empty_like(g)
@@ -402,10 +488,10 @@ class SchurTRF:
                 gmax = r0[1, 2:3]
             u1 = pb.jvp(self._cams(x), self._pts(x), self._cams(ghs), self._pts(ghs)).reshape(-1)   # J (d g_h)
             d11_t = self._dots_sharded([(u1, u1)])
-            if termination is not None or nfev == max_nfev:
-                g_norm = float(gmax.item())
+            if state == _TrfDecide.FINAL:
+                td.on_final(float(gmax.item()))
                 if verbose == 2:
-                    _print_iteration(iteration, nfev, cost, actual, step_norm, g_norm)
+                    _print_iteration(*td.log[-1])
                 break
             # Cauchy-derived regulariser (trf.py:473-477) computed on the device: the reduced system is built and
             # factored without the host having seen |g|, |g_h| or |J_h g_h| (they arrive with sync A).
@@ -414,10 +500,10 @@ class SchurTRF:
             # LSMR copes with a singular system, a Cholesky factorisation needs `reg` to stay above rounding:
             # a floor of 1e-9 (relative to the unit diagonal of the scaled system), x100 on a bad pivot, and the
             # raised floor is kept for the rest of the solve (a system that needed it once needs it again).
-            damp = pb.trf_damping(gh2_t, d11_t, Delta, self.min_damping)
+            damp = pb.trf_damping(gh2_t, d11_t, td.Delta, td.min_damping)
             reg_eff = damp[1:2]
             gc, gp = self._cams(g), self._pts(g)
-            for attempt in range(6):
+            while True:
                 Bd, Cd = self._damped_blocks(B, C, si, reg_eff)
                 if self.allreduce is None and hasattr(pb, "schur_solve"):
                     # one GPU: the build of S and its factorisation overlap (mm_ba_schur_solve)
@@ -473,9 +559,10 @@ class SchurTRF:
                 # ---- host sync A ----
                 vals = torch.cat([info.to(torch.float64), wn2.reshape(1), gn2.reshape(1), bs, nn, gmax,
                                   gh2_t.reshape(1), d11_t.reshape(1), reg_eff]).tolist()
-                if int(vals[0]) == 0:
-                    break
-                if int(vals[0]) < 0:
+                info_h, wn2, gn2, u1Jq2, b22, n11, n12, n22, g2, xx, g_norm, gh2, d11, reg_used = vals
+                solved = td.on_solve(int(info_h), reg_used, g_norm, xx)
+                self.min_damping = td.min_damping      # (a raised floor outlives the solve)
+                if solved == _TrfDecide.ABANDONED:
                     # the single-launch factorisation gave up waiting (its workgroups or the producer of S were not
                     # co-resident: another tenant, a profiler attaching mid-run).  One GPU: redo this attempt with the
                     # build and the solve one after the other and stay there; otherwise there is nothing to fall back to.
@@ -483,66 +570,47 @@ class SchurTRF:
                         self._serial_fallback(x, Bd, Cd, gc, gp, half_bw, solve=False)
                         continue
                     raise MMError("mm_chol_solve: the fused banded factorisation was abandoned (info = -1)")
-                reg_eff = reg_eff * 100.0
-                if vals[-1] <= self.min_damping * (1.0 + 1e-12):      # failed AT the floor: the floor was too low
-                    self.min_damping *= 100.0
-            else:
-                raise MMError(f"reduced camera system is not positive definite (pivot {int(vals[0])})")
-            _, wn2, gn2, u1Jq2, b22, n11, n12, n22, g2, xx, g_norm, gh2, d11, _ = vals
+                if solved != _TrfDecide.RETRY:
+                    break
+                reg_eff = torch.full_like(reg_eff, td.reg)
+            if solved == _TrfDecide.INDEFINITE:
+                raise MMError(f"reduced camera system is not positive definite (pivot {int(info_h)})")
             gh_norm = np.sqrt(gh2)
             b11, b12 = d11 / gh2, u1Jq2 / gh_norm
             t_now = time.perf_counter()
             seg["to_syncA"] += t_now - t_mark
             t_mark = t_now
-            if g_norm < gtol:                              # (checked before the step is used, as trf.py:443 does)
-                termination = 1
             if verbose == 2:
-                _print_iteration(iteration, nfev, cost, actual, step_norm, g_norm)
-            if termination is not None:
+                _print_iteration(*td.log[-1])
+            if solved == _TrfDecide.DONE:                             # gtol
                 break
             if not (wn2 > 1e-28 * max(gn2, 1e-300)):       # gn_h parallel to g_h: the subspace is one-dimensional
                 s2 = torch.zeros_like(s1)
                 b12, b22, n12, n22, g2 = 0.0, 1.0, 0.0, 0.0, 0.0
             B_S = np.array([[b11, b12], [b12, b22]])
             g_S = np.array([gh_norm, g2])
-            x_norm = np.sqrt(xx)
-            actual = -1.0
-            while actual <= 0 and nfev < max_nfev:
-                p_S, _ = _solve_trust_region_2d(B_S, g_S, Delta)
+            state = _TrfDecide.TRIAL
+            while state == _TrfDecide.TRIAL:      # (the machine says when another trial step of this iteration is needed)
+                p_S, _ = _solve_trust_region_2d(B_S, g_S, td.Delta)
                 predicted = -(0.5 * p_S @ B_S @ p_S + g_S @ p_S)
                 x_new = torch.empty_like(x)
                 pb.trf_fused(4, [x, s1, s2], [x_new], h0=float(p_S[0]), h1=float(p_S[1]), split=nc)
-                cost_new = 0.5 * float(self._cost_dev(x_new).item())      # ---- host sync 3 (per trial step) ----
-                nfev += 1
-                step_h_norm = float(_norm(p_S))
-                if not np.isfinite(cost_new):
-                    Delta = 0.25 * step_h_norm
-                    continue
-                actual = cost - cost_new
-                Delta_new, ratio = _update_tr_radius(Delta, actual, predicted, step_h_norm, step_h_norm > 0.95 * Delta)
+                cost2_new = float(self._cost_dev(x_new).item())           # ---- host sync 3 (per trial step) ----
                 step_norm = float(np.sqrt(max(p_S[0] ** 2 * n11 + 2 * p_S[0] * p_S[1] * n12 + p_S[1] ** 2 * n22, 0.0)))
-                termination = _check_termination(actual, cost, step_norm, x_norm, ratio, ftol, xtol)
-                if termination is not None:
-                    break
-                alpha *= Delta / Delta_new
-                Delta = Delta_new
+                state = td.on_trial(predicted, float(_norm(p_S)), step_norm, cost2_new)
             t_now = time.perf_counter()
             seg["syncA_to_accept"] += t_now - t_mark
             t_mark = t_now
-            if actual > 0:
-                x, cost = x_new, cost_new
+            if td.accepted:
+                x = x_new
                 B, C = self._normal(x, g)
-                njev += 1
                 si = self._scale_inv(B, C, si)
-            else:
-                step_norm = 0
-                actual = 0
-            iteration += 1
-        if termination is None:
-            termination = 0
-        return BAResult(cams=self._cams(x).clone(), pts=self._pts(x).clone(), cost=cost, optimality=g_norm, nfev=nfev,
-                        njev=njev, status=termination, message=_MESSAGES[termination], success=termination > 0,
-                        iterations=iteration, host_segments_ms={k: 1e3 * v for k, v in seg.items()})
+        return self._result(td, x, seg)
+
+    def _result(self, td, x, seg):
+        return BAResult(cams=self._cams(x).clone(), pts=self._pts(x).clone(), cost=td.cost, optimality=td.g_norm,
+                        nfev=td.nfev, njev=td.njev, status=td.status, message=_MESSAGES[td.status], success=td.status > 0,
+                        iterations=td.iteration, host_segments_ms={k: 1e3 * v for k, v in seg.items()})
 
 
 def _solve_library(self, x, ftol, xtol, gtol, max_nfev, verbose, dist=None):
@@ -560,8 +628,8 @@ def _solve_library(self, x, ftol, xtol, gtol, max_nfev, verbose, dist=None):
     self.min_damping = rep.min_damping
     if verbose == 2:
         _print_header()
-        for it, nf, c, red, stp, opt in rows:
-            _print_iteration(it, nf, c, None if np.isnan(red) else red, None if np.isnan(stp) else stp, opt)
+        for row in rows:
+            _print_iteration(*row)
         if rep.log_rows > len(rows):
             print(f"... ({rep.log_rows - len(rows)} more iterations)")
     return BAResult(cams=self._cams(x).clone(), pts=self._pts(x).clone(), cost=rep.cost, optimality=rep.optimality,
@@ -648,40 +716,35 @@ def _solve_device_loop(self, x, g, cost, half_bw, ftol, xtol, gtol, max_nfev, ve
     n = nc + 3 * P
     f64 = dict(dtype=torch.float64, device=pb.device)
     cams, pts = self._cams, self._pts
-    nfev, njev = 1, 1
     B, C = self._normal(x, g)
     si = self._scale_inv(B, C)
     xs = x * si
-    Delta = float(torch.sqrt(fix_params(pb.multi_dot([(xs, xs)], nc), 1)[0, 2]).item())
+    # every decision from here on is the machine's; this loop does the device work its answers ask for
+    td = _TrfDecide(cost, float(fix_params(pb.multi_dot([(xs, xs)], nc), 1)[0, 2].item()), n, ftol, xtol, gtol, max_nfev,
+                    self.min_damping, log=[] if verbose == 2 else None)
     del xs
-    if Delta == 0:
-        Delta = 1.0
-    if max_nfev is None:
-        max_nfev = n * 100
     gh, ghs, gn, q1, w, q2, s1, s2, x_new = (torch.empty_like(g) for _ in range(9))
     board = torch.zeros(16, **f64)
     cost_slot = board[14:15]
-    alpha = 0.0
-    termination, iteration, step_norm, actual, g_norm = None, 0, None, None, None
     if verbose == 2:
         _print_header()
     seg = {"to_syncA": 0.0, "syncA_to_accept": 0.0}
     t_mark = time.perf_counter()
+    state = td.begin()
     while True:
         r0 = fix_params(pb.trf_fused(0, [g, si], [gh, ghs], split=nc), 1, max_row=1)   # rows: |g_h|^2 ; max |g|
         gh2_t = r0[0, 2:3]
         u1, d11 = pb.jvp_dots(cams(x), pts(x), cams(ghs), pts(ghs))         # J (d g_h) and |J d g_h|^2 in one sweep
         d11 = fix_residual(d11)
-        if termination is not None or nfev == max_nfev:
-            g_norm = float(r0[1, 2].item())
+        if state == _TrfDecide.FINAL:
+            td.on_final(float(r0[1, 2].item()))
             if verbose == 2:
-                _print_iteration(iteration, nfev, cost, actual, step_norm, g_norm)
+                _print_iteration(*td.log[-1])
             break
-        damp = pb.trf_damping(gh2_t, d11[0, 2:3], Delta, self.min_damping)
+        damp = pb.trf_damping(gh2_t, d11[0, 2:3], td.Delta, td.min_damping)
         reg_eff = damp[1:2]
         gc, gp = cams(g), pts(g)
-        vals = None
-        for attempt in range(6):
+        while True:
             Bd, Cd = self._damped_blocks(B, C, si, reg_eff)
             info, v, Cinv = reduced_solve(x, Bd, Cd, gc, gp)
             dp = pb.backsub(cams(x), pts(x), Cinv, gp, v.view(F, 6)).reshape(-1)
@@ -700,11 +763,10 @@ def _solve_device_loop(self, x, g, cost, half_bw, ftol, xtol, gtol, max_nfev, ve
                     ar(cost_slot)
                 return board.tolist()                                     # ---- the host sync of a trial step ----
 
-            vals = trial(Delta)          # enqueued before the host knows whether the factorisation succeeded
-            inf = int(vals[6])
-            if inf == 0:
-                break
-            if inf < 0:
+            vals = trial(td.Delta)       # enqueued before the host knows whether the factorisation succeeded
+            solved = td.on_solve(int(vals[6]), vals[13], vals[10], vals[9])
+            self.min_damping = td.min_damping      # (a raised floor outlives the solve)
+            if solved == _TrfDecide.ABANDONED:
                 # the single-launch factorisation gave up waiting (see the generic loop): build and solve one after
                 # the other from here on
                 if ar is None and getattr(pb, "overlap", False):
@@ -720,60 +782,30 @@ def _solve_device_loop(self, x, g, cost, half_bw, ftol, xtol, gtol, max_nfev, ve
                         pb.ctx.control(pb.ctx.CTL_CHOL_AVOID_FUSED, 1)
                         continue
                 raise MMError("mm_chol_solve: the fused banded factorisation was abandoned (info = -1)")
-            if vals[13] <= self.min_damping * (1.0 + 1e-12):      # failed AT the floor: the floor was too low
-                self.min_damping *= 100.0
-            reg_eff = reg_eff * 100.0
-        else:
+            if solved != _TrfDecide.RETRY:
+                break
+            reg_eff = torch.full_like(reg_eff, td.reg)
+        if solved == _TrfDecide.INDEFINITE:
             raise MMError(f"reduced camera system is not positive definite (pivot {int(vals[6])})")
-        g_norm, xx = vals[10], vals[9]
         t_now = time.perf_counter()
         seg["to_syncA"] += t_now - t_mark
         t_mark = t_now
-        if g_norm < gtol:                              # (checked before the step is used, as trf.py:443 does; the
-            termination = 1                            # trial point enqueued above is simply dropped)
         if verbose == 2:
-            _print_iteration(iteration, nfev, cost, actual, step_norm, g_norm)
-        if termination is not None:
+            _print_iteration(*td.log[-1])
+        if solved == _TrfDecide.DONE:                                 # gtol: the trial point enqueued above is simply dropped
             break
-        x_norm = np.sqrt(xx)
-        actual = -1.0
-        have = True
-        while actual <= 0 and nfev < max_nfev:
-            if not have:
-                vals = trial(Delta)
-            have = False
-            predicted, step_h_norm, step_norm_dev = vals[2], vals[3], vals[4]
-            cost_new = 0.5 * vals[14]
-            nfev += 1
-            if not np.isfinite(cost_new):
-                Delta = 0.25 * step_h_norm
-                continue
-            actual = cost - cost_new
-            Delta_new, ratio = _update_tr_radius(Delta, actual, predicted, step_h_norm, step_h_norm > 0.95 * Delta)
-            step_norm = float(step_norm_dev)
-            termination = _check_termination(actual, cost, step_norm, x_norm, ratio, ftol, xtol)
-            if termination is not None:
-                break
-            alpha *= Delta / Delta_new
-            Delta = Delta_new
+        state = td.on_trial(vals[2], vals[3], vals[4], vals[14])
+        while state == _TrfDecide.TRIAL:      # (the machine says when another trial step of this iteration is needed)
+            vals = trial(td.Delta)
+            state = td.on_trial(vals[2], vals[3], vals[4], vals[14])
         t_now = time.perf_counter()
         seg["syncA_to_accept"] += t_now - t_mark
         t_mark = t_now
-        if actual > 0:
+        if td.accepted:
             x, x_new = x_new, x
-            cost = cost_new
             B, C = self._normal(x, g)
-            njev += 1
             si = self._scale_inv(B, C, si)
-        else:
-            step_norm = 0
-            actual = 0
-        iteration += 1
-    if termination is None:
-        termination = 0
-    return BAResult(cams=cams(x).clone(), pts=pts(x).clone(), cost=cost, optimality=g_norm, nfev=nfev,
-                    njev=njev, status=termination, message=_MESSAGES[termination], success=termination > 0,
-                    iterations=iteration, host_segments_ms={k: 1e3 * v for k, v in seg.items()})
+    return self._result(td, x, seg)
 
 
 SchurTRF._solve_device = _solve_device

@@ -10,6 +10,7 @@
 // 16-double board copied to the host after the trial cost is known).  Everything lives in the caller's workspace; no
 // allocation, no second stream unless the overlapped build is requested.
 #include "mm_common.h"
+#include "trf_decide.h"
 #include <chrono>
 #include <vector>
 #include <algorithm>
@@ -32,6 +33,7 @@ __global__ __launch_bounds__(256) void vec_mul_kernel(const double *__restrict__
 struct HostBoard {
     double v[16];
     unsigned long long seq;
+    unsigned long long pad[7];      // 192 bytes: the batch's mailboxes of different problems never share a cache line
 };
 
 __global__ __launch_bounds__(64) void board_publish_kernel(const double *__restrict__ dev, int count, HostBoard *hb,
@@ -214,27 +216,25 @@ TrfWs carve_trf(const mm_ba_problem *pb, void *base, int64_t ex_half_bw = -1) {
     return t;
 }
 
-// SciPy's update_tr_radius / check_termination (scipy/optimize/_lsq/common.py:222-245, 705-717)
-void update_tr_radius(double &Delta, double actual, double predicted, double step_norm, bool bound_hit, double &ratio) {
-    if (predicted > 0)
-        ratio = actual / predicted;
-    else if (predicted == 0 && actual == 0)
-        ratio = 1;
-    else
-        ratio = 0;
-    if (ratio < 0.25)
-        Delta = 0.25 * step_norm;
-    else if (ratio > 0.75 && bound_hit)
-        Delta *= 2.0;
+// The host side of a hand-over: spin until a mailbox's sequence word shows `seq`.  `what` (and the batch's problem number)
+// name the scalars in the message of a wait that ends without them.
+int wait_seq(mm_ctx *ctx, const unsigned long long *word, unsigned long long seq, const char *what, int problem = -1) {
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned long spins = 0;
+    while (__atomic_load_n(word, __ATOMIC_ACQUIRE) != seq) {
+        __builtin_ia32_pause();
+        if ((++spins & 0xFFFFF) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
+            // never seen: a failed launch upstream -- let the runtime report it
+            MM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) break;
+            if (problem < 0) return mm_fail(ctx, MM_ERR_HIP, "%s never arrived", what);
+            return mm_fail(ctx, MM_ERR_HIP, "%s %d never arrived", what, problem);
+        }
+    }
+    return MM_OK;
 }
-int check_termination(double dF, double F, double dx_norm, double x_norm, double ratio, double ftol, double xtol) {
-    const bool ftol_ok = dF < ftol * F && ratio > 0.25;
-    const bool xtol_ok = dx_norm < xtol * (xtol + x_norm);
-    if (ftol_ok && xtol_ok) return 4;
-    if (ftol_ok) return 2;
-    if (xtol_ok) return 3;
-    return -100;  // (None)
-}
+
+using namespace mm_trf;      // TrfDecide and its outcomes: every accept / reject / retry / terminate decision (trf_decide.h)
 
 }  // namespace
 
@@ -296,7 +296,6 @@ static int trf_run(mm_ctx *ctx, const mm_ba_problem *pb, double *cams, double *p
     const int F = pb->F, P = pb->P;
     const int64_t nc = 6 * (int64_t)F, n = nc + 3 * (int64_t)P;
     hipStream_t st = ctx->stream;
-    auto cams_of = [&](double *v) { return v; };
     auto pts_of = [&](double *v) { return v + nc; };
     // the reduction workspaces count arrivals: zero once
     MM_HIP(ctx, hipMemsetAsync(t.ws_md, 0, t.ws_md_b, st));
@@ -333,53 +332,35 @@ static int trf_run(mm_ctx *ctx, const mm_ba_problem *pb, double *cams, double *p
     };
     // block normal equations at v: B and g_c are sums over ALL observations
     auto normal_eq = [&](double *v) -> int {
-        TRF_CALL(mm_ba_normal_eq(ctx, pb, cams_of(v), pts_of(v), t.B, cams_of(t.g), t.C, pts_of(t.g)));
+        TRF_CALL(mm_ba_normal_eq(ctx, pb, v, pts_of(v), t.B, t.g, t.C, pts_of(t.g)));
         if (!dist) return MM_OK;
         MM_HIP(ctx, hipMemcpyAsync(t.ex, t.B, (size_t)F * 36 * sizeof(double), hipMemcpyDeviceToDevice, st));
-        MM_HIP(ctx, hipMemcpyAsync(t.ex + (size_t)F * 36, cams_of(t.g), (size_t)nc * sizeof(double), hipMemcpyDeviceToDevice, st));
+        MM_HIP(ctx, hipMemcpyAsync(t.ex + (size_t)F * 36, t.g, (size_t)nc * sizeof(double), hipMemcpyDeviceToDevice, st));
         TRF_CALL(ar(t.ex, (int64_t)F * 42));
         MM_HIP(ctx, hipMemcpyAsync(t.B, t.ex, (size_t)F * 36 * sizeof(double), hipMemcpyDeviceToDevice, st));
-        MM_HIP(ctx, hipMemcpyAsync(cams_of(t.g), t.ex + (size_t)F * 36, (size_t)nc * sizeof(double), hipMemcpyDeviceToDevice, st));
+        MM_HIP(ctx, hipMemcpyAsync(t.g, t.ex + (size_t)F * 36, (size_t)nc * sizeof(double), hipMemcpyDeviceToDevice, st));
         return MM_OK;
     };
-    static const bool spin = !(getenv("MM_TRF_SPIN") && getenv("MM_TRF_SPIN")[0] == '0');
-    if (spin && !ctx->host_board) {
+    if (!ctx->host_board) {
         MM_HIP(ctx, hipHostMalloc(&ctx->host_board, sizeof(HostBoard), hipHostMallocDefault));
         memset(ctx->host_board, 0, sizeof(HostBoard));
         ctx->host_board_seq = 0;
     }
-    auto wait_board = [&](unsigned long long seq, int count) -> int {
-        HostBoard *hb = (HostBoard *)ctx->host_board;
-        const auto t0 = std::chrono::steady_clock::now();
-        unsigned long spins = 0;
-        while (__atomic_load_n(&hb->seq, __ATOMIC_ACQUIRE) != seq) {
-            __builtin_ia32_pause();
-            if ((++spins & 0xFFFFF) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
-                // never seen: a failed launch upstream -- let the runtime report it
-                MM_HIP(ctx, hipStreamSynchronize(st));
-                if (__atomic_load_n(&hb->seq, __ATOMIC_ACQUIRE) != seq)
-                    return mm_fail(ctx, MM_ERR_HIP, "mm_ba_trf: the trial-step scalars never arrived");
-            }
-        }
+    HostBoard *hb = (HostBoard *)ctx->host_board;
+    auto take_board = [&](unsigned long long seq, int count) -> int {
+        TRF_CALL(wait_seq(ctx, &hb->seq, seq, "mm_ba_trf: the trial-step scalars"));
         for (int i = 0; i < count; ++i) host[i] = ((volatile double *)hb->v)[i];
         mm_chol_release_budget(ctx);      // the stream has passed everything enqueued before the publishing kernel
         return MM_OK;
     };
     auto read_board = [&](const double *dev, int count) -> int {
-        if (!spin) {
-            MM_HIP(ctx, hipMemcpyAsync(host, dev, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, st));
-            MM_HIP(ctx, hipStreamSynchronize(st));
-            mm_chol_release_budget(ctx);
-            return MM_OK;
-        }
-        HostBoard *hb = (HostBoard *)ctx->host_board;
         const unsigned long long seq = ++ctx->host_board_seq;
         hipLaunchKernelGGL(board_publish_kernel, dim3(1), dim3(64), 0, st, dev, count, hb, seq);
         MM_LAUNCH_CHECK(ctx, "board_publish_kernel");
-        return wait_board(seq, count);
+        return take_board(seq, count);
     };
     // initial cost
-    TRF_CALL(mm_ba_residual(ctx, pb, cams_of(x), pts_of(x), nullptr, t.cost2, t.ws_res, t.ws_res_b));
+    TRF_CALL(mm_ba_residual(ctx, pb, x, pts_of(x), nullptr, t.cost2, t.ws_res, t.ws_res_b));
     if (dist) {
         // "this rank's context is set to avoid the single-launch factorisation" rides with the initial cost: if any rank
         // is, all are -- the two paths order their sums differently and the replicated cameras must stay bit-identical
@@ -391,14 +372,13 @@ static int trf_run(mm_ctx *ctx, const mm_ba_problem *pb, double *cams, double *p
         if (host[0] > 0) ctx->chol_avoid_fused = true;
     }
     TRF_CALL(read_board(t.cost2, 1));
-    double cost = 0.5 * host[0];
-    rep->cost0 = cost;
-    if (!std::isfinite(cost)) {
+    const double cost0 = 0.5 * host[0];
+    rep->cost0 = cost0;
+    if (!std::isfinite(cost0)) {
         rep->status = -2;
         return mm_fail(ctx, MM_ERR_NUMERIC, "mm_ba_trf: residuals are not finite in the initial point");
     }
     const int half_bw = dist ? dist->half_bandwidth : 6 * pb->cam_span + 5;
-    int nfev = 1, njev = 1;
     TRF_CALL(normal_eq(x));
     TRF_CALL(mm_ba_scale_update(ctx, F, P, t.B, t.C, t.si, 1));
     {   // Delta0 = |x * scale_inv|  (trf.py:428)
@@ -408,48 +388,38 @@ static int trf_run(mm_ctx *ctx, const mm_ba_problem *pb, double *cams, double *p
         TRF_CALL(exchange({{t.rowsx, 0}}));
         TRF_CALL(read_board(t.rowsx, 3));
     }
-    double Delta = std::sqrt(host[2]);
-    if (Delta == 0) Delta = 1.0;
-    const long max_nfev = prm->max_nfev > 0 ? prm->max_nfev : (long)n * 100;
-    double min_damping = prm->min_damping > 0 ? prm->min_damping : 1e-9;
-    double alpha = 0.0;
-    (void)alpha;
-    int termination = -100, iteration = 0, n_log = 0;
-    double step_norm = NAN, actual = NAN, g_norm = NAN;
-    auto log_row = [&](int it, int nf, double c, double red, double stepn, double opt) {
-        if (n_log < log_cap) log[n_log] = mm_trf_row{it, nf, c, red, stepn, opt};
-        ++n_log;
-    };
+    // every decision from here on is the machine's (trf_decide.h); this function enqueues what its answers ask for
+    TrfDecide d(cost0, host[2], n, *prm, log, log_cap);
+    Outcome next = d.begin();
     static const bool timing = getenv("MM_TRF_TIMING") && atoi(getenv("MM_TRF_TIMING")) > 0;      // wall clock per iteration on stderr
     const auto t_loop = std::chrono::steady_clock::now();
     auto t_iter = t_loop;
     if (timing) fprintf(stderr, "mm_ba_trf timing: prologue %.1f us\n", std::chrono::duration<double, std::micro>(t_loop - t_enter).count());
     for (;;) {
-        if (timing && iteration > 0) {
+        if (timing && d.iteration > 0) {
             const auto now = std::chrono::steady_clock::now();
-            fprintf(stderr, "mm_ba_trf timing: iteration %d %.1f us (nfev %d)\n", iteration - 1,
-                    std::chrono::duration<double, std::micro>(now - t_iter).count(), nfev);
+            fprintf(stderr, "mm_ba_trf timing: iteration %d %.1f us (nfev %d)\n", d.iteration - 1,
+                    std::chrono::duration<double, std::micro>(now - t_iter).count(), d.nfev);
             t_iter = now;
         }
-        if (!dist && iteration > 0) {      // (the running maximum of the Jacobian scaling rides with the pass: idempotent)
+        if (!dist && d.iteration > 0) {      // (the running maximum of the Jacobian scaling rides with the pass: idempotent)
             TRF_CALL(mm_trf_fused0_scaled(ctx, t.g, t.si, t.B, t.C, t.gh, t.ghs, n, nc, t.r0, t.ws_md, t.ws_md_b));
         } else {
             const double *in[2] = {t.g, t.si};
             double *outv[2] = {t.gh, t.ghs};
             TRF_CALL(mm_trf_fused(ctx, 0, in, outv, nullptr, 0, 0, n, nc, t.r0, t.ws_md, t.ws_md_b));
         }
-        TRF_CALL(mm_ba_jvp_dots(ctx, pb, cams_of(x), pts_of(x), cams_of(t.ghs), pts_of(t.ghs), t.u1, nullptr, t.d11, t.ws_jvp, t.ws_jvp_b));
+        TRF_CALL(mm_ba_jvp_dots(ctx, pb, x, pts_of(x), t.ghs, pts_of(t.ghs), t.u1, nullptr, t.d11, t.ws_jvp, t.ws_jvp_b));
         TRF_CALL(exchange({{t.r0, 0}, {t.r0 + 3, 2}, {t.d11, 1}, {t.d11 + 3, 1}}));      // |g_h|^2, |g|_inf, |J d g_h|^2
-        if (termination != -100 || nfev == max_nfev) {
+        if (next == FINAL) {
             TRF_CALL(read_board(t.r0, 6));
-            g_norm = host[5];
-            log_row(iteration, nfev, cost, actual, step_norm, g_norm);
+            d.on_final(host[5]);
             break;
         }
         // (the damping of the iteration is computed by the first damped-blocks sweep itself: mm_trf_damping's formula, one
         // launch less; a retry with raised damping reads damp[1] as the host left it)
         double *reg_eff = t.damp + 1;
-        bool solved = false, rows_pending = false;
+        bool rows_pending = false;
         auto trial = [&](double Delta_) -> int {
             if (rows_pending) {      // first trial of the attempt: the sums of J s2 are still per-workgroup partials
                 rows_pending = false;
@@ -460,7 +430,7 @@ static int trf_run(mm_ctx *ctx, const mm_ba_problem *pb, double *cams, double *p
             }
             if (F > 0 && !dist) {      // x_new and its cameras' rotation coefficients in one launch
                 void *ctab = nullptr;
-                TRF_CALL(mm_cam_table_adopt(ctx, cams_of(x_new), (int)F, &ctab));
+                TRF_CALL(mm_cam_table_adopt(ctx, x_new, (int)F, &ctab));
                 TRF_CALL(mm_trf_fused5_coef(ctx, x, t.s1, t.s2, x_new, t.board, n, nc, ctab, (int)F));
             } else {
                 const double *in[3] = {x, t.s1, t.s2};
@@ -469,33 +439,34 @@ static int trf_run(mm_ctx *ctx, const mm_ba_problem *pb, double *cams, double *p
                 TRF_CALL(mm_trf_fused(ctx, 5, in, outv, sc, 0, 0, n, nc, nullptr, t.ws_md, t.ws_md_b));
                 mm_cam_table_invalidate(ctx);      // x_new has new contents
             }
-            if (spin && !dist) {      // the residual's final sum and the hand-over to the host mailbox are one launch
+            if (!dist) {      // the residual's final sum and the hand-over to the host mailbox are one launch
                 const unsigned long long seq = ++ctx->host_board_seq;
-                TRF_CALL(mm_ba_residual_publish(ctx, pb, cams_of(x_new), pts_of(x_new), t.ws_res, t.ws_res_b, t.board, 14, 16,
+                TRF_CALL(mm_ba_residual_publish(ctx, pb, x_new, pts_of(x_new), t.ws_res, t.ws_res_b, t.board, 14, 16,
                                                 ctx->host_board, seq));
-                return wait_board(seq, 16);   // ---- the host sync of a trial step ----
+                return take_board(seq, 16);   // ---- the host sync of a trial step ----
             }
-            TRF_CALL(mm_ba_residual(ctx, pb, cams_of(x_new), pts_of(x_new), nullptr, t.board + 14, t.ws_res, t.ws_res_b));
+            TRF_CALL(mm_ba_residual(ctx, pb, x_new, pts_of(x_new), nullptr, t.board + 14, t.ws_res, t.ws_res_b));
             // sharded: the trial cost is a sum over all ranks; and whether ANY rank's factorisation was abandoned (a
             // rank-local event) comes back in board[15], so that all ranks fall back together
             TRF_CALL(exchange({{t.board + 14, 3}, {t.board + 15, 4}}));
             return read_board(t.board, 16);
         };
         bool damping_known = false;
-        for (int attempt = 0; attempt < 6 && !solved; ++attempt) {
+        Outcome solve;
+        do {
             if (!dist) {
                 // damping, reduced system, factorisation and both substitutions: four launches (schur.hip)
-                mm_damp_spec dmp = {t.B, t.C, t.si, nullptr, nullptr, Delta, min_damping, t.damp, reg_eff};
+                mm_damp_spec dmp = {t.B, t.C, t.si, nullptr, nullptr, d.Delta, d.min_damping, t.damp, reg_eff};
                 if (!damping_known) {
                     dmp.gh2 = t.r0 + 2;
                     dmp.d11 = t.d11 + 2;
                     damping_known = true;
                 }
-                TRF_CALL(mm_ba_schur_solve_damped(ctx, pb, cams_of(x), pts_of(x), &dmp, t.Bd, t.Cd, cams_of(t.g), pts_of(t.g), t.S, t.v, t.Cinv,
+                TRF_CALL(mm_ba_schur_solve_damped(ctx, pb, x, pts_of(x), &dmp, t.Bd, t.Cd, t.g, pts_of(t.g), t.S, t.v, t.Cinv,
                                                   half_bw, t.info, t.ws_schur, t.ws_schur_b, t.ws_chol, t.ws_chol_b));
             } else {
                 if (!damping_known) {
-                    TRF_CALL(mm_ba_damp_damping(ctx, F, P, t.B, t.C, t.si, t.r0 + 2, t.d11 + 2, Delta, min_damping, t.damp, t.Bd, t.Cd));
+                    TRF_CALL(mm_ba_damp_damping(ctx, F, P, t.B, t.C, t.si, t.r0 + 2, t.d11 + 2, d.Delta, d.min_damping, t.damp, t.Bd, t.Cd));
                     damping_known = true;
                 } else {
                     TRF_CALL(mm_ba_damp(ctx, F, P, t.B, t.C, t.si, reg_eff, t.Bd, t.Cd));
@@ -503,7 +474,7 @@ static int trf_run(mm_ctx *ctx, const mm_ba_problem *pb, double *cams, double *p
                 // every rank's S / v hold its points' share plus the FULL blockdiag(Bd) / g_c: sum, then remove the
                 // duplicates.  Band exchange (decided by the caller from global quantities): n (hb + 1) + n doubles in one
                 // collective instead of the dense matrix; only the lower band then holds the sum.
-                TRF_CALL(mm_ba_schur(ctx, pb, cams_of(x), pts_of(x), t.Bd, t.Cd, cams_of(t.g), pts_of(t.g), t.S, t.v, t.Cinv, t.ws_schur,
+                TRF_CALL(mm_ba_schur(ctx, pb, x, pts_of(x), t.Bd, t.Cd, t.g, pts_of(t.g), t.S, t.v, t.Cinv, t.ws_schur,
                                      t.ws_schur_b));
                 const double dup = (double)(dist->world - 1);
                 if (dist->band_exchange) {
@@ -523,11 +494,11 @@ static int trf_run(mm_ctx *ctx, const mm_ba_problem *pb, double *cams, double *p
                     hipLaunchKernelGGL(dedup_dense_kernel, dim3((unsigned)((nc * 6 + 255) / 256)), dim3(256), 0, st, t.S, nc,
                                        (const double *)t.Bd, dup);
                 }
-                hipLaunchKernelGGL(axpy_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, st, t.v, (const double *)cams_of(t.g), -dup, nc);
+                hipLaunchKernelGGL(axpy_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, st, t.v, (const double *)t.g, -dup, nc);
                 MM_LAUNCH_CHECK(ctx, "axpy_kernel");
                 TRF_CALL(mm_chol_solve_sym(ctx, t.S, (int)nc, t.v, half_bw, dist->band_exchange ? 0 : 1, t.info, t.ws_chol, t.ws_chol_b));
             }
-            TRF_CALL(mm_ba_backsub(ctx, pb, cams_of(x), pts_of(x), t.Cinv, pts_of(t.g), t.v, t.dp, t.ws_back, t.ws_back_b));
+            TRF_CALL(mm_ba_backsub(ctx, pb, x, pts_of(x), t.Cinv, pts_of(t.g), t.v, t.dp, t.ws_back, t.ws_back_b));
             {
                 const double *in[4] = {t.v, t.dp, t.si, t.gh};
                 double *outv[2] = {t.gn, t.q1};
@@ -550,91 +521,44 @@ static int trf_run(mm_ctx *ctx, const mm_ba_problem *pb, double *cams, double *p
             }
             ctx->jvp_rows_deferred = !dist && P > 0 && pb->O > 0;      // (sharded: the sums are exchanged first)
             {
-                const int rc_ = mm_ba_jvp_dots(ctx, pb, cams_of(x), pts_of(x), cams_of(t.s2), pts_of(t.s2), t.Jq2, t.u1, t.bs, t.ws_jvp, t.ws_jvp_b);
+                const int rc_ = mm_ba_jvp_dots(ctx, pb, x, pts_of(x), t.s2, pts_of(t.s2), t.Jq2, t.u1, t.bs, t.ws_jvp, t.ws_jvp_b);
                 rows_pending = ctx->jvp_rows_deferred;
                 ctx->jvp_rows_deferred = false;
                 if (rc_) return rc_;
             }
             // (the step inner products and the two of J s2 travel together: the Jacobian product only needs s2)
             TRF_CALL(exchange({{t.r3, 0}, {t.r3 + 3, 0}, {t.r3 + 6, 0}, {t.r3 + 9, 0}, {t.r3 + 12, 0}, {t.bs, 1}, {t.bs + 3, 1}}));
-            TRF_CALL(trial(Delta));   // enqueued before the host knows whether the factorisation succeeded
-            const int inf = dist && host[15] > 0 ? -1 : (int)host[6];
-            if (inf == 0) {
-                solved = true;
-                break;
-            }
-            if (inf < 0) {
+            TRF_CALL(trial(d.Delta));   // enqueued before the host knows whether the factorisation succeeded
+            // (sharded: "a rank's factorisation was abandoned" came back with the trial cost)
+            solve = d.on_solve(dist && host[15] > 0 ? -1 : (int)host[6], host[13], host[10], host[9]);
+            if (solve == ABANDONED) {
                 // the single-launch factorisation gave up waiting (another tenant on the GPU, a profiler serialising
                 // kernels): repeat this attempt -- same damping -- with the launch-per-column factorisation and stay there
                 if (ctx->chol_avoid_fused) return mm_fail(ctx, MM_ERR_HIP, "mm_ba_trf: the banded factorisation reported info = -1");
                 ctx->chol_avoid_fused = true;
                 ++rep->chol_fallbacks;
-                --attempt;
-                continue;
+            } else if (solve == RETRY) {
+                // the raised damping goes to the device: damp[1] is a plain double
+                MM_HIP(ctx, hipMemcpyAsync(t.damp + 1, &d.reg, sizeof(double), hipMemcpyHostToDevice, st));
+                MM_HIP(ctx, hipStreamSynchronize(st));
             }
-            if (host[13] <= min_damping * (1.0 + 1e-12)) min_damping *= 100.0;   // failed AT the floor: the floor was too low
-            // reg_eff *= 100 on the device: damp[1] is a plain double
-            double r100 = host[13] * 100.0;
-            MM_HIP(ctx, hipMemcpyAsync(t.damp + 1, &r100, sizeof(double), hipMemcpyHostToDevice, st));
-            MM_HIP(ctx, hipStreamSynchronize(st));
-        }
-        if (!solved) return mm_fail(ctx, MM_ERR_NUMERIC, "mm_ba_trf: reduced camera system is not positive definite (pivot %d)", (int)host[6]);
-        g_norm = host[10];
-        const double xx = host[9];
-        if (g_norm < prm->gtol) termination = 1;   // (checked before the step is used, as trf.py:443 does)
-        log_row(iteration, nfev, cost, actual, step_norm, g_norm);
-        if (termination != -100) break;
-        const double x_norm = std::sqrt(xx);
-        actual = -1.0;
-        bool have = true;
-        double cost_new = cost;
-        while (actual <= 0 && nfev < max_nfev) {
-            if (!have) TRF_CALL(trial(Delta));
-            have = false;
-            const double predicted = host[2], step_h_norm = host[3], step_norm_dev = host[4];
-            cost_new = 0.5 * host[14];
-            ++nfev;
-            if (!std::isfinite(cost_new)) {
-                Delta = 0.25 * step_h_norm;
-                continue;
-            }
-            actual = cost - cost_new;
-            double Delta_new = Delta, ratio;
-            update_tr_radius(Delta_new, actual, predicted, step_h_norm, step_h_norm > 0.95 * Delta, ratio);
-            step_norm = step_norm_dev;
-            termination = check_termination(actual, cost, step_norm, x_norm, ratio, prm->ftol, prm->xtol);
-            if (termination != -100) break;
-            alpha *= Delta / Delta_new;
-            Delta = Delta_new;
-        }
-        if (actual > 0) {
-            double *tmp = x;
-            x = x_new;
-            x_new = tmp;
-            cost = cost_new;
+        } while (solve == ABANDONED || solve == RETRY);
+        if (solve == INDEFINITE)
+            return mm_fail(ctx, MM_ERR_NUMERIC, "mm_ba_trf: reduced camera system is not positive definite (pivot %d)", (int)host[6]);
+        if (solve == DONE) break;      // gtol: the trial point enqueued above is simply dropped
+        while ((next = d.on_trial(host[2], host[3], host[4], host[14])) == TRIAL) TRF_CALL(trial(d.Delta));
+        if (d.accepted) {
+            std::swap(x, x_new);
             TRF_CALL(normal_eq(x));
-            ++njev;
             if (dist) TRF_CALL(mm_ba_scale_update(ctx, F, P, t.B, t.C, t.si, 0));      // (else: with the next pass 0)
-        } else {
-            step_norm = 0;
-            actual = 0;
         }
-        ++iteration;
     }
-    if (termination == -100) termination = 0;
     MM_HIP(ctx, hipMemcpyAsync(cams, x, (size_t)nc * sizeof(double), hipMemcpyDeviceToDevice, st));
     if (P) MM_HIP(ctx, hipMemcpyAsync(pts, x + nc, (size_t)3 * P * sizeof(double), hipMemcpyDeviceToDevice, st));
     MM_HIP(ctx, hipStreamSynchronize(st));
     if (timing) fprintf(stderr, "mm_ba_trf timing: total %.1f us, %d iterations\n",
-                        std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_enter).count(), iteration);
-    rep->cost = cost;
-    rep->optimality = g_norm;
-    rep->nfev = nfev;
-    rep->njev = njev;
-    rep->status = termination;
-    rep->iterations = iteration;
-    rep->log_rows = n_log;
-    rep->min_damping = min_damping;
+                        std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_enter).count(), d.iteration);
+    d.fill(*rep);
     return MM_OK;
 }
 
@@ -683,19 +607,6 @@ extern "C" int mm_ba_trf_fixed(mm_ctx *ctx, const mm_ba_problem *pb, const mm_ba
 // after six raises, is taken out of the batch and solved by mm_ba_trf itself afterwards, from its initial point: every
 // result equals the one mm_ba_trf alone would have produced.
 namespace {
-struct BState {
-    int phase;      // 0 body + trial, 1 trial only, 2 final gradient norm, 3 done, 4 solve alone afterwards,
-                    // 5 reduced solve again with 100x the damping (+ trial)
-    double Delta, cost, cost0, x_norm, step_norm, actual, g_norm, alpha, min_damping, reg;
-    int nfev, njev, iteration, termination, attempt;
-    long max_nfev;
-    unsigned long long seq;
-};
-struct BHostBoard {
-    double v[16];
-    unsigned long long seq;
-    unsigned long long pad[7];      // 192 bytes: mailboxes of different problems never share a cache line
-};
 size_t batch_tables_bytes(const mm_ba_problem *pb) { return 2 * mm_align_up((size_t)pb->F * 5 * sizeof(double), 256); }
 }  // namespace
 
@@ -770,7 +681,7 @@ extern "C" int mm_ba_trf_batched(mm_ctx *ctx, int n_prob, const mm_ba_problem *c
     const size_t list_b = mm_align_up((size_t)n_prob * sizeof(int32_t), 256);
     constexpr int N_LISTS = 7;      // fused0 | final | body (new iteration) | trial | body (all) | retry | accept
     const size_t dev_need = tab_b + dyn_b + N_LISTS * list_b;
-    const size_t host_need = dyn_b + N_LISTS * list_b + (size_t)n_prob * sizeof(BHostBoard) + (size_t)n_prob * 4 * sizeof(double);
+    const size_t host_need = dyn_b + N_LISTS * list_b + (size_t)n_prob * sizeof(HostBoard) + (size_t)n_prob * 4 * sizeof(double);
     if (ctx->batch_dev_cap < dev_need) {
         if (ctx->batch_dev) (void)hipFree(ctx->batch_dev);
         ctx->batch_dev = nullptr;
@@ -793,9 +704,9 @@ extern "C" int mm_ba_trf_batched(mm_ctx *ctx, int n_prob, const mm_ba_problem *c
     mm_batch_dyn *h_dyn = (mm_batch_dyn *)hbase;
     int32_t *h_list[N_LISTS];
     for (int q = 0; q < N_LISTS; ++q) h_list[q] = (int32_t *)(hbase + dyn_b + q * list_b);
-    BHostBoard *mail = (BHostBoard *)(hbase + dyn_b + N_LISTS * list_b);
+    HostBoard *mail = (HostBoard *)(hbase + dyn_b + N_LISTS * list_b);
     double *h_init = (double *)(mail + n_prob);      // per problem: cost2, |x si|^2 (3 doubles)
-    memset(mail, 0, (size_t)n_prob * sizeof(BHostBoard));
+    memset(mail, 0, (size_t)n_prob * sizeof(HostBoard));
     for (int p = 0; p < n_prob; ++p) tab[p].mailbox = &mail[p];
     MM_HIP(ctx, hipMemcpyAsync(d_tab, tab.data(), (size_t)n_prob * sizeof(mm_batch_prob), hipMemcpyHostToDevice, st));
     // ---- prologue, problem by problem with the single-problem calls (initial cost, normal equations, scale, Delta0) ----
@@ -817,23 +728,21 @@ extern "C" int mm_ba_trf_batched(mm_ctx *ctx, int n_prob, const mm_ba_problem *c
         MM_HIP(ctx, hipMemcpyAsync(h_init + 4 * p + 1, t.rowsx, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
     }
     MM_HIP(ctx, hipStreamSynchronize(st));
-    std::vector<BState> S((size_t)n_prob);
+    // one decision machine per problem (trf_decide.h, the one trf_run asks) and what its last answer wants enqueued in the
+    // next round: BODY (a new iteration: body + trial step), RETRY (the reduced solve again with the raised damping + trial
+    // step), TRIAL (trial step only), FINAL (the gradient pass alone), DONE (nothing more); ABANDONED and INDEFINITE take
+    // the problem out of the batch, to be solved alone afterwards
+    std::vector<TrfDecide> D;
+    std::vector<Outcome> next((size_t)n_prob);
+    D.reserve((size_t)n_prob);
     for (int p = 0; p < n_prob; ++p) {
-        BState &s_ = S[p];
-        s_ = BState{};
-        s_.cost = s_.cost0 = 0.5 * h_init[4 * p];
-        if (!std::isfinite(s_.cost)) {
+        const double cost0 = 0.5 * h_init[4 * p];
+        if (!std::isfinite(cost0)) {
             reports[p].status = -2;
             return mm_fail(ctx, MM_ERR_NUMERIC, "mm_ba_trf_batched: residuals of problem %d are not finite in the initial point", p);
         }
-        s_.Delta = std::sqrt(h_init[4 * p + 3]);
-        if (s_.Delta == 0) s_.Delta = 1.0;
-        s_.max_nfev = prm->max_nfev > 0 ? prm->max_nfev : (long)tab[p].n * 100;
-        s_.nfev = s_.njev = 1;
-        s_.termination = -100;
-        s_.step_norm = s_.actual = s_.g_norm = NAN;
-        s_.phase = 0;
-        s_.min_damping = prm->min_damping > 0 ? prm->min_damping : 1e-9;
+        D.emplace_back(cost0, h_init[4 * p + 3], tab[p].n, *prm);
+        next[p] = D[p].begin();
     }
     // every problem's rotation coefficients at its starting point
     auto upload_lists = [&]() -> int {
@@ -851,36 +760,23 @@ extern "C" int mm_ba_trf_batched(mm_ctx *ctx, int n_prob, const mm_ba_problem *c
         TRF_CALL(upload_lists());
         TRF_CALL(mm_batch_cam_coef(ctx, d_tab, d_list[2], n_prob, max_of(h_list[2], n_prob, &mm_batch_prob::g_coef), 0));
     }
-    auto wait_mail = [&](int p, unsigned long long seq) -> int {
-        BHostBoard *hb = &mail[p];
-        const auto t0 = std::chrono::steady_clock::now();
-        unsigned long spins = 0;
-        while (__atomic_load_n(&hb->seq, __ATOMIC_ACQUIRE) != seq) {
-            __builtin_ia32_pause();
-            if ((++spins & 0xFFFFF) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
-                MM_HIP(ctx, hipStreamSynchronize(st));
-                if (__atomic_load_n(&hb->seq, __ATOMIC_ACQUIRE) != seq)
-                    return mm_fail(ctx, MM_ERR_HIP, "mm_ba_trf_batched: the scalars of problem %d never arrived", p);
-            }
-        }
-        return MM_OK;
-    };
     // ---- rounds ----
-    for (;;) {
+    // (a problem is in every round from the first to its last: the round number is the sequence number of its mailbox)
+    for (unsigned long long round = 1;; ++round) {
         int n_f0 = 0, n_final = 0, n_body = 0, n_trial = 0, n_all = 0, n_retry = 0;
         for (int p = 0; p < n_prob; ++p) {
-            BState &s_ = S[p];
-            if (s_.phase == 3 || s_.phase == 4) continue;
-            h_dyn[p].Delta = s_.Delta;
-            h_dyn[p].seq = ++s_.seq;
-            h_dyn[p].min_damping = s_.min_damping;
-            h_dyn[p].reg = s_.reg;
-            if (s_.phase == 0 || s_.phase == 2) h_list[0][n_f0++] = p;
-            if (s_.phase == 2) h_list[1][n_final++] = p;
-            if (s_.phase == 0) h_list[2][n_body++] = p;
-            if (s_.phase != 2) h_list[3][n_trial++] = p;
-            if (s_.phase == 0 || s_.phase == 5) h_list[4][n_all++] = p;
-            if (s_.phase == 5) h_list[5][n_retry++] = p;
+            const Outcome w = next[p];
+            if (w == DONE || w == ABANDONED || w == INDEFINITE) continue;
+            h_dyn[p].Delta = D[p].Delta;
+            h_dyn[p].seq = round;
+            h_dyn[p].min_damping = D[p].min_damping;
+            h_dyn[p].reg = D[p].reg;
+            if (w == BODY || w == FINAL) h_list[0][n_f0++] = p;
+            if (w == FINAL) h_list[1][n_final++] = p;
+            if (w == BODY) h_list[2][n_body++] = p;
+            if (w != FINAL) h_list[3][n_trial++] = p;
+            if (w == BODY || w == RETRY) h_list[4][n_all++] = p;
+            if (w == RETRY) h_list[5][n_retry++] = p;
         }
         if (n_f0 + n_trial == 0) break;
         TRF_CALL(upload_lists());
@@ -912,81 +808,26 @@ extern "C" int mm_ba_trf_batched(mm_ctx *ctx, int n_prob, const mm_ba_problem *c
             TRF_CALL(mm_batch_cam_coef(ctx, d_tab, L, n_trial, max_of(h_list[3], n_trial, &mm_batch_prob::g_coef), 1));
             TRF_CALL(mm_batch_residual_publish(ctx, d_tab, L, n_trial, max_of(h_list[3], n_trial, &mm_batch_prob::g_res), d_dyn));
         }
-        // ---- the host side of the round: every listed problem's decision, exactly as trf_run takes it ----
+        // ---- the host side of the round: every listed problem's board goes to its machine ----
         int n_accept = 0;
         for (int q = 0; q < n_final; ++q) {
             const int p = h_list[1][q];
-            BState &s_ = S[p];
             // (a final problem is also in no other mailbox-writing list this round: its publish carries this round's seq)
-            TRF_CALL(wait_mail(p, s_.seq));
-            s_.g_norm = ((volatile double *)mail[p].v)[5];
-            s_.phase = 3;
+            TRF_CALL(wait_seq(ctx, &mail[p].seq, round, "mm_ba_trf_batched: the scalars of problem", p));
+            next[p] = D[p].on_final(((volatile double *)mail[p].v)[5]);
         }
         for (int q = 0; q < n_trial; ++q) {
             const int p = h_list[3][q];
-            BState &s_ = S[p];
-            TRF_CALL(wait_mail(p, s_.seq));
+            TrfDecide &d = D[p];
+            TRF_CALL(wait_seq(ctx, &mail[p].seq, round, "mm_ba_trf_batched: the scalars of problem", p));
             double host[16];
             for (int i = 0; i < 16; ++i) host[i] = ((volatile double *)mail[p].v)[i];
-            if (s_.phase == 0 || s_.phase == 5) {      // first trial point of an iteration (or of a retry with raised damping)
-                const int inf = (int)host[6];
-                if (inf < 0) {      // the factorisation was abandoned: off the common road
-                    s_.phase = 4;
-                    continue;
-                }
-                if (inf > 0) {      // not positive definite at this damping: 100x, as mm_ba_trf (the trial point is dropped)
-                    if (++s_.attempt >= 6) {
-                        s_.phase = 4;      // (mm_ba_trf will report the failure)
-                        continue;
-                    }
-                    if (host[13] <= s_.min_damping * (1.0 + 1e-12)) s_.min_damping *= 100.0;
-                    s_.reg = host[13] * 100.0;
-                    s_.phase = 5;
-                    continue;
-                }
-                s_.attempt = 0;
-                s_.g_norm = host[10];
-                if (s_.g_norm < prm->gtol) {      // (checked before the step is used; the trial point is dropped)
-                    s_.termination = 1;
-                    s_.phase = 3;
-                    continue;
-                }
-                s_.x_norm = std::sqrt(host[9]);
-                s_.actual = -1.0;
+            if (next[p] != TRIAL) {      // first trial point of an iteration (or of a retry with raised damping)
+                next[p] = d.on_solve((int)host[6], host[13], host[10], host[9]);
+                if (next[p] != USABLE) continue;
             }
-            const double predicted = host[2], step_h_norm = host[3], step_norm_dev = host[4];
-            const double cost_new = 0.5 * host[14];
-            ++s_.nfev;
-            bool again = false;      // another trial step of the same iteration
-            if (!std::isfinite(cost_new)) {
-                s_.Delta = 0.25 * step_h_norm;
-                again = s_.nfev < s_.max_nfev;
-            } else {
-                s_.actual = s_.cost - cost_new;
-                double Delta_new = s_.Delta, ratio;
-                update_tr_radius(Delta_new, s_.actual, predicted, step_h_norm, step_h_norm > 0.95 * s_.Delta, ratio);
-                s_.step_norm = step_norm_dev;
-                s_.termination = check_termination(s_.actual, s_.cost, s_.step_norm, s_.x_norm, ratio, prm->ftol, prm->xtol);
-                if (s_.termination == -100) {
-                    s_.alpha *= s_.Delta / Delta_new;
-                    s_.Delta = Delta_new;
-                    again = s_.actual <= 0 && s_.nfev < s_.max_nfev;
-                }
-            }
-            if (again) {
-                s_.phase = 1;
-                continue;
-            }
-            if (s_.actual > 0) {
-                s_.cost = cost_new;
-                ++s_.njev;
-                h_list[6][n_accept++] = p;
-            } else {
-                s_.step_norm = 0;
-                s_.actual = 0;
-            }
-            ++s_.iteration;
-            s_.phase = (s_.termination != -100 || s_.nfev == s_.max_nfev) ? 2 : 0;
+            next[p] = d.on_trial(host[2], host[3], host[4], host[14]);
+            if (next[p] != TRIAL && d.accepted) h_list[6][n_accept++] = p;
         }
         if (n_accept) {
             MM_HIP(ctx, hipMemcpyAsync(d_list[6], h_list[6], (size_t)n_accept * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -999,27 +840,19 @@ extern "C" int mm_ba_trf_batched(mm_ctx *ctx, int n_prob, const mm_ba_problem *c
     }
     // ---- results ----
     for (int p = 0; p < n_prob; ++p) {
-        BState &s_ = S[p];
-        if (s_.phase != 3) continue;
+        if (next[p] != DONE) continue;
         const int64_t nc = tab[p].nc;
         MM_HIP(ctx, hipMemcpyAsync(cams[p], tws[p].x, (size_t)nc * sizeof(double), hipMemcpyDeviceToDevice, st));
         MM_HIP(ctx, hipMemcpyAsync(pts[p], tws[p].x + nc, (size_t)3 * pbs[p]->P * sizeof(double), hipMemcpyDeviceToDevice, st));
         mm_trf_report &r = reports[p];
-        r.cost0 = s_.cost0;
-        r.cost = s_.cost;
-        r.optimality = s_.g_norm;
-        r.nfev = s_.nfev;
-        r.njev = s_.njev;
-        r.status = s_.termination == -100 ? 0 : s_.termination;
-        r.iterations = s_.iteration;
-        r.log_rows = 0;
-        r.min_damping = s_.min_damping;
+        D[p].fill(r);
+        r.log_rows = 0;      // (the batch keeps no table)
         r.chol_fallbacks = 0;
         r.collectives = 0;
     }
     MM_HIP(ctx, hipStreamSynchronize(st));
     for (int p = 0; p < n_prob; ++p)
-        if (S[p].phase == 4) {
+        if (next[p] != DONE) {
             --ctx->batch_last;
             TRF_CALL(solve_alone(p));
         }

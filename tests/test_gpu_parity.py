@@ -1677,7 +1677,8 @@ def test_trf_batched_equals_one_problem_at_a_time():
     every kernel per round with blockIdx.y = problem -- against mm_ba_trf on each of them alone: identical cameras and
     points bit for bit, identical nfev / njev / status / iterations / cost / optimality.  The problems differ in size, in
     how many evaluations they need (a tight and a loose tolerance would not fit one call, so the spread comes from noise
-    and outliers), in whether they stop on max_nfev, and one of them has observations no trial step improves at first."""
+    and outliers), in whether they stop on max_nfev, and one of them has observations no trial step improves at first.
+    max_nfev = 1 leaves nothing but the final gradient pass, in the batch as alone: one evaluation, the starting point back."""
     _needs_single_launch_chol()
     _needs_library_driver()
     ctx = default_context()
@@ -1695,7 +1696,7 @@ def test_trf_batched_equals_one_problem_at_a_time():
             cams0 = bundleAdjuster.frameParameters(pr["ext"]).reshape(F, 6)
         probs.append(ops.BADevice(pr["K"], pr["fi"], pr["pi"], obs, F, P, DEV, ctx))
         x0.append((dev(cams0), dev(pr["pts0"].copy())))
-    for max_nfev in (None, 7):
+    for max_nfev in (None, 7, 1):
         alone = []
         for pb, (c0, p0) in zip(probs, x0):
             c, p_ = c0.clone(), p0.clone()
@@ -1712,8 +1713,12 @@ def test_trf_batched_equals_one_problem_at_a_time():
             nf.append(rep.nfev)
         if max_nfev is None:
             assert len(set(nf)) > 1 and all(r.status > 0 for r in reps)      # (the lock-step had problems finishing early)
-        else:
+        elif max_nfev == 7:
             assert all(r.nfev <= 7 for r in reps) and any(r.status == 0 for r in reps)
+        else:
+            assert all((r.nfev, r.njev, r.status, r.iterations) == (1, 1, 0, 0) for r in reps)
+            assert all(torch.equal(c2, c0) and torch.equal(p2, p0) for c2, p2, (c0, p0) in zip(cb, pbs_, x0))
+            assert not any(solved_alone)
     # a problem the batched kernels cannot take (10 cameras: the reduced system is smaller than two Cholesky blocks) sends
     # the call down the one-by-one road: same results, flagged
     pr = synth.make_ba_problem(10, 500, 5, seed=9)
