@@ -190,6 +190,42 @@ int mm_ba_build_index(int F, int P, int64_t O, const int32_t *fi, const int32_t 
 int mm_triangulate_dlt(mm_ctx *ctx, const double *proj /*dev*/, const int32_t *f0 /*dev*/, const int32_t *f1 /*dev*/,
                        const double *x0 /*dev [n,2]*/, const double *x1 /*dev [n,2]*/, int64_t n,
                        double *X /*dev [n,3]*/);
+/* Multi-view triangulation of whole tracks, with a per-track verdict.  The tracks are a CSR over observations
+ * (mm_link_tracks_device): track t owns observations track_ptr[t] .. track_ptr[t+1] - 1 (m of them), observation o was made
+ * in frame obs_frame[o] (0 <= obs_frame[o] < F: the caller checks) at pixel obs_xy[o] -- what mm_flatten_tracks over all
+ * tracks produces.  All pointers are DEVICE pointers; ws holds mm_triangulate_tracks_workspace_bytes(F) bytes (camera
+ * centres C_f = -P[:, :3]^-1 P[:, 3] and |P[2, :3]| of every frame, written by a small pre-kernel).
+ *   Linear stage: every observation contributes the rows x P[2] - P[0] and y P[2] - P[1] (unnormalised, the rows OpenCV
+ *   builds); X is the de-homogenised eigenvector of the smallest eigenvalue of A^T A (cyclic Jacobi).  For m = 2 that is the
+ *   vector mm_triangulate_dlt finds.
+ *   Refinement: refine_iters Levenberg-Marquardt TRIAL steps on sum |pi(P X) - x|^2 with H = sum J^T J, g = sum J^T r,
+ *   J = (P[:2, :3] - u P[2, :3]) / w, (H + lambda diag H) delta = -g by Cholesky, lambda = 1e-3 at the start; a trial whose
+ *   cost is finite and strictly lower is accepted (lambda <- max(lambda / 10, 1e-12)), anything else -- a failed pivot, a
+ *   non-finite cost -- is rejected (lambda <- 10 lambda).  The cost never rises; refine_iters = 0 returns the linear X.
+ *   quality [T,4] at the returned X = (rms_px = sqrt(sum |r|^2 / m), max_px = max |r|, min_depth = min_i P_i[2].(X,1) /
+ *   |P_i[2, :3]|, cos_parallax = min over i != first of cos angle(C_first - X, C_i - X)).  Every pairwise angle is at most
+ *   the sum of two angles to the first ray, so acos(cos_parallax) is within a factor of two of the largest pairwise angle
+ *   of the track, at O(m) instead of O(m^2) cost.
+ *   A residual, depth or cosine that is not a number (w = 0 at X; X on the first camera's centre) makes its column NaN, as
+ *   NumPy's max / min would; a comparison with NaN is false, so that test does not flag the track: a caller that culls on
+ *   flags == 0 and can meet such input also asks for finite quality.
+ *   flags [T]: MM_TRI_BEHIND min_depth <= prm.min_depth | MM_TRI_REPROJ max_px > prm.max_reproj_px | MM_TRI_PARALLAX
+ *   cos_parallax > prm.max_cos_parallax (thresholds -inf, +inf, 2.0 switch a test off) | MM_TRI_DEGENERATE m < 2 or a
+ *   non-finite component of X: such a track is not refined and its quality is NaN.
+ * Four lanes per track, sums in a fixed order that depends on the track alone, no atomics: a call repeats bit for bit and a
+ * track's result does not depend on which other tracks share the call.  T = 0 returns MM_OK without a launch. */
+#define MM_TRI_BEHIND 1
+#define MM_TRI_REPROJ 2
+#define MM_TRI_PARALLAX 4
+#define MM_TRI_DEGENERATE 8
+typedef struct mm_tri_params {
+    int32_t refine_iters, reserved;
+    double max_reproj_px, max_cos_parallax, min_depth;
+} mm_tri_params;
+size_t mm_triangulate_tracks_workspace_bytes(int F);
+int mm_triangulate_tracks(mm_ctx *ctx, const double *proj /*[F,3,4]*/, int F, const int32_t *track_ptr /*[T+1]*/, int64_t T,
+                          const int32_t *obs_frame /*[O]*/, const double *obs_xy /*[O,2]*/, const mm_tri_params *prm,
+                          double *X /*[T,3]*/, double *quality /*[T,4]*/, int32_t *flags /*[T]*/, void *ws, size_t ws_bytes);
 
 /* ---- a-7..a-9: bundle adjustment sweeps -----------------------------------------------------------
  * Cost model of bundleAdjuster.py:7-52,81-102 (Rodrigues rotate, translate, full 3x3 K, divide, minus obs),

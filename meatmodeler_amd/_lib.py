@@ -51,6 +51,12 @@ class TrfRow(C.Structure):
                 ("step_norm", C.c_double), ("optimality", C.c_double)]
 
 
+class TriParams(C.Structure):
+    """mm_tri_params: trial steps and flag thresholds of mm_triangulate_tracks."""
+    _fields_ = [("refine_iters", C.c_int32), ("reserved", C.c_int32), ("max_reproj_px", C.c_double),
+                ("max_cos_parallax", C.c_double), ("min_depth", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, vp, vp, C.c_int64)
 
 
@@ -100,6 +106,8 @@ SIGNATURES = {
                                       c_i64p, c_i32p, c_i32p, C.c_int64]),
     "mm_ba_build_index": (C.c_int, [C.c_int, C.c_int, C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]),
     "mm_triangulate_dlt": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int64, vp]),
+    "mm_triangulate_tracks_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "mm_triangulate_tracks": (C.c_int, [vp, vp, C.c_int, vp, C.c_int64, vp, vp, C.POINTER(TriParams), vp, vp, vp, vp, C.c_size_t]),
     "mm_ba_residual": (C.c_int, [vp, C.POINTER(BAProblem), vp, vp, vp, vp, vp, C.c_size_t]),
     "mm_ba_jacobian": (C.c_int, [vp, C.POINTER(BAProblem), vp, vp, vp, vp]),
     "mm_ba_normal_eq": (C.c_int, [vp, C.POINTER(BAProblem), vp, vp, vp, vp, vp, vp]),

@@ -4,6 +4,7 @@ torch is used for device memory and streams only; every computation below is a H
 `libmeatmodeler_hip.so`.  All functions take/return torch tensors on the context's device.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -137,6 +138,54 @@ def triangulate_dlt(proj, f0, f1, x0, x1, ctx=None):
         ctx.check(lib.mm_triangulate_dlt(ctx.h, ptr(proj.contiguous()), ptr(_i32(f0)), ptr(_i32(f1)),
                                          ptr(x0.contiguous()), ptr(x1.contiguous()), n, ptr(X)), "mm_triangulate_dlt")
     return X
+
+
+TRI_BEHIND, TRI_REPROJ, TRI_PARALLAX, TRI_DEGENERATE = 1, 2, 4, 8      # MM_TRI_* of include/meatmodeler.h
+
+
+def triangulate_tracks(proj, track_ptr, obs_frame, obs_xy, refine_iters=8, max_reproj_px=math.inf, min_angle_deg=0,
+                       min_depth=-math.inf, ctx=None):
+    """Multi-view triangulation of whole tracks (mm_triangulate_tracks): proj [F,3,4] f64, track_ptr [T+1] i32, obs_frame [O]
+    i32, obs_xy [O,2] f64 in CSR order (device tensors; what flatten_tracks over all tracks gives)
+    -> (X [T,3] f64, quality [T,4] f64 = (rms_px, max_px, min_depth, cos_parallax), flags [T] i32 of TRI_* bits).
+    A track is flagged when max_px > max_reproj_px, its parallax angle is below min_angle_deg (0: test off) or
+    min_depth <= min_depth; refine_iters Levenberg-Marquardt trial steps follow the linear solution."""
+    if proj.dim() != 3 or tuple(proj.shape[1:]) != (3, 4):
+        raise ValueError("triangulate_tracks: proj must be [F,3,4]")
+    if not 0 <= int(refine_iters) <= 1000:
+        raise ValueError("triangulate_tracks: refine_iters must be in 0 .. 1000")
+    if not min_angle_deg >= 0:
+        raise ValueError("triangulate_tracks: min_angle_deg must not be negative")
+    ctx = ctx or default_context()
+    d = proj.device
+    F = proj.shape[0]
+    tp = _i32(track_ptr.to(torch.int32).contiguous())
+    of_ = _i32(obs_frame.to(torch.int32).contiguous())
+    xy = obs_xy.to(torch.float64).contiguous()
+    T, O = tp.numel() - 1, of_.numel()
+    if T < 0 or xy.shape != (O, 2):
+        raise ValueError("triangulate_tracks: track_ptr [T+1], obs_frame [O] and obs_xy [O,2] expected")
+    X = torch.empty((T, 3), dtype=torch.float64, device=d)
+    quality = torch.empty((T, 4), dtype=torch.float64, device=d)
+    flags = torch.empty(T, dtype=torch.int32, device=d)
+    if T == 0:
+        return X, quality, flags
+    lim = [tp[0], tp[-1], (tp[1:] - tp[:-1]).min()] + ([of_.min(), of_.max()] if O else [])
+    lim = torch.stack([v.long() for v in lim]).tolist()      # (one read-back)
+    if lim[0] < 0 or lim[1] > O or lim[2] < 0:
+        raise ValueError("triangulate_tracks: track_ptr is not a CSR over the observations")
+    if O and (lim[3] < 0 or lim[4] >= F):
+        raise IndexError("triangulate_tracks: frame index outside the projection table")
+    max_cos = math.cos(math.radians(min_angle_deg)) if min_angle_deg > 0 else 2.0
+    prm = _lib.TriParams(int(refine_iters), 0, float(max_reproj_px), max_cos, float(min_depth))
+    ws = torch.empty(max(lib.mm_triangulate_tracks_workspace_bytes(F), 256), dtype=torch.uint8, device=d)
+    if O == 0:      # (no observation at all: a valid pointer for the kernel's never-read arrays)
+        of_ = torch.zeros(1, dtype=torch.int32, device=d)
+        xy = torch.zeros((1, 2), dtype=torch.float64, device=d)
+    ctx.check(lib.mm_triangulate_tracks(ctx.h, ptr(proj.to(torch.float64).contiguous()), F, ptr(tp), T, ptr(of_), ptr(xy),
+                                        C.byref(prm), ptr(X), ptr(quality), ptr(flags), ptr(ws), ws.numel()),
+              "mm_triangulate_tracks")
+    return X, quality, flags
 
 
 # ------------------------------------------------------------------------------------------------ track linking

@@ -112,6 +112,13 @@ class ClipPipeline:
         proj = torch.as_tensor(np.ascontiguousarray(projections, np.float64)).to(d)
         return ops.triangulate_dlt(proj, f0.contiguous(), f1.contiguous(), x0, x1, self.ctx)
 
+    def triangulate_multi_view(self, track_ptr, obs_frame, obs_kp, kp_xy_dev, projections, **thresholds):
+        """Every track from ALL its observations (ops.triangulate_tracks on the flattened CSR) -> (points [T,3] f64,
+        quality [T,4] f64, flags [T] i32) on the device.  `thresholds` as ops.triangulate_tracks takes them."""
+        coords, of_, _ = ops.flatten_tracks(track_ptr, obs_frame, obs_kp, kp_xy_dev, ctx=self.ctx)
+        proj = torch.as_tensor(np.ascontiguousarray(projections, np.float64)).to(self.device)
+        return ops.triangulate_tracks(proj, track_ptr, of_, coords, ctx=self.ctx, **thresholds)
+
     # ------------------------------------------------------------------------------------------- flatten (managePoints)
     @staticmethod
     def flatten(track_ptr, obs_frame, obs_kp, kp_xy_host):
@@ -448,15 +455,34 @@ class ClipPipeline:
 
     # ------------------------------------------------------------------------------------------- whole clip
     def run(self, frames, K, extrinsics, ba=True, ftol=1e-4, verbose=0, dist=None, timers=None, max_nfev=None,
-            force_collectives=False):
+            force_collectives=False, triangulation="two_view", cull=None):
         """frames [F,H,W] u8 (device).  With `dist` = torch.distributed (initialised), frames are the FULL clip on
         every rank (synthetic input is generated locally) and the work is sharded as described in parallel.py.
         `max_nfev`: evaluation budget of the adjustment (None = SciPy's default, as adjustPoints).
         `force_collectives`: take the gather / all-reduce path even in a one-rank group (the collectives are trivial
-        but travel the real backend: how backend "nccl" is exercised on a single GPU)."""
+        but travel the real backend: how backend "nccl" is exercised on a single GPU).
+        `triangulation`: "two_view" (default) triangulates a track from its first and last observation, as the reference
+        does; "multi_view" from all its observations (`triangulate_multi_view`), and the result gains `track_quality`
+        [T,4] and `track_flags` [T].  `points0` is [T,3] over all tracks either way.
+        `cull` (needs "multi_view"; one rank only -- the track partition of the sharded adjustment works on contiguous
+        ranges): dict of the thresholds of ops.triangulate_tracks (max_reproj_px, min_angle_deg, min_depth, refine_iters).
+        The adjustment then takes only the tracks no test flagged, `kept_tracks` (indices in track order), and its
+        points are aligned with that list."""
+        if triangulation not in ("two_view", "multi_view"):
+            raise ValueError("triangulation must be 'two_view' or 'multi_view'")
         F = frames.shape[0]
         world = dist.get_world_size() if dist is not None else 1
         rank = dist.get_rank() if dist is not None else 0
+        if cull is not None and triangulation != "multi_view":
+            raise ValueError("cull needs triangulation='multi_view' (the two-view path has no per-track verdict)")
+        if cull is not None and world > 1:
+            raise ValueError("cull is not supported with more than one rank: the track partition takes contiguous ranges")
+        if cull is not None:
+            tests = {"max_reproj_px", "min_angle_deg", "min_depth"}
+            unknown = set(cull) - tests - {"refine_iters"}
+            if unknown or not tests & set(cull):
+                raise ValueError("cull takes max_reproj_px, min_angle_deg, min_depth (at least one) and refine_iters"
+                                 + (f"; not {sorted(unknown)}" if unknown else ""))
         sharded = world > 1 or (dist is not None and force_collectives)
         T = timers if timers is not None else {}
 
@@ -511,13 +537,22 @@ class ClipPipeline:
         ext = np.asarray(extrinsics, float)[:, :3, :]
         proj = np.einsum("ij,fjk->fik", np.asarray(K, float), ext)   # K [R|t], processor.py:184,448
         tic("triangulate")
-        X = self.triangulate(track_ptr, obs_frame, obs_kp, xy_dev, proj)
+        if triangulation == "multi_view":
+            X, quality, flags = self.triangulate_multi_view(track_ptr, obs_frame, obs_kp, xy_dev, proj, **(cull or {}))
+        else:
+            X = self.triangulate(track_ptr, obs_frame, obs_kp, xy_dev, proj)
         toc("triangulate")
         P, O = track_ptr.shape[0] - 1, obs_frame.shape[0]
         out = dict(det=det, n_tracks=P, n_obs=O, points0=X, track_ptr_dev=track_ptr, obs_frame_dev=obs_frame,
                    obs_kp_dev=obs_kp, xy_dev=xy_dev, match_count=m_h, kp_count=n_h, pairs_local=int(p_hi - p_lo),
                    frames_local=int(f_hi - f_lo))
-        if not ba or O == 0:
+        kept = None
+        if triangulation == "multi_view":
+            out.update(track_quality=quality, track_flags=flags)
+            if cull is not None:
+                kept = torch.nonzero(flags == 0).reshape(-1)
+                out["kept_tracks"] = kept
+        if not ba or O == 0 or (kept is not None and kept.numel() == 0):
             T.pop("_open", None)
             return out
         tic("ba")
@@ -525,14 +560,20 @@ class ClipPipeline:
             cams0 = frameParameters(ext).reshape(F, 6)
         # managePoints order (point-major, insertion order inside a track), assembled on the device
         d = self.device
-        if world > 1:
-            lo, hi, o_lo, o_hi = parallel.partition_tracks(track_ptr, rank, world)
+        if kept is not None:
+            # (mm_flatten_offsets + mm_flatten_tracks: the kept tracks, in track order)
+            coords_d, of_d, pi_d = ops.flatten_tracks(track_ptr, obs_frame, obs_kp, xy_dev, sel=kept, ctx=self.ctx)
+            pb = ops.BADevice(K, of_d, pi_d, coords_d, F, int(kept.numel()), d, self.ctx)
+            pts0 = X[kept].contiguous()
         else:
-            lo, hi, o_lo, o_hi = 0, P, 0, O
-        # (mm_flatten_tracks: this rank's tracks lo .. hi - 1)
-        coords_d, of_d, pi_d = ops.flatten_tracks(track_ptr, obs_frame, obs_kp, xy_dev, t_lo=lo, n_sel=hi - lo, ctx=self.ctx)
-        pb = ops.BADevice(K, of_d, pi_d, coords_d, F, hi - lo, d, self.ctx)
-        pts0 = X[lo:hi].contiguous()
+            if world > 1:
+                lo, hi, o_lo, o_hi = parallel.partition_tracks(track_ptr, rank, world)
+            else:
+                lo, hi, o_lo, o_hi = 0, P, 0, O
+            # (mm_flatten_tracks: this rank's tracks lo .. hi - 1)
+            coords_d, of_d, pi_d = ops.flatten_tracks(track_ptr, obs_frame, obs_kp, xy_dev, t_lo=lo, n_sel=hi - lo, ctx=self.ctx)
+            pb = ops.BADevice(K, of_d, pi_d, coords_d, F, hi - lo, d, self.ctx)
+            pts0 = X[lo:hi].contiguous()
         solver = SchurTRF(pb, allreduce=parallel.AllReduce(force=force_collectives) if sharded else None)
         cams_d = torch.as_tensor(cams0).to(self.device)
         tic("ba_solve")

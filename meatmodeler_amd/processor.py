@@ -7,6 +7,7 @@ return order, HIP kernels underneath (no CPU fallback: a missing extension or GP
     featureTracking                processor.py:113  featureTracking     (mm_orb_detect_compute + mm_bf_knn2_* + ratio)
     pointTracking                  processor.py:190  pointTracking       (hash join; same list semantics)
     triangulatePoints              processor.py:246  triangulatePoints   (mm_triangulate_dlt, batched over tracks)
+    (no counterpart)                                 triangulateTracks   (mm_triangulate_tracks: all views, quality, flags)
     managePoints                   processor.py:264  managePoints
     keyframeTracking               processor.py:61   keyframeTracking    (mm-LK + mm-GFTT: calcOpticalFlowPyrLK / goodFeaturesToTrack)
     increaseContrast               processor.py:12   increaseContrast    (fixed-point L*a*b* + CLAHE), cvtColorBGR2GRAY
@@ -372,6 +373,38 @@ def triangulatePoints(tracks, projections):
                             torch.as_tensor(x0).to(dev), torch.as_tensor(x1).to(dev), ctx).cpu().numpy()
     for i, track in enumerate(tracks):
         track.setPoint(X[i:i + 1].copy())
+
+
+def triangulateTracks(tracks, projections, **thresholds):
+    """Multi-view sibling of triangulatePoints: every track is triangulated from ALL of track.getCoordinates(), in
+    insertion order (ops.triangulate_tracks: linear least squares + a few Levenberg-Marquardt steps), and receives a (1,3)
+    float64 array via setPoint.  `thresholds`: refine_iters, max_reproj_px, min_angle_deg, min_depth.
+    -> (quality [n,4] f64 = (rms_px, max_px, min_depth, cos_parallax), flags [n] i32 of ops.TRI_* bits) as NumPy arrays.
+    Frame IDs behave as in triangulatePoints: a negative ID indexes from the end, one outside the list raises IndexError."""
+    n = len(tracks)
+    if n == 0:
+        return np.zeros((0, 4)), np.zeros(0, np.int32)
+    lens = np.fromiter((len(t.getCoordinates()) for t in tracks), np.int64, n)
+    track_ptr = np.zeros(n + 1, np.int64)
+    np.cumsum(lens, out=track_ptr[1:])
+    if track_ptr[-1] >= 2 ** 31:
+        raise ValueError("triangulateTracks: more than 2^31 - 1 observations")
+    frames = np.fromiter((f for t in tracks for f in t.getCoordinates().keys()), np.int64, int(track_ptr[-1]))
+    xy = np.array([(c[0], c[1]) for t in tracks for c in t.getCoordinates().values()], np.float64).reshape(-1, 2)
+    n_proj = len(projections)
+    if len(frames) and (frames.min() < -n_proj or frames.max() >= n_proj):
+        raise IndexError("list index out of range")          # what projections[frame_ID] raises, processor.py:257-258
+    frames[frames < 0] += n_proj
+    ctx = default_context()
+    dev = ctx.device
+    proj = torch.as_tensor(np.ascontiguousarray(np.asarray(projections, np.float64).reshape(-1, 3, 4))).to(dev)
+    X, quality, flags = ops.triangulate_tracks(proj, torch.as_tensor(track_ptr.astype(np.int32)).to(dev),
+                                               torch.as_tensor(frames.astype(np.int32)).to(dev), torch.as_tensor(xy).to(dev),
+                                               ctx=ctx, **thresholds)
+    X = X.cpu().numpy()
+    for i, track in enumerate(tracks):
+        track.setPoint(X[i:i + 1].copy())
+    return quality.cpu().numpy(), flags.cpu().numpy()
 
 
 # ----------------------------------------------------------------------------------------------- managePoints
