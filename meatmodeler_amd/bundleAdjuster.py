@@ -13,8 +13,11 @@ trust-region step, ratio test, ftol/xtol/gtol termination) runs with
 So the iterates follow SciPy's to within LSMR's own 1e-6 tolerance and the finite-difference error of the reference's
 Jacobian; see DESIGN.md §BA for what "parity" means on this gauge-free problem.
 
-Host Python only sequences launches and does the 2x2 / scalar algebra of the trust region; torch is used for
-device buffers and a handful of axpy / dot reductions on the parameter vector.
+The iteration of `adjustPoints` has two drivers, same kernels and bit-identical iterates: the loop inside the C-ABI
+library (mm_ba_trf and its fixed-camera and sharded forms; the default) and the device-resident loop sequenced from
+here (`SchurTRF._solve_device`).  Either way the 2x2 trust-region subproblem is solved on the device; host Python
+only sequences launches and takes the accept / reject / terminate decisions (`_TrfDecide`) from one small board of
+scalars per trial step.  torch is used for device buffers.
 """
 import math
 import os
@@ -24,7 +27,6 @@ import warnings
 import numpy as np
 import torch
 from numpy.linalg import norm as _norm
-from scipy.linalg import cho_factor, cho_solve, LinAlgError
 from scipy.sparse import csr_matrix
 
 from . import ops
@@ -125,47 +127,6 @@ def poseFun(parameters, camera_intrinsic_matrix, n_frames, frame_indices, point_
 
 # ----------------------------------------------------------------------------------------------- trust region (host scalars)
 
-_COMPANION4 = np.diag(np.ones(3), -1)
-
-
-def _solve_trust_region_2d(B, g, Delta):
-    """2-D trust-region subproblem exactly as scipy/optimize/_lsq/common.py:171-219 solves it: the Cholesky attempt
-    goes through the same LAPACK routines, the boundary case through the same quartic in t = tan(theta / 2).  The
-    quartic's roots are np.roots's own recipe (eigenvalues of the companion matrix, same LAPACK call) applied directly
-    when no coefficient vanishes, and the handful of candidate points is evaluated with scalar arithmetic instead of
-    NumPy temporaries: this sits between two GPU launches on the host (150 us of an iteration before, ~110 after)."""
-    try:
-        R, lower = cho_factor(B)
-        p = -cho_solve((R, lower), g)
-        if np.dot(p, p) <= Delta ** 2:
-            return p, True
-    except (LinAlgError, ValueError):
-        pass
-    b00, b01, b11 = float(B[0, 0]), float(B[0, 1]), float(B[1, 1])
-    g0, g1 = float(g[0]), float(g[1])
-    a = b00 * Delta ** 2
-    b = b01 * Delta ** 2
-    c = b11 * Delta ** 2
-    d = g0 * Delta
-    f = g1 * Delta
-    coeffs = np.array([-b + d, 2 * (a - c + f), 6 * b, 2 * (-a + c + f), -b - d])
-    if coeffs[0] != 0.0 and coeffs[-1] != 0.0:
-        A = _COMPANION4.copy()
-        A[0, :] = -coeffs[1:] / coeffs[0]
-        t = np.linalg.eigvals(A)
-    else:
-        t = np.roots(coeffs)
-    best, best_val = None, np.inf
-    for ti in t[np.isreal(t)].real.tolist():      # (in the order np.argmin would scan them: first minimum wins)
-        q = 1 + ti * ti
-        p0 = Delta * (2 * ti / q)
-        p1 = Delta * ((1 - ti * ti) / q)
-        val = 0.5 * (p0 * (b00 * p0 + b01 * p1) + p1 * (b01 * p0 + b11 * p1)) + (g0 * p0 + g1 * p1)
-        if val < best_val:
-            best, best_val = (p0, p1), val
-    return np.array(best), False
-
-
 def _update_tr_radius(Delta, actual, predicted, step_norm, bound_hit):
     if predicted > 0:
         ratio = actual / predicted
@@ -195,7 +156,7 @@ def _check_termination(dF, F, dx_norm, x_norm, ratio, ftol, xtol):
 class _TrfDecide:
     """The host's decisions of the trust-region solve -- accept / reject / try again / terminate as SciPy's trf_no_bounds
     takes them, plus the rule for raising the damping when the reduced camera system is not positive definite -- stated
-    once for the two loops sequenced from Python.  The Python statement of csrc/trf_decide.h, method for method and field
+    once for the loop sequenced from Python.  The Python statement of csrc/trf_decide.h, method for method and field
     for field (tests/test_trf_decisions_cpu.py replays the same boards through both); see there for a driver's iteration.
     `log` (a list, optional) receives the rows of the verbose=2 table, NaN where SciPy prints nothing."""
 
@@ -314,19 +275,19 @@ class SchurTRF:
     (points partitioned over GPUs, cameras replicated): it is called on every tensor that is a sum over
     observations.
 
-    The parameter vector lives in ONE flat device buffer x = [cams (6F) | points (3P)] (views are handed to the sweeps),
-    so every axpy / dot of the iteration is a single launch, and the host reads device scalars three times per
-    iteration (before the damping is known, after the step basis is built, after each trial step)."""
+    `solve` hands the iteration to one of two drivers: `_solve_library` (the loop inside the C-ABI library) or
+    `_solve_device` (the same loop sequenced from Python).  The parameter vector lives in ONE flat device buffer
+    x = [cams (6F) | points (3P)] (views are handed to the sweeps), so every axpy / dot of the iteration is a single
+    launch, and the host reads one board of device scalars per trial step."""
 
-    def __init__(self, pb, allreduce=None, timers=None, min_damping=1e-9, driver=None):
+    def __init__(self, pb, allreduce=None, min_damping=1e-9, driver=None):
         self.pb = pb
         self.allreduce = allreduce
-        self.timers = timers
         self.min_damping = min_damping
-        # "library": the loop itself runs inside the C-ABI library (mm_ba_trf; one GPU only); "python": sequenced from
-        # here (what the sharded path and the CPU stand-in of the tests use).  Same kernels, bit-identical iterates.
+        # "library": the loop itself runs inside the C-ABI library (mm_ba_trf, mm_ba_trf_fixed, mm_ba_trf_dist); "python":
+        # sequenced from here (also what the overlapped build, more than 16 ranks and a problem object without the library
+        # entry points -- the CPU stand-in of the tests -- get).  Same kernels, bit-identical iterates.
         self.driver = driver or os.environ.get("MM_TRF_DRIVER", "library")
-        self._overlap_checked = False
         self._avoid_fused = False
 
     # -- reductions that need the cross-rank sum when sharded --
@@ -351,12 +312,6 @@ class SchurTRF:
     def _pts(self, v):
         return v[self.nc:].view(self.pb.P, 3)
 
-    def _dots(self, pairs):
-        """[<a, b> for (a, b) in pairs] as a device vector; the camera part of the parameter vector is replicated on
-        every rank, the point part is sharded."""
-        out = self.pb.multi_dot(pairs, self.nc)          # [k, 3] = (camera part, point part, total), one launch
-        return self._combine(out)
-
     def _combine(self, rows):
         """rows [k, 3] of a fused pass -> [k] totals (the point part is summed across ranks when sharded)."""
         if self.allreduce is None:
@@ -365,317 +320,41 @@ class SchurTRF:
         # the ranks' copies differ in the last bit.  Rank 0's copy is the one that enters the sum: every rank then
         # holds the same scalars bit for bit, takes the same accept / reject / terminate decisions and stays inside the
         # same sequence of collectives.
-        t = (rows[:, 0] + rows[:, 1]) if getattr(self.allreduce, "rank", 0) == 0 else rows[:, 1].clone()
+        t = (rows[:, 0] + rows[:, 1]) if self.allreduce.rank == 0 else rows[:, 1].clone()
         t = t.contiguous()
         self.allreduce(t)
         return t
 
-    def _dots_sharded(self, pairs):
-        """Inner products of residual-space vectors (every rank holds its own observations)."""
-        out = self.pb.multi_dot(pairs, 0)[:, 2].contiguous()
-        self._ar(out)
-        return out
-
-    def _normal(self, x, g):
-        """Block normal equations at x; the gradient goes straight into the flat buffer g."""
-        if self._native:      # the sweeps write B / C into the persistent blocks and g_c / g_p into the two halves of g
-            out = (self._B, self._cams(g), self._C, self._pts(g))
-            B, gc, C, gp = self.pb.normal_eq(self._cams(x), self._pts(x), out=out)
-            self._ar(B, gc)
-            return B, C
-        B, gc, C, gp = self.pb.normal_eq(self._cams(x), self._pts(x))
-        self._ar(B, gc)          # camera blocks are sums over all observations; point blocks are local
-        g[:self.nc] = gc.reshape(-1)
-        g[self.nc:] = gp.reshape(-1)
-        return B, C
-
-    def _scale_inv(self, B, C, old=None):
-        if self._native:      # one launch: sqrt of the block diagonals, zeros -> 1 / running maximum, in place
-            return self.pb.scale_update(B, C, self._si, old is None)
-        si = torch.cat([torch.diagonal(B, dim1=1, dim2=2).reshape(-1), C[:, self.diag_idx].reshape(-1)]).sqrt_()
-        if old is None:
-            si[si == 0] = 1.0
-            return si
-        return torch.maximum(si, old)
-
-    def _damped_blocks(self, B, C, si, reg):
-        """B + reg diag(scale_inv^2), C + reg diag(scale_inv^2) (packed 6)."""
-        if self._native:
-            return self.pb.damp(B, C, si, reg, self._Bd, self._Cd)
-        nc, F, P = self.nc, self.pb.F, self.pb.P
-        sic2_36 = torch.diag_embed((si[:nc] * si[:nc]).view(F, 6))
-        sip2_6 = torch.zeros((P, 6), dtype=si.dtype, device=si.device)
-        sip2_6[:, self.diag_idx] = (si[nc:] * si[nc:]).view(P, 3)
-        return torch.addcmul(B, sic2_36, reg), torch.addcmul(C, sip2_6, reg)
-
-    def _serial_fallback(self, x, Bd, Cd, gc, gp, half_bw, solve=True):
-        warnings.warn("mm_ba_schur_solve: kernels are being serialised; building and solving the reduced system one "
-                      "after the other from here on")
-        self.pb.overlap = False
-        if solve:
-            return self.pb.schur_solve(self._cams(x), self._pts(x), Bd, Cd, gc, gp, half_bw)
-
-    def solve(self, cams0, pts0, ftol=1e-4, xtol=1e-8, gtol=1e-8, max_nfev=None, verbose=0, local_points_norm=None):
-        pb = self.pb
-        dev = pb.device
-        F, P = pb.F, pb.P
-        self.nc = nc = 6 * F
-        n = nc + 3 * P
-        f64 = dict(dtype=torch.float64, device=dev)
-        x = torch.cat([cams0.reshape(-1), pts0.reshape(-1)]).to(**f64).contiguous()
-        g = torch.empty(n, **f64)
-        self.diag_idx = torch.tensor([0, 3, 5], device=dev)
-        # block glue as single launches on persistent buffers when the problem object provides them (ops.BADevice)
-        self._native = hasattr(pb, "damp") and hasattr(pb, "scale_update")
-        if self._native:
-            self._B, self._C = torch.empty((F, 6, 6), **f64), torch.empty((P, 6), **f64)
-            self._Bd, self._Cd = torch.empty((F, 6, 6), **f64), torch.empty((P, 6), **f64)
-            self._si = torch.empty(n, **f64)
-
-        if getattr(pb, "F_fixed", 0):      # fixed cameras: the library loop only (mm_ba_trf_fixed)
-            if self.driver != "library" or self.allreduce is not None:
-                raise NotImplementedError("fixed cameras: only the library driver on one GPU (mm_ba_trf_fixed)")
-            return self._solve_library(x, ftol, xtol, gtol, max_nfev, verbose)
-        if (self.driver == "library" and self.allreduce is None and hasattr(pb, "trf_solve")
-                and not getattr(pb, "overlap", False)):
-            return self._solve_library(x, ftol, xtol, gtol, max_nfev, verbose)
-        c2 = self._cost_dev(x)
-        cost = 0.5 * float(c2.item())
-        if not np.isfinite(cost):
-            raise ValueError("Residuals are not finite in the initial point.")
-        # band of the reduced camera system: |camera i - camera j| <= span  ->  |row - col| <= 6 span + 5
-        span = torch.tensor([float(pb.cam_span)], **f64)
-        if self.allreduce is not None:
-            self.allreduce(span, op="max")
-        span_all = int(span.item())
-        half_bw = 6 * span_all + 5
-        # Sharded: what is exchanged for the reduced camera system is decided from GLOBAL quantities only, so that every
-        # rank enters the same collective with the same size whatever its own shard looks like (a rank whose points
-        # include one very long track, or no observation at all, builds S with the general kernel; the others with the
-        # pair-list kernel).  Every rank's S is zero outside the lower band |i - j| <= half_bw or symmetric inside it,
-        # so the packed band [n, half_bw + 1] carries everything the factorisation reads.
-        band_exchange = (self.allreduce is not None and hasattr(pb, "band_view")
-                         and span_all <= getattr(pb, "max_band_span", 192) and half_bw < nc)
-        if (self.driver == "library" and self.allreduce is not None and hasattr(pb, "trf_solve_dist")
-                and getattr(self.allreduce, "world_size", 1) <= 16):
-            # sharded: the same library loop, with this process group's all-reduce as its callback (mm_ba_trf_dist)
-            return self._solve_library(x, ftol, xtol, gtol, max_nfev, verbose, dist=(half_bw, band_exchange))
-        if self._native and hasattr(pb, "trf_step2d") and hasattr(pb, "schur_solve") and hasattr(pb, "jvp_dots"):
-            return self._solve_device(x, g, cost, half_bw, band_exchange, ftol, xtol, gtol, max_nfev, verbose)
-        B, C = self._normal(x, g)
-        si = self._scale_inv(B, C)
-        xs = x * si
-        # every decision from here on is the machine's; this loop does the device work its answers ask for
-        td = _TrfDecide(cost, float(self._dots([(xs, xs)])[0].item()), n, ftol, xtol, gtol, max_nfev, self.min_damping,
-                        log=[] if verbose == 2 else None)
-        if verbose == 2:
-            _print_header()
-        # wall time between the host synchronisation points of an iteration (the syncs drain the stream, so these are
-        # real intervals): normal equations, damping, Schur, Cholesky, subspace .. sync A | trial steps .. accept
-        seg = {"to_syncA": 0.0, "syncA_to_accept": 0.0}
-        t_mark = time.perf_counter()
-        state = td.begin()
-        while True:
-            # g_h = d * g (d = 1 / scale_inv) and d * g_h in one pass that also yields |g_h|^2 and |g|_inf
-            gh, ghs = torch.empty_like(g), torch.empty_like(g)
-            r0 = pb.trf_fused(0, [g, si], [gh, ghs], split=nc)
-            gh2_t = self._combine(r0[:1]).contiguous()
-            if self.allreduce is not None:
-                gmax_p = r0[1, 1:2].contiguous()
-                self.allreduce(gmax_p, op="max")
-                gmax = torch.maximum(r0[1, 0:1], gmax_p)
-            else:
-                gmax = r0[1, 2:3]
-            u1 = pb.jvp(self._cams(x), self._pts(x), self._cams(ghs), self._pts(ghs)).reshape(-1)   # J (d g_h)
-            d11_t = self._dots_sharded([(u1, u1)])
-            if state == _TrfDecide.FINAL:
-                td.on_final(float(gmax.item()))
-                if verbose == 2:
-                    _print_iteration(*td.log[-1])
-                break
-            # Cauchy-derived regulariser (trf.py:473-477) computed on the device: the reduced system is built and
-            # factored without the host having seen |g|, |g_h| or |J_h g_h| (they arrive with sync A).
-            # Damped blocks: J^T J + reg * D^-2  (D^-2 = scale_inv^2).  No gauge is fixed (as in the reference), so
-            # J^T J has a 7-dimensional null space and only the damping makes the reduced system definite; SciPy's
-            # LSMR copes with a singular system, a Cholesky factorisation needs `reg` to stay above rounding:
-            # a floor of 1e-9 (relative to the unit diagonal of the scaled system), x100 on a bad pivot, and the
-            # raised floor is kept for the rest of the solve (a system that needed it once needs it again).
-            damp = pb.trf_damping(gh2_t, d11_t, td.Delta, td.min_damping)
-            reg_eff = damp[1:2]
-            gc, gp = self._cams(g), self._pts(g)
-            while True:
-                Bd, Cd = self._damped_blocks(B, C, si, reg_eff)
-                if self.allreduce is None and hasattr(pb, "schur_solve"):
-                    # one GPU: the build of S and its factorisation overlap (mm_ba_schur_solve)
-                    info, v, Cinv = pb.schur_solve(self._cams(x), self._pts(x), Bd, Cd, gc, gp, half_bw)
-                    if getattr(pb, "overlap", False) and not self._overlap_checked:
-                        # first overlapped solve: make sure the two streams really ran concurrently (a profiler that
-                        # serialises kernels starves the consumer, which then gives up with info = -1)
-                        self._overlap_checked = True
-                        if int(info.item()) < 0:
-                            info, v, Cinv = self._serial_fallback(x, Bd, Cd, gc, gp, half_bw)
-                else:
-                    S, v, Cinv = pb.schur(self._cams(x), self._pts(x), Bd, Cd, gc, gp)
-                if self.allreduce is not None:
-                    # every rank added the full blockdiag(Bd) and gc: remove the duplicates after the sum
-                    ws = self.allreduce.world_size
-                    if band_exchange:
-                        # only the lower band is populated (pair-list Schur kernel): exchange n x (hb + 1) doubles
-                        # (12.7 MB at 500 cameras) instead of the dense 72 MB
-                        band = pb.band_view(half_bw)
-                        packed = band.contiguous()
-                        self.allreduce(packed)
-                        band.copy_(packed)
-                    else:
-                        self.allreduce(S)
-                    self.allreduce(v)
-                    if ws > 1:
-                        blk = S.reshape(F, 6, F, 6)
-                        f = torch.arange(F, device=dev)
-                        blk[f, :, f, :] -= (ws - 1) * Bd
-                        v -= (ws - 1) * gc.reshape(-1)
-                if self.allreduce is not None or not hasattr(pb, "schur_solve"):
-                    if hasattr(pb, "chol_solve_sym"):
-                        # after a band exchange only the lower band is the sum; the dense exchange sums everything
-                        info = pb.chol_solve_sym(S, v, half_bw, both_triangles=not band_exchange)
-                    else:
-                        info = pb.chol_solve(S, v, half_bandwidth=half_bw)
-                # q = [v ; dp] = (J^T J + reg D^-2)^-1 g, the unscaled Gauss-Newton step
-                dp = pb.backsub(self._cams(x), self._pts(x), Cinv, gp, v.view(F, 6)).reshape(-1)
-                # orthonormal basis of span{g_h, gn_h} (trf.py:481-482) in three fused passes:
-                #   gn_h = q * scale_inv, q1 = g_h / |g_h|            (+ <q1, gn_h>, |gn_h|^2)
-                #   w = gn_h - <q1, gn_h> q1                            (+ |w|^2)
-                #   q2 = w / |w|, s1 = d q1, s2 = d q2 (unscaled steps) (+ the five step inner products)
-                gn, q1, w = torch.empty_like(g), torch.empty_like(g), torch.empty_like(g)
-                r1 = self._combine(pb.trf_fused(1, [v, dp, si, gh], [gn, q1], [gh2_t], split=nc)[:2])
-                sc, gn2 = r1[0:1].contiguous(), r1[1]
-                wn2 = self._combine(pb.trf_fused(2, [gn, q1], [w], [sc], split=nc)[:1]).contiguous()
-                q2, s1, s2 = torch.empty_like(g), torch.empty_like(g), torch.empty_like(g)
-                nn = self._combine(pb.trf_fused(3, [w, q1, si, gh, x], [q2, s1, s2], [wn2], split=nc)[:5])
-                wn2 = wn2[0]
-                Jq2 = pb.jvp(self._cams(x), self._pts(x), self._cams(s2), self._pts(s2)).reshape(-1)
-                # J_h q1 = J (d q1) = u1 / |g_h|: <Jq1, Jq1> = d11 / |g_h|^2, <Jq1, Jq2> = <u1, Jq2> / |g_h|
-                bs = self._dots_sharded([(u1, Jq2), (Jq2, Jq2)])
-                # ---- host sync A ----
-                vals = torch.cat([info.to(torch.float64), wn2.reshape(1), gn2.reshape(1), bs, nn, gmax,
-                                  gh2_t.reshape(1), d11_t.reshape(1), reg_eff]).tolist()
-                info_h, wn2, gn2, u1Jq2, b22, n11, n12, n22, g2, xx, g_norm, gh2, d11, reg_used = vals
-                solved = td.on_solve(int(info_h), reg_used, g_norm, xx)
-                self.min_damping = td.min_damping      # (a raised floor outlives the solve)
-                if solved == _TrfDecide.ABANDONED:
-                    # the single-launch factorisation gave up waiting (its workgroups or the producer of S were not
-                    # co-resident: another tenant, a profiler attaching mid-run).  One GPU: redo this attempt with the
-                    # build and the solve one after the other and stay there; otherwise there is nothing to fall back to.
-                    if self.allreduce is None and getattr(pb, "overlap", False):
-                        self._serial_fallback(x, Bd, Cd, gc, gp, half_bw, solve=False)
-                        continue
-                    raise MMError("mm_chol_solve: the fused banded factorisation was abandoned (info = -1)")
-                if solved != _TrfDecide.RETRY:
-                    break
-                reg_eff = torch.full_like(reg_eff, td.reg)
-            if solved == _TrfDecide.INDEFINITE:
-                raise MMError(f"reduced camera system is not positive definite (pivot {int(info_h)})")
-            gh_norm = np.sqrt(gh2)
-            b11, b12 = d11 / gh2, u1Jq2 / gh_norm
-            t_now = time.perf_counter()
-            seg["to_syncA"] += t_now - t_mark
-            t_mark = t_now
-            if verbose == 2:
-                _print_iteration(*td.log[-1])
-            if solved == _TrfDecide.DONE:                             # gtol
-                break
-            if not (wn2 > 1e-28 * max(gn2, 1e-300)):       # gn_h parallel to g_h: the subspace is one-dimensional
-                s2 = torch.zeros_like(s1)
-                b12, b22, n12, n22, g2 = 0.0, 1.0, 0.0, 0.0, 0.0
-            B_S = np.array([[b11, b12], [b12, b22]])
-            g_S = np.array([gh_norm, g2])
-            state = _TrfDecide.TRIAL
-            while state == _TrfDecide.TRIAL:      # (the machine says when another trial step of this iteration is needed)
-                p_S, _ = _solve_trust_region_2d(B_S, g_S, td.Delta)
-                predicted = -(0.5 * p_S @ B_S @ p_S + g_S @ p_S)
-                x_new = torch.empty_like(x)
-                pb.trf_fused(4, [x, s1, s2], [x_new], h0=float(p_S[0]), h1=float(p_S[1]), split=nc)
-                cost2_new = float(self._cost_dev(x_new).item())           # ---- host sync 3 (per trial step) ----
-                step_norm = float(np.sqrt(max(p_S[0] ** 2 * n11 + 2 * p_S[0] * p_S[1] * n12 + p_S[1] ** 2 * n22, 0.0)))
-                state = td.on_trial(predicted, float(_norm(p_S)), step_norm, cost2_new)
-            t_now = time.perf_counter()
-            seg["syncA_to_accept"] += t_now - t_mark
-            t_mark = t_now
-            if td.accepted:
-                x = x_new
-                B, C = self._normal(x, g)
-                si = self._scale_inv(B, C, si)
-        return self._result(td, x, seg)
-
-    def _result(self, td, x, seg):
-        return BAResult(cams=self._cams(x).clone(), pts=self._pts(x).clone(), cost=td.cost, optimality=td.g_norm,
-                        nfev=td.nfev, njev=td.njev, status=td.status, message=_MESSAGES[td.status], success=td.status > 0,
-                        iterations=td.iteration, host_segments_ms={k: 1e3 * v for k, v in seg.items()})
-
-
-def _solve_library(self, x, ftol, xtol, gtol, max_nfev, verbose, dist=None):
-    """The whole loop of `_solve_device` inside the library: mm_ba_trf on one GPU, mm_ba_trf_dist (dist = (half bandwidth,
-    band exchange), both decided from all-reduced quantities) when the points are sharded over ranks (csrc/trf.hip)."""
-    nc = self.nc
-    cams, pts = x[:nc], x[nc:]
-    t0 = time.perf_counter()
-    if dist is None:
-        rep, rows = self.pb.trf_solve(cams, pts, ftol, xtol, gtol, max_nfev, self.min_damping,
-                                      log_cap=4096 if verbose == 2 else 0)
-    else:
-        rep, rows = self.pb.trf_solve_dist(cams, pts, ftol, xtol, gtol, self.allreduce, dist[0], dist[1], max_nfev,
-                                           self.min_damping, log_cap=4096 if verbose == 2 else 0)
-    self.min_damping = rep.min_damping
-    if verbose == 2:
-        _print_header()
-        for row in rows:
-            _print_iteration(*row)
-        if rep.log_rows > len(rows):
-            print(f"... ({rep.log_rows - len(rows)} more iterations)")
-    return BAResult(cams=self._cams(x).clone(), pts=self._pts(x).clone(), cost=rep.cost, optimality=rep.optimality,
-                    nfev=rep.nfev, njev=rep.njev, status=rep.status, message=_MESSAGES[rep.status],
-                    success=rep.status > 0, iterations=rep.iterations, chol_fallbacks=rep.chol_fallbacks,
-                    collectives=rep.collectives,
-                    host_segments_ms={"library": 1e3 * (time.perf_counter() - t0)})
-
-
-SchurTRF._solve_library = _solve_library
-
-
-def _solve_device(self, x, g, cost, half_bw, band_exchange, ftol, xtol, gtol, max_nfev, verbose):
-    """The same iteration as `SchurTRF.solve`'s generic loop (which serves the CPU stand-in of the tests), with everything
-    device resident: the 2-D trust-region subproblem is solved by a kernel from the fused passes' results
-    (mm_trf_step2d), the trial point is formed from its output and the host reads one small board of scalars per trial
-    step -- after the trial cost is known -- instead of synchronising twice per iteration.  Sharded (points partitioned
-    over ranks): every sum over observations / points is all-reduced on the device before the next kernel reads it (the
-    "total" column of the fused passes' result rows is overwritten with the cross-rank total), so all ranks feed
-    identical scalars to identical kernels and read identical boards."""
-    pb = self.pb
-    ar = self.allreduce
-
-    def fix_params(rows, k, max_row=None):
+    def _fix_params(self, rows, k, max_row=None):
         """result rows of a pass over the PARAMETER vector: column 2 <- cross-rank total (camera part replicated)."""
-        if ar is None:
+        if self.allreduce is None:
             return rows
         rows[:k, 2] = self._combine(rows[:k])
         if max_row is not None:
             m = rows[max_row, 1:2].contiguous()
-            ar(m, op="max")
+            self.allreduce(m, op="max")
             rows[max_row, 2:3] = torch.maximum(rows[max_row, 0:1], m)
         return rows
 
-    def fix_residual(rows):
+    def _fix_residual(self, rows):
         """result rows of inner products of RESIDUAL-space vectors (every rank holds its own observations)."""
-        if ar is None:
+        if self.allreduce is None:
             return rows
         t = rows[:, 2].contiguous()
-        ar(t)
+        self.allreduce(t)
         rows[:, 2] = t
         return rows
 
-    def reduced_solve(x, Bd, Cd, gc, gp):
+    def _normal(self, x, g, B, C):
+        """Block normal equations at x: the sweeps write into the persistent blocks B / C and put g_c / g_p straight into
+        the two halves of the flat gradient g.  Camera blocks are sums over all observations; point blocks are local."""
+        self.pb.normal_eq(self._cams(x), self._pts(x), out=(B, self._cams(g), C, self._pts(g)))
+        self._ar(B, self._cams(g))
+
+    def _reduced_solve(self, x, Bd, Cd, gc, gp, half_bw, band_exchange):
         """-> (info, v = solution of the reduced camera system, Cinv) at the current iterate x."""
-        if ar is None:
+        pb, ar = self.pb, self.allreduce
+        if ar is None:      # one GPU: S is built and factored in one call (mm_ba_schur_solve)
             return pb.schur_solve(self._cams(x), self._pts(x), Bd, Cd, gc, gp, half_bw)
         S, v, Cinv = pb.schur(self._cams(x), self._pts(x), Bd, Cd, gc, gp)
         ws = ar.world_size
@@ -693,122 +372,211 @@ def _solve_device(self, x, g, cost, half_bw, band_exchange, ftol, xtol, gtol, ma
             f = torch.arange(pb.F, device=pb.device)
             blk[f, :, f, :] -= (ws - 1) * Bd
             v -= (ws - 1) * gc.reshape(-1)
+        # after a band exchange only the lower band is the sum; the dense exchange sums everything
         info = pb.chol_solve_sym(S, v, half_bw, both_triangles=not band_exchange)
         return info, v, Cinv
 
-    # an abandoned single-launch factorisation switches THIS solve to the launch-per-column path; the context's setting
-    # (normally the shared default context) and this object's flag are restored on the way out, as trf.hip's FusedGuard does
-    self._avoid_fused = False
-    prev_avoid = pb.ctx.control(pb.ctx.CTL_CHOL_AVOID_FUSED, -1) if hasattr(pb, "ctx") else None
-    try:
-        return _solve_device_loop(self, x, g, cost, half_bw, ftol, xtol, gtol, max_nfev, verbose, fix_params, fix_residual,
-                                  reduced_solve)
-    finally:
-        if prev_avoid is not None:
-            pb.ctx.control(pb.ctx.CTL_CHOL_AVOID_FUSED, prev_avoid)
-        self._avoid_fused = False
+    def _serial_fallback(self):
+        warnings.warn("mm_ba_schur_solve: kernels are being serialised; building and solving the reduced system one "
+                      "after the other from here on")
+        self.pb.overlap = False
 
+    def solve(self, cams0, pts0, ftol=1e-4, xtol=1e-8, gtol=1e-8, max_nfev=None, verbose=0, local_points_norm=None):
+        pb, ar = self.pb, self.allreduce
+        self.nc = nc = 6 * pb.F
+        f64 = dict(dtype=torch.float64, device=pb.device)
+        x = torch.cat([cams0.reshape(-1), pts0.reshape(-1)]).to(**f64).contiguous()
+        # the one thing a problem object may lack: the library's entry points (trf_solve and trf_solve_dist come together)
+        library = self.driver == "library" and hasattr(pb, "trf_solve")
+        if pb.F_fixed:      # fixed cameras: the library loop only (mm_ba_trf_fixed)
+            if self.driver != "library" or ar is not None:
+                raise NotImplementedError("fixed cameras: only the library driver on one GPU (mm_ba_trf_fixed)")
+            return self._solve_library(x, ftol, xtol, gtol, max_nfev, verbose)
+        if library and ar is None and not pb.overlap:      # (the overlapped build is sequenced from Python)
+            return self._solve_library(x, ftol, xtol, gtol, max_nfev, verbose)
+        cost = 0.5 * float(self._cost_dev(x).item())
+        if not np.isfinite(cost):
+            raise ValueError("Residuals are not finite in the initial point.")
+        # band of the reduced camera system: |camera i - camera j| <= span  ->  |row - col| <= 6 span + 5
+        span = torch.tensor([float(pb.cam_span)], **f64)
+        if ar is not None:
+            ar(span, op="max")
+        span_all = int(span.item())
+        half_bw = 6 * span_all + 5
+        # Sharded: what is exchanged for the reduced camera system is decided from GLOBAL quantities only, so that every
+        # rank enters the same collective with the same size whatever its own shard looks like (a rank whose points
+        # include one very long track, or no observation at all, builds S with the general kernel; the others with the
+        # pair-list kernel).  Every rank's S is zero outside the lower band |i - j| <= half_bw or symmetric inside it,
+        # so the packed band [n, half_bw + 1] carries everything the factorisation reads.
+        band_exchange = ar is not None and span_all <= pb.max_band_span and half_bw < nc
+        if library and ar is not None and ar.world_size <= 16:
+            # sharded: the same library loop, with this process group's all-reduce as its callback (mm_ba_trf_dist)
+            return self._solve_library(x, ftol, xtol, gtol, max_nfev, verbose, dist=(half_bw, band_exchange))
+        return self._solve_device(x, cost, half_bw, band_exchange, ftol, xtol, gtol, max_nfev, verbose)
 
-def _solve_device_loop(self, x, g, cost, half_bw, ftol, xtol, gtol, max_nfev, verbose, fix_params, fix_residual, reduced_solve):
-    pb = self.pb
-    ar = self.allreduce
-    F, P, nc = pb.F, pb.P, self.nc
-    n = nc + 3 * P
-    f64 = dict(dtype=torch.float64, device=pb.device)
-    cams, pts = self._cams, self._pts
-    B, C = self._normal(x, g)
-    si = self._scale_inv(B, C)
-    xs = x * si
-    # every decision from here on is the machine's; this loop does the device work its answers ask for
-    td = _TrfDecide(cost, float(fix_params(pb.multi_dot([(xs, xs)], nc), 1)[0, 2].item()), n, ftol, xtol, gtol, max_nfev,
-                    self.min_damping, log=[] if verbose == 2 else None)
-    del xs
-    gh, ghs, gn, q1, w, q2, s1, s2, x_new = (torch.empty_like(g) for _ in range(9))
-    board = torch.zeros(16, **f64)
-    cost_slot = board[14:15]
-    if verbose == 2:
-        _print_header()
-    seg = {"to_syncA": 0.0, "syncA_to_accept": 0.0}
-    t_mark = time.perf_counter()
-    state = td.begin()
-    while True:
-        r0 = fix_params(pb.trf_fused(0, [g, si], [gh, ghs], split=nc), 1, max_row=1)   # rows: |g_h|^2 ; max |g|
-        gh2_t = r0[0, 2:3]
-        u1, d11 = pb.jvp_dots(cams(x), pts(x), cams(ghs), pts(ghs))         # J (d g_h) and |J d g_h|^2 in one sweep
-        d11 = fix_residual(d11)
-        if state == _TrfDecide.FINAL:
-            td.on_final(float(r0[1, 2].item()))
-            if verbose == 2:
-                _print_iteration(*td.log[-1])
-            break
-        damp = pb.trf_damping(gh2_t, d11[0, 2:3], td.Delta, td.min_damping)
-        reg_eff = damp[1:2]
-        gc, gp = cams(g), pts(g)
-        while True:
-            Bd, Cd = self._damped_blocks(B, C, si, reg_eff)
-            info, v, Cinv = reduced_solve(x, Bd, Cd, gc, gp)
-            dp = pb.backsub(cams(x), pts(x), Cinv, gp, v.view(F, 6)).reshape(-1)
-            # orthonormal basis of span{g_h, gn_h} (trf.py:481-482) in three fused passes (see the generic loop)
-            r1 = fix_params(pb.trf_fused(1, [v, dp, si, gh], [gn, q1], [gh2_t], split=nc), 2)
-            r2 = fix_params(pb.trf_fused(2, [gn, q1], [w], [r1[0, 2:3]], split=nc), 1)
-            r3 = fix_params(pb.trf_fused(3, [w, q1, si, gh, x], [q2, s1, s2], [r2[0, 2:3]], split=nc), 5)
-            _, bs = pb.jvp_dots(cams(x), pts(x), cams(s2), pts(s2), other=u1)   # <J s2, u1>, |J s2|^2
-            bs = fix_residual(bs)
+    def _result(self, td, x, seg):
+        return BAResult(cams=self._cams(x).clone(), pts=self._pts(x).clone(), cost=td.cost, optimality=td.g_norm,
+                        nfev=td.nfev, njev=td.njev, status=td.status, message=_MESSAGES[td.status], success=td.status > 0,
+                        iterations=td.iteration, host_segments_ms={k: 1e3 * v for k, v in seg.items()})
 
-            def trial(Delta_):
-                pb.trf_step2d(r0, d11, r1, r2, r3, bs, reg_eff, info, Delta_, board)
-                pb.trf_fused(5, [x, s1, s2], [x_new], [board], split=nc)
-                pb.residual(cams(x_new), pts(x_new), cost_out=cost_slot)
-                if ar is not None:
-                    ar(cost_slot)
-                return board.tolist()                                     # ---- the host sync of a trial step ----
-
-            vals = trial(td.Delta)       # enqueued before the host knows whether the factorisation succeeded
-            solved = td.on_solve(int(vals[6]), vals[13], vals[10], vals[9])
-            self.min_damping = td.min_damping      # (a raised floor outlives the solve)
-            if solved == _TrfDecide.ABANDONED:
-                # the single-launch factorisation gave up waiting (see the generic loop): build and solve one after
-                # the other from here on
-                if ar is None and getattr(pb, "overlap", False):
-                    self._serial_fallback(x, Bd, Cd, gc, gp, half_bw, solve=False)
-                    continue
-                if not self._avoid_fused and hasattr(pb, "ctx"):
-                    # its workgroups were not co-resident (another tenant on the GPU): repeat the attempt, same
-                    # damping, on the launch-per-column factorisation and stay there for the rest of the solve.
-                    # (Sharded: every rank reads the same replicated board... but info is LOCAL -- a rank-local decision
-                    # would desynchronise the collectives, so the switch is only taken on one GPU.)
-                    if ar is None:
-                        self._avoid_fused = True
-                        pb.ctx.control(pb.ctx.CTL_CHOL_AVOID_FUSED, 1)
-                        continue
-                raise MMError("mm_chol_solve: the fused banded factorisation was abandoned (info = -1)")
-            if solved != _TrfDecide.RETRY:
-                break
-            reg_eff = torch.full_like(reg_eff, td.reg)
-        if solved == _TrfDecide.INDEFINITE:
-            raise MMError(f"reduced camera system is not positive definite (pivot {int(vals[6])})")
-        t_now = time.perf_counter()
-        seg["to_syncA"] += t_now - t_mark
-        t_mark = t_now
+    def _solve_library(self, x, ftol, xtol, gtol, max_nfev, verbose, dist=None):
+        """The whole loop of `_solve_device` inside the library: mm_ba_trf on one GPU, mm_ba_trf_dist (dist = (half
+        bandwidth, band exchange), both decided from all-reduced quantities) when the points are sharded over ranks
+        (csrc/trf.hip)."""
+        nc = self.nc
+        cams, pts = x[:nc], x[nc:]
+        t0 = time.perf_counter()
+        if dist is None:
+            rep, rows = self.pb.trf_solve(cams, pts, ftol, xtol, gtol, max_nfev, self.min_damping,
+                                          log_cap=4096 if verbose == 2 else 0)
+        else:
+            rep, rows = self.pb.trf_solve_dist(cams, pts, ftol, xtol, gtol, self.allreduce, dist[0], dist[1], max_nfev,
+                                               self.min_damping, log_cap=4096 if verbose == 2 else 0)
+        self.min_damping = rep.min_damping
         if verbose == 2:
-            _print_iteration(*td.log[-1])
-        if solved == _TrfDecide.DONE:                                 # gtol: the trial point enqueued above is simply dropped
-            break
-        state = td.on_trial(vals[2], vals[3], vals[4], vals[14])
-        while state == _TrfDecide.TRIAL:      # (the machine says when another trial step of this iteration is needed)
-            vals = trial(td.Delta)
-            state = td.on_trial(vals[2], vals[3], vals[4], vals[14])
-        t_now = time.perf_counter()
-        seg["syncA_to_accept"] += t_now - t_mark
-        t_mark = t_now
-        if td.accepted:
-            x, x_new = x_new, x
-            B, C = self._normal(x, g)
-            si = self._scale_inv(B, C, si)
-    return self._result(td, x, seg)
+            _print_header()
+            for row in rows:
+                _print_iteration(*row)
+            if rep.log_rows > len(rows):
+                print(f"... ({rep.log_rows - len(rows)} more iterations)")
+        return BAResult(cams=self._cams(x).clone(), pts=self._pts(x).clone(), cost=rep.cost, optimality=rep.optimality,
+                        nfev=rep.nfev, njev=rep.njev, status=rep.status, message=_MESSAGES[rep.status],
+                        success=rep.status > 0, iterations=rep.iterations, chol_fallbacks=rep.chol_fallbacks,
+                        collectives=rep.collectives,
+                        host_segments_ms={"library": 1e3 * (time.perf_counter() - t0)})
 
+    def _solve_device(self, x, cost, half_bw, band_exchange, ftol, xtol, gtol, max_nfev, verbose):
+        """The iteration sequenced from Python, with everything device resident: block scaling and damping are single
+        launches on persistent buffers, the 2-D trust-region subproblem is solved by a kernel from the fused passes'
+        results (mm_trf_step2d), the trial point is formed from its output and the host reads one small board of scalars
+        per trial step -- after the trial cost is known.  Sharded (points partitioned over ranks): every sum over
+        observations / points is all-reduced on the device before the next kernel reads it (the "total" column of the
+        fused passes' result rows is overwritten with the cross-rank total), so all ranks feed identical scalars to
+        identical kernels and read identical boards."""
+        pb, ar = self.pb, self.allreduce
+        F, P, nc = pb.F, pb.P, self.nc
+        n = nc + 3 * P
+        f64 = dict(dtype=torch.float64, device=pb.device)
+        cams, pts = self._cams, self._pts
+        g, si = torch.empty(n, **f64), torch.empty(n, **f64)
+        B, C = torch.empty((F, 6, 6), **f64), torch.empty((P, 6), **f64)
+        Bd, Cd = torch.empty((F, 6, 6), **f64), torch.empty((P, 6), **f64)
+        self._normal(x, g, B, C)
+        pb.scale_update(B, C, si, True)      # si = sqrt of the block diagonals of J^T J, zeros -> 1
+        xs = x * si
+        # every decision from here on is the machine's; this loop does the device work its answers ask for
+        td = _TrfDecide(cost, float(self._fix_params(pb.multi_dot([(xs, xs)], nc), 1)[0, 2].item()), n, ftol, xtol, gtol,
+                        max_nfev, self.min_damping, log=[] if verbose == 2 else None)
+        del xs
+        gh, ghs, gn, q1, w, q2, s1, s2, x_new = (torch.empty_like(g) for _ in range(9))
+        board = torch.zeros(16, **f64)
+        cost_slot = board[14:15]
+        if verbose == 2:
+            _print_header()
+        # wall time between the host synchronisation points of an iteration (the syncs drain the stream, so these are real
+        # intervals): normal equations, damping, Schur, Cholesky, subspace, first trial step .. sync | further trial steps
+        seg = {"to_syncA": 0.0, "syncA_to_accept": 0.0}
+        t_mark = time.perf_counter()
+        state = td.begin()
+        # an abandoned single-launch factorisation switches THIS solve to the launch-per-column path; the context's setting
+        # (normally the shared default context) and this object's flag are restored on the way out, as trf.hip's
+        # FusedGuard does
+        has_ctx = getattr(pb, "ctx", None) is not None
+        self._avoid_fused = False
+        prev_avoid = pb.ctx.control(pb.ctx.CTL_CHOL_AVOID_FUSED, -1) if has_ctx else None
+        try:
+            while True:
+                # g_h = d * g (d = 1 / scale_inv) and d * g_h in one pass that also yields |g_h|^2 and max |g|
+                r0 = self._fix_params(pb.trf_fused(0, [g, si], [gh, ghs], split=nc), 1, max_row=1)
+                gh2_t = r0[0, 2:3]
+                u1, d11 = pb.jvp_dots(cams(x), pts(x), cams(ghs), pts(ghs))      # J (d g_h) and |J d g_h|^2 in one sweep
+                d11 = self._fix_residual(d11)
+                if state == _TrfDecide.FINAL:
+                    td.on_final(float(r0[1, 2].item()))
+                    if verbose == 2:
+                        _print_iteration(*td.log[-1])
+                    break
+                # Cauchy-derived regulariser (trf.py:473-477) computed on the device: the reduced system is built and
+                # factored without the host having seen |g|, |g_h| or |J_h g_h| (they arrive with the board).
+                # Damped blocks: J^T J + reg * D^-2  (D^-2 = scale_inv^2).  No gauge is fixed (as in the reference), so
+                # J^T J has a 7-dimensional null space and only the damping makes the reduced system definite; SciPy's
+                # LSMR copes with a singular system, a Cholesky factorisation needs `reg` to stay above rounding:
+                # a floor of 1e-9 (relative to the unit diagonal of the scaled system), x100 on a bad pivot, and the
+                # raised floor is kept for the rest of the solve (a system that needed it once needs it again).
+                reg_eff = pb.trf_damping(gh2_t, d11[0, 2:3], td.Delta, td.min_damping)[1:2]
+                gc, gp = cams(g), pts(g)
+                while True:
+                    pb.damp(B, C, si, reg_eff, Bd, Cd)      # Bd, Cd = B, C (packed 6) + reg diag(scale_inv^2)
+                    info, v, Cinv = self._reduced_solve(x, Bd, Cd, gc, gp, half_bw, band_exchange)
+                    # q = [v ; dp] = (J^T J + reg D^-2)^-1 g, the unscaled Gauss-Newton step
+                    dp = pb.backsub(cams(x), pts(x), Cinv, gp, v.view(F, 6)).reshape(-1)
+                    # orthonormal basis of span{g_h, gn_h} (trf.py:481-482) in three fused passes:
+                    #   gn_h = q * scale_inv, q1 = g_h / |g_h|            (+ <q1, gn_h>, |gn_h|^2)
+                    #   w = gn_h - <q1, gn_h> q1                            (+ |w|^2)
+                    #   q2 = w / |w|, s1 = d q1, s2 = d q2 (unscaled steps) (+ the five step inner products)
+                    r1 = self._fix_params(pb.trf_fused(1, [v, dp, si, gh], [gn, q1], [gh2_t], split=nc), 2)
+                    r2 = self._fix_params(pb.trf_fused(2, [gn, q1], [w], [r1[0, 2:3]], split=nc), 1)
+                    r3 = self._fix_params(pb.trf_fused(3, [w, q1, si, gh, x], [q2, s1, s2], [r2[0, 2:3]], split=nc), 5)
+                    # J_h q1 = J (d q1) = u1 / |g_h|: <Jq1, Jq1> = d11 / |g_h|^2, <Jq1, Jq2> = <u1, J s2> / |g_h|
+                    _, bs = pb.jvp_dots(cams(x), pts(x), cams(s2), pts(s2), other=u1)      # <J s2, u1>, |J s2|^2
+                    bs = self._fix_residual(bs)
 
-SchurTRF._solve_device = _solve_device
+                    def trial(Delta_):
+                        pb.trf_step2d(r0, d11, r1, r2, r3, bs, reg_eff, info, Delta_, board)
+                        pb.trf_fused(5, [x, s1, s2], [x_new], [board], split=nc)
+                        pb.residual(cams(x_new), pts(x_new), cost_out=cost_slot)
+                        if ar is not None:
+                            ar(cost_slot)
+                        return board.tolist()                                 # ---- the host sync of a trial step ----
+
+                    vals = trial(td.Delta)       # enqueued before the host knows whether the factorisation succeeded
+                    solved = td.on_solve(int(vals[6]), vals[13], vals[10], vals[9])
+                    self.min_damping = td.min_damping      # (a raised floor outlives the solve)
+                    if solved == _TrfDecide.ABANDONED:
+                        # the single-launch factorisation gave up waiting (its workgroups or the producer of S were not
+                        # co-resident: another tenant, a profiler attaching mid-run).  Overlapped build: redo this attempt
+                        # with the build and the solve one after the other and stay there.
+                        if ar is None and pb.overlap:
+                            self._serial_fallback()
+                            continue
+                        if not self._avoid_fused and has_ctx:
+                            # otherwise repeat the attempt, same damping, on the launch-per-column factorisation and stay
+                            # there for the rest of the solve.  (Sharded: every rank reads the same replicated board... but
+                            # info is LOCAL -- a rank-local decision would desynchronise the collectives, so the switch is
+                            # only taken on one GPU.)
+                            if ar is None:
+                                self._avoid_fused = True
+                                pb.ctx.control(pb.ctx.CTL_CHOL_AVOID_FUSED, 1)
+                                continue
+                        raise MMError("mm_chol_solve: the fused banded factorisation was abandoned (info = -1)")
+                    if solved != _TrfDecide.RETRY:
+                        break
+                    reg_eff = torch.full_like(reg_eff, td.reg)
+                if solved == _TrfDecide.INDEFINITE:
+                    raise MMError(f"reduced camera system is not positive definite (pivot {int(vals[6])})")
+                t_now = time.perf_counter()
+                seg["to_syncA"] += t_now - t_mark
+                t_mark = t_now
+                if verbose == 2:
+                    _print_iteration(*td.log[-1])
+                if solved == _TrfDecide.DONE:      # gtol: the trial point enqueued above is simply dropped
+                    break
+                state = td.on_trial(vals[2], vals[3], vals[4], vals[14])
+                while state == _TrfDecide.TRIAL:      # (the machine says when this iteration needs another trial step)
+                    vals = trial(td.Delta)
+                    state = td.on_trial(vals[2], vals[3], vals[4], vals[14])
+                t_now = time.perf_counter()
+                seg["syncA_to_accept"] += t_now - t_mark
+                t_mark = t_now
+                if td.accepted:
+                    x, x_new = x_new, x
+                    self._normal(x, g, B, C)
+                    pb.scale_update(B, C, si, False)      # running maximum
+            return self._result(td, x, seg)
+        finally:
+            if prev_avoid is not None:
+                pb.ctx.control(pb.ctx.CTL_CHOL_AVOID_FUSED, prev_avoid)
+            self._avoid_fused = False
 
 
 def _finish_verbose(res, cost0, verbose):

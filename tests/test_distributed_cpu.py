@@ -4,7 +4,8 @@
 * the sharded trust-region driver (`SchurTRF` with an `AllReduce`): points are split over the ranks, cameras are
   replicated, camera-side blocks / the reduced camera system / a few scalars are all-reduced.  The HIP sweeps cannot
   run here, so the test plugs a NumPy stand-in for `ops.BADevice` (built on the oracle's cost function) into the
-  product driver — what is under test is the driver's sharding algebra and collective placement, which must
+  product driver.  The loop under test is the Python-sequenced loop production runs (`SchurTRF._solve_device`, which
+  a problem object without the library's entry points gets): its sharding algebra and collective placement must
   reproduce the single-process iterates.
 """
 import os
@@ -16,6 +17,7 @@ import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
+from scipy.optimize._lsq.common import solve_trust_region_2d
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
@@ -26,7 +28,10 @@ from oracle import ba_oracle as bo  # noqa: E402
 
 
 class NumpyBA:
-    """Test double for ops.BADevice on CPU tensors (dense NumPy algebra; central-difference Jacobian blocks)."""
+    """Test double for ops.BADevice on CPU tensors, as far as `SchurTRF._solve_device` uses it (dense NumPy algebra;
+    central-difference Jacobian blocks; NumPy / torch restatements of what the product's kernels compute)."""
+    F_fixed, overlap = 0, False
+    max_band_span = -1      # there is no band_view: the ranks exchange the dense reduced system
 
     def __init__(self, K, fi, pi, obs, F, P):
         self.K, self.fi, self.pi, self.obs = np.asarray(K, float), np.asarray(fi), np.asarray(pi), np.asarray(obs, float)
@@ -50,11 +55,14 @@ class NumpyBA:
     def _jac(self, cams, pts):
         return bo.jacobian_fd(self._x(cams, pts), self.K, self.F, self.P, self.fi, self.pi, self.obs, h=1e-6)
 
-    def residual(self, cams, pts, want_res=False):
+    def residual(self, cams, pts, want_res=False, cost_out=None):
         r = self._res(cams, pts)
-        return torch.tensor([float((r * r).sum())], dtype=torch.float64), (torch.from_numpy(r) if want_res else None)
+        c2 = torch.tensor([float((r * r).sum())], dtype=torch.float64)
+        if cost_out is not None:
+            c2 = cost_out.copy_(c2)
+        return c2, (torch.from_numpy(r) if want_res else None)
 
-    def normal_eq(self, cams, pts, want_cams=True, want_pts=True):
+    def normal_eq(self, cams, pts, want_cams=True, want_pts=True, out=None):
         Jc, Jp = self._jac(cams, pts)
         r = self._res(cams, pts)
         B = np.zeros((self.F, 6, 6)); gc = np.zeros((self.F, 6)); C = np.zeros((self.P, 3, 3)); gp = np.zeros((self.P, 3))
@@ -63,12 +71,32 @@ class NumpyBA:
         np.add.at(C, self.pi, np.einsum("omi,omj->oij", Jp, Jp))
         np.add.at(gp, self.pi, np.einsum("omi,om->oi", Jp, r))
         C6 = np.stack([C[:, 0, 0], C[:, 0, 1], C[:, 0, 2], C[:, 1, 1], C[:, 1, 2], C[:, 2, 2]], 1)
-        return torch.from_numpy(B), torch.from_numpy(gc), torch.from_numpy(C6), torch.from_numpy(gp)
+        res = tuple(torch.from_numpy(a) for a in (B, gc, C6, gp))
+        return res if out is None else tuple(o.copy_(a) for o, a in zip(out, res))
+
+    def scale_update(self, B, C6, si, first):
+        d = torch.cat([torch.diagonal(B, dim1=1, dim2=2).reshape(-1), C6[:, [0, 3, 5]].reshape(-1)]).sqrt_()
+        if first:
+            d[d == 0] = 1.0
+        return si.copy_(d if first else torch.maximum(si, d))
+
+    def damp(self, B, C6, si, reg, Bd, Cd):
+        nc = 6 * self.F
+        Bd.copy_(torch.addcmul(B, torch.diag_embed((si[:nc] * si[:nc]).view(self.F, 6)), reg))
+        Cd.copy_(C6)
+        Cd[:, [0, 3, 5]] = torch.addcmul(C6[:, [0, 3, 5]], (si[nc:] * si[nc:]).view(self.P, 3), reg)
+        return Bd, Cd
 
     def jvp(self, cams, pts, wc, wp):
         Jc, Jp = self._jac(cams, pts)
         out = np.einsum("omi,oi->om", Jc, wc.numpy()[self.fi]) + np.einsum("omi,oi->om", Jp, wp.numpy()[self.pi])
         return torch.from_numpy(out)
+
+    def jvp_dots(self, cams, pts, wc, wp, other=None):
+        out = self.jvp(cams, pts, wc, wp)
+        z, oo = torch.zeros((), dtype=torch.float64), (out * out).sum()
+        oa = oo if other is None else (out * other).sum()
+        return out, torch.stack([torch.stack([z, oa, oa]), torch.stack([z, oo, oo])])
 
     def multi_dot(self, pairs, split=0):
         rows = [[torch.dot(a[:split], b[:split]), torch.dot(a[split:], b[split:]), torch.dot(a, b)] for a, b in pairs]
@@ -105,9 +133,25 @@ class NumpyBA:
             outs[1].copy_(q1 / si)
             outs[2].copy_(outs[0] / si)
             return rows([(outs[1], outs[1]), (outs[1], outs[2]), (outs[2], outs[2]), (outs[0], gh), (x, x)])
-        x, s1, s2 = ins
-        outs[0].copy_(x + h0 * s1 + h1 * s2)
+        x, s1, s2 = ins      # op 5: the step coefficients are the first two entries of the board; p1 == 0 skips s2
+        p0, p1 = scalars[0][0], scalars[0][1]
+        outs[0].copy_(x + p0 * s1 + p1 * s2 if p1 != 0 else x + p0 * s1)
         return torch.zeros((1, 3), dtype=torch.float64)
+
+    def trf_step2d(self, r0, d11, r1, r2, r3, bs, reg, info, Delta, board):
+        """mm_trf_step2d (trf_step2d_body, csrc/vec.hip) with the 2x2 problem handed to SciPy's own solver."""
+        gh2, gmax, d, gn2, wn2 = (float(t) for t in (r0[0, 2], r0[1, 2], d11[0, 2], r1[1, 2], r2[0, 2]))
+        n11, n12, n22, g2, xx = r3[:5, 2].tolist()
+        b12, b22 = float(bs[0, 2]) / np.sqrt(gh2), float(bs[1, 2])
+        degenerate = not (wn2 > 1e-28 * max(gn2, 1e-300))      # gn_h parallel to g_h: the subspace is one-dimensional
+        if degenerate:
+            b12, b22, n12, n22, g2 = 0.0, 1.0, 0.0, 0.0, 0.0
+        B_S, g_S = np.array([[d / gh2, b12], [b12, b22]]), np.array([np.sqrt(gh2), g2])
+        p0, p1 = solve_trust_region_2d(B_S, g_S, Delta)[0]
+        p = np.array([p0, 0.0 if degenerate else p1])
+        step_norm = np.sqrt(max(p[0] ** 2 * n11 + 2 * p[0] * p[1] * n12 + p[1] ** 2 * n22, 0.0))
+        board[:14] = torch.tensor([p[0], p[1], -(0.5 * p @ B_S @ p + g_S @ p), np.hypot(*p), step_norm, float(degenerate),
+                                   float(info), wn2, gn2, xx, gmax, gh2, d, float(reg)], dtype=torch.float64)
 
     def trf_damping(self, gh2, d11, Delta, min_damping):
         """SciPy trf.py:473-477 (the product runs this as a one-thread kernel, mm_trf_damping)."""
@@ -156,6 +200,13 @@ class NumpyBA:
             return torch.tensor([1], dtype=torch.int32)
         v.copy_(torch.from_numpy(np.linalg.solve(A, v.numpy())))
         return torch.tensor([0], dtype=torch.int32)
+
+    def schur_solve(self, cams, pts, Bd, Cd, gc, gp, half_bandwidth):
+        S, v, Cinv = self.schur(cams, pts, Bd, Cd, gc, gp)
+        return self.chol_solve(S, v, half_bandwidth), v, Cinv
+
+    def chol_solve_sym(self, S, v, half_bandwidth, both_triangles):
+        return self.chol_solve(S, v, half_bandwidth)
 
     def backsub(self, cams, pts, Cinv, gp, dc):
         Jc, Jp = self._jac(cams, pts)

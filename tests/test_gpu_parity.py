@@ -764,6 +764,71 @@ def test_trf_damping_vs_scipy_formula():
         np.testing.assert_allclose(out, [reg, max(reg, floor)], rtol=1e-13, atol=0)
 
 
+STEP2D_MODEL_TOL = 64 * np.finfo(float).eps      # max(64 eps, 16 x 3.8e-16, the largest excess measured on an MI355X)
+
+
+def _step2d_boards(rows, regs, Deltas):
+    """rows [N, 6, 5, 3] (per case: r0, d11, r1, r2, r3, bs as [5, 3] result blocks), info = 0 -> boards [N, 16]; one wave per case."""
+    ctx = default_context()
+    rows_d, regs_d, info = dev(rows), dev(np.asarray(regs, float)), torch.zeros(1, dtype=torch.int32, device=DEV)
+    boards = torch.full((len(rows), 16), np.nan, dtype=torch.float64, device=DEV)
+    for k, Delta in enumerate(Deltas):
+        ctx.check(ops.lib.mm_trf_step2d(ctx.h, *(ops.ptr(rows_d[k, j]) for j in range(6)), ops.ptr(regs_d[k:k + 1]), ops.ptr(info),
+                                        float(Delta), ops.ptr(boards[k])), "mm_trf_step2d")
+    return boards.cpu().numpy()
+
+
+def test_trf_step2d_vs_scipy_solver():
+    """mm_trf_step2d against scipy's solve_trust_region_2d: 50 random SPD B x three radii, as a two-dimensional and as
+    a one-dimensional (|w|^2 = 0) subspace.  The two minimisers round differently on the boundary (eigenvalues of a
+    companion matrix there, a 64-ary search here), so the steps are compared through the model value they reach."""
+    from scipy.optimize._lsq.common import solve_trust_region_2d
+    eps = np.finfo(float).eps
+    rng = np.random.default_rng(0)
+    cases = []
+    for _ in range(50):
+        M = rng.normal(size=(2, 2))
+        B = M @ M.T + 1e-3 * np.eye(2)
+        g = rng.normal(size=2) * 10
+        g[0] = abs(g[0])      # it stands for |g_h|
+        n11, n22, xx, gmax, reg = rng.uniform(0.5, 2.0, 5)
+        cases += [(B, g, Delta, wn2, n11, 0.3 * np.sqrt(n11 * n22), n22, xx, gmax, reg)
+                  for wn2 in (1.0, 0.0) for Delta in (1e-3, 0.5, 10.0)]
+    rows = np.zeros((len(cases), 6, 5, 3))
+    for R, (B, g, Delta, wn2, n11, n12, n22, xx, gmax, reg) in zip(rows, cases):
+        R[0, :2, 2] = g[0] ** 2, gmax
+        R[1, 0, 2] = B[0, 0] * g[0] ** 2
+        R[2, 1, 2], R[3, 0, 2] = 1.0, wn2
+        R[4, :, 2] = n11, n12, n22, g[1], xx
+        R[5, :2, 2] = B[0, 1] * g[0], B[1, 1]
+    boards = _step2d_boards(rows, [c[9] for c in cases], [c[2] for c in cases])
+    near, excess = 0, 0.0
+    for R, bd, (_, _, Delta, wn2, n11, n12, n22, xx, gmax, reg) in zip(rows, boards, cases):
+        gh2, d11 = R[0, 0, 2], R[1, 0, 2]      # B and g as the kernel forms them from the rows
+        B = np.array([[d11 / gh2, R[5, 0, 2] / np.sqrt(gh2)], [R[5, 0, 2] / np.sqrt(gh2), R[5, 1, 2]]])
+        g = np.array([np.sqrt(gh2), R[4, 3, 2]])
+        if wn2 == 0.0:
+            B, g, n12, n22 = np.diag([B[0, 0], 1.0]), np.array([g[0], 0.0]), 0.0, 0.0
+            assert bd[1] == 0.0 and bd[5] == 1.0
+        ps, newton = solve_trust_region_2d(B, g, Delta)
+        p = bd[:2]
+        assert bd[3] <= Delta * (1 + 4 * eps)
+        if newton and np.linalg.norm(ps) >= Delta * (1 - 1e-9):
+            near += 1
+        else:      # (a step ON the circle has |p| within rounding of Delta on either side; a Newton step kept here is 1e-9 inside)
+            assert (bd[3] < Delta * (1 - 4 * eps)) == newton
+        scale = 0.5 * np.linalg.norm(B, 2) * Delta ** 2 + np.linalg.norm(g) * Delta
+        model = lambda q: 0.5 * q @ B @ q + g @ q      # noqa: E731
+        excess = max(excess, (model(p) - model(ps)) / scale)
+        assert model(p) <= model(ps) + STEP2D_MODEL_TOL * scale
+        assert abs(bd[2] + model(p)) <= STEP2D_MODEL_TOL * scale
+        # three products of like sign up to the cross term (|n12| = 0.3 sqrt(n11 n22)): no cancellation beyond 1.3 / 0.7
+        np.testing.assert_allclose(bd[4], np.sqrt(max(p[0] ** 2 * n11 + 2 * p[0] * p[1] * n12 + p[1] ** 2 * n22, 0.0)), rtol=8 * eps)
+        np.testing.assert_array_equal(bd[5:14], [float(wn2 == 0.0), 0.0, wn2, 1.0, xx, gmax, gh2, d11, reg])
+    print(f"mm_trf_step2d: largest relative model excess over scipy {excess:.3e}, {near} near-boundary cases excluded")
+    assert near <= 2
+
+
 def test_band_view_addresses_lower_band():
     pr = synth.make_ba_problem(12, 80, 4, seed=2)
     pb = ops.BADevice(pr["K"], pr["fi"], pr["pi"], pr["obs"], 12, 80, DEV)
