@@ -184,6 +184,65 @@ int64_t mm_ba_build_pairs(int F, int P, int64_t O, const int32_t *fi, const int3
 int mm_ba_build_index(int F, int P, int64_t O, const int32_t *fi, const int32_t *pi, int32_t *pt_ptr /*[P+1]*/,
                       int32_t *pt_obs /*[O]*/, int32_t *cam_ptr /*[F+1]*/, int32_t *cam_obs /*[O]*/);
 
+/* ---- a-2b: epipolar verification of the matches of consecutive frame pairs (no reference counterpart) -------------
+ * A fundamental matrix per frame pair, estimated robustly (RANSAC with the MSAC score), and the matches that agree with it:
+ * the stage between mm_ratio_filter_batched and mm_link_tracks_device.  It needs no poses and no calibration.
+ *   Inputs.  Pair p joins frame p (query) and frame p + 1 (train) of a block of n_pairs + 1 frames: kp_xy [n_pairs+1, cap, 2]
+ *   f32, pairs [n_pairs, cap, 2] i32 = (queryIdx, trainIdx), m [n_pairs] i32 (clamped to 0 .. cap) -- what
+ *   mm_ratio_filter_batched writes.  Match j gives x = kp_xy[p, q_j], x' = kp_xy[p+1, t_j], widened to f64; the convention is
+ *   x'^T F x = 0 on homogeneous pixels, F row-major.  A match with an index outside [0, cap) is MALFORMED: never an inlier, a
+ *   hypothesis that samples it is invalid, the pair is flagged, nothing is read through the index.
+ *   Distance.  Sampson: d^2 = (x'^T F x)^2 / ((F x)_0^2 + (F x)_1^2 + (F^T x')_0^2 + (F^T x')_1^2); a match is an inlier when
+ *   d^2 is finite and d^2 <= tau^2, tau = threshold_px.
+ *   Score.  MSAC: cost(F) = sum_j (inlier_j ? d_j^2 : tau^2) -- a malformed match contributes tau^2 -- continuous in F, so the
+ *   winner does not hinge on a match on the threshold.  An invalid hypothesis costs +inf.  The lowest FINITE cost wins, ties go
+ *   to the lowest h.
+ *   Normalisation (Hartley), per image, over all well-formed matches of the pair: centroid c, mean distance dbar to c,
+ *   s = sqrt(2) / dbar, T = [[s, 0, -s c_x], [0, s, -s c_y], [0, 0, 1]].  A non-finite s (all points equal, no well-formed
+ *   match) leaves the pair without a valid hypothesis.
+ *   Sampling, integers only (arithmetic mod 2^32):  pcg(v): s = v * 747796405 + 2891336453;
+ *   w = ((s >> ((s >> 28) + 4)) ^ s) * 277803737;  return (w >> 22) ^ w.   Hypothesis h of pair p:
+ *   base = pcg(pcg(seed + pcg(pair_base + p)) + h); pick k = 0 .. 7 tries a = 0 .. 7: i = (uint64(pcg(base + 8 k + a)) * m) >> 32
+ *   and takes the first i that is not among the earlier picks; eight collisions make the hypothesis invalid (at most (7/16)^8
+ *   per pick for m >= 16: why min_matches is floored at 16).  pair_base is the global index of pair 0 of the call, so a
+ *   rank's block of pairs gives the rows the whole clip would give.
+ *   Hypothesis.  The eight normalised matches give the rows [x'x, x'y, x', y'x, y'y, y', x, y, 1]; f is the unit right null
+ *   vector of that 8 x 9 matrix (rows orthonormalised in registers, twice each; the null vector is the largest column of
+ *   I - Q^T Q); rank 2: F^ <- F^ - (F^ v3) v3^T with v3 the eigenvector of the smallest eigenvalue of F^^T F^ (3 x 3 cyclic
+ *   Jacobi); F = T'^T F^ T scaled to unit Frobenius norm; a non-finite F makes the hypothesis invalid.
+ *   Refit.  refit_iters rounds (a fixed count): take the inliers of the current F -- fewer than 8: nothing changes any more --
+ *   normalise over them, M = A^T A (9 x 9) over them, f = eigenvector of the smallest eigenvalue of M (cyclic Jacobi, a
+ *   rotation skipped once |m_pq| <= eps sqrt(m_pp m_qq)), rank 2, denormalise, unit norm; the refit replaces F only if it is
+ *   finite and its cost over ALL matches is finite and strictly lower.
+ *   Outputs.  pairs_out [n_pairs, cap, 2] (must not alias pairs): the inliers of the final F in their input order, m_out
+ *   [n_pairs] their number; rows at or beyond m_out[p] are left untouched.  Fm [n_pairs, 9] f64 unit norm (NaN: no model),
+ *   cost [n_pairs] f64 of the final F (NaN: no model), info [n_pairs, 4] i32 = (flags, n_inliers, best_h or -1, number of valid
+ *   hypotheses).
+ *   Flags.  MM_VERIFY_TOO_FEW m < max(min_matches, 16): no RANSAC is run | MM_VERIFY_NO_MODEL no hypothesis with a finite
+ *   cost | MM_VERIFY_WEAK n_inliers < min_inliers | MM_VERIFY_MALFORMED.  The first three are failures: on_fail = 0 passes all
+ *   m matches of the pair through unchanged (a malformed one included -- the flag says so), on_fail = 1 drops them (m_out = 0).
+ * Sums run in an order that depends on the pair alone (per-thread strides, fixed trees), no atomics: a call repeats bit for
+ * bit, a pair's row does not depend on which other pairs share the call, and rows [a, b) of a call equal a call on that
+ * sub-block with pair_base + a.  n_pairs = 0 returns MM_OK without a launch.  All pointers are DEVICE pointers except prm;
+ * kp_xy, pairs and pairs_out 8-byte aligned; ws holds mm_verify_workspace_bytes(n_pairs, n_hyp) bytes (normalisations, every
+ * hypothesis' F and cost).  Argument errors -- n_hyp outside 1 .. 4096, a negative or NaN threshold_px, null pointers:
+ * MM_ERR_ARG; a workspace that is too small: MM_ERR_WORKSPACE -- are returned before the device is touched. */
+#define MM_VERIFY_TOO_FEW 1
+#define MM_VERIFY_NO_MODEL 2
+#define MM_VERIFY_WEAK 4
+#define MM_VERIFY_MALFORMED 8
+typedef struct mm_verify_params {
+    int32_t n_hyp, min_matches, min_inliers, refit_iters;
+    uint32_t seed, pair_base;
+    int32_t on_fail, reserved;
+    double threshold_px;
+} mm_verify_params;
+size_t mm_verify_workspace_bytes(int n_pairs, int n_hyp);
+int mm_verify_matches(mm_ctx *ctx, const float *kp_xy /*[n_pairs+1,cap,2]*/, const int32_t *pairs /*[n_pairs,cap,2]*/,
+                      const int32_t *m /*[n_pairs]*/, int n_pairs, int cap, const mm_verify_params *prm,
+                      int32_t *pairs_out /*[n_pairs,cap,2]*/, int32_t *m_out /*[n_pairs]*/, double *Fm /*[n_pairs,9]*/,
+                      double *cost /*[n_pairs]*/, int32_t *info /*[n_pairs,4]*/, void *ws, size_t ws_bytes);
+
 /* ---- a-4: two-view DLT triangulation ------------------------------------------------------------
  * Replaces the per-track cv2.triangulatePoints + dehomogenise loop, processor.py:254-261.
  * proj [F,3,4] f64; track i uses views f0[i], f1[i] with pixels x0[i], x1[i]; X [n,3]. */

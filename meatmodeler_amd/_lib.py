@@ -57,6 +57,13 @@ class TriParams(C.Structure):
                 ("max_cos_parallax", C.c_double), ("min_depth", C.c_double)]
 
 
+class VerifyParams(C.Structure):
+    """mm_verify_params: hypotheses, threshold, sampling key and failure policy of mm_verify_matches."""
+    _fields_ = [("n_hyp", C.c_int32), ("min_matches", C.c_int32), ("min_inliers", C.c_int32), ("refit_iters", C.c_int32),
+                ("seed", C.c_uint32), ("pair_base", C.c_uint32), ("on_fail", C.c_int32), ("reserved", C.c_int32),
+                ("threshold_px", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, vp, vp, C.c_int64)
 
 
@@ -105,6 +112,8 @@ SIGNATURES = {
     "mm_ba_build_pairs": (C.c_int64, [C.c_int, C.c_int, C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int,
                                       c_i64p, c_i32p, c_i32p, C.c_int64]),
     "mm_ba_build_index": (C.c_int, [C.c_int, C.c_int, C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]),
+    "mm_verify_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "mm_verify_matches": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(VerifyParams), vp, vp, vp, vp, vp, vp, C.c_size_t]),
     "mm_triangulate_dlt": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int64, vp]),
     "mm_triangulate_tracks_workspace_bytes": (C.c_size_t, [C.c_int]),
     "mm_triangulate_tracks": (C.c_int, [vp, vp, C.c_int, vp, C.c_int64, vp, vp, C.POINTER(TriParams), vp, vp, vp, vp, C.c_size_t]),

@@ -1,0 +1,676 @@
+// Epipolar verification of the matches of consecutive frame pairs: a RANSAC fundamental matrix per pair (gfx950, f64).
+//
+// No reference counterpart: the reference hands every Lowe-ratio survivor to pointTracking.  The definition -- sampling,
+// 8-point hypotheses, MSAC score, refit, flags -- is in include/meatmodeler.h (mm_verify_matches); this file maps it:
+//   vfy_normalise_kernel   one workgroup per pair: Hartley centroid / scale of both images over the well-formed matches
+//   vfy_hypothesis_kernel  one lane per (pair, hypothesis): eight sampled rows orthonormalised in registers (every index
+//                          static, nothing in scratch), null vector, rank 2, denormalise
+//   vfy_score_kernel       lane = hypothesis, F in nine registers; the pair's matches go through LDS in tiles and every lane
+//                          reads the same address (broadcast), summing min(d^2, tau^2) over j ascending: no cross-lane step
+//   vfy_refit_kernel       one workgroup per pair: argmin, refit rounds (45 sums of A^T A, 9 x 9 Jacobi in LDS), inlier mask,
+//                          order-preserving compaction, outputs
+// Plain f64 VALU work; sums in an order that depends on the pair alone (per-thread strides, xor butterflies, waves in order),
+// no atomics: a pair's row repeats bit for bit whatever else shares the call.
+#include "mm_common.h"
+
+namespace {
+
+constexpr int VFY_THREADS = 256;      // normalise / refit: one workgroup per pair
+constexpr int VFY_WAVES = VFY_THREADS / 64;
+constexpr int VFY_TILE = 256;         // matches per LDS tile of the score kernel
+constexpr double VFY_EPS = 2.220446049250313e-16;
+
+__host__ __device__ __forceinline__ uint32_t vfy_pcg(uint32_t v) {
+    const uint32_t s = v * 747796405u + 2891336453u;
+    const uint32_t w = ((s >> ((s >> 28) + 4u)) ^ s) * 277803737u;
+    return (w >> 22) ^ w;
+}
+
+struct VfyArgs {
+    const float *kp_xy;
+    const int32_t *pairs, *m;
+    int n_pairs, cap, n_hyp, min_matches, min_inliers, refit_iters, on_fail;
+    uint32_t seed, pair_base;
+    double tau2;
+    double *norm;      // [n_pairs, 8]: cx, cy, s, cx', cy', s', number of malformed matches, -
+    double *Fh;        // [n_pairs, n_hyp, 9] (NaN: invalid hypothesis)
+    double *cost_h;    // [n_pairs, n_hyp] (+inf: invalid hypothesis)
+};
+
+__device__ __forceinline__ int vfy_count(const VfyArgs &a, int p) {
+    const int mm = a.m[p];
+    return mm < 0 ? 0 : (mm > a.cap ? a.cap : mm);
+}
+
+// match j of pair p, widened; false (and NaN coordinates) for a malformed match -- nothing is read through a bad index
+__device__ __forceinline__ bool vfy_load(const VfyArgs &a, int p, int j, double &x, double &y, double &xp, double &yp) {
+    const int2 qt = reinterpret_cast<const int2 *>(a.pairs)[(size_t)p * a.cap + j];
+    const bool wf = (unsigned)qt.x < (unsigned)a.cap && (unsigned)qt.y < (unsigned)a.cap;
+    const double nan = __builtin_nan("");
+    x = y = xp = yp = nan;
+    if (wf) {
+        const float2 u = reinterpret_cast<const float2 *>(a.kp_xy)[(size_t)p * a.cap + qt.x];
+        const float2 v = reinterpret_cast<const float2 *>(a.kp_xy)[(size_t)(p + 1) * a.cap + qt.y];
+        x = (double)u.x;
+        y = (double)u.y;
+        xp = (double)v.x;
+        yp = (double)v.y;
+    }
+    return wf;
+}
+
+__device__ __forceinline__ double vfy_sampson(const double (&F)[9], double x, double y, double xp, double yp) {
+    const double fx0 = F[0] * x + F[1] * y + F[2], fx1 = F[3] * x + F[4] * y + F[5], fx2 = F[6] * x + F[7] * y + F[8];
+    const double ft0 = F[0] * xp + F[3] * yp + F[6], ft1 = F[1] * xp + F[4] * yp + F[7];
+    const double e = xp * fx0 + yp * fx1 + fx2;
+    return e * e / (fx0 * fx0 + fx1 * fx1 + ft0 * ft0 + ft1 * ft1);
+}
+__device__ __forceinline__ bool vfy_inlier(double d2, double tau2) { return isfinite(d2) && d2 <= tau2; }
+
+// sum over the workgroup in a fixed order: xor butterfly inside a wave (addition commutes: every lane ends with the same
+// bits), then the waves' sums in wave order.  sm holds VFY_WAVES * N doubles.  Every thread of the workgroup calls it.
+template <int N>
+__device__ __forceinline__ void vfy_block_sum(double (&v)[N], double *sm) {
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) v[i] += __shfl_xor(v[i], off, 64);
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    __syncthreads();
+    if (l == 0) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) sm[w * N + i] = v[i];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = ((sm[i] + sm[N + i]) + sm[2 * N + i]) + sm[3 * N + i];
+}
+
+// F^ <- F^ - (F^ v3) v3^T, v3 the eigenvector of the smallest eigenvalue of F^^T F^ (3 x 3 cyclic Jacobi in registers)
+__device__ __forceinline__ void vfy_rank2(double (&F)[9]) {
+    double G[3][3], V[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            G[r][c] = F[r] * F[c] + F[3 + r] * F[3 + c] + F[6 + r] * F[6 + c];
+            V[r][c] = (r == c) ? 1.0 : 0.0;
+        }
+    for (int sweep = 0; sweep < 30; ++sweep) {
+        bool rotated = false;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+#pragma unroll
+            for (int q = p + 1; q < 3; ++q) {
+                const double apq = G[p][q];
+                if (fabs(apq) > VFY_EPS * sqrt(fabs(G[p][p] * G[q][q])) && apq != 0.0) {
+                    rotated = true;
+                    const double zeta = (G[q][q] - G[p][p]) / (2.0 * apq);
+                    const double tn = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                    const double cs = 1.0 / sqrt(1.0 + tn * tn);
+                    const double sn = cs * tn;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        const double akp = G[k][p], akq = G[k][q];
+                        G[k][p] = cs * akp - sn * akq;
+                        G[k][q] = sn * akp + cs * akq;
+                        const double vkp = V[k][p], vkq = V[k][q];
+                        V[k][p] = cs * vkp - sn * vkq;
+                        V[k][q] = sn * vkp + cs * vkq;
+                    }
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        const double apk = G[p][k], aqk = G[q][k];
+                        G[p][k] = cs * apk - sn * aqk;
+                        G[q][k] = sn * apk + cs * aqk;
+                    }
+                    G[p][q] = G[q][p] = 0.0;
+                }
+            }
+        }
+        if (!rotated) break;
+    }
+    double best = G[0][0], v0 = V[0][0], v1 = V[1][0], v2 = V[2][0];
+#pragma unroll
+    for (int c = 1; c < 3; ++c) {
+        if (G[c][c] < best) {
+            best = G[c][c];
+            v0 = V[0][c];
+            v1 = V[1][c];
+            v2 = V[2][c];
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const double fv = F[3 * r] * v0 + F[3 * r + 1] * v1 + F[3 * r + 2] * v2;
+        F[3 * r] -= fv * v0;
+        F[3 * r + 1] -= fv * v1;
+        F[3 * r + 2] -= fv * v2;
+    }
+}
+
+// rank 2, F = T'^T F^ T with T = [[s, 0, -s cx], [0, s, -s cy], [0, 0, 1]], unit Frobenius norm; false: not finite
+__device__ __forceinline__ bool vfy_finish(double (&F)[9], double cx, double cy, double s, double cx2, double cy2, double s2) {
+    vfy_rank2(F);
+    double G[9];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {      // G = F^ T
+        G[3 * r] = s * F[3 * r];
+        G[3 * r + 1] = s * F[3 * r + 1];
+        G[3 * r + 2] = F[3 * r + 2] - s * cx * F[3 * r] - s * cy * F[3 * r + 1];
+    }
+    double nn = 0.0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {      // F = T'^T G
+        F[c] = s2 * G[c];
+        F[3 + c] = s2 * G[3 + c];
+        F[6 + c] = G[6 + c] - s2 * cx2 * G[c] - s2 * cy2 * G[3 + c];
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) nn += F[k] * F[k];
+    const double inv = 1.0 / sqrt(nn);
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        F[k] *= inv;
+        ok = ok && isfinite(F[k]);
+    }
+    return ok;
+}
+
+// ---- normalisation over all well-formed matches of the pair -----------------------------------------------------------------
+__global__ __launch_bounds__(VFY_THREADS) void vfy_normalise_kernel(VfyArgs a) {
+    __shared__ double sm[VFY_WAVES * 5];
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int mm = vfy_count(a, p);
+    double s5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int j = tid; j < mm; j += VFY_THREADS) {
+        double x, y, xp, yp;
+        if (vfy_load(a, p, j, x, y, xp, yp)) {
+            s5[0] += 1.0;
+            s5[1] += x;
+            s5[2] += y;
+            s5[3] += xp;
+            s5[4] += yp;
+        }
+    }
+    vfy_block_sum<5>(s5, sm);
+    const double n = s5[0], cx = s5[1] / n, cy = s5[2] / n, cx2 = s5[3] / n, cy2 = s5[4] / n;
+    double d2[2] = {0.0, 0.0};
+    for (int j = tid; j < mm; j += VFY_THREADS) {
+        double x, y, xp, yp;
+        if (vfy_load(a, p, j, x, y, xp, yp)) {
+            d2[0] += sqrt((x - cx) * (x - cx) + (y - cy) * (y - cy));
+            d2[1] += sqrt((xp - cx2) * (xp - cx2) + (yp - cy2) * (yp - cy2));
+        }
+    }
+    vfy_block_sum<2>(d2, sm);
+    if (tid == 0) {
+        double *o = a.norm + 8 * (size_t)p;
+        o[0] = cx;
+        o[1] = cy;
+        o[2] = 1.4142135623730951 / (d2[0] / n);
+        o[3] = cx2;
+        o[4] = cy2;
+        o[5] = 1.4142135623730951 / (d2[1] / n);
+        o[6] = (double)mm - n;
+        o[7] = 0.0;
+    }
+}
+
+// ---- one hypothesis per lane --------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void vfy_hypothesis_kernel(VfyArgs a) {
+    const int p = blockIdx.x;
+    const int h = blockIdx.y * 64 + threadIdx.x;
+    const int mm = vfy_count(a, p);
+    if (h >= a.n_hyp || mm < a.min_matches) return;      // (a pair with too few matches is never scored either)
+    const double *nr = a.norm + 8 * (size_t)p;
+    const double cx = nr[0], cy = nr[1], s = nr[2], cx2 = nr[3], cy2 = nr[4], s2 = nr[5];
+    bool ok = isfinite(s) && isfinite(s2);
+    // eight distinct match indices, integer arithmetic only
+    const uint32_t base = vfy_pcg(vfy_pcg(a.seed + vfy_pcg(a.pair_base + (uint32_t)p)) + (uint32_t)h);
+    int pick[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        int chosen = -1;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const uint32_t r = vfy_pcg(base + (uint32_t)(8 * k + t));
+            const int i = (int)(((uint64_t)r * (uint64_t)mm) >> 32);
+            bool dup = false;
+#pragma unroll
+            for (int e = 0; e < k; ++e) dup = dup || pick[e] == i;
+            if (chosen < 0 && !dup) chosen = i;
+        }
+        ok = ok && chosen >= 0;
+        pick[k] = chosen < 0 ? 0 : chosen;
+    }
+    double A[8][9];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        double x, y, xp, yp;
+        ok = vfy_load(a, p, pick[k], x, y, xp, yp) && ok;
+        x = s * (x - cx);
+        y = s * (y - cy);
+        xp = s2 * (xp - cx2);
+        yp = s2 * (yp - cy2);
+        A[k][0] = xp * x;
+        A[k][1] = xp * y;
+        A[k][2] = xp;
+        A[k][3] = yp * x;
+        A[k][4] = yp * y;
+        A[k][5] = yp;
+        A[k][6] = x;
+        A[k][7] = y;
+        A[k][8] = 1.0;
+    }
+    // the rows orthonormalised in place (modified Gram-Schmidt, each row twice against its predecessors); the null vector
+    // is then the normalised column of I - Q^T Q with the largest diagonal entry, cleaned once more against the rows
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+#pragma unroll
+        for (int pass = 0; pass < 2; ++pass) {
+#pragma unroll
+            for (int k = 0; k < i; ++k) {
+                double d = 0.0;
+#pragma unroll
+                for (int c = 0; c < 9; ++c) d += A[i][c] * A[k][c];
+#pragma unroll
+                for (int c = 0; c < 9; ++c) A[i][c] -= d * A[k][c];
+            }
+        }
+        double nn = 0.0;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) nn += A[i][c] * A[i][c];
+        const double inv = 1.0 / sqrt(nn);
+#pragma unroll
+        for (int c = 0; c < 9; ++c) A[i][c] *= inv;
+    }
+    double col[8];      // column kbest of Q (selected without a runtime index)
+    {
+        double best = -1.0;
+        int kbest = 0;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) {
+            double dg = 1.0;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) dg -= A[i][c] * A[i][c];
+            if (dg > best) {
+                best = dg;
+                kbest = c;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            double v = A[i][0];
+#pragma unroll
+            for (int c = 1; c < 9; ++c) v = (kbest == c) ? A[i][c] : v;
+            col[i] = v;
+        }
+        double F[9];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) {
+            double v = (kbest == c) ? 1.0 : 0.0;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) v -= A[i][c] * col[i];
+            F[c] = v;
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            double d = 0.0;
+#pragma unroll
+            for (int c = 0; c < 9; ++c) d += F[c] * A[i][c];
+#pragma unroll
+            for (int c = 0; c < 9; ++c) F[c] -= d * A[i][c];
+        }
+        double nn = 0.0;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) nn += F[c] * F[c];
+        const double inv = 1.0 / sqrt(nn);
+#pragma unroll
+        for (int c = 0; c < 9; ++c) F[c] *= inv;
+        ok = vfy_finish(F, cx, cy, s, cx2, cy2, s2) && ok;
+        double *o = a.Fh + ((size_t)p * a.n_hyp + h) * 9;
+        const double nan = __builtin_nan("");
+#pragma unroll
+        for (int c = 0; c < 9; ++c) o[c] = ok ? F[c] : nan;
+    }
+}
+
+// ---- MSAC cost of every hypothesis --------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void vfy_score_kernel(VfyArgs a) {
+    __shared__ double tile[VFY_TILE * 4];
+    const int p = blockIdx.x;
+    const int h = blockIdx.y * 64 + threadIdx.x;
+    const int mm = vfy_count(a, p);
+    if (mm < a.min_matches) return;      // (uniform over the workgroup)
+    const bool live = h < a.n_hyp;
+    double F[9];
+    const double *src = a.Fh + ((size_t)p * a.n_hyp + (live ? h : 0)) * 9;
+#pragma unroll
+    for (int c = 0; c < 9; ++c) F[c] = src[c];
+    double cost = 0.0;
+    for (int j0 = 0; j0 < mm; j0 += VFY_TILE) {
+        const int nt = min(VFY_TILE, mm - j0);
+        __syncthreads();
+        for (int j = threadIdx.x; j < nt; j += 64) {
+            double x, y, xp, yp;
+            vfy_load(a, p, j0 + j, x, y, xp, yp);
+            tile[4 * j] = x;
+            tile[4 * j + 1] = y;
+            tile[4 * j + 2] = xp;
+            tile[4 * j + 3] = yp;
+        }
+        __syncthreads();
+        for (int j = 0; j < nt; ++j) {
+            const double d2 = vfy_sampson(F, tile[4 * j], tile[4 * j + 1], tile[4 * j + 2], tile[4 * j + 3]);
+            cost += vfy_inlier(d2, a.tau2) ? d2 : a.tau2;
+        }
+    }
+    if (live) a.cost_h[(size_t)p * a.n_hyp + h] = isfinite(F[0]) ? cost : __builtin_huge_val();
+}
+
+// ---- winner, refit, compaction --------------------------------------------------------------------------------------------
+// MSAC cost and inlier count of F over all matches of the pair (every thread returns the same bits)
+__device__ __forceinline__ void vfy_cost(const VfyArgs &a, int p, int mm, const double (&F)[9], double *sm, double &cost, int &n_in) {
+    double v[2] = {0.0, 0.0};
+    for (int j = threadIdx.x; j < mm; j += VFY_THREADS) {
+        double x, y, xp, yp;
+        vfy_load(a, p, j, x, y, xp, yp);
+        const double d2 = vfy_sampson(F, x, y, xp, yp);
+        const bool in = vfy_inlier(d2, a.tau2);
+        v[0] += in ? d2 : a.tau2;
+        v[1] += in ? 1.0 : 0.0;
+    }
+    vfy_block_sum<2>(v, sm);
+    cost = v[0];
+    n_in = (int)v[1];
+}
+
+__global__ __launch_bounds__(VFY_THREADS) void vfy_refit_kernel(VfyArgs a, int32_t *__restrict__ pairs_out, int32_t *__restrict__ m_out,
+                                                                double *__restrict__ Fm, double *__restrict__ cost_out,
+                                                                int32_t *__restrict__ info) {
+    __shared__ double sm[VFY_WAVES * 45];
+    __shared__ double M[9][9], V[9][9];
+    __shared__ double bc[VFY_WAVES];
+    __shared__ int bh[VFY_WAVES], wcount[VFY_WAVES];
+    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int mm = vfy_count(a, p);
+    const double nan = __builtin_nan("");
+    int flags = a.norm[8 * (size_t)p + 6] > 0.0 ? MM_VERIFY_MALFORMED : 0;
+    double F[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) F[c] = nan;
+    double cost = nan;
+    int n_in = 0, best_h = -1, n_valid = 0;
+    bool model = false;
+
+    if (mm < a.min_matches) {
+        flags |= MM_VERIFY_TOO_FEW;
+    } else {
+        // lowest finite cost, ties to the lowest h; and the number of valid hypotheses
+        double c_best = __builtin_huge_val();
+        int h_best = INT32_MAX;
+        double nv[1] = {0.0};
+        for (int h = tid; h < a.n_hyp; h += VFY_THREADS) {
+            const double c = a.cost_h[(size_t)p * a.n_hyp + h];
+            nv[0] += isfinite(a.Fh[((size_t)p * a.n_hyp + h) * 9]) ? 1.0 : 0.0;
+            if (isfinite(c) && c < c_best) {
+                c_best = c;
+                h_best = h;
+            }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const double oc = __shfl_xor(c_best, off, 64);
+            const int oh = __shfl_xor(h_best, off, 64);
+            if (oc < c_best || (oc == c_best && oh < h_best)) {
+                c_best = oc;
+                h_best = oh;
+            }
+        }
+        if (lane == 0) {
+            bc[wave] = c_best;
+            bh[wave] = h_best;
+        }
+        vfy_block_sum<1>(nv, sm);      // (its barriers also publish bc / bh)
+        n_valid = (int)nv[0];
+        c_best = bc[0];
+        h_best = bh[0];
+#pragma unroll
+        for (int w = 1; w < VFY_WAVES; ++w) {
+            if (bc[w] < c_best || (bc[w] == c_best && bh[w] < h_best)) {
+                c_best = bc[w];
+                h_best = bh[w];
+            }
+        }
+        if (h_best == INT32_MAX) {
+            flags |= MM_VERIFY_NO_MODEL;
+        } else {
+            model = true;
+            best_h = h_best;
+#pragma unroll
+            for (int c = 0; c < 9; ++c) F[c] = a.Fh[((size_t)p * a.n_hyp + h_best) * 9 + c];
+            vfy_cost(a, p, mm, F, sm, cost, n_in);
+        }
+    }
+
+    if (model) {
+        for (int it = 0; it < a.refit_iters; ++it) {
+            if (n_in < 8) break;      // (uniform: nothing changes any more)
+            // Hartley normalisation over the inliers of the current F
+            double s5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+            for (int j = tid; j < mm; j += VFY_THREADS) {
+                double x, y, xp, yp;
+                vfy_load(a, p, j, x, y, xp, yp);
+                if (vfy_inlier(vfy_sampson(F, x, y, xp, yp), a.tau2)) {
+                    s5[0] += 1.0;
+                    s5[1] += x;
+                    s5[2] += y;
+                    s5[3] += xp;
+                    s5[4] += yp;
+                }
+            }
+            vfy_block_sum<5>(s5, sm);
+            const double n = s5[0], cx = s5[1] / n, cy = s5[2] / n, cx2 = s5[3] / n, cy2 = s5[4] / n;
+            double dd[2] = {0.0, 0.0};
+            for (int j = tid; j < mm; j += VFY_THREADS) {
+                double x, y, xp, yp;
+                vfy_load(a, p, j, x, y, xp, yp);
+                if (vfy_inlier(vfy_sampson(F, x, y, xp, yp), a.tau2)) {
+                    dd[0] += sqrt((x - cx) * (x - cx) + (y - cy) * (y - cy));
+                    dd[1] += sqrt((xp - cx2) * (xp - cx2) + (yp - cy2) * (yp - cy2));
+                }
+            }
+            vfy_block_sum<2>(dd, sm);
+            const double s = 1.4142135623730951 / (dd[0] / n), s2 = 1.4142135623730951 / (dd[1] / n);
+            // M = A^T A over the inliers: 45 sums (upper triangle, row-major)
+            double acc[45];
+#pragma unroll
+            for (int k = 0; k < 45; ++k) acc[k] = 0.0;
+            for (int j = tid; j < mm; j += VFY_THREADS) {
+                double x, y, xp, yp;
+                vfy_load(a, p, j, x, y, xp, yp);
+                if (vfy_inlier(vfy_sampson(F, x, y, xp, yp), a.tau2)) {
+                    x = s * (x - cx);
+                    y = s * (y - cy);
+                    xp = s2 * (xp - cx2);
+                    yp = s2 * (yp - cy2);
+                    const double r[9] = {xp * x, xp * y, xp, yp * x, yp * y, yp, x, y, 1.0};
+                    int k = 0;
+#pragma unroll
+                    for (int i = 0; i < 9; ++i)
+#pragma unroll
+                        for (int c = i; c < 9; ++c) acc[k++] += r[i] * r[c];
+                }
+            }
+            vfy_block_sum<45>(acc, sm);
+            __syncthreads();
+            if (tid == 0) {
+                int k = 0;
+#pragma unroll
+                for (int i = 0; i < 9; ++i)
+#pragma unroll
+                    for (int c = i; c < 9; ++c) {
+                        M[i][c] = acc[k];
+                        M[c][i] = acc[k];
+                        ++k;
+                    }
+            }
+            if (tid < 81) V[tid / 9][tid % 9] = (tid / 9 == tid % 9) ? 1.0 : 0.0;
+            __syncthreads();
+            // cyclic Jacobi on M with V in LDS: every thread takes the same decisions from the same LDS words, lane k < 9
+            // rotates row / column k.  A rotation is skipped once |m_pq| <= eps sqrt(m_pp m_qq).
+            for (int sweep = 0; sweep < 30; ++sweep) {
+                bool rotated = false;
+                for (int pp = 0; pp < 8; ++pp) {
+                    for (int q = pp + 1; q < 9; ++q) {
+                        const double apq = M[pp][q], app = M[pp][pp], aqq = M[q][q];
+                        if (fabs(apq) > VFY_EPS * sqrt(fabs(app * aqq)) && apq != 0.0) {      // (uniform)
+                            rotated = true;
+                            const double zeta = (aqq - app) / (2.0 * apq);
+                            const double tn = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                            const double cs = 1.0 / sqrt(1.0 + tn * tn);
+                            const double sn = cs * tn;
+                            __syncthreads();
+                            if (tid < 9) {
+                                const double akp = M[tid][pp], akq = M[tid][q];
+                                M[tid][pp] = cs * akp - sn * akq;
+                                M[tid][q] = sn * akp + cs * akq;
+                                const double vkp = V[tid][pp], vkq = V[tid][q];
+                                V[tid][pp] = cs * vkp - sn * vkq;
+                                V[tid][q] = sn * vkp + cs * vkq;
+                            }
+                            __syncthreads();
+                            if (tid < 9) {
+                                const double apk = M[pp][tid], aqk = M[q][tid];
+                                M[pp][tid] = cs * apk - sn * aqk;
+                                M[q][tid] = sn * apk + cs * aqk;
+                            }
+                            __syncthreads();
+                            if (tid == 0) M[pp][q] = M[q][pp] = 0.0;
+                            __syncthreads();
+                        }
+                    }
+                }
+                if (!rotated) break;
+            }
+            int cbest = 0;
+            double ev = M[0][0];
+            for (int c = 1; c < 9; ++c) {
+                if (M[c][c] < ev) {
+                    ev = M[c][c];
+                    cbest = c;
+                }
+            }
+            double Fn[9];
+#pragma unroll
+            for (int c = 0; c < 9; ++c) Fn[c] = V[c][cbest];
+            __syncthreads();      // (M and V are rewritten by the next round)
+            const bool okF = vfy_finish(Fn, cx, cy, s, cx2, cy2, s2);
+            double cn;
+            int nn_in;
+            vfy_cost(a, p, mm, Fn, sm, cn, nn_in);
+            if (okF && isfinite(cn) && cn < cost) {
+                cost = cn;
+                n_in = nn_in;
+#pragma unroll
+                for (int c = 0; c < 9; ++c) F[c] = Fn[c];
+            }
+        }
+        if (n_in < a.min_inliers) flags |= MM_VERIFY_WEAK;
+    }
+
+    const bool failed = (flags & (MM_VERIFY_TOO_FEW | MM_VERIFY_NO_MODEL | MM_VERIFY_WEAK)) != 0;
+    // the kept matches in their input order: the inliers of F, or -- a failed pair -- all of them (on_fail 0) / none (1)
+    int kept = 0;
+    if (!(failed && a.on_fail != 0)) {
+        for (int j0 = 0; j0 < mm; j0 += VFY_THREADS) {
+            const int j = j0 + tid;
+            bool keep = false;
+            int2 qt = make_int2(0, 0);
+            if (j < mm) {
+                qt = reinterpret_cast<const int2 *>(a.pairs)[(size_t)p * a.cap + j];
+                keep = true;
+                if (!failed) {
+                    double x, y, xp, yp;
+                    vfy_load(a, p, j, x, y, xp, yp);
+                    keep = vfy_inlier(vfy_sampson(F, x, y, xp, yp), a.tau2);
+                }
+            }
+            const unsigned long long bal = __ballot(keep);
+            __syncthreads();
+            if (lane == 0) wcount[wave] = __popcll(bal);
+            __syncthreads();
+            int at = kept;
+            for (int w = 0; w < wave; ++w) at += wcount[w];
+            at += __popcll(bal & ((1ull << lane) - 1ull));
+            if (keep) reinterpret_cast<int2 *>(pairs_out)[(size_t)p * a.cap + at] = qt;
+            kept += wcount[0] + wcount[1] + wcount[2] + wcount[3];
+        }
+    }
+    if (tid == 0) {
+        m_out[p] = kept;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) Fm[9 * (size_t)p + c] = F[c];
+        cost_out[p] = cost;
+        info[4 * (size_t)p] = flags;
+        info[4 * (size_t)p + 1] = n_in;
+        info[4 * (size_t)p + 2] = best_h;
+        info[4 * (size_t)p + 3] = n_valid;
+    }
+}
+
+}  // namespace
+
+extern "C" size_t mm_verify_workspace_bytes(int n_pairs, int n_hyp) {
+    const size_t np = n_pairs > 0 ? (size_t)n_pairs : 0, nh = n_hyp > 0 ? (size_t)n_hyp : 0;
+    return mm_align_up(np * 8 * sizeof(double), 256) + mm_align_up(np * nh * 9 * sizeof(double), 256) +
+           mm_align_up(np * nh * sizeof(double), 256);
+}
+
+extern "C" int mm_verify_matches(mm_ctx *ctx, const float *kp_xy, const int32_t *pairs, const int32_t *m, int n_pairs, int cap,
+                                 const mm_verify_params *prm, int32_t *pairs_out, int32_t *m_out, double *Fm, double *cost,
+                                 int32_t *info, void *ws, size_t ws_bytes) {
+    // every argument is judged before the context is looked at: nothing below this block runs on a bad call
+    if (!prm || n_pairs < 0) return mm_fail(ctx, MM_ERR_ARG, "mm_verify_matches: bad argument");
+    if (prm->n_hyp < 1 || prm->n_hyp > 4096) return mm_fail(ctx, MM_ERR_ARG, "mm_verify_matches: n_hyp must be in 1 .. 4096");
+    if (!(prm->threshold_px >= 0.0))      // (negative or NaN; +inf keeps every well-formed match)
+        return mm_fail(ctx, MM_ERR_ARG, "mm_verify_matches: threshold_px must not be negative");
+    if (prm->refit_iters < 0 || prm->refit_iters > 1000 || prm->min_inliers < 0 || (prm->on_fail != 0 && prm->on_fail != 1))
+        return mm_fail(ctx, MM_ERR_ARG, "mm_verify_matches: bad parameter");
+    if (n_pairs > 0 && (!kp_xy || !pairs || !m || !pairs_out || !m_out || !Fm || !cost || !info || !ws || cap <= 0 || pairs == pairs_out))
+        return mm_fail(ctx, MM_ERR_ARG, "mm_verify_matches: bad argument");
+    if (n_pairs > 0 && ws_bytes < mm_verify_workspace_bytes(n_pairs, prm->n_hyp))
+        return mm_fail(ctx, MM_ERR_WORKSPACE, "mm_verify_matches: workspace too small");
+    if (!ctx) return MM_ERR_ARG;
+    if (n_pairs == 0) return MM_OK;
+    if (((uintptr_t)kp_xy | (uintptr_t)pairs | (uintptr_t)pairs_out) & 7)
+        return mm_fail(ctx, MM_ERR_ARG, "mm_verify_matches: kp_xy, pairs and pairs_out must be 8-byte aligned");
+    VfyArgs a;
+    a.kp_xy = kp_xy;
+    a.pairs = pairs;
+    a.m = m;
+    a.n_pairs = n_pairs;
+    a.cap = cap;
+    a.n_hyp = prm->n_hyp;
+    a.min_matches = prm->min_matches < 16 ? 16 : prm->min_matches;
+    a.min_inliers = prm->min_inliers;
+    a.refit_iters = prm->refit_iters;
+    a.on_fail = prm->on_fail;
+    a.seed = prm->seed;
+    a.pair_base = prm->pair_base;
+    a.tau2 = prm->threshold_px * prm->threshold_px;
+    char *w = (char *)ws;
+    a.norm = (double *)w;
+    w += mm_align_up((size_t)n_pairs * 8 * sizeof(double), 256);
+    a.Fh = (double *)w;
+    w += mm_align_up((size_t)n_pairs * a.n_hyp * 9 * sizeof(double), 256);
+    a.cost_h = (double *)w;
+    const dim3 per_hyp((unsigned)n_pairs, (unsigned)((a.n_hyp + 63) / 64));
+    MM_LAUNCH(ctx, "vfy_normalise_kernel", vfy_normalise_kernel, dim3((unsigned)n_pairs), dim3(VFY_THREADS), 0, a);
+    MM_LAUNCH(ctx, "vfy_hypothesis_kernel", vfy_hypothesis_kernel, per_hyp, dim3(64), 0, a);
+    MM_LAUNCH(ctx, "vfy_score_kernel", vfy_score_kernel, per_hyp, dim3(64), 0, a);
+    MM_LAUNCH(ctx, "vfy_refit_kernel", vfy_refit_kernel, dim3((unsigned)n_pairs), dim3(VFY_THREADS), 0, a, pairs_out, m_out, Fm, cost, info);
+    return MM_OK;
+}

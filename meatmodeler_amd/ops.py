@@ -72,6 +72,49 @@ def ratio_filter_batched(idx, dist, threshold=0.75, nq=None, ctx=None):
     return pairs, m
 
 
+VERIFY_TOO_FEW, VERIFY_NO_MODEL, VERIFY_WEAK, VERIFY_MALFORMED = 1, 2, 4, 8      # MM_VERIFY_* of include/meatmodeler.h
+
+
+def verify_matches(kp_xy, pairs, m, n_hyp=256, threshold_px=2.0, min_matches=16, min_inliers=16, refit_iters=2, seed=0,
+                   pair_base=0, on_fail="keep", ctx=None):
+    """Epipolar verification of consecutive frame pairs (mm_verify_matches): kp_xy [n_pairs+1, cap, 2] f32, pairs
+    [n_pairs, cap, 2] i32, m [n_pairs] i32 (device tensors; what ratio_filter_batched returns)
+    -> (pairs_out [n_pairs, cap, 2] i32 -- the inliers of each pair's fundamental matrix in input order, -1 beyond m_out --,
+    m_out [n_pairs] i32, F [n_pairs, 9] f64 (x'^T F x = 0, unit norm, NaN without a model), cost [n_pairs] f64,
+    info [n_pairs, 4] i32 = (VERIFY_* flags, n_inliers, best_h, valid hypotheses)).
+    on_fail: "keep" passes the matches of a failed pair (too few, no model, weak) through, "drop" removes them."""
+    if on_fail not in ("keep", "drop"):
+        raise ValueError("verify_matches: on_fail must be 'keep' or 'drop'")
+    if not 1 <= int(n_hyp) <= 4096:
+        raise ValueError("verify_matches: n_hyp must be in 1 .. 4096")
+    if not float(threshold_px) >= 0:
+        raise ValueError("verify_matches: threshold_px must not be negative")
+    if not 0 <= int(refit_iters) <= 1000 or int(min_inliers) < 0:
+        raise ValueError("verify_matches: refit_iters must be in 0 .. 1000 and min_inliers not negative")
+    if pairs.dim() != 3 or pairs.shape[2] != 2 or kp_xy.dim() != 3 or tuple(kp_xy.shape) != (pairs.shape[0] + 1, pairs.shape[1], 2) \
+            or tuple(m.shape) != (pairs.shape[0],):
+        raise ValueError("verify_matches: kp_xy [n_pairs+1, cap, 2], pairs [n_pairs, cap, 2] and m [n_pairs] expected")
+    ctx = ctx or default_context()
+    d = pairs.device
+    n_pairs, cap = pairs.shape[0], pairs.shape[1]
+    pairs_out = torch.full((n_pairs, cap, 2), -1, dtype=torch.int32, device=d)
+    m_out = torch.zeros(n_pairs, dtype=torch.int32, device=d)
+    F = torch.full((n_pairs, 9), math.nan, dtype=torch.float64, device=d)
+    cost = torch.full((n_pairs,), math.nan, dtype=torch.float64, device=d)
+    info = torch.zeros((n_pairs, 4), dtype=torch.int32, device=d)
+    if n_pairs == 0 or cap == 0:
+        return pairs_out, m_out, F, cost, info
+    prm = _lib.VerifyParams(int(n_hyp), int(min_matches), int(min_inliers), int(refit_iters), int(seed) & 0xFFFFFFFF,
+                            int(pair_base) & 0xFFFFFFFF, 1 if on_fail == "drop" else 0, 0, float(threshold_px))
+    wsb = lib.mm_verify_workspace_bytes(n_pairs, int(n_hyp))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=d)
+    assert kp_xy.dtype == torch.float32
+    ctx.check(lib.mm_verify_matches(ctx.h, ptr(kp_xy.contiguous()), ptr(_i32(pairs.contiguous())), ptr(_i32(m.contiguous())),
+                                    n_pairs, cap, C.byref(prm), ptr(pairs_out), ptr(m_out), ptr(F), ptr(cost), ptr(info),
+                                    ptr(ws), wsb), "mm_verify_matches")
+    return pairs_out, m_out, F, cost, info
+
+
 # ------------------------------------------------------------------------------------------------ ORB
 
 def orb_params(nfeatures, nlevels=8, scale_factor=1.2, edge_threshold=31, fast_threshold=20):

@@ -20,6 +20,22 @@ from .bundleAdjuster import SchurTRF, frameParameters
 from .orb_pattern import brief_pattern
 
 
+VERIFY_KEYS = ("n_hyp", "threshold_px", "min_matches", "min_inliers", "refit_iters", "seed", "on_fail")
+
+
+def verify_options(verify):
+    """`run(..., verify=)`: None (no verification) or a dict of the parameters of ops.verify_matches -- pair_base and ctx are
+    the pipeline's own.  Returns it as a dict; an unknown key raises ValueError."""
+    if verify is None:
+        return None
+    if not isinstance(verify, dict):
+        raise ValueError("verify must be None or a dict of " + ", ".join(VERIFY_KEYS))
+    unknown = set(verify) - set(VERIFY_KEYS)
+    if unknown:
+        raise ValueError(f"verify takes {', '.join(VERIFY_KEYS)}; not {sorted(unknown)}")
+    return dict(verify)
+
+
 class ClipPipeline:
     def __init__(self, height, width, nfeatures, batch=32, ratio=0.75, device=None, ctx=None, nlevels=8):
         self.ctx = ctx or default_context()
@@ -68,6 +84,14 @@ class ClipPipeline:
         idx, dist = ops.bf_knn2_batched(q, t, n[pair_lo:pair_hi].contiguous(), n[pair_lo + 1:pair_hi + 1].contiguous(),
                                         self.ctx)
         return ops.ratio_filter_batched(idx, dist, self.ratio, n[pair_lo:pair_hi].contiguous(), self.ctx)
+
+    # ------------------------------------------------------------------------------------------- verify
+    def verify(self, det, pairs, m, pair_lo=0, **params):
+        """Epipolar verification of the matches `match` returned for the frames in `det` (ops.verify_matches): pair k of
+        `pairs` joins frames k and k + 1 of `det`, and is pair pair_lo + k of the clip -- the key of its sampling, so a rank's
+        block gives the rows the whole clip would.  -> (pairs_out, m_out, F [n,9], cost [n], info [n,4]), device tensors."""
+        n = pairs.shape[0]
+        return ops.verify_matches(det["xy"][:n + 1], pairs, m, pair_base=pair_lo, ctx=self.ctx, **params)
 
     # ------------------------------------------------------------------------------------------- link
     def link(self, kp_count, kp_xy, match_count, matches):
@@ -455,7 +479,7 @@ class ClipPipeline:
 
     # ------------------------------------------------------------------------------------------- whole clip
     def run(self, frames, K, extrinsics, ba=True, ftol=1e-4, verbose=0, dist=None, timers=None, max_nfev=None,
-            force_collectives=False, triangulation="two_view", cull=None):
+            force_collectives=False, triangulation="two_view", cull=None, verify=None):
         """frames [F,H,W] u8 (device).  With `dist` = torch.distributed (initialised), frames are the FULL clip on
         every rank (synthetic input is generated locally) and the work is sharded as described in parallel.py.
         `max_nfev`: evaluation budget of the adjustment (None = SciPy's default, as adjustPoints).
@@ -467,7 +491,12 @@ class ClipPipeline:
         `cull` (needs "multi_view"; one rank only -- the track partition of the sharded adjustment works on contiguous
         ranges): dict of the thresholds of ops.triangulate_tracks (max_reproj_px, min_angle_deg, min_depth, refine_iters).
         The adjustment then takes only the tracks no test flagged, `kept_tracks` (indices in track order), and its
-        points are aligned with that list."""
+        points are aligned with that list.
+        `verify`: None (default: every Lowe-ratio survivor goes to the linker, as in the reference) or a dict of the
+        parameters of ops.verify_matches ({} for the defaults): each rank verifies its own pairs against a RANSAC
+        fundamental matrix between `match` and the gather / `link`, and only the inliers are linked.  The result gains
+        `verify` = dict(info [n,4], cost [n], F [n,9], matches_in [n]) over this rank's pairs; timer "verify"."""
+        verify = verify_options(verify)
         if triangulation not in ("two_view", "multi_view"):
             raise ValueError("triangulation must be 'two_view' or 'multi_view'")
         F = frames.shape[0]
@@ -505,6 +534,18 @@ class ClipPipeline:
             pairs = torch.zeros((0, self.cap, 2), dtype=torch.int32, device=self.device)
             m = torch.zeros(0, dtype=torch.int32, device=self.device)
         toc("match")
+        verified = None
+        if verify is not None:
+            tic("verify")
+            matches_in = m
+            if det is not None:
+                pairs, m, F_v, cost_v, info_v = self.verify(det, pairs, m, pair_lo=p_lo, **verify)
+            else:
+                F_v = torch.zeros((0, 9), dtype=torch.float64, device=self.device)
+                cost_v = torch.zeros(0, dtype=torch.float64, device=self.device)
+                info_v = torch.zeros((0, 4), dtype=torch.int32, device=self.device)
+            verified = dict(info=info_v, cost=cost_v, F=F_v, matches_in=matches_in)
+            toc("verify")
         tic("link")
         if sharded:
             # every rank needs every frame's key points and every pair's matches to link identical tracks.  The block
@@ -546,6 +587,8 @@ class ClipPipeline:
         out = dict(det=det, n_tracks=P, n_obs=O, points0=X, track_ptr_dev=track_ptr, obs_frame_dev=obs_frame,
                    obs_kp_dev=obs_kp, xy_dev=xy_dev, match_count=m_h, kp_count=n_h, pairs_local=int(p_hi - p_lo),
                    frames_local=int(f_hi - f_lo))
+        if verified is not None:
+            out["verify"] = verified
         kept = None
         if triangulation == "multi_view":
             out.update(track_quality=quality, track_flags=flags)

@@ -5,6 +5,7 @@ return order, HIP kernels underneath (no CPU fallback: a missing extension or GP
     ---------------------------------------------  ---------------------------------------------------------
     cv2.ORB_create(nfeatures=...)  processor.py:308  ORB_create(nfeatures=...) -> ORB (detectAndCompute on device)
     featureTracking                processor.py:113  featureTracking     (mm_orb_detect_compute + mm_bf_knn2_* + ratio)
+    (no counterpart)                                 verifyMatches       (mm_verify_matches: RANSAC fundamental matrix, inlier mask)
     pointTracking                  processor.py:190  pointTracking       (hash join; same list semantics)
     triangulatePoints              processor.py:246  triangulatePoints   (mm_triangulate_dlt, batched over tracks)
     (no counterpart)                                 triangulateTracks   (mm_triangulate_tracks: all views, quality, flags)
@@ -310,6 +311,29 @@ def featureTracking(new_keyframe, prev_orb_points, prev_orb_descriptors, orb, fl
     prev_matches = pxy[good[:, 0]].astype(np.float64)
     curr_matches = nxy[good[:, 1]].astype(np.float64)
     return prev_matches, curr_matches, new_points, new_descriptors
+
+
+def verifyMatches(prev_matches, curr_matches, **params):
+    """Epipolar verification of what `featureTracking` returns: prev_matches / curr_matches [n,2] pixel coordinates of the
+    matched key points in the previous and the new keyframe -> (mask [n] bool, F [3,3] f64 with curr^T F prev = 0, NaN if
+    no model was found).  `params` as ops.verify_matches takes them (n_hyp, threshold_px, min_matches, min_inliers,
+    refit_iters, seed, pair_base, on_fail): with on_fail="keep" a pair that fails keeps all its matches."""
+    prev = np.asarray(prev_matches, np.float32).reshape(-1, 2)
+    curr = np.asarray(curr_matches, np.float32).reshape(-1, 2)
+    if prev.shape != curr.shape:
+        raise ValueError("verifyMatches: prev_matches and curr_matches must have the same length")
+    n = prev.shape[0]
+    if n == 0:
+        return np.zeros(0, bool), np.full((3, 3), np.nan)
+    dev = default_context().device
+    kp = torch.as_tensor(np.stack([prev, curr])).to(dev)
+    idx = torch.arange(n, dtype=torch.int32, device=dev)
+    pairs = torch.stack([idx, idx], dim=1).unsqueeze(0).contiguous()
+    m = torch.full((1,), n, dtype=torch.int32, device=dev)
+    pairs_out, m_out, F, _, _ = ops.verify_matches(kp, pairs, m, **params)
+    mask = np.zeros(n, bool)
+    mask[pairs_out[0, :int(m_out[0].item()), 0].cpu().numpy()] = True
+    return mask, F[0].cpu().numpy().reshape(3, 3)
 
 
 # ----------------------------------------------------------------------------------------------- pointTracking
