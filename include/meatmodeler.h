@@ -92,10 +92,11 @@ int mm_profile_report(mm_ctx *ctx, char *buf, size_t buf_len);
  *   dist [n_pairs, nq_cap, 2] int32 : their Hamming distances (-1 if absent)
  * Rows >= nq[p] are left untouched.
  * The distances are computed on the matrix cores (descriptors expanded to +1 / -1 FP4 values: dot product = 256 - 2 dist,
- * exact); the workspace holds the expanded train sets, 128 bytes per train descriptor (mm_bf_workspace_bytes; 16-byte
- * aligned).  Train sets of fewer than 64 or of 65536 and more descriptors take the xor / popcount kernel instead;
- * MM_BF_VARIANT=114 (xor / popcount), 200 (int8 MFMA), 300 (FP4 MFMA, default) in the environment selects one -- all
- * return identical results.
+ * exact).  The default kernel (MM_BF_VARIANT=314, or 310) expands the train descriptors tile by tile on their way into LDS
+ * and needs a token workspace only; variants 300 (FP4 MFMA, packed streams) and 200 (int8 MFMA) expand the train sets in
+ * a pass of their own and the workspace holds them, 128 / 256 bytes per train descriptor (mm_bf_workspace_bytes, never 0;
+ * 16-byte aligned).  Train sets of fewer than 64 or of 65536 and more descriptors take the xor / popcount kernel
+ * (MM_BF_VARIANT=114) instead -- all return identical results.
  */
 size_t mm_bf_workspace_bytes(int n_pairs, int nq_cap, int nt_cap);
 int mm_bf_knn2_batched(mm_ctx *ctx, const uint8_t *q /*dev*/, const int32_t *nq /*dev|NULL*/, int nq_cap,
@@ -110,6 +111,18 @@ int mm_bf_knn2_hamming(mm_ctx *ctx, const uint8_t *q /*dev*/, int nq, const uint
 int mm_ratio_filter_batched(mm_ctx *ctx, const int32_t *idx /*dev*/, const int32_t *dist /*dev*/,
                             const int32_t *nq /*dev|NULL*/, int nq_cap, int n_pairs, double threshold,
                             int32_t *pairs /*dev [n_pairs,nq_cap,2]*/, int32_t *m_out /*dev [n_pairs]*/);
+/* The whole match stage in one call: exactly what mm_bf_knn2_batched followed by mm_ratio_filter_batched produce, without
+ * idx / dist ever being stored where the kernel has the ratio test in its epilogue (variants 314 / 310: one int32 per query
+ * goes to the workspace instead; the other variants keep idx / dist there).  Every element of pairs [n_pairs, nq_cap, 2]
+ * and of m_out [n_pairs] is written: pairs[p, j] = (queryIdx, trainIdx) of the j-th kept match in query order for
+ * j < m_out[p], -1 from there on -- the outputs need no initialisation.  Workspace: mm_bf_match_ratio_workspace_bytes,
+ * 16-byte aligned. */
+size_t mm_bf_match_ratio_workspace_bytes(int n_pairs, int nq_cap, int nt_cap);
+int mm_bf_match_ratio_batched(mm_ctx *ctx, const uint8_t *q /*dev*/, const int32_t *nq /*dev|NULL*/, int nq_cap,
+                              size_t q_set_stride, const uint8_t *t /*dev*/, const int32_t *nt /*dev|NULL*/, int nt_cap,
+                              size_t t_set_stride, int n_pairs, double threshold,
+                              int32_t *pairs /*dev [n_pairs,nq_cap,2]*/, int32_t *m_out /*dev [n_pairs]*/,
+                              void *ws /*dev*/, size_t ws_bytes);
 
 /* ---- a-1: ORB detect + describe ----------------------------------------------------------------
  * Replaces orb.detectAndCompute(img, None), processor.py:129,328 with cv2.ORB_create(nfeatures=...) defaults
@@ -352,6 +365,35 @@ size_t mm_ba_schur_workspace_bytes(const mm_ba_problem *pb); /* 42 doubles per c
 int mm_ba_pairs_count(mm_ctx *ctx, const mm_ba_problem *pb, int32_t *cnt /*dev [O]*/, int32_t *span_out /*dev [1]*/);
 int mm_ba_pairs_emit(mm_ctx *ctx, const mm_ba_problem *pb, const int64_t *offsets /*dev [O]*/, int span,
                      int32_t *key /*dev [n]*/, int32_t *pair_o /*dev [n]*/, int32_t *pair_o2 /*dev [n]*/);
+/* All of the above in two native calls, for POINT-MAJOR observations (pi non-decreasing, as mm_flatten_tracks emits
+ * them; pt_obs is then the identity).  Every array is what the count / scan / emit / stable sort construction yields,
+ * byte for byte.
+ *   stage 0: pt_ptr [P+1], pt_obs [O], cam_ptr [F+1], cam_obs [O] (stable by camera) and head [8] (dev):
+ *            head[0] = cam_span, head[1] = number of pairs, head[2] != 0: an index out of range, head[3] != 0: not
+ *            point-major.  With head[2] or head[3] set nothing else is valid.
+ *   stage 1: (the caller read head, set cam_span and n_pairs and allocated the pair arrays [n_pairs], seg_ids [seg_cap],
+ *            seg_chunk_ptr [seg_cap + 1] and the chunk arrays [chunk_cap]: mm_ba_index_bounds)  the pair list in
+ *            segment order, its segment and chunk tables, head[4] = n_seg, head[5] = n_chunks.  chunk = pairs per
+ *            chunk, a multiple of 64.  Needs cam_span < F and F * (cam_span + 1) < 2^31.  ws0 is stage 0's workspace,
+ *            untouched since.
+ * Workspaces (16-byte aligned): mm_ba_index_workspace_bytes(ctx, ix, stage); it asks the sort / scan library, which
+ * needs the context's device, and returns 0 when it cannot. */
+typedef struct mm_ba_index {
+    int32_t F, P;
+    int64_t O;
+    const int32_t *fi, *pi;                         /* dev [O] */
+    int32_t *pt_ptr, *pt_obs, *cam_ptr, *cam_obs;   /* dev, stage 0 */
+    int64_t *head;                                  /* dev [8] */
+    int32_t cam_span, chunk;                        /* stage 1 inputs */
+    int64_t n_pairs;
+    int32_t *pair_o, *pair_o2, *pair_p;             /* dev [n_pairs], stage 1 */
+    int32_t *seg_ids, *seg_chunk_ptr;
+    int32_t *chunk_seg, *chunk_begin, *chunk_end;
+} mm_ba_index;
+int mm_ba_index_bounds(int F, int cam_span, int64_t n_pairs, int chunk, int64_t *seg_cap, int64_t *chunk_cap);
+size_t mm_ba_index_workspace_bytes(mm_ctx *ctx, const mm_ba_index *ix, int stage);
+int mm_ba_index_build(mm_ctx *ctx, const mm_ba_index *ix, int stage, void *ws0 /*dev*/, size_t ws0_bytes,
+                      void *ws1 /*dev, stage 1*/, size_t ws1_bytes);
 /* k <= 8 inner products <a_q, b_q> over vectors of length n in one launch (the trust-region driver's reductions, SciPy
  * trf.py via bundleAdjuster.py:180-192).  a, b: HOST arrays of k device pointers.  out [k,3] dev = {sum over i < split,
  * sum over i >= split, total}; deterministic.  The workspace must be zero-filled once before its first use. */

@@ -9,6 +9,8 @@
 //  314  matrix cores, FP4 operands, ONE candidate per lane and train tile (bf_knn2_fp4min_kernel: the vector unit only
 //       takes a minimum over the lane's 16 accumulators; 4 waves per SIMD): 0.95 ms = 8.4 T pairs/s       <- default
 //       (310: the same at 3 waves per SIMD with the A operand read one tile ahead: no faster)
+//       Both read the PACKED train descriptors and expand each 32-row tile to FP4 on its way into LDS (no expand pass, no
+//       expanded copy in memory), and have the ratio test in their epilogue for mm_bf_match_ratio_batched.
 //  300  matrix cores, FP4 operands, packed per-accumulator streams (bf_knn2_fp4_kernel): 1.15-1.2 ms = 6.6-6.9 T pairs/s
 //  200  matrix cores, int8 operands (bf_knn2_mfma_kernel): 1.9 ms = 4.2 T pairs/s
 //  114  xor / popcount on the vector unit (bf_knn2_lds_kernel, below): 3.9-4.2 ms = 2.0 T pairs/s; also what small
@@ -339,6 +341,47 @@ __global__ __launch_bounds__(256) void ratio_filter_kernel(const int32_t *__rest
     if (threadIdx.x == 0) m_out[pair] = base_s;
 }
 
+// The same compaction for the whole match stage (mm_bf_match_ratio_batched), one workgroup per pair.  CODES: the matching
+// kernel has applied the ratio test already and `idx` holds one int32 per query [n_pairs, nq_cap], the train index of a
+// match or -1; otherwise idx / dist are what the 2-NN kernels write and the test is made here.  Writes m_out and the -1
+// tail pairs[p, m:nq_cap] itself, so the outputs need no fill; rows from nq on are never read.
+template <bool CODES>
+__global__ __launch_bounds__(256) void match_compact_kernel(const int32_t *__restrict__ idx,
+                                                            const int32_t *__restrict__ dist,
+                                                            const int32_t *__restrict__ nq_dev, int nq_cap,
+                                                            double threshold, int32_t *__restrict__ pairs,
+                                                            int32_t *__restrict__ m_out) {
+    __shared__ int wave_cnt[2][4];      // (two sets: one barrier per round)
+    const int pair = blockIdx.x;
+    const int nq = nq_dev ? max(min(nq_dev[pair], nq_cap), 0) : nq_cap;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int2 *__restrict__ out = reinterpret_cast<int2 *>(pairs) + (size_t)pair * nq_cap;
+    int base = 0, par = 0;
+    for (int q0 = 0; q0 < nq; q0 += 256, par ^= 1) {
+        const int qi = q0 + threadIdx.x;
+        int ti = -1;
+        if (qi < nq) {
+            if constexpr (CODES) {
+                ti = idx[(size_t)pair * nq_cap + qi];
+            } else {
+                const size_t o = ((size_t)pair * nq_cap + qi) * 2;
+                const int d0 = dist[o], d1 = dist[o + 1];
+                if ((d0 >= 0) && (d1 >= 0) && ((double)d0 < threshold * (double)d1)) ti = idx[o];
+            }
+        }
+        const bool keep = ti >= 0;
+        const unsigned long long m = __ballot(keep);
+        if (lane == 0) wave_cnt[par][wave] = __builtin_popcountll(m);
+        __syncthreads();
+        const int c0 = wave_cnt[par][0], c1 = wave_cnt[par][1], c2 = wave_cnt[par][2], c3 = wave_cnt[par][3];
+        const int off = base + (wave > 0 ? c0 : 0) + (wave > 1 ? c1 : 0) + (wave > 2 ? c2 : 0);
+        if (keep) out[off + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = make_int2(qi, ti);
+        base += c0 + c1 + c2 + c3;
+    }
+    for (int j = base + (int)threadIdx.x; j < nq_cap; j += 256) out[j] = make_int2(-1, -1);
+    if (threadIdx.x == 0) m_out[pair] = base;
+}
+
 // ---- Hamming distances on the matrix cores ------------------------------------------------------------------------------
 // With the bits of a descriptor written as 256 int8 values +1 / -1, the dot product of two descriptors is
 // (#equal bits) - (#different bits) = 256 - 2 dist: all-pairs matching is a [queries x 256] x [256 x trains] int8 GEMM, exact
@@ -346,7 +389,8 @@ __global__ __launch_bounds__(256) void ratio_filter_kernel(const int32_t *__rest
 // nominal rate, against the 19 VALU instructions per pair (1.2 cycles per pair and SIMD) of the xor / popcount formulation,
 // which sits at 91 % of ITS roof (see the header).  (Measured: the int8 instruction issues every 29 ns per SIMD with the
 // whole chip busy, 2.3 POP/s -- tools/dev/mfma_rate.hip -- and this kernel runs at that rate: 4.2 T pairs/s.)  The matching IS compute bound (0.02 B/pair), so this is where it belongs.
-//   * a pre-pass expands every train set once ([nt, 256] int8, 8x the packed size, written to the workspace);
+//   * a pre-pass expands every train set once ([nt, 256] int8, 8x the packed size, written to the workspace; variants 200
+//     and 300 -- the default kernel expands in LDS);
 //   * a wave keeps 64 queries resident as the B operand (2 column tiles x 8 K-steps x 16 bytes per lane = 64 VGPRs,
 //     expanded from the packed descriptors at kernel start); the workgroup (4 waves, 256 queries) streams train tiles of
 //     32 descriptors through LDS (double buffered, 272-byte row pitch: conflict-free ds_read_b128) as the A operand;
@@ -596,6 +640,17 @@ __device__ __forceinline__ bf_v4i bf_fp4x32(uint32_t bits) {
     r[1] = (int)bf_fp4x8((bits >> 8) & 255u);
     r[2] = (int)bf_fp4x8((bits >> 16) & 255u);
     r[3] = (int)bf_fp4x8(bits >> 24);
+    return r;
+}
+
+// The same 32 values in another order and with the opposite sign: nibble i of word k is bit 4 i + k, set -> -1 (0xA),
+// clear -> +1 (0x2).  Three shifts, four ands and four ors instead of the ~36 instructions of bf_fp4x32.  A dot product does not care about the
+// order of its terms nor about a sign common to both factors, so a kernel that expands BOTH operands this way gets the
+// sums of bf_fp4x32 exactly (bf_knn2_fp4min_kernel does, to expand its train tiles on the way into LDS).
+__device__ __forceinline__ bf_v4i bf_fp4x32_planes(uint32_t bits) {
+    bf_v4i r;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r[k] = (int)(((bits << (3 - k)) & 0x88888888u) | 0x22222222u);
     return r;
 }
 
@@ -881,11 +936,13 @@ __device__ long long g_bf_clock[2 * 4096];
 #endif
 // PIPE: the A operand of the next train tile is read from LDS behind the last use of the current one (see below); without
 // it a wave reads its operand after the barrier -- fewer registers: four waves per SIMD fit
-template <int WAVES, bool PIPE>
+// RATIO: the epilogue applies the ratio test of ratio_filter_kernel to the two neighbours it holds and writes ONE int32
+// per query to idx [n_pairs, nq_cap] -- the train index of a match, or -1 -- instead of idx / dist (dist is not used).
+template <int WAVES, bool PIPE, bool RATIO>
 __global__ __launch_bounds__(BF_THREADS, WAVES) void bf_knn2_fp4min_kernel(
     const uint8_t *__restrict__ q, const int32_t *__restrict__ nq_dev, int nq_cap, size_t q_stride,
-    const uint8_t *__restrict__ tx, const uint8_t *__restrict__ tpk, size_t t_stride, const int32_t *__restrict__ nt_dev,
-    int nt_cap, int ntp, int32_t *__restrict__ idx, int32_t *__restrict__ dist, int qtiles, int n_pairs) {
+    const uint8_t *__restrict__ tpk, size_t t_stride, const int32_t *__restrict__ nt_dev,
+    int nt_cap, int32_t *__restrict__ idx, int32_t *__restrict__ dist, int qtiles, int n_pairs, double threshold) {
     __shared__ __attribute__((aligned(16))) uint8_t tile[3][MF_TT][F4_PITCH];
     // XCD-aware order: workgroups are dealt round-robin to the 8 XCDs (each with its own L2), so the linear id is read as
     // (slot, xcd) and an XCD walks ITS pairs one after the other, all query tiles of a pair side by side: the expanded
@@ -918,7 +975,7 @@ __global__ __launch_bounds__(BF_THREADS, WAVES) void bf_knn2_fp4min_kernel(
         const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const bf_v4i e = bf_fp4x32(~(h ? w[2 * j + 1] : w[2 * j]));      // queries enter NEGATED
+            const bf_v4i e = bf_fp4x32_planes(~(h ? w[2 * j + 1] : w[2 * j]));      // queries enter NEGATED
             B4[u][j] = e;
         }
     }
@@ -928,13 +985,17 @@ __global__ __launch_bounds__(BF_THREADS, WAVES) void bf_knn2_fp4min_kernel(
     for (int i = 0; i < 16; ++i) cinit[i] = 12582912.0f + 262144.0f + (float)(8 * (i >> 2) + 4 * h + (i & 3));
     uint32_t b0[2] = {BF_NONE, BF_NONE}, b1[2] = {BF_NONE, BF_NONE};      // the two smallest tile minima per query
     const int ntiles = (nt + MF_TT - 1) / MF_TT;
-    const uint8_t *txp = tx + (size_t)pair * ntp * 128;
+    // Train tiles come straight from the PACKED descriptors: a tile is 1 KB, thread e0 takes word e0 & 7 of row e0 >> 3 (a
+    // wave reads 256 contiguous bytes), keeps it in one register while it is in flight and expands it to its 16 bytes of
+    // FP4 on the way into LDS (11 vector instructions per tile).  Rows from nt_cap on read as 0 bits.
+    const uint8_t *tp = tpk + (size_t)pair * t_stride;
     const int e0 = threadIdx.x;
-    bf_v4i ra, rb, rc;
+    uint32_t ra, rb, rc;
     auto fetch = [&](int tt, auto set) __attribute__((always_inline)) {
         constexpr int S = decltype(set)::value;
         if (tt < ntiles) {      // (workgroup-uniform)
-            const bf_v4i v = reinterpret_cast<const bf_v4i *>(txp + (size_t)tt * MF_TT * 128)[e0];
+            const uint32_t v = tt * MF_TT + (e0 >> 3) < nt_cap
+                                   ? reinterpret_cast<const uint32_t *>(tp + (size_t)tt * MF_TT * 32)[e0] : 0u;
             if constexpr (S == 0) ra = v;
             if constexpr (S == 1) rb = v;
             if constexpr (S == 2) rc = v;
@@ -943,9 +1004,9 @@ __global__ __launch_bounds__(BF_THREADS, WAVES) void bf_knn2_fp4min_kernel(
     auto commit = [&](int buf, auto set) __attribute__((always_inline)) {
         constexpr int S = decltype(set)::value;
         bf_v4i *d = reinterpret_cast<bf_v4i *>(&tile[buf][e0 >> 3][(e0 & 7) * 16]);
-        if constexpr (S == 0) *d = ra;
-        if constexpr (S == 1) *d = rb;
-        if constexpr (S == 2) *d = rc;
+        if constexpr (S == 0) *d = bf_fp4x32_planes(ra);
+        if constexpr (S == 1) *d = bf_fp4x32_planes(rb);
+        if constexpr (S == 2) *d = bf_fp4x32_planes(rc);
     };
     // One train tile = two phases of 4 matrix instructions (query tile 0, query tile 1); the 13 vector instructions that
     // go with a phase's results run in the shadow of the NEXT phase's matrix instructions (query tile 1 of tile t-1 beside
@@ -1067,7 +1128,6 @@ __global__ __launch_bounds__(BF_THREADS, WAVES) void bf_knn2_fp4min_kernel(
         book(acc1, (uint32_t)nfull * MF_TT, 1, std::true_type{}, dead_from);
     }
     // the second smallest INSIDE the best tile, by xor / popcount on the lane's 15 other rows of that tile
-    const uint8_t *tp = tpk + (size_t)pair * t_stride;
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const int qi = qbase + 64 * wv + 32 * u + c;
@@ -1107,11 +1167,17 @@ __global__ __launch_bounds__(BF_THREADS, WAVES) void bf_knn2_fp4min_kernel(
         top2_insert(o0, b0[u], b1[u]);
         top2_insert(o1, b0[u], b1[u]);
         if (h == 0 && qi < nq) {
-            const size_t o = ((size_t)pair * nq_cap + qi) * 2;
-            idx[o] = b0[u] == BF_NONE ? -1 : (int32_t)(b0[u] & 0xFFFFu);
-            idx[o + 1] = b1[u] == BF_NONE ? -1 : (int32_t)(b1[u] & 0xFFFFu);
-            dist[o] = b0[u] == BF_NONE ? -1 : (int32_t)(b0[u] >> 22);
-            dist[o + 1] = b1[u] == BF_NONE ? -1 : (int32_t)(b1[u] >> 22);
+            if constexpr (RATIO) {      // (the comparison of ratio_filter_kernel; fewer than two neighbours: never a match)
+                const bool keep = b0[u] != BF_NONE && b1[u] != BF_NONE &&
+                                  (double)(int32_t)(b0[u] >> 22) < threshold * (double)(int32_t)(b1[u] >> 22);
+                idx[(size_t)pair * nq_cap + qi] = keep ? (int32_t)(b0[u] & 0xFFFFu) : -1;
+            } else {
+                const size_t o = ((size_t)pair * nq_cap + qi) * 2;
+                idx[o] = b0[u] == BF_NONE ? -1 : (int32_t)(b0[u] & 0xFFFFu);
+                idx[o + 1] = b1[u] == BF_NONE ? -1 : (int32_t)(b1[u] & 0xFFFFu);
+                dist[o] = b0[u] == BF_NONE ? -1 : (int32_t)(b0[u] >> 22);
+                dist[o + 1] = b1[u] == BF_NONE ? -1 : (int32_t)(b1[u] >> 22);
+            }
         }
     }
 #ifdef MM_BF_CLOCK
@@ -1140,6 +1206,12 @@ bool bf_use_mfma(int n_pairs, int nq_cap, int nt_cap) {
     const int v = bf_variant(n_pairs, nq_cap);
     return (v == 200 || v == 300 || v == 310 || v == 314) && nt_cap >= 64 && nt_cap < 65536;
 }
+// the kernel that expands its train tiles itself (needs no workspace) and has the ratio test in its epilogue
+bool bf_fp4min(int n_pairs, int nq_cap) {
+    const int v = bf_variant(n_pairs, nq_cap);
+    return v == 310 || v == 314;
+}
+bool bf_fused(int n_pairs, int nq_cap, int nt_cap) { return bf_use_mfma(n_pairs, nq_cap, nt_cap) && bf_fp4min(n_pairs, nq_cap); }
 int bf_ntp(int nt_cap) { return (nt_cap + MF_TT - 1) / MF_TT * MF_TT; }
 
 int bf_choose_splits(int n_pairs, int nq_cap, int nt_cap) {
@@ -1168,19 +1240,26 @@ extern "C" int mm_debug_bf_clock(long long *host /*[2*4096]*/) {
 extern "C" {
 
 size_t mm_bf_workspace_bytes(int n_pairs, int nq_cap, int nt_cap) {
-    if (n_pairs > 0 && nq_cap > 0 && bf_use_mfma(n_pairs, nq_cap, nt_cap))
+    if (n_pairs > 0 && nq_cap > 0 && bf_use_mfma(n_pairs, nq_cap, nt_cap)) {
+        if (bf_fp4min(n_pairs, nq_cap)) return 256;      // (expands its train tiles itself: nothing to hold)
         return mm_align_up((size_t)n_pairs * bf_ntp(nt_cap) * (bf_variant(n_pairs, nq_cap) >= 300 ? 128 : 256), 256);   // expanded train sets
+    }
     int s = bf_choose_splits(n_pairs, nq_cap, nt_cap);
     if (s == 1) return 256;
     return mm_align_up((size_t)n_pairs * s * nq_cap * 2 * sizeof(uint32_t), 256);
 }
 
-int mm_bf_knn2_batched(mm_ctx *ctx, const uint8_t *q, const int32_t *nq, int nq_cap, size_t q_set_stride,
-                       const uint8_t *t, const int32_t *nt, int nt_cap, size_t t_set_stride, int n_pairs,
-                       int32_t *idx, int32_t *dist, void *ws, size_t ws_bytes) {
-    if (!ctx) return MM_ERR_ARG;
+}  // extern "C"
+
+namespace {
+
+// The 2-NN search of mm_bf_knn2_batched.  ratio != nullptr asks for the fused form where the variant has one (bf_fused):
+// idx then receives one int32 per query, the train index of a match under threshold *ratio or -1, and dist is not used.
+int bf_knn2_run(mm_ctx *ctx, const uint8_t *q, const int32_t *nq, int nq_cap, size_t q_set_stride, const uint8_t *t,
+                const int32_t *nt, int nt_cap, size_t t_set_stride, int n_pairs, int32_t *idx, int32_t *dist, void *ws,
+                size_t ws_bytes, const double *ratio) {
     if (n_pairs == 0 || nq_cap == 0) return MM_OK;
-    if (!q || (!t && nt_cap > 0) || !idx || !dist || n_pairs < 0 || nq_cap < 0 || nt_cap < 0)
+    if (!q || (!t && nt_cap > 0) || !idx || (!dist && !ratio) || n_pairs < 0 || nq_cap < 0 || nt_cap < 0)
         return mm_fail(ctx, MM_ERR_ARG, "mm_bf_knn2_batched: bad argument");
     if (nt_cap >= (1 << BF_IDX_BITS)) return mm_fail(ctx, MM_ERR_ARG, "mm_bf_knn2_batched: nt_cap must be < 2^20");
     if (((uintptr_t)q | (uintptr_t)t | q_set_stride | t_set_stride) & 15)
@@ -1194,22 +1273,25 @@ int mm_bf_knn2_batched(mm_ctx *ctx, const uint8_t *q, const int32_t *nq, int nq_
             return mm_fail(ctx, MM_ERR_WORKSPACE, "mm_bf_knn2_batched: workspace too small or misaligned");
         const int ntp = bf_ntp(nt_cap);
         const dim3 grid((nq_cap + BF_THREADS - 1) / BF_THREADS, 1, n_pairs);
+        if (bf_fp4min(n_pairs, nq_cap)) {      // no expand pass: the kernel reads the packed descriptors
+            const int qtiles = (int)grid.x;
+            const dim3 grid_x(8u * (unsigned)((n_pairs + 7) / 8) * grid.x);      // (slot, xcd): see the kernel
+            const double thr = ratio ? *ratio : 0.0;
+#define BF_GO_MIN(W, P, R)                                                                                                \
+    MM_LAUNCH(ctx, "bf_knn2_fp4min_kernel", (bf_knn2_fp4min_kernel<W, P, R>), grid_x, dim3(BF_THREADS), 0, q, nq, nq_cap, \
+              q_set_stride, t, t_set_stride, nt, nt_cap, idx, dist, qtiles, n_pairs, thr)
+            if (bf_variant(n_pairs, nq_cap) == 310) {
+                if (ratio) BF_GO_MIN(3, true, true); else BF_GO_MIN(3, true, false);
+            } else {
+                if (ratio) BF_GO_MIN(4, false, true); else BF_GO_MIN(4, false, false);
+            }
+#undef BF_GO_MIN
+            return MM_OK;
+        }
         if (bf_variant(n_pairs, nq_cap) >= 300) {
             const size_t chunks = (size_t)n_pairs * ntp * 8;
             MM_LAUNCH(ctx, "bf_expand_kernel", bf_expand_fp4_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, t, nt_cap,
                       t_set_stride, ntp, n_pairs, (uint8_t *)ws);
-            const int qtiles = (int)grid.x;
-            const dim3 grid_x(8u * (unsigned)((n_pairs + 7) / 8) * grid.x);      // (slot, xcd): see the kernel
-            if (bf_variant(n_pairs, nq_cap) == 310) {
-                MM_LAUNCH(ctx, "bf_knn2_fp4min_kernel", (bf_knn2_fp4min_kernel<3, true>), grid_x, dim3(BF_THREADS), 0, q, nq, nq_cap, q_set_stride,
-                          (const uint8_t *)ws, t, t_set_stride, nt, nt_cap, ntp, idx, dist, qtiles, n_pairs);
-                return MM_OK;
-            }
-            if (bf_variant(n_pairs, nq_cap) == 314) {
-                MM_LAUNCH(ctx, "bf_knn2_fp4min_kernel", (bf_knn2_fp4min_kernel<4, false>), grid_x, dim3(BF_THREADS), 0, q, nq, nq_cap, q_set_stride,
-                          (const uint8_t *)ws, t, t_set_stride, nt, nt_cap, ntp, idx, dist, qtiles, n_pairs);
-                return MM_OK;
-            }
             MM_LAUNCH(ctx, "bf_knn2_fp4_kernel", bf_knn2_fp4_kernel, grid, dim3(BF_THREADS), 0, q, nq, nq_cap, q_set_stride,
                       (const uint8_t *)ws, nt, nt_cap, ntp, idx, dist);
             return MM_OK;
@@ -1259,6 +1341,61 @@ int mm_bf_knn2_batched(mm_ctx *ctx, const uint8_t *q, const int32_t *nq, int nq_
         dim3 g2((nq_cap + 255) / 256, n_pairs);
         MM_LAUNCH(ctx, "bf_merge_kernel", bf_merge_kernel, g2, dim3(256), 0, (const uint32_t *)ws, nq, nq_cap, s, idx, dist);
     }
+    return MM_OK;
+}
+
+// workspace of mm_bf_match_ratio_batched: the search's own, then what the search hands to the compaction
+struct BfMatchWs {
+    size_t knn, idx, dist, total;      // byte offsets of idx / dist behind the search's workspace of `knn` bytes
+};
+BfMatchWs bf_match_ws(int n_pairs, int nq_cap, int nt_cap) {
+    BfMatchWs w;
+    w.knn = mm_align_up(mm_bf_workspace_bytes(n_pairs, nq_cap, nt_cap), 256);
+    const size_t rows = (size_t)max(n_pairs, 0) * (size_t)max(nq_cap, 0);
+    const bool fused = n_pairs > 0 && nq_cap > 0 && bf_fused(n_pairs, nq_cap, nt_cap);
+    const size_t one = mm_align_up(rows * (fused ? 1 : 2) * sizeof(int32_t), 256);
+    w.idx = w.knn;
+    w.dist = fused ? w.idx : w.idx + one;
+    w.total = w.dist + one;
+    return w;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mm_bf_knn2_batched(mm_ctx *ctx, const uint8_t *q, const int32_t *nq, int nq_cap, size_t q_set_stride,
+                       const uint8_t *t, const int32_t *nt, int nt_cap, size_t t_set_stride, int n_pairs,
+                       int32_t *idx, int32_t *dist, void *ws, size_t ws_bytes) {
+    if (!ctx) return MM_ERR_ARG;
+    return bf_knn2_run(ctx, q, nq, nq_cap, q_set_stride, t, nt, nt_cap, t_set_stride, n_pairs, idx, dist, ws, ws_bytes, nullptr);
+}
+
+size_t mm_bf_match_ratio_workspace_bytes(int n_pairs, int nq_cap, int nt_cap) {
+    return bf_match_ws(n_pairs, nq_cap, nt_cap).total;
+}
+
+int mm_bf_match_ratio_batched(mm_ctx *ctx, const uint8_t *q, const int32_t *nq, int nq_cap, size_t q_set_stride,
+                              const uint8_t *t, const int32_t *nt, int nt_cap, size_t t_set_stride, int n_pairs,
+                              double threshold, int32_t *pairs, int32_t *m_out, void *ws, size_t ws_bytes) {
+    if (!ctx) return MM_ERR_ARG;
+    if (n_pairs == 0) return MM_OK;
+    if (n_pairs < 0 || nq_cap < 0 || nt_cap < 0 || !m_out || (!pairs && nq_cap > 0))
+        return mm_fail(ctx, MM_ERR_ARG, "mm_bf_match_ratio_batched: bad argument");
+    const BfMatchWs w = bf_match_ws(n_pairs, nq_cap, nt_cap);
+    if (!ws || ws_bytes < w.total || ((uintptr_t)ws & 15))
+        return mm_fail(ctx, MM_ERR_WORKSPACE, "mm_bf_match_ratio_batched: workspace too small or misaligned");
+    int32_t *idx = (int32_t *)((uint8_t *)ws + w.idx), *dist = (int32_t *)((uint8_t *)ws + w.dist);
+    const bool fused = nq_cap > 0 && bf_fused(n_pairs, nq_cap, nt_cap);
+    const int rc = bf_knn2_run(ctx, q, nq, nq_cap, q_set_stride, t, nt, nt_cap, t_set_stride, n_pairs, idx, dist, ws, w.knn,
+                               fused ? &threshold : nullptr);
+    if (rc != MM_OK) return rc;
+    if (fused)
+        MM_LAUNCH(ctx, "match_compact_kernel", match_compact_kernel<true>, dim3(n_pairs), dim3(256), 0, idx, (const int32_t *)nullptr, nq, nq_cap,
+                  threshold, pairs, m_out);
+    else
+        MM_LAUNCH(ctx, "match_compact_kernel", match_compact_kernel<false>, dim3(n_pairs), dim3(256), 0, idx, dist, nq, nq_cap,
+                  threshold, pairs, m_out);
     return MM_OK;
 }
 

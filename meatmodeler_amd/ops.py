@@ -72,6 +72,29 @@ def ratio_filter_batched(idx, dist, threshold=0.75, nq=None, ctx=None):
     return pairs, m
 
 
+def bf_match_ratio_batched(q, t, nq=None, nt=None, threshold=0.75, ctx=None):
+    """The match stage in one call (mm_bf_match_ratio_batched): what bf_knn2_batched + ratio_filter_batched return for the
+    same arguments -- pairs int32 [n_pairs, nq_cap, 2] (queryIdx, trainIdx; -1 beyond m), m int32 [n_pairs] -- with every
+    element written by the kernels (no fills) and without idx / dist in memory."""
+    ctx = ctx or default_context()
+    assert q.dtype == torch.uint8 and t.dtype == torch.uint8 and q.shape[-1] == 32 and t.shape[-1] == 32
+    assert q.stride(-1) == 1 and q.stride(-2) == 32 and t.stride(-1) == 1 and t.stride(-2) == 32
+    n_pairs, nq_cap, nt_cap = q.shape[0], q.shape[1], t.shape[1]
+    assert t.shape[0] == n_pairs
+    pairs = torch.empty((n_pairs, nq_cap, 2), dtype=torch.int32, device=q.device)
+    m = torch.empty(n_pairs, dtype=torch.int32, device=q.device)
+    if n_pairs == 0:
+        return pairs, m
+    wsb = lib.mm_bf_match_ratio_workspace_bytes(n_pairs, nq_cap, nt_cap)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
+    qs = q.stride(0) if n_pairs > 1 else 0
+    ts = t.stride(0) if n_pairs > 1 else 0
+    ctx.check(lib.mm_bf_match_ratio_batched(ctx.h, ptr(q), ptr(nq), nq_cap, qs, ptr(t), ptr(nt), nt_cap, ts, n_pairs,
+                                            float(threshold), ptr(pairs), ptr(m), ptr(ws), wsb),
+              "mm_bf_match_ratio_batched")
+    return pairs, m
+
+
 VERIFY_TOO_FEW, VERIFY_NO_MODEL, VERIFY_WEAK, VERIFY_MALFORMED = 1, 2, 4, 8      # MM_VERIFY_* of include/meatmodeler.h
 
 
@@ -314,10 +337,14 @@ def ba_build_index(F, P, fi, pi):
 class BADevice:
     """Device-resident BA problem: observation arrays, CSR indices and the mm_ba_problem descriptor."""
 
-    def __init__(self, K, fi, pi, obs, F, P, device, ctx=None, pairs=True, max_band_span=192, fixed_cams=None):
+    def __init__(self, K, fi, pi, obs, F, P, device, ctx=None, pairs=True, max_band_span=192, fixed_cams=None,
+                 native_index=True):
         """fi, pi: int [O] (numpy or device tensors), obs [O,2] f64 (numpy or device tensor).  All index structures
-        (CSR by point, CSR by camera, co-observation pair list and its chunk table) are built on the device: torch
-        provides the sorts / scans (index plumbing), two HIP kernels enumerate the pairs.
+        (CSR by point, CSR by camera, co-observation pair list and its chunk table) are built on the device, by
+        mm_ba_index_build (two native calls, two host read-backs) for the plain case: point-major observations and no
+        fixed cameras.  Problems with fixed_cams, observations that are not point-major and native_index=False take the
+        earlier construction, in which torch provides the sorts / scans and two HIP kernels enumerate the pairs; both
+        give the same arrays byte for byte (tests/test_ba_index_gpu.py).
 
         fixed_cams: [F_fixed, 6] f64 device tensor of cameras that are observed but not optimised (mm_ba_fixed):
         fi in [F, F + F_fixed) is fixed camera fi - F.  The CSR by camera and the pair list then cover the F free
@@ -348,6 +375,116 @@ class BADevice:
                 self.fixed_cams = fixed_cams.contiguous()
                 self.fx = _lib.BAFixed(self.F_fixed, 0, ptr(self.fixed_cams))
         F_all = F + self.F_fixed
+        self.cam_span = 0
+        self.max_band_span = int(max_band_span)
+        self._slabs, self._slab_src = None, None
+        self.n_pairs = 0
+        # build + solve overlapped on two streams (mm_ba_schur_solve).  Needs concurrent kernel execution: tools that
+        # serialise kernels (rocprofv3 --pmc, launch-blocking debug modes) make the consumer wait for a producer that
+        # cannot start; its bounded spins then give up (info = -1) and the driver falls back to one after the other.
+        # Off by default since the factorisation became two-ended: its 137 workgroups use the whole register file of
+        # their CUs (one wave per SIMD), the build slows down by 1.6x beside them and build-then-solve (0.32 + 0.59 ms at
+        # 500 cameras) beats the overlapped pair (0.93 ms).  MM_SCHUR_OVERLAP=1 selects the overlapped path.
+        self.overlap = os.environ.get("MM_SCHUR_OVERLAP", "0") != "0"
+        self.index_build = "torch"
+        if native_index and O and F > 0 and P > 0 and not self.F_fixed and self._build_index_native(pairs):
+            self.index_build = "native"
+        else:
+            self._build_index_torch(pairs, F_all)
+        self._ws = torch.empty(2048 * 8, dtype=torch.uint8, device=dev)
+        self._cost2 = torch.zeros(1, dtype=torch.float64, device=dev)
+        self._S = None  # reduced camera system, allocated once (6F x 6F doubles)
+        self._schur_ws = None
+        self._chol_ws = None
+
+    @staticmethod
+    def _chunk_pairs():
+        # pairs per chunk = per wave of the pair kernel (a multiple of 64: whole lane strides).  512 since the second
+        # half of round 4: 230 us per build at the bench shape against 249 with 256 (384: 230; 1024: slower)
+        return max(64, int(os.environ.get("MM_SCHUR_CHUNK", "512")) // 64 * 64)
+
+    @property
+    def slabs(self):
+        """Camera slabs for the overlapped build + solve (mm_ba_schur_solve): first segment / chunk of each slab, or
+        None.  The native index build leaves them to the first reader (two more host read-backs; the path that wants
+        them, MM_SCHUR_OVERLAP=1, is off by default)."""
+        if self._slabs is None and self._slab_src is not None:
+            seg_ids, seg_chunk_ptr = self._slab_src
+            self._slab_src = None
+            self._set_slabs(seg_ids.to(torch.int64), seg_chunk_ptr.to(torch.int64))
+        return self._slabs
+
+    def _set_slabs(self, seg_ids, seg_chunk_ptr):
+        n_slabs = 8
+        cps = -(-self.F // n_slabs)
+        if cps >= 16:
+            seg_cam = seg_ids // (self.cam_span + 1)
+            bounds = torch.arange(n_slabs + 1, dtype=torch.int64, device=self.device) * cps
+            sseg = torch.searchsorted(seg_cam, bounds)
+            schunk = seg_chunk_ptr[sseg]
+            self._slabs = (n_slabs, cps, np.ascontiguousarray(sseg.cpu().numpy(), np.int64),
+                           np.ascontiguousarray(schunk.cpu().numpy(), np.int64))
+
+    def _build_index_native(self, pairs):
+        """mm_ba_index_build.  -> False (nothing set) when the observations are not point-major."""
+        F, P, O, dev = self.F, self.P, self.O, self.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        pt_ptr, pt_obs = torch.empty(P + 1, **i32), torch.empty(O, **i32)
+        cam_ptr, cam_obs = torch.empty(F + 1, **i32), torch.empty(O, **i32)
+        head = torch.empty(8, dtype=torch.int64, device=dev)
+        ix = _lib.BAIndex(F, P, O, ptr(self.fi), ptr(self.pi), ptr(pt_ptr), ptr(pt_obs), ptr(cam_ptr), ptr(cam_obs), ptr(head),
+                          0, self._chunk_pairs(), 0, None, None, None, None, None, None, None, None)
+        ws0b = lib.mm_ba_index_workspace_bytes(self.ctx.h, C.byref(ix), 0)
+        if not ws0b:
+            raise _lib.MMError("mm_ba_index_workspace_bytes: no workspace size for stage 0")
+        ws0 = torch.empty(ws0b, dtype=torch.uint8, device=dev)
+        self.ctx.check(lib.mm_ba_index_build(self.ctx.h, C.byref(ix), 0, ptr(ws0), ws0b, None, 0), "mm_ba_index_build")
+        span, n, bad_range, not_point_major = head[:4].tolist()      # read-back 1 of 2
+        if bad_range:
+            raise ValueError("frame / point index out of range")
+        if not_point_major:
+            return False
+        self.pt_ptr, self.pt_obs, self.cam_ptr, self.cam_obs = pt_ptr, pt_obs, cam_ptr, cam_obs
+        self.cam_span = int(span)
+        self.pb = BAProblem(F, P, O, ptr(self.K), ptr(self.fi), ptr(self.pi), ptr(self.obs),
+                            ptr(self.pt_ptr), ptr(self.pt_obs), ptr(self.cam_ptr), ptr(self.cam_obs),
+                            self.cam_span, 0, 0, None, None, 0, None, None, None, None, None, None)
+        # banded problems: co-observation pair list for the atomic-free, bitwise reproducible Schur kernel;
+        # wide spans keep the general kernel
+        if pairs and self.cam_span <= self.max_band_span and self.cam_span < F and F * (self.cam_span + 1) < 2 ** 31:
+            n = int(n)
+            seg_cap, chunk_cap = C.c_int64(0), C.c_int64(0)
+            lib.mm_ba_index_bounds(F, self.cam_span, n, ix.chunk, C.byref(seg_cap), C.byref(chunk_cap))
+            seg_cap, chunk_cap = seg_cap.value, chunk_cap.value
+            pair_o, pair_o2, pair_p = torch.empty(n, **i32), torch.empty(n, **i32), torch.empty(n, **i32)
+            seg_ids, seg_chunk_ptr = torch.empty(seg_cap, **i32), torch.empty(seg_cap + 1, **i32)
+            chunk_seg, chunk_begin, chunk_end = (torch.empty(chunk_cap, **i32) for _ in range(3))
+            ix.cam_span, ix.n_pairs = self.cam_span, n
+            ix.pair_o, ix.pair_o2, ix.pair_p = ptr(pair_o), ptr(pair_o2), ptr(pair_p)
+            ix.seg_ids, ix.seg_chunk_ptr = ptr(seg_ids), ptr(seg_chunk_ptr)
+            ix.chunk_seg, ix.chunk_begin, ix.chunk_end = ptr(chunk_seg), ptr(chunk_begin), ptr(chunk_end)
+            ws1b = lib.mm_ba_index_workspace_bytes(self.ctx.h, C.byref(ix), 1)
+            if not ws1b:
+                raise _lib.MMError("mm_ba_index_workspace_bytes: no workspace size for stage 1")
+            ws1 = torch.empty(ws1b, dtype=torch.uint8, device=dev)
+            self.ctx.check(lib.mm_ba_index_build(self.ctx.h, C.byref(ix), 1, ptr(ws0), ws0b, ptr(ws1), ws1b), "mm_ba_index_build")
+            n_seg, n_chunks = head[4:6].tolist()      # read-back 2 of 2 (the workspaces are free to go after it)
+            self.pair_o, self.pair_o2, self.pair_p = pair_o, pair_o2, pair_p
+            self.seg_ids, self.seg_chunk_ptr = seg_ids[:n_seg], seg_chunk_ptr[:n_seg + 1]
+            self.chunk_seg, self.chunk_begin, self.chunk_end = chunk_seg[:n_chunks], chunk_begin[:n_chunks], chunk_end[:n_chunks]
+            self.n_pairs = n
+            self.pb.n_seg = n_seg
+            self.pb.n_chunks = n_chunks
+            self.pb.seg_ids, self.pb.seg_chunk_ptr = ptr(self.seg_ids), ptr(self.seg_chunk_ptr)
+            self.pb.chunk_seg, self.pb.chunk_begin, self.pb.chunk_end = ptr(self.chunk_seg), ptr(self.chunk_begin), ptr(self.chunk_end)
+            self.pb.pair_o, self.pb.pair_o2, self.pb.pair_p = ptr(self.pair_o), ptr(self.pair_o2), ptr(self.pair_p)
+            self._slab_src = (self.seg_ids, self.seg_chunk_ptr)
+        return True
+
+    def _build_index_torch(self, pairs, F_all):
+        """The construction from torch sorts / scans and the two pair kernels (fixed cameras, any observation order)."""
+        F, P, O, dev = self.F, self.P, self.O, self.device
+        max_band_span = self.max_band_span
         i64 = dict(dtype=torch.int64, device=dev)
         if O:
             lim = torch.stack([self.fi.min(), self.fi.max(), self.pi.min(), self.pi.max(),
@@ -375,20 +512,9 @@ class BADevice:
             self.cam_obs = torch.sort(self.fi, stable=True)[1].to(torch.int32)      # stable: observation order kept
         else:
             self.cam_obs = torch.zeros(0, dtype=torch.int32, device=dev)
-        self.cam_span = 0
-        self.max_band_span = int(max_band_span)
-        self.slabs = None
-        # build + solve overlapped on two streams (mm_ba_schur_solve).  Needs concurrent kernel execution: tools that
-        # serialise kernels (rocprofv3 --pmc, launch-blocking debug modes) make the consumer wait for a producer that
-        # cannot start; its bounded spins then give up (info = -1) and the driver falls back to one after the other.
-        # Off by default since the factorisation became two-ended: its 137 workgroups use the whole register file of
-        # their CUs (one wave per SIMD), the build slows down by 1.6x beside them and build-then-solve (0.32 + 0.59 ms at
-        # 500 cameras) beats the overlapped pair (0.93 ms).  MM_SCHUR_OVERLAP=1 selects the overlapped path.
-        self.overlap = os.environ.get("MM_SCHUR_OVERLAP", "0") != "0"
         self.pb = BAProblem(F, P, O, ptr(self.K), ptr(self.fi), ptr(self.pi), ptr(self.obs),
                             ptr(self.pt_ptr), ptr(self.pt_obs), ptr(self.cam_ptr), ptr(self.cam_obs),
                             0, 0, 0, None, None, 0, None, None, None, None, None, None)
-        self.n_pairs = 0
         # the pair list and cam_span are over the free cameras: with fixed ones the two pair kernels see the free
         # observations only (a problem of its own, same order), and the pairs are mapped back to observation indices
         pair_pb, free_idx, O_pairs = self.pb, None, O
@@ -432,9 +558,7 @@ class BADevice:
                 seg_ids, counts = torch.unique_consecutive(key_s, return_counts=True)
                 seg_hi = torch.cumsum(counts, 0)
                 seg_lo = seg_hi - counts
-                # pairs per chunk = per wave of the pair kernel (a multiple of 64: whole lane strides).  512 since the second
-                # half of round 4: 230 us per build at the bench shape against 249 with 256 (384: 230; 1024: slower)
-                CH = max(64, int(os.environ.get("MM_SCHUR_CHUNK", "512")) // 64 * 64)
+                CH = self._chunk_pairs()
                 cntc = (counts + (CH - 1)) // CH
                 first_hi = torch.cumsum(cntc, 0)
                 first = first_hi - cntc
@@ -454,21 +578,7 @@ class BADevice:
                 self.pb.pair_o, self.pb.pair_o2 = ptr(self.pair_o), ptr(self.pair_o2)
                 self.pair_p = self.pi[self.pair_o.long()].contiguous()   # saves the pair kernel a dependent gather
                 self.pb.pair_p = ptr(self.pair_p)
-                # camera slabs for the overlapped build + solve (mm_ba_schur_solve): first segment / chunk of each slab
-                n_slabs = 8
-                cps = -(-F // n_slabs)
-                if cps >= 16:
-                    seg_cam = seg_ids.to(torch.int64) // (self.cam_span + 1)
-                    bounds = torch.arange(n_slabs + 1, **i64) * cps
-                    sseg = torch.searchsorted(seg_cam, bounds)
-                    schunk = torch.cat([first, first_hi[-1:]])[sseg]
-                    self.slabs = (n_slabs, cps, np.ascontiguousarray(sseg.cpu().numpy(), np.int64),
-                                  np.ascontiguousarray(schunk.cpu().numpy(), np.int64))
-        self._ws = torch.empty(2048 * 8, dtype=torch.uint8, device=dev)
-        self._cost2 = torch.zeros(1, dtype=torch.float64, device=dev)
-        self._S = None  # reduced camera system, allocated once (6F x 6F doubles)
-        self._schur_ws = None
-        self._chol_ws = None
+                self._set_slabs(seg_ids.to(torch.int64), torch.cat([first, first_hi[-1:]]))
 
     def residual(self, cams, pts, want_res=False, cost_out=None):
         """-> (sum of squared residuals as a 1-element device tensor, res [O,2] or None).  cost_out: where to put the
@@ -583,7 +693,7 @@ class BADevice:
         if self._chol_ws is None:
             self._chol_ws = torch.empty(lib.mm_chol_workspace_bytes(n), dtype=torch.uint8, device=self.device)
         hb = int(min(half_bandwidth, n))
-        if self.slabs is not None and self.overlap:
+        if self.overlap and self.slabs is not None:
             ns, cps, sseg, schunk = self.slabs
             a_seg, a_chunk = sseg.ctypes.data_as(_lib.c_i64p), schunk.ctypes.data_as(_lib.c_i64p)
         else:

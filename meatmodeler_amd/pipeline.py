@@ -81,9 +81,8 @@ class ClipPipeline:
                     torch.zeros(0, dtype=torch.int32, device=self.device))
         q = desc[pair_lo:pair_hi]
         t = desc[pair_lo + 1:pair_hi + 1]
-        idx, dist = ops.bf_knn2_batched(q, t, n[pair_lo:pair_hi].contiguous(), n[pair_lo + 1:pair_hi + 1].contiguous(),
-                                        self.ctx)
-        return ops.ratio_filter_batched(idx, dist, self.ratio, n[pair_lo:pair_hi].contiguous(), self.ctx)
+        return ops.bf_match_ratio_batched(q, t, n[pair_lo:pair_hi].contiguous(), n[pair_lo + 1:pair_hi + 1].contiguous(),
+                                          self.ratio, self.ctx)
 
     # ------------------------------------------------------------------------------------------- verify
     def verify(self, det, pairs, m, pair_lo=0, **params):

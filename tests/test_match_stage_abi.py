@@ -1,0 +1,41 @@
+"""CPU: how mm_bf_match_ratio_batched carves its workspace (no compute calls)."""
+import pytest
+
+
+def up(x):
+    return (x + 255) // 256 * 256
+
+
+def sizes(n_pairs, nq_cap, nt_cap):
+    from meatmodeler_amd import _lib      # (inside the tests, as in test_abi.py: not while the suite is being collected)
+    return (_lib.lib.mm_bf_match_ratio_workspace_bytes(n_pairs, nq_cap, nt_cap),
+            _lib.lib.mm_bf_workspace_bytes(n_pairs, nq_cap, nt_cap))
+
+
+@pytest.mark.parametrize("variant", ["314", "310"])
+def test_fused_variants_hold_one_code_per_query_and_no_expanded_train_set(variant, monkeypatch):
+    monkeypatch.setenv("MM_BF_VARIANT", variant)
+    total, knn = sizes(499, 4000, 4000)
+    assert knn == 256                                          # (never 0: the search wants a workspace pointer)
+    assert total == knn + up(499 * 4000 * 4)
+    # train sets the matrix-core kernels do not take (fewer than 64, 65536 and more): idx and dist behind the split buffers
+    for nt_cap in (63, 65536):
+        total, knn = sizes(9, 300, nt_cap)
+        assert knn % 256 == 0 and total == knn + 2 * up(9 * 300 * 2 * 4)
+
+
+@pytest.mark.parametrize("variant,per_train", [("300", 128), ("200", 256), ("114", 0)])
+def test_other_variants_keep_idx_and_dist_behind_the_search_workspace(variant, per_train, monkeypatch):
+    monkeypatch.setenv("MM_BF_VARIANT", variant)
+    total, knn = sizes(9, 300, 300)
+    if per_train:
+        assert knn == up(9 * 320 * per_train)                  # expanded train sets, 300 rows padded to 10 tiles of 32
+    assert knn > 0 and knn % 256 == 0
+    assert total == knn + 2 * up(9 * 300 * 2 * 4)
+
+
+def test_degenerate_shapes():
+    for shape in ((0, 300, 300), (9, 0, 300), (9, 300, 0)):
+        total, knn = sizes(*shape)
+        assert total >= knn > 0 and total % 256 == 0
+    assert sizes(9, 0, 300)[0] == sizes(9, 0, 300)[1]          # no queries: nothing behind the search's workspace
