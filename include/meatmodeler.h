@@ -256,6 +256,76 @@ int mm_verify_matches(mm_ctx *ctx, const float *kp_xy /*[n_pairs+1,cap,2]*/, con
                       int32_t *pairs_out /*[n_pairs,cap,2]*/, int32_t *m_out /*[n_pairs]*/, double *Fm /*[n_pairs,9]*/,
                       double *cost /*[n_pairs]*/, int32_t *info /*[n_pairs,4]*/, void *ws, size_t ws_bytes);
 
+/* ---- a-2c: camera poses from the verified matches (no reference counterpart: the reference reads every keyframe's pose off
+ * a chessboard) -------------------------------------------------------------------------------------------------------------
+ * mm_recover_poses: the relative pose of every consecutive frame pair from that pair's fundamental matrix, the calibration and
+ * the pair's inlier matches; mm_chain_poses: the pairs chained into one set of extrinsics [n_pairs+1, 3, 4] that goes into
+ * mm_triangulate_tracks and the adjustment.
+ *   Inputs.  K [9] f64 HOST, row-major, upper triangular with K[8] = 1; kp_xy [n_pairs+1, cap, 2] f32; pairs [n_pairs, cap, 2]
+ *   i32 and m [n_pairs] (clamped to 0 .. cap): what mm_verify_matches wrote to pairs_out / m_out; Fm [n_pairs, 9] f64 with
+ *   x'^T F x = 0.  Pair p joins frame p (query, camera 1) and frame p + 1 (train, camera 2).
+ *   Convention.  A point X1 in camera-1 coordinates is X2 = R X1 + t in camera 2, |t| = 1.
+ *   Decomposition (no SVD).  E = K^T (F K), G = E^T E; eigen-decomposition of G by the 3 x 3 cyclic Jacobi of
+ *   mm_verify_matches' rank-2 step (pairs (0,1), (0,2), (1,2) per sweep, a rotation skipped once |g_pq| <= eps sqrt(|g_pp g_qq|),
+ *   at most 30 sweeps, V starts as the identity).  v3 = eigenvector of the smallest eigenvalue, v1 of the largest, ties to the
+ *   lowest column; v2 = v3 x v1; u1 = E v1 / s1, s1 = |E v1|; u2 = (E v2 - (u1 . E v2) u1) / s2, s2 that vector's norm;
+ *   u3 = u1 x u2.  U = [u1 u2 u3] and V = [v1 v2 v3] have determinant +1 by construction.  W = [[0,-1,0],[1,0,0],[0,0,1]],
+ *   Ra = U W V^T, Rb = U W^T V^T; candidates c = 0 .. 3 are (Ra, +u3), (Ra, -u3), (Rb, +u3), (Rb, -u3).
+ *   Depths.  K^-1 is formed once on the host, in closed form: with K = [[fx, s, cx], [0, fy, cy], [0, 0, 1]],
+ *   K^-1 = [[1/fx, -s/(fx fy), (s cy - cx fy)/(fx fy)], [0, 1/fy, -cy/fy], [0, 0, 1]].  A match has the rays
+ *   a = K^-1 (x, y, 1) and b = K^-1 (x', y', 1); with r = R a: det = (r.r)(b.b) - (r.b)^2,
+ *   l1 = ((r.b)(b.t) - (r.t)(b.b)) / det, l2 = ((r.r)(b.t) - (r.b)(r.t)) / det -- the least-squares solution of
+ *   l2 b = l1 r + t, the depths along a and b.  A match votes for c when both depths are finite and > 0.  A match with an
+ *   index outside [0, cap) is MALFORMED: it never votes and nothing is read through it.
+ *   Winner.  The largest vote count, ties to the lowest c.
+ *   Outputs.  R [n_pairs, 9] row-major and t [n_pairs, 3] f64 of the winner (NaN: no model); sigma [n_pairs, 2] = (s1, s2) --
+ *   a true essential matrix has s1 = s2, so the caller sees how far F and K disagree (NaN for a pair with too few matches);
+ *   depth [n_pairs, cap, 2] f64 = (l1, l2) under the winner for every row that voted for it, NaN in every other row, rows at
+ *   or beyond m[p] included; info [n_pairs, 8] i32 = (flags, winner or -1, votes[0 .. 3], m used, 0).
+ *   Flags.  MM_POSE_TOO_FEW m < max(min_matches, 8): nothing is decomposed | MM_POSE_NO_MODEL a non-finite F, or s1 or s2 not
+ *   finite and positive | MM_POSE_AMBIGUOUS votes[winner] < min_front_frac m, or the runner-up has >= ambiguous_frac
+ *   votes[winner] (rotation-only and planar pairs land here; R and t are still written) | MM_POSE_MALFORMED.
+ * One 256-thread workgroup per pair, integer counts: a call repeats bit for bit and a pair's row does not depend on which
+ * other pairs share the call.  n_pairs = 0 returns MM_OK without a launch.  kp_xy and pairs 8-byte aligned, depth 16-byte.
+ * Null pointers, cap <= 0, a K that is not finite / upper triangular / K[8] = 1 or has a zero focal length, and fractions
+ * outside [0, 1] return MM_ERR_ARG before the device is touched. */
+#define MM_POSE_TOO_FEW 1
+#define MM_POSE_NO_MODEL 2
+#define MM_POSE_AMBIGUOUS 4
+#define MM_POSE_MALFORMED 8
+typedef struct mm_pose_params {
+    int32_t min_matches, reserved;
+    double min_front_frac, ambiguous_frac;      /* defaults 0.5, 0.5 */
+} mm_pose_params;
+int mm_recover_poses(mm_ctx *ctx, const double *K /*host [9]*/, const float *kp_xy /*[n_pairs+1,cap,2]*/,
+                     const int32_t *pairs /*[n_pairs,cap,2]*/, const int32_t *m /*[n_pairs]*/, const double *Fm /*[n_pairs,9]*/,
+                     int n_pairs, int cap, const mm_pose_params *prm, double *R /*[n_pairs,9]*/, double *t /*[n_pairs,3]*/,
+                     double *sigma /*[n_pairs,2]*/, double *depth /*[n_pairs,cap,2]*/, int32_t *info /*[n_pairs,8]*/);
+/* One scale and one coordinate frame for the pairs of mm_recover_poses.  pairs, m, depth, R, t, info as above -- all of them
+ * inputs --, cap <= 8192; E0 [12] f64 HOST: the first frame's extrinsic; min_common >= 0.
+ *   Scale ratio of pair p >= 1 against pair p - 1.  Key point k of frame p is a train of pair p - 1 and a query of pair p.
+ *   prev(k) = the lowest row i < m[p-1] of pair p - 1 with train k and depth[p-1, i, 1] finite and > 0.  Every row j < m[p]
+ *   of pair p whose query has a prev and whose depth[p, j, 0] is finite and > 0 gives rho_j = depth[p-1, prev, 1] /
+ *   depth[p, j, 0] (one IEEE division); rho_p is the lower median of those n_common values, the (n_common - 1) / 2-th
+ *   smallest.  An index outside [0, cap) has no prev and gives no ratio.
+ *   Flags (chain_info [n_pairs, 2] i32 = (flags, n_common)).  MM_CHAIN_BROKEN: the pair has MM_POSE_TOO_FEW or
+ *   MM_POSE_NO_MODEL; its motion is taken as identity rotation and zero translation, rho_p = 1, n_common = 0, and the next
+ *   pair is MM_CHAIN_FEW_COMMON with n_common = 0.  MM_CHAIN_FEW_COMMON: n_common < min_common; rho_p = 1, the previous scale
+ *   is carried.  Pair 0 has no ratio: rho_0 = 1, n_common = 0, no flag.  An AMBIGUOUS pair is chained as it is.
+ *   Composition, in this order: s_0 = 1 (times rho_0), s_p = s_{p-1} rho_p; T_0 = E0;
+ *   T_{p+1} = [R_p T_p[:, :3] | R_p T_p[:, 3] + s_p t_p], every dot product summed left to right.
+ *   Outputs.  extrinsics [n_pairs+1, 3, 4], scale [n_pairs] = s_p, rho [n_pairs], chain_info.
+ * The median is an element of the set (a radix select on the bit patterns), the only atomics are integer min / add: the
+ * result repeats bit for bit.  n_pairs = 0 returns MM_OK without a launch (extrinsics is not written).  Null pointers, cap
+ * outside 1 .. 8192 and a negative min_common return MM_ERR_ARG before the device is touched. */
+#define MM_CHAIN_FEW_COMMON 1
+#define MM_CHAIN_BROKEN 2
+int mm_chain_poses(mm_ctx *ctx, const int32_t *pairs /*[n_pairs,cap,2]*/, const int32_t *m /*[n_pairs]*/,
+                   const double *depth /*[n_pairs,cap,2]*/, const double *R /*[n_pairs,9]*/, const double *t /*[n_pairs,3]*/,
+                   const int32_t *info /*[n_pairs,8]*/, int n_pairs, int cap, const double *E0 /*host [12]*/, int min_common,
+                   double *extrinsics /*[n_pairs+1,3,4]*/, double *scale /*[n_pairs]*/, double *rho /*[n_pairs]*/,
+                   int32_t *chain_info /*[n_pairs,2]*/);
+
 /* ---- a-4: two-view DLT triangulation ------------------------------------------------------------
  * Replaces the per-track cv2.triangulatePoints + dehomogenise loop, processor.py:254-261.
  * proj [F,3,4] f64; track i uses views f0[i], f1[i] with pixels x0[i], x1[i]; X [n,3]. */

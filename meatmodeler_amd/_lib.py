@@ -73,7 +73,13 @@ class VerifyParams(C.Structure):
                 ("threshold_px", C.c_double)]
 
 
-ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, vp, vp, C.c_int64)
+class PoseParams(C.Structure):
+    """mm_pose_params: match floor and the two vote fractions of mm_recover_poses."""
+    _fields_ = [("min_matches", C.c_int32), ("reserved", C.c_int32), ("min_front_frac", C.c_double),
+                ("ambiguous_frac", C.c_double)]
+
+
+ALLREDUCE_FN =C.CFUNCTYPE(C.c_int, vp, vp, C.c_int64)
 
 
 class Dist(C.Structure):
@@ -126,6 +132,8 @@ SIGNATURES = {
     "mm_ba_build_index": (C.c_int, [C.c_int, C.c_int, C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]),
     "mm_verify_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "mm_verify_matches": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(VerifyParams), vp, vp, vp, vp, vp, vp, C.c_size_t]),
+    "mm_recover_poses": (C.c_int, [vp, c_f64p, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(PoseParams), vp, vp, vp, vp, vp]),
+    "mm_chain_poses": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, c_f64p, C.c_int, vp, vp, vp, vp]),
     "mm_triangulate_dlt": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int64, vp]),
     "mm_triangulate_tracks_workspace_bytes": (C.c_size_t, [C.c_int]),
     "mm_triangulate_tracks": (C.c_int, [vp, vp, C.c_int, vp, C.c_int64, vp, vp, C.POINTER(TriParams), vp, vp, vp, vp, C.c_size_t]),

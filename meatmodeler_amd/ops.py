@@ -138,6 +138,82 @@ def verify_matches(kp_xy, pairs, m, n_hyp=256, threshold_px=2.0, min_matches=16,
     return pairs_out, m_out, F, cost, info
 
 
+POSE_TOO_FEW, POSE_NO_MODEL, POSE_AMBIGUOUS, POSE_MALFORMED = 1, 2, 4, 8      # MM_POSE_* of include/meatmodeler.h
+CHAIN_FEW_COMMON, CHAIN_BROKEN = 1, 2                                         # MM_CHAIN_*
+CHAIN_MAX_CAP = 8192
+
+
+def _host_f64(a, n, what):
+    a = np.ascontiguousarray(np.asarray(a.detach().cpu() if torch.is_tensor(a) else a, dtype=np.float64)).reshape(-1)
+    if a.size != n:
+        raise ValueError(f"{what}: {n} numbers expected")
+    return a
+
+
+def recover_poses(kp_xy, pairs, m, F, K, min_matches=8, min_front_frac=0.5, ambiguous_frac=0.5, ctx=None):
+    """Relative pose of every consecutive frame pair (mm_recover_poses): kp_xy [n_pairs+1, cap, 2] f32, pairs [n_pairs, cap, 2]
+    i32, m [n_pairs] i32 and F [n_pairs, 9] f64 as verify_matches returns them (device tensors), K 3 x 3 on the host
+    -> (R [n_pairs, 9] f64, t [n_pairs, 3] f64 with X2 = R X1 + t and |t| = 1, NaN without a model; sigma [n_pairs, 2] f64;
+    depth [n_pairs, cap, 2] f64 -- the winner's depths of the rows that voted for it, NaN elsewhere;
+    info [n_pairs, 8] i32 = (POSE_* flags, winner or -1, votes[0..3], m used, 0))."""
+    Kh = _host_f64(K, 9, "recover_poses: K")
+    if not np.isfinite(Kh).all() or Kh[3] != 0 or Kh[6] != 0 or Kh[7] != 0 or Kh[8] != 1 or Kh[0] == 0 or Kh[4] == 0:
+        raise ValueError("recover_poses: K must be finite, upper triangular with K[2, 2] = 1 and non-zero focal lengths")
+    if not (0.0 <= float(min_front_frac) <= 1.0 and 0.0 <= float(ambiguous_frac) <= 1.0):
+        raise ValueError("recover_poses: min_front_frac and ambiguous_frac must be in [0, 1]")
+    if pairs.dim() != 3 or pairs.shape[2] != 2 or kp_xy.dim() != 3 or tuple(kp_xy.shape) != (pairs.shape[0] + 1, pairs.shape[1], 2) \
+            or tuple(m.shape) != (pairs.shape[0],) or tuple(F.shape) != (pairs.shape[0], 9):
+        raise ValueError("recover_poses: kp_xy [n_pairs+1, cap, 2], pairs [n_pairs, cap, 2], m [n_pairs] and F [n_pairs, 9] expected")
+    ctx = ctx or default_context()
+    d = pairs.device
+    n_pairs, cap = pairs.shape[0], pairs.shape[1]
+    R = torch.full((n_pairs, 9), math.nan, dtype=torch.float64, device=d)
+    t = torch.full((n_pairs, 3), math.nan, dtype=torch.float64, device=d)
+    sigma = torch.full((n_pairs, 2), math.nan, dtype=torch.float64, device=d)
+    depth = torch.empty((n_pairs, cap, 2), dtype=torch.float64, device=d)      # (every element is written by the kernel)
+    info = torch.zeros((n_pairs, 8), dtype=torch.int32, device=d)
+    if n_pairs == 0 or cap == 0:
+        return R, t, sigma, depth, info
+    assert kp_xy.dtype == torch.float32 and F.dtype == torch.float64
+    prm = _lib.PoseParams(int(min_matches), 0, float(min_front_frac), float(ambiguous_frac))
+    ctx.check(lib.mm_recover_poses(ctx.h, Kh.ctypes.data_as(_lib.c_f64p), ptr(kp_xy.contiguous()), ptr(_i32(pairs.contiguous())),
+                                   ptr(_i32(m.contiguous())), ptr(F.contiguous()), n_pairs, cap, C.byref(prm), ptr(R), ptr(t),
+                                   ptr(sigma), ptr(depth), ptr(info)), "mm_recover_poses")
+    return R, t, sigma, depth, info
+
+
+def chain_poses(pairs, m, depth, R, t, info, E0=None, min_common=8, ctx=None):
+    """The pairs of recover_poses in one scale and one coordinate frame (mm_chain_poses); every argument is an input (device
+    tensors), E0 the first frame's extrinsic [3, 4] on the host ([I | 0] by default)
+    -> (extrinsics [n_pairs+1, 3, 4] f64, scale [n_pairs] f64, rho [n_pairs] f64, chain_info [n_pairs, 2] i32 =
+    (CHAIN_* flags, n_common))."""
+    E0h = _host_f64(np.eye(3, 4) if E0 is None else np.asarray(E0, float)[:3, :], 12, "chain_poses: E0")
+    if int(min_common) < 0:
+        raise ValueError("chain_poses: min_common must not be negative")
+    n_pairs = pairs.shape[0]
+    if pairs.dim() != 3 or pairs.shape[2] != 2 or tuple(m.shape) != (n_pairs,) or tuple(depth.shape) != tuple(pairs.shape) \
+            or tuple(R.shape) != (n_pairs, 9) or tuple(t.shape) != (n_pairs, 3) or tuple(info.shape) != (n_pairs, 8):
+        raise ValueError("chain_poses: pairs / depth [n_pairs, cap, 2], m [n_pairs], R [n_pairs, 9], t [n_pairs, 3], info [n_pairs, 8] expected")
+    cap = pairs.shape[1]
+    if cap > CHAIN_MAX_CAP:
+        raise ValueError(f"chain_poses: cap must not exceed {CHAIN_MAX_CAP}")
+    ctx = ctx or default_context()
+    d = pairs.device
+    ext = torch.empty((n_pairs + 1, 3, 4), dtype=torch.float64, device=d)
+    scale = torch.ones(n_pairs, dtype=torch.float64, device=d)
+    rho = torch.ones(n_pairs, dtype=torch.float64, device=d)
+    cinfo = torch.zeros((n_pairs, 2), dtype=torch.int32, device=d)
+    if n_pairs == 0 or cap == 0:
+        ext[:] = torch.as_tensor(E0h.reshape(3, 4)).to(d)
+        return ext, scale, rho, cinfo
+    assert depth.dtype == torch.float64 and R.dtype == torch.float64 and t.dtype == torch.float64
+    ctx.check(lib.mm_chain_poses(ctx.h, ptr(_i32(pairs.contiguous())), ptr(_i32(m.contiguous())), ptr(depth.contiguous()),
+                                 ptr(R.contiguous()), ptr(t.contiguous()), ptr(_i32(info.contiguous())), n_pairs, cap,
+                                 E0h.ctypes.data_as(_lib.c_f64p), int(min_common), ptr(ext), ptr(scale), ptr(rho), ptr(cinfo)),
+              "mm_chain_poses")
+    return ext, scale, rho, cinfo
+
+
 # ------------------------------------------------------------------------------------------------ ORB
 
 def orb_params(nfeatures, nlevels=8, scale_factor=1.2, edge_threshold=31, fast_threshold=20):

@@ -4,7 +4,8 @@ adjust.  Same stages and semantics as the per-keyframe drop-in functions in `pro
 and key points stay in HBM and each stage is a few large launches instead of one small launch per keyframe.
 
 Keyframe gating, calibration and PnP are outside the scope: the caller provides K and one extrinsic
-per frame (the reference gets them from calibrate / poseEstimation / adjustPose, processor.py:422-448).
+per frame (the reference gets them from calibrate / poseEstimation / adjustPose, processor.py:422-448) -- or, with
+`run(verify={...}, poses={...})`, K alone: the extrinsics are then recovered from the verified matches.
 """
 import ctypes as C
 import queue
@@ -34,6 +35,22 @@ def verify_options(verify):
     if unknown:
         raise ValueError(f"verify takes {', '.join(VERIFY_KEYS)}; not {sorted(unknown)}")
     return dict(verify)
+
+
+POSE_KEYS = ("min_matches", "min_front_frac", "ambiguous_frac", "min_common", "E0")
+
+
+def pose_options(poses):
+    """`run(..., poses=)`: None (the caller provides the extrinsics) or a dict of the parameters of ops.recover_poses and
+    ops.chain_poses.  Returns it as a dict; an unknown key raises ValueError."""
+    if poses is None:
+        return None
+    if not isinstance(poses, dict):
+        raise ValueError("poses must be None or a dict of " + ", ".join(POSE_KEYS))
+    unknown = set(poses) - set(POSE_KEYS)
+    if unknown:
+        raise ValueError(f"poses takes {', '.join(POSE_KEYS)}; not {sorted(unknown)}")
+    return dict(poses)
 
 
 class ClipPipeline:
@@ -91,6 +108,17 @@ class ClipPipeline:
         block gives the rows the whole clip would.  -> (pairs_out, m_out, F [n,9], cost [n], info [n,4]), device tensors."""
         n = pairs.shape[0]
         return ops.verify_matches(det["xy"][:n + 1], pairs, m, pair_base=pair_lo, ctx=self.ctx, **params)
+
+    # ------------------------------------------------------------------------------------------- poses
+    def recover_poses(self, det, pairs, m, F, K, E0=None, min_common=8, **params):
+        """Camera poses from what `verify` returned for the frames in `det`: a relative pose per pair (ops.recover_poses,
+        `params` as it takes them), chained into one scale and one frame (ops.chain_poses; E0 = the first frame's extrinsic,
+        [I | 0] by default).  -> dict(extrinsics [n+1, 3, 4] f64, R, t, sigma, info, depth, scale, rho, chain_info), device
+        tensors.  The first baseline is the unit of length."""
+        n = pairs.shape[0]
+        R, t, sigma, depth, info = ops.recover_poses(det["xy"][:n + 1], pairs, m, F, K, ctx=self.ctx, **params)
+        ext, scale, rho, cinfo = ops.chain_poses(pairs, m, depth, R, t, info, E0=E0, min_common=min_common, ctx=self.ctx)
+        return dict(extrinsics=ext, R=R, t=t, sigma=sigma, info=info, depth=depth, scale=scale, rho=rho, chain_info=cinfo)
 
     # ------------------------------------------------------------------------------------------- link
     def link(self, kp_count, kp_xy, match_count, matches):
@@ -477,8 +505,8 @@ class ClipPipeline:
         return out
 
     # ------------------------------------------------------------------------------------------- whole clip
-    def run(self, frames, K, extrinsics, ba=True, ftol=1e-4, verbose=0, dist=None, timers=None, max_nfev=None,
-            force_collectives=False, triangulation="two_view", cull=None, verify=None):
+    def run(self, frames, K, extrinsics=None, ba=True, ftol=1e-4, verbose=0, dist=None, timers=None, max_nfev=None,
+            force_collectives=False, triangulation="two_view", cull=None, verify=None, poses=None):
         """frames [F,H,W] u8 (device).  With `dist` = torch.distributed (initialised), frames are the FULL clip on
         every rank (synthetic input is generated locally) and the work is sharded as described in parallel.py.
         `max_nfev`: evaluation budget of the adjustment (None = SciPy's default, as adjustPoints).
@@ -494,8 +522,18 @@ class ClipPipeline:
         `verify`: None (default: every Lowe-ratio survivor goes to the linker, as in the reference) or a dict of the
         parameters of ops.verify_matches ({} for the defaults): each rank verifies its own pairs against a RANSAC
         fundamental matrix between `match` and the gather / `link`, and only the inliers are linked.  The result gains
-        `verify` = dict(info [n,4], cost [n], F [n,9], matches_in [n]) over this rank's pairs; timer "verify"."""
+        `verify` = dict(info [n,4], cost [n], F [n,9], matches_in [n]) over this rank's pairs; timer "verify".
+        `poses`: None (default: `extrinsics` holds one [3,4] per frame) or a dict of the parameters of ops.recover_poses and
+        ops.chain_poses ({} for the defaults; needs `verify`, which supplies each pair's F; one rank only -- the chain needs the
+        neighbouring pair's depths across every rank boundary): the extrinsics are recovered from the verified matches and
+        K, `extrinsics` may be None, and the result gains `poses` = dict(extrinsics [F,3,4], R, t, sigma, info, scale, rho,
+        chain_info); timer "poses".  The first baseline is the unit of length."""
         verify = verify_options(verify)
+        poses = pose_options(poses)
+        if poses is not None and verify is None:
+            raise ValueError("poses needs verify (it supplies each pair's fundamental matrix): pass verify={} for the defaults")
+        if poses is None and extrinsics is None:
+            raise ValueError("extrinsics is required unless poses is set")
         if triangulation not in ("two_view", "multi_view"):
             raise ValueError("triangulation must be 'two_view' or 'multi_view'")
         F = frames.shape[0]
@@ -505,6 +543,9 @@ class ClipPipeline:
             raise ValueError("cull needs triangulation='multi_view' (the two-view path has no per-track verdict)")
         if cull is not None and world > 1:
             raise ValueError("cull is not supported with more than one rank: the track partition takes contiguous ranges")
+        if poses is not None and world > 1:
+            raise ValueError("poses is not supported with more than one rank: the chain needs the neighbouring pair's depths "
+                             "across every rank boundary")
         if cull is not None:
             tests = {"max_reproj_px", "min_angle_deg", "min_depth"}
             unknown = set(cull) - tests - {"refine_iters"}
@@ -574,7 +615,15 @@ class ClipPipeline:
         if bad:
             raise MMError("link: match index outside the key point tables")
         toc("link")
-        ext = np.asarray(extrinsics, float)[:, :3, :]
+        recovered = None
+        if poses is not None:
+            tic("poses")
+            recovered = self.recover_poses(det, pairs, m, F_v, K, **poses)
+            recovered.pop("depth")
+            ext = recovered["extrinsics"].cpu().numpy()
+            toc("poses")
+        else:
+            ext = np.asarray(extrinsics, float)[:, :3, :]
         proj = np.einsum("ij,fjk->fik", np.asarray(K, float), ext)   # K [R|t], processor.py:184,448
         tic("triangulate")
         if triangulation == "multi_view":
@@ -588,6 +637,8 @@ class ClipPipeline:
                    frames_local=int(f_hi - f_lo))
         if verified is not None:
             out["verify"] = verified
+        if recovered is not None:
+            out["poses"] = recovered
         kept = None
         if triangulation == "multi_view":
             out.update(track_quality=quality, track_flags=flags)

@@ -336,6 +336,29 @@ def verifyMatches(prev_matches, curr_matches, **params):
     return mask, F[0].cpu().numpy().reshape(3, 3)
 
 
+def recoverPose(prev_matches, curr_matches, K, F, **params):
+    """The relative pose of two keyframes from their matches, the calibration and the fundamental matrix `verifyMatches`
+    returned (curr^T F prev = 0): -> (n_front, R [3,3], t [3], mask [n] bool) with X_curr = R X_prev + t, |t| = 1; mask marks
+    the matches in front of both cameras (a finite depth), n_front their number.  R and t are NaN when there is no model.
+    `params` as ops.recover_poses takes them (min_matches, min_front_frac, ambiguous_frac)."""
+    prev = np.asarray(prev_matches, np.float32).reshape(-1, 2)
+    curr = np.asarray(curr_matches, np.float32).reshape(-1, 2)
+    if prev.shape != curr.shape:
+        raise ValueError("recoverPose: prev_matches and curr_matches must have the same length")
+    n = prev.shape[0]
+    if n == 0:
+        return 0, np.full((3, 3), np.nan), np.full(3, np.nan), np.zeros(0, bool)
+    dev = default_context().device
+    kp = torch.as_tensor(np.stack([prev, curr])).to(dev)
+    idx = torch.arange(n, dtype=torch.int32, device=dev)
+    pairs = torch.stack([idx, idx], dim=1).unsqueeze(0).contiguous()
+    m = torch.full((1,), n, dtype=torch.int32, device=dev)
+    Fd = torch.as_tensor(np.ascontiguousarray(np.asarray(F, np.float64).reshape(1, 9))).to(dev)
+    R, t, _, depth, _ = ops.recover_poses(kp, pairs, m, Fd, K, **params)
+    mask = torch.isfinite(depth[0, :, 0]).cpu().numpy()
+    return int(mask.sum()), R[0].cpu().numpy().reshape(3, 3), t[0].cpu().numpy(), mask
+
+
 # ----------------------------------------------------------------------------------------------- pointTracking
 
 def pointTracking(tracks, prev_keyframe_ID, feature_points, keyframe_ID, correspondents):
