@@ -326,6 +326,83 @@ int mm_chain_poses(mm_ctx *ctx, const int32_t *pairs /*[n_pairs,cap,2]*/, const 
                    double *extrinsics /*[n_pairs+1,3,4]*/, double *scale /*[n_pairs]*/, double *rho /*[n_pairs]*/,
                    int32_t *chain_info /*[n_pairs,2]*/);
 
+/* ---- a-2d: camera registration against existing 3-D points, a RANSAC resection (PnP) per camera ---------------------------------
+ * Reference counterpart: the pose source cv2.solvePnP(..., SOLVEPNP_ITERATIVE) at processor.py:175 (there on the chessboard; the
+ * refinement that follows it, adjustPose, is the adjustment with fixed points).  Every camera of the call is estimated from the
+ * 3-D points it observes; cameras do not see each other.
+ *   Inputs.  K [9] f64 HOST, row-major, upper triangular with K[8] = 1; K^-1 in closed form as in mm_recover_poses.  X [P, 3] f64,
+ *   obs [O, 2] f64 pixels, pi [O] i32: observation o sees point pi[o] at obs[o].  The camera CSR cam_ptr [n_cams+1], cam_obs
+ *   [n_rows] i32 -- the arrays an mm_ba_problem carries: row q in cam_ptr[c] .. cam_ptr[c+1] - 1 (clamped to 0 .. n_rows) of
+ *   camera c is observation o = cam_obs[q].  pt_ok [P] u8 or NULL (every point usable).  prior [n_cams, 12] f64 or NULL: one
+ *   [R|t] per camera; a prior with a non-finite entry counts as absent.
+ *   Usable rows.  A row is usable when o is in [0, O), pi[o] in [0, P), obs[o] and X[pi[o]] are finite and pt_ok is NULL or
+ *   pt_ok[pi[o]] != 0.  An index out of range or a non-finite pixel also sets MALFORMED; nothing is read through a bad index.  A
+ *   masked-out or non-finite point is skipped without a flag.  The usable rows of a camera are compacted once, order preserved;
+ *   n_use is their number and everything below works on the compacted list only, so sampling never meets an unusable row.
+ *   Normalisation, per camera over its usable rows: centroid c (each coordinate sum / n_use), dbar the mean of
+ *   sqrt(((X-c)_0^2 + (X-c)_1^2) + (X-c)_2^2), s = sqrt(3) / dbar, X^ = (s (X - c), 1).  The image side is calibrated:
+ *   u = (Ki0 x + Ki1 y) + Ki2, v = Ki3 y + Ki4.
+ *   Sampling, the integer scheme of mm_verify_matches with six picks: base = pcg(pcg(seed + pcg(cam_base + c)) + h); pick
+ *   k = 0 .. 5 tries a = 0 .. 7: i = (uint64(pcg(base + 8 k + a)) * n_use) >> 32 and takes the first i that is not an earlier
+ *   pick; eight collisions make the hypothesis invalid (at most (5/12)^8 < 1e-3 per pick for n_use >= 12: why min_rows is floored
+ *   at 12).  cam_base is the global index of camera 0 of the call.
+ *   Hypothesis and refit -- one routine, a reduced DLT without SVD and without a 12 x 12 system.  Over the chosen rows, in their
+ *   order, four symmetric 4 x 4 sums (upper triangles, 40 numbers): with w_ij = X^_i X^_j, S += w, Bu += u w, Bv += v w,
+ *   C += (u u + v v) w.  Cholesky S = L L^T, column by column, each entry reduced by its products left to right; a pivot that is
+ *   not finite or <= 1e-12 times the diagonal entry it started from makes the hypothesis invalid (planar and otherwise
+ *   degenerate samples leave here).  Yu = L^-1 Bu, Yv = L^-1 Bv (forward substitution), M = (C - Yu^T Yu) - Yv^T Yv; p3 = the
+ *   eigenvector of the smallest eigenvalue of M, ties to the lowest column (4 x 4 cyclic Jacobi, pairs (p, q) ascending, a
+ *   rotation skipped once |m_pq| <= eps sqrt(|m_pp m_qq|), at most 30 sweeps); p1 = L^-T (Yu p3), p2 = L^-T (Yv p3).
+ *   P = [p1; p2; p3] T with T = [[s I, -s c], [0, 1]]: A = P[:, :3] = s [p1; p2; p3][:, :3], b = [p1; p2; p3][:, 3]; both
+ *   negated when det A < 0.  3 x 3 Jacobi on A^T A gives lambda and V; a lambda that is not finite and positive is invalid.
+ *   R = A (V diag(lambda^-1/2) V^T), sigma = ((sqrt l0 + sqrt l1) + sqrt l2) / 3, t = b / sigma - R c; a non-finite entry is
+ *   invalid.  (For an exact scaled rotation A that t is P[:, 3] / sigma = (b - A c) / sigma; taken about the centroid, what the
+ *   polar step removes from a noisy A is not multiplied by the distance of the points from the world's origin.)
+ *   Score.  Q = K [R|t], y = Q (X, 1), d^2 = (y0/y2 - x)^2 + (y1/y2 - y)^2; a row is an inlier iff y2 > 0 and d^2 is finite and
+ *   <= tau^2, tau = threshold_px.  MSAC: cost = sum over the usable rows of (inlier ? d^2 : tau^2); an invalid hypothesis costs
+ *   +inf.  The hypotheses are ranked by that sum taken over the rows ascending; the lowest finite cost wins, ties go to the
+ *   lowest h.  Every cost from here on -- the winner's, the prior's, a refit's, the polished pose's -- is the same sum in the
+ *   workgroup's fixed order.  A present prior competes as hypothesis number n_hyp: it replaces the winner only with a finite,
+ *   strictly lower cost (or when there is none).
+ *   Refit.  refit_iters rounds (a fixed count) of the reduced DLT over the inliers of the current model, with the camera's
+ *   normalisation; fewer than 6 inliers: nothing changes any more.  A refit is accepted only when it is valid and its cost over
+ *   ALL usable rows is finite and strictly lower.
+ *   Polish.  polish_iters Levenberg-Marquardt TRIAL steps on sum |r|^2 over the inlier set fixed at entry, with Y = R X + t,
+ *   r = ((fx Y0 + sk Y1) / Y2 + cx - x, fy Y1 / Y2 + cy - y).  The update is R <- cay(w) R, t <- t + dt with the Cayley map
+ *   cay(w) = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a), a = w / 2 -- rational, so the whole estimator uses + * / sqrt only.
+ *   J = J_pi(Y) [ -[Y - t]x | I ], H = sum J^T J, g = sum J^T r, (H + lambda diag H) delta = -g by 6 x 6 Cholesky (a pivot
+ *   that is not positive fails the trial); lambda = 1e-3 at the start, accept / reject and the lambda schedule as in
+ *   mm_triangulate_tracks.  A trial is accepted only if every row of the set keeps Y2 > 0 and the cost is finite and strictly
+ *   lower.  The polished pose replaces the model only if it is finite and its MSAC cost over all usable rows is strictly lower;
+ *   info then carries the number of accepted trials, otherwise 0.
+ *   Outputs.  extrinsics [n_cams, 3, 4] f64; cost [n_cams] f64 (NaN: no model); inlier [O] u8, written at o for every usable
+ *   or malformed (o in range) row of a camera and left untouched elsewhere; info [n_cams, 6] i32 = (flags, n_inliers, best_h or
+ *   -1 (n_hyp: the prior), valid hypotheses, n_use, accepted polish steps).
+ *   Flags.  MM_RESECT_TOO_FEW n_use < max(min_rows, 12): no RANSAC is run | MM_RESECT_NO_MODEL no finite-cost hypothesis, the
+ *   prior included | MM_RESECT_WEAK n_inliers < min_inliers | MM_RESECT_MALFORMED.  On TOO_FEW or NO_MODEL the camera's
+ *   extrinsic is the prior when present, else NaN, and its inlier rows are 0.
+ * Sums run in an order that depends on the camera alone (per-thread strides, fixed trees), no atomics: a call repeats bit for
+ * bit, a camera's row does not depend on which other cameras share the call, and rows [a, b) of a call equal a call on that
+ * block with cam_base + a.  n_cams = 0 returns MM_OK without a launch.  All pointers are DEVICE pointers except K and prm; ws
+ * holds mm_resect_workspace_bytes(n_cams, n_hyp, n_rows) bytes.  Argument errors -- n_hyp outside 1 .. 4096, a negative or NaN
+ * threshold_px, null pointers, a K that is not finite / upper triangular / K[8] = 1 or has a zero focal length: MM_ERR_ARG; a
+ * workspace that is too small: MM_ERR_WORKSPACE -- are returned before the device is touched. */
+#define MM_RESECT_TOO_FEW 1
+#define MM_RESECT_NO_MODEL 2
+#define MM_RESECT_WEAK 4
+#define MM_RESECT_MALFORMED 8
+typedef struct mm_resect_params {
+    int32_t n_hyp, min_rows, min_inliers, refit_iters, polish_iters, reserved;      /* defaults 256, 12, 12, 2, 8 */
+    uint32_t seed, cam_base;
+    double threshold_px;                                                            /* default 2 */
+} mm_resect_params;
+size_t mm_resect_workspace_bytes(int n_cams, int n_hyp, int64_t n_rows);
+int mm_resect_cameras(mm_ctx *ctx, const double *K /*host [9]*/, const double *X /*[P,3]*/, int64_t P, const double *obs /*[O,2]*/,
+                      const int32_t *pi /*[O]*/, int64_t O, const int32_t *cam_ptr /*[n_cams+1]*/,
+                      const int32_t *cam_obs /*[n_rows]*/, int64_t n_rows, int n_cams, const uint8_t *pt_ok /*[P] or NULL*/,
+                      const double *prior /*[n_cams,12] or NULL*/, const mm_resect_params *prm, double *extrinsics /*[n_cams,3,4]*/,
+                      double *cost /*[n_cams]*/, uint8_t *inlier /*[O]*/, int32_t *info /*[n_cams,6]*/, void *ws, size_t ws_bytes);
+
 /* ---- a-4: two-view DLT triangulation ------------------------------------------------------------
  * Replaces the per-track cv2.triangulatePoints + dehomogenise loop, processor.py:254-261.
  * proj [F,3,4] f64; track i uses views f0[i], f1[i] with pixels x0[i], x1[i]; X [n,3]. */

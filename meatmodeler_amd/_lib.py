@@ -79,6 +79,14 @@ class PoseParams(C.Structure):
                 ("ambiguous_frac", C.c_double)]
 
 
+class ResectParams(C.Structure):
+    """mm_resect_params: hypotheses, row and inlier floors, refit and polish counts, sampling key and threshold of
+    mm_resect_cameras."""
+    _fields_ = [("n_hyp", C.c_int32), ("min_rows", C.c_int32), ("min_inliers", C.c_int32), ("refit_iters", C.c_int32),
+                ("polish_iters", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint32), ("cam_base", C.c_uint32),
+                ("threshold_px", C.c_double)]
+
+
 ALLREDUCE_FN =C.CFUNCTYPE(C.c_int, vp, vp, C.c_int64)
 
 
@@ -134,6 +142,9 @@ SIGNATURES = {
     "mm_verify_matches": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(VerifyParams), vp, vp, vp, vp, vp, vp, C.c_size_t]),
     "mm_recover_poses": (C.c_int, [vp, c_f64p, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(PoseParams), vp, vp, vp, vp, vp]),
     "mm_chain_poses": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, c_f64p, C.c_int, vp, vp, vp, vp]),
+    "mm_resect_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int64]),
+    "mm_resect_cameras": (C.c_int, [vp, c_f64p, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int, vp, vp,
+                                    C.POINTER(ResectParams), vp, vp, vp, vp, vp, C.c_size_t]),
     "mm_triangulate_dlt": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int64, vp]),
     "mm_triangulate_tracks_workspace_bytes": (C.c_size_t, [C.c_int]),
     "mm_triangulate_tracks": (C.c_int, [vp, vp, C.c_int, vp, C.c_int64, vp, vp, C.POINTER(TriParams), vp, vp, vp, vp, C.c_size_t]),

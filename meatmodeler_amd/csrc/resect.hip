@@ -1,0 +1,840 @@
+// Camera registration against existing 3-D points: a RANSAC resection (PnP) per camera (gfx950, f64).
+//
+// Reference counterpart: the pose source cv2.solvePnP(..., SOLVEPNP_ITERATIVE) at processor.py:175 -- there on a chessboard,
+// here on whatever points the camera observes, robustly.  The definition -- usable rows, normalisation, sampling, the reduced
+// DLT, MSAC score, refit, polish, flags -- is in include/meatmodeler.h (mm_resect_cameras); this file maps it:
+//   rs_prepare_kernel     one workgroup per camera: the usable rows compacted in order (ballot / popcount prefix), centroid and
+//                         scale of their points
+//   rs_hypothesis_kernel  one lane per (camera, hypothesis): six sampled rows summed into the 40 numbers of the reduced DLT, both
+//                         factorisations and both Jacobis in registers (every index static, nothing in scratch)
+//   rs_score_kernel       lane = hypothesis, K [R|t] in twelve registers; the camera's rows go through LDS in tiles and every
+//                         lane reads the same address (broadcast), summing min(d^2, tau^2) over the rows ascending
+//   rs_finish_kernel      one workgroup per camera: argmin, the prior, refit rounds, Levenberg-Marquardt polish, mask, outputs
+// Built without FMA contraction (Makefile): a product-sum then has one value whatever the compiler makes of its surroundings,
+// and the NumPy restatement of the tests can follow the header operation by operation.  Plain f64 VALU work; sums in an order
+// that depends on the camera alone (per-thread strides, xor butterflies, waves in order), no atomics.
+#include "mm_common.h"
+
+namespace {
+
+constexpr int RS_THREADS = 256;      // prepare / finish: one workgroup per camera
+constexpr int RS_WAVES = RS_THREADS / 64;
+constexpr int RS_TILE = 256;         // rows per LDS tile of the score kernel
+constexpr double RS_EPS = 2.220446049250313e-16;
+
+__host__ __device__ __forceinline__ uint32_t rs_pcg(uint32_t v) {
+    const uint32_t s = v * 747796405u + 2891336453u;
+    const uint32_t w = ((s >> ((s >> 28) + 4u)) ^ s) * 277803737u;
+    return (w >> 22) ^ w;
+}
+
+struct RsArgs {
+    const double *X, *obs;
+    const int32_t *pi, *cam_ptr, *cam_obs;
+    const uint8_t *pt_ok;
+    const double *prior;
+    long long P, O, n_rows;
+    int n_cams, n_hyp, min_rows, min_inliers, refit_iters, polish_iters;
+    uint32_t seed, cam_base;
+    double tau2;
+    double K[9];
+    double Ki[5];      // K^-1 = [[Ki0, Ki1, Ki2], [0, Ki3, Ki4], [0, 0, 1]]
+    double *norm;      // [n_cams, 8]: cx, cy, cz, s, n_use, number of malformed rows, -, -
+    double *Eh;        // [n_cams, n_hyp, 12] (NaN: invalid hypothesis)
+    double *cost_h;    // [n_cams, n_hyp] (+inf: invalid hypothesis)
+    int32_t *rows;     // [n_rows]: the usable observations of camera c at cam_ptr[c] .. + n_use, in order
+    uint8_t *mask;     // [n_rows]: the polish set, by compacted row
+    double *ext, *cost;
+    uint8_t *inlier;
+    int32_t *info;
+};
+
+// rows of camera c in cam_obs, clamped to the array: nothing is read outside it whatever cam_ptr holds
+__device__ __forceinline__ void rs_range(const RsArgs &a, int c, int &lo, int &hi) {
+    long long l = a.cam_ptr[c], h = a.cam_ptr[c + 1];
+    l = l < 0 ? 0 : (l > a.n_rows ? a.n_rows : l);
+    h = h < l ? l : (h > a.n_rows ? a.n_rows : h);
+    lo = (int)l;
+    hi = (int)h;
+}
+
+// compacted row k of the camera whose rows start at lo (validated by the prepare kernel)
+__device__ __forceinline__ void rs_load(const RsArgs &a, int lo, int k, double &X, double &Y, double &Z, double &ox, double &oy) {
+    const int o = a.rows[lo + k];
+    const int p = a.pi[o];
+    X = a.X[3 * (size_t)p];
+    Y = a.X[3 * (size_t)p + 1];
+    Z = a.X[3 * (size_t)p + 2];
+    ox = a.obs[2 * (size_t)o];
+    oy = a.obs[2 * (size_t)o + 1];
+}
+
+// sum over the workgroup in a fixed order: xor butterfly inside a wave, then the waves' sums in wave order (verify.hip's
+// vfy_block_sum).  sm holds RS_WAVES * N doubles.  Every thread of the workgroup calls it and ends with the same bits.
+template <int N>
+__device__ __forceinline__ void rs_block_sum(double (&v)[N], double *sm) {
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) v[i] += __shfl_xor(v[i], off, 64);
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    __syncthreads();
+    if (l == 0) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) sm[w * N + i] = v[i];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = ((sm[i] + sm[N + i]) + sm[2 * N + i]) + sm[3 * N + i];
+}
+
+// eigenvectors of the symmetric G in the columns of V, eigenvalues on G's diagonal: the cyclic Jacobi of verify.hip's
+// vfy_rank2 / pose.hip's pose_jacobi3 (a copy: those files compile to what they compiled to), for N = 3 and N = 4
+template <int N>
+__device__ __forceinline__ void rs_jacobi(double (&G)[N][N], double (&V)[N][N]) {
+#pragma unroll
+    for (int r = 0; r < N; ++r)
+#pragma unroll
+        for (int c = 0; c < N; ++c) V[r][c] = (r == c) ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 30; ++sweep) {
+        bool rotated = false;
+#pragma unroll
+        for (int p = 0; p < N - 1; ++p) {
+#pragma unroll
+            for (int q = p + 1; q < N; ++q) {
+                const double apq = G[p][q];
+                if (fabs(apq) > RS_EPS * sqrt(fabs(G[p][p] * G[q][q])) && apq != 0.0) {
+                    rotated = true;
+                    const double zeta = (G[q][q] - G[p][p]) / (2.0 * apq);
+                    const double tn = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                    const double cs = 1.0 / sqrt(1.0 + tn * tn);
+                    const double sn = cs * tn;
+#pragma unroll
+                    for (int k = 0; k < N; ++k) {
+                        const double akp = G[k][p], akq = G[k][q];
+                        G[k][p] = cs * akp - sn * akq;
+                        G[k][q] = sn * akp + cs * akq;
+                        const double vkp = V[k][p], vkq = V[k][q];
+                        V[k][p] = cs * vkp - sn * vkq;
+                        V[k][q] = sn * vkp + cs * vkq;
+                    }
+#pragma unroll
+                    for (int k = 0; k < N; ++k) {
+                        const double apk = G[p][k], aqk = G[q][k];
+                        G[p][k] = cs * apk - sn * aqk;
+                        G[q][k] = sn * apk + cs * aqk;
+                    }
+                    G[p][q] = G[q][p] = 0.0;
+                }
+            }
+        }
+        if (!rotated) break;
+    }
+}
+
+// one row into the 40 sums: S, Bu, Bv, C, each the upper triangle of a 4 x 4, row-major
+__device__ __forceinline__ void rs_accumulate(double (&acc)[40], const RsArgs &a, double cx, double cy, double cz, double s,
+                                              double X, double Y, double Z, double ox, double oy) {
+    const double x[4] = {s * (X - cx), s * (Y - cy), s * (Z - cz), 1.0};
+    const double u = (a.Ki[0] * ox + a.Ki[1] * oy) + a.Ki[2], v = a.Ki[3] * oy + a.Ki[4];
+    const double r2 = u * u + v * v;
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = i; j < 4; ++j) {
+            const double w = x[i] * x[j];
+            acc[k] += w;
+            acc[10 + k] += u * w;
+            acc[20 + k] += v * w;
+            acc[30 + k] += r2 * w;
+            ++k;
+        }
+}
+
+// the reduced DLT: [R|t] from the 40 sums; false: a failed pivot, a non-positive eigenvalue or a non-finite result
+__device__ __forceinline__ bool rs_solve(const double (&acc)[40], double cx, double cy, double cz, double s, double (&E)[12]) {
+    double S[4][4], Bu[4][4], Bv[4][4], M[4][4];
+    {
+        int k = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = i; j < 4; ++j) {
+                S[i][j] = S[j][i] = acc[k];
+                Bu[i][j] = Bu[j][i] = acc[10 + k];
+                Bv[i][j] = Bv[j][i] = acc[20 + k];
+                M[i][j] = M[j][i] = acc[30 + k];
+                ++k;
+            }
+    }
+    bool ok = true;
+    double L[4][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        double d = S[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
+        ok = ok && isfinite(d) && d > 1e-12 * S[j][j];
+        const double ljj = sqrt(d);
+        L[j][j] = ljj;
+#pragma unroll
+        for (int i = j + 1; i < 4; ++i) {
+            double v = S[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
+            L[i][j] = v / ljj;
+        }
+    }
+    double Yu[4][4], Yv[4][4];      // L^-1 Bu, L^-1 Bv
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            double vu = Bu[i][c], vv = Bv[i][c];
+#pragma unroll
+            for (int k = 0; k < i; ++k) {
+                vu -= L[i][k] * Yu[k][c];
+                vv -= L[i][k] * Yv[k][c];
+            }
+            Yu[i][c] = vu / L[i][i];
+            Yv[i][c] = vv / L[i][i];
+        }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = i; j < 4; ++j) {
+            const double tu = ((Yu[0][i] * Yu[0][j] + Yu[1][i] * Yu[1][j]) + Yu[2][i] * Yu[2][j]) + Yu[3][i] * Yu[3][j];
+            const double tv = ((Yv[0][i] * Yv[0][j] + Yv[1][i] * Yv[1][j]) + Yv[2][i] * Yv[2][j]) + Yv[3][i] * Yv[3][j];
+            M[i][j] = M[j][i] = (M[i][j] - tu) - tv;
+        }
+    double V4[4][4];
+    rs_jacobi<4>(M, V4);
+    double ev = M[0][0], p3[4] = {V4[0][0], V4[1][0], V4[2][0], V4[3][0]};      // smallest eigenvalue, ties to the lowest column
+#pragma unroll
+    for (int c = 1; c < 4; ++c) {
+        if (M[c][c] < ev) {
+            ev = M[c][c];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) p3[r] = V4[r][c];
+        }
+    }
+    double p1[4], p2[4];      // S^-1 Bu p3 = L^-T (Yu p3), S^-1 Bv p3
+    {
+        double wu[4], wv[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            wu[i] = ((Yu[i][0] * p3[0] + Yu[i][1] * p3[1]) + Yu[i][2] * p3[2]) + Yu[i][3] * p3[3];
+            wv[i] = ((Yv[i][0] * p3[0] + Yv[i][1] * p3[1]) + Yv[i][2] * p3[2]) + Yv[i][3] * p3[3];
+        }
+#pragma unroll
+        for (int i = 3; i >= 0; --i) {
+            double vu = wu[i], vv = wv[i];
+#pragma unroll
+            for (int k = i + 1; k < 4; ++k) {
+                vu -= L[k][i] * p1[k];
+                vv -= L[k][i] * p2[k];
+            }
+            p1[i] = vu / L[i][i];
+            p2[i] = vv / L[i][i];
+        }
+    }
+    // P = [p1; p2; p3] T, T = [[s I, -s c], [0, 1]]: A = P[:, :3]; the translation is taken about the centroid (below)
+    double A[3][3], b[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        A[0][c] = s * p1[c];
+        A[1][c] = s * p2[c];
+        A[2][c] = s * p3[c];
+    }
+    b[0] = p1[3];
+    b[1] = p2[3];
+    b[2] = p3[3];
+    const double det = (A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0])) +
+                       A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
+    if (det < 0.0) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            b[r] = -b[r];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) A[r][c] = -A[r][c];
+        }
+    }
+    double G[3][3], V[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) G[r][c] = (A[0][r] * A[0][c] + A[1][r] * A[1][c]) + A[2][r] * A[2][c];
+    rs_jacobi<3>(G, V);
+    double dk[3], sig = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double lam = G[k][k];
+        ok = ok && isfinite(lam) && lam > 0.0;
+        const double rt = sqrt(lam);
+        dk[k] = 1.0 / rt;
+        sig = (k == 0) ? rt : sig + rt;
+    }
+    sig = sig / 3.0;
+    double W[3][3];      // V diag(lambda^-1/2) V^T
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) W[i][j] = ((V[i][0] * dk[0]) * V[j][0] + (V[i][1] * dk[1]) * V[j][1]) + (V[i][2] * dk[2]) * V[j][2];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) E[4 * r + c] = (A[r][0] * W[0][c] + A[r][1] * W[1][c]) + A[r][2] * W[2][c];
+        E[4 * r + 3] = b[r] / sig - ((E[4 * r] * cx + E[4 * r + 1] * cy) + E[4 * r + 2] * cz);
+    }
+#pragma unroll
+    for (int k = 0; k < 12; ++k) ok = ok && isfinite(E[k]);
+    return ok;
+}
+
+// Q = K [R|t], every dot product summed left to right
+__device__ __forceinline__ void rs_camera(const RsArgs &a, const double (&E)[12], double (&Q)[12]) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) Q[4 * r + c] = (a.K[3 * r] * E[c] + a.K[3 * r + 1] * E[4 + c]) + a.K[3 * r + 2] * E[8 + c];
+}
+
+// squared pixel distance of the projection to the observation; true: an inlier (in front, d^2 finite and <= tau^2)
+__device__ __forceinline__ bool rs_distance(const double (&Q)[12], double X, double Y, double Z, double ox, double oy, double tau2,
+                                            double &d2) {
+    const double y0 = ((Q[0] * X + Q[1] * Y) + Q[2] * Z) + Q[3];
+    const double y1 = ((Q[4] * X + Q[5] * Y) + Q[6] * Z) + Q[7];
+    const double y2 = ((Q[8] * X + Q[9] * Y) + Q[10] * Z) + Q[11];
+    const double ex = y0 / y2 - ox, ey = y1 / y2 - oy;
+    d2 = ex * ex + ey * ey;
+    return y2 > 0.0 && isfinite(d2) && d2 <= tau2;
+}
+
+// ---- usable rows, centroid and scale ----------------------------------------------------------------------------------------
+__global__ __launch_bounds__(RS_THREADS) void rs_prepare_kernel(RsArgs a) {
+    __shared__ double sm[RS_WAVES * 3];
+    __shared__ int wcount[RS_WAVES], wbad[RS_WAVES];
+    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int lo, hi;
+    rs_range(a, c, lo, hi);
+    int n_use = 0, bad = 0;
+    for (int q0 = lo; q0 < hi; q0 += RS_THREADS) {
+        const int q = q0 + tid;
+        bool use = false;
+        int o = 0;
+        if (q < hi) {
+            o = a.cam_obs[q];
+            bool mal = !(o >= 0 && (long long)o < a.O);
+            if (!mal) {
+                const int p = a.pi[o];
+                const double ox = a.obs[2 * (size_t)o], oy = a.obs[2 * (size_t)o + 1];
+                mal = !(p >= 0 && (long long)p < a.P) || !(isfinite(ox) && isfinite(oy));
+                if (!mal && (a.pt_ok == nullptr || a.pt_ok[p] != 0))
+                    use = isfinite(a.X[3 * (size_t)p]) && isfinite(a.X[3 * (size_t)p + 1]) && isfinite(a.X[3 * (size_t)p + 2]);
+                if (mal || use) a.inlier[o] = 0;
+            }
+            bad += mal ? 1 : 0;
+        }
+        const unsigned long long bal = __ballot(use);
+        __syncthreads();
+        if (lane == 0) wcount[wave] = __popcll(bal);
+        __syncthreads();
+        int at = n_use;
+        for (int w = 0; w < wave; ++w) at += wcount[w];
+        at += __popcll(bal & ((1ull << lane) - 1ull));
+        if (use) a.rows[lo + at] = o;
+        n_use += wcount[0] + wcount[1] + wcount[2] + wcount[3];
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) bad += __shfl_xor(bad, off, 64);
+    if (lane == 0) wbad[wave] = bad;
+    __syncthreads();      // (also publishes rows to the whole workgroup)
+    bad = wbad[0] + wbad[1] + wbad[2] + wbad[3];
+    double s3[3] = {0.0, 0.0, 0.0};
+    for (int k = tid; k < n_use; k += RS_THREADS) {
+        double X, Y, Z, ox, oy;
+        rs_load(a, lo, k, X, Y, Z, ox, oy);
+        s3[0] += X;
+        s3[1] += Y;
+        s3[2] += Z;
+    }
+    rs_block_sum<3>(s3, sm);
+    const double n = (double)n_use, cx = s3[0] / n, cy = s3[1] / n, cz = s3[2] / n;
+    double dd[1] = {0.0};
+    for (int k = tid; k < n_use; k += RS_THREADS) {
+        double X, Y, Z, ox, oy;
+        rs_load(a, lo, k, X, Y, Z, ox, oy);
+        dd[0] += sqrt(((X - cx) * (X - cx) + (Y - cy) * (Y - cy)) + (Z - cz) * (Z - cz));
+    }
+    rs_block_sum<1>(dd, sm);
+    if (tid == 0) {
+        double *o = a.norm + 8 * (size_t)c;
+        o[0] = cx;
+        o[1] = cy;
+        o[2] = cz;
+        o[3] = 1.7320508075688772 / (dd[0] / n);
+        o[4] = n;
+        o[5] = (double)bad;
+        o[6] = 0.0;
+        o[7] = 0.0;
+    }
+}
+
+// ---- one hypothesis per lane --------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void rs_hypothesis_kernel(RsArgs a) {
+    const int c = blockIdx.x;
+    const int h = blockIdx.y * 64 + threadIdx.x;
+    const double *nr = a.norm + 8 * (size_t)c;
+    const int n_use = (int)nr[4];
+    if (h >= a.n_hyp || n_use < a.min_rows) return;      // (a camera with too few rows is never scored either)
+    int lo, hi;
+    rs_range(a, c, lo, hi);
+    const double cx = nr[0], cy = nr[1], cz = nr[2], s = nr[3];
+    bool ok = isfinite(s) && isfinite(cx) && isfinite(cy) && isfinite(cz);
+    // six distinct rows, integer arithmetic only
+    const uint32_t base = rs_pcg(rs_pcg(a.seed + rs_pcg(a.cam_base + (uint32_t)c)) + (uint32_t)h);
+    int pick[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        int chosen = -1;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const uint32_t r = rs_pcg(base + (uint32_t)(8 * k + t));
+            const int i = (int)(((uint64_t)r * (uint64_t)n_use) >> 32);
+            bool dup = false;
+#pragma unroll
+            for (int e = 0; e < k; ++e) dup = dup || pick[e] == i;
+            if (chosen < 0 && !dup) chosen = i;
+        }
+        ok = ok && chosen >= 0;
+        pick[k] = chosen < 0 ? 0 : chosen;
+    }
+    double acc[40];
+#pragma unroll
+    for (int k = 0; k < 40; ++k) acc[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        double X, Y, Z, ox, oy;
+        rs_load(a, lo, pick[k], X, Y, Z, ox, oy);
+        rs_accumulate(acc, a, cx, cy, cz, s, X, Y, Z, ox, oy);
+    }
+    double E[12];
+    ok = rs_solve(acc, cx, cy, cz, s, E) && ok;
+    double *o = a.Eh + ((size_t)c * a.n_hyp + h) * 12;
+    const double nan = __builtin_nan("");
+#pragma unroll
+    for (int k = 0; k < 12; ++k) o[k] = ok ? E[k] : nan;
+}
+
+// ---- MSAC cost of every hypothesis ----------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void rs_score_kernel(RsArgs a) {
+    __shared__ double tile[RS_TILE * 5];
+    const int c = blockIdx.x;
+    const int h = blockIdx.y * 64 + threadIdx.x;
+    const int n_use = (int)a.norm[8 * (size_t)c + 4];
+    if (n_use < a.min_rows) return;      // (uniform over the workgroup)
+    int lo, hi;
+    rs_range(a, c, lo, hi);
+    const bool live = h < a.n_hyp;
+    double E[12], Q[12];
+    const double *src = a.Eh + ((size_t)c * a.n_hyp + (live ? h : 0)) * 12;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) E[k] = src[k];
+    rs_camera(a, E, Q);
+    double cost = 0.0;
+    for (int j0 = 0; j0 < n_use; j0 += RS_TILE) {
+        const int nt = min(RS_TILE, n_use - j0);
+        __syncthreads();
+        for (int j = threadIdx.x; j < nt; j += 64) {
+            double X, Y, Z, ox, oy;
+            rs_load(a, lo, j0 + j, X, Y, Z, ox, oy);
+            tile[5 * j] = X;
+            tile[5 * j + 1] = Y;
+            tile[5 * j + 2] = Z;
+            tile[5 * j + 3] = ox;
+            tile[5 * j + 4] = oy;
+        }
+        __syncthreads();
+        for (int j = 0; j < nt; ++j) {
+            double d2;
+            const bool in = rs_distance(Q, tile[5 * j], tile[5 * j + 1], tile[5 * j + 2], tile[5 * j + 3], tile[5 * j + 4], a.tau2, d2);
+            cost += in ? d2 : a.tau2;
+        }
+    }
+    if (live) a.cost_h[(size_t)c * a.n_hyp + h] = isfinite(E[0]) ? cost : __builtin_huge_val();
+}
+
+// ---- winner, prior, refit, polish, outputs ----------------------------------------------------------------------------------
+// MSAC cost and inlier count of [R|t] over the usable rows of the camera (every thread returns the same bits)
+__device__ __forceinline__ void rs_cost(const RsArgs &a, int lo, int n_use, const double (&E)[12], double *sm, double &cost, int &n_in) {
+    double Q[12];
+    rs_camera(a, E, Q);
+    double v[2] = {0.0, 0.0};
+    for (int k = threadIdx.x; k < n_use; k += RS_THREADS) {
+        double X, Y, Z, ox, oy, d2;
+        rs_load(a, lo, k, X, Y, Z, ox, oy);
+        const bool in = rs_distance(Q, X, Y, Z, ox, oy, a.tau2, d2);
+        v[0] += in ? d2 : a.tau2;
+        v[1] += in ? 1.0 : 0.0;
+    }
+    rs_block_sum<2>(v, sm);
+    cost = v[0];
+    n_in = (int)v[1];
+}
+
+// one pass of the polish over the set in a.mask: v = (sum |r|^2, rows not in front, H upper triangle (21), g (6))
+__device__ __forceinline__ void rs_polish_pass(const RsArgs &a, int lo, int n_use, const double (&E)[12], double *sm, double (&v)[29]) {
+    const double fx = a.K[0], sk = a.K[1], pcx = a.K[2], fy = a.K[4], pcy = a.K[5];
+#pragma unroll
+    for (int k = 0; k < 29; ++k) v[k] = 0.0;
+    for (int k = threadIdx.x; k < n_use; k += RS_THREADS) {
+        if (a.mask[lo + k] == 0) continue;
+        double X, Y, Z, ox, oy;
+        rs_load(a, lo, k, X, Y, Z, ox, oy);
+        const double D0 = (E[0] * X + E[1] * Y) + E[2] * Z, D1 = (E[4] * X + E[5] * Y) + E[6] * Z, D2 = (E[8] * X + E[9] * Y) + E[10] * Z;
+        const double Y0 = D0 + E[3], Y1 = D1 + E[7], Y2 = D2 + E[11];
+        const double nu = fx * Y0 + sk * Y1, nv = fy * Y1;
+        const double ru = (nu / Y2 + pcx) - ox, rv = (nv / Y2 + pcy) - oy;
+        const double a0 = fx / Y2, a1 = sk / Y2, a2 = -((nu / Y2) / Y2), b1 = fy / Y2, b2 = -((nv / Y2) / Y2);
+        const double Ju[6] = {a2 * D1 - a1 * D2, a0 * D2 - a2 * D0, a1 * D0 - a0 * D1, a0, a1, a2};
+        const double Jv[6] = {b2 * D1 - b1 * D2, -(b2 * D0), b1 * D0, 0.0, b1, b2};
+        v[0] += ru * ru + rv * rv;
+        v[1] += (Y2 > 0.0) ? 0.0 : 1.0;
+        int idx = 2;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = i; j < 6; ++j) v[idx++] += Ju[i] * Ju[j] + Jv[i] * Jv[j];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) v[23 + i] += Ju[i] * ru + Jv[i] * rv;
+    }
+    rs_block_sum<29>(v, sm);
+}
+
+// (H + lam diag H) delta = -g by a 6 x 6 Cholesky; false: a pivot that is not positive
+__device__ __forceinline__ bool rs_lm_step(const double (&v)[29], double lam, double (&e)[6]) {
+    double H[6][6], L[6][6], y[6];
+    {
+        int idx = 2;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = i; j < 6; ++j) {
+                H[i][j] = H[j][i] = v[idx];
+                ++idx;
+            }
+    }
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double d = H[j][j] + lam * H[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
+        ok = ok && d > 0.0;
+        const double ljj = sqrt(d);
+        L[j][j] = ljj;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double w = H[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) w -= L[i][k] * L[j][k];
+            L[i][j] = w / ljj;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double w = -v[23 + i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) w -= L[i][k] * y[k];
+        y[i] = w / L[i][i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        double w = y[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; ++k) w -= L[k][i] * e[k];
+        e[i] = w / L[i][i];
+    }
+    return ok;
+}
+
+// R <- cay(w) R, t <- t + dt
+__device__ __forceinline__ void rs_update(const double (&E)[12], const double (&e)[6], double (&N)[12]) {
+    const double a0 = e[0] / 2.0, a1 = e[1] / 2.0, a2 = e[2] / 2.0;
+    const double aa = (a0 * a0 + a1 * a1) + a2 * a2;
+    const double den = 1.0 + aa, dg = 1.0 - aa;
+    const double C[3][3] = {{(dg + 2.0 * (a0 * a0)) / den, (2.0 * (a0 * a1) - 2.0 * a2) / den, (2.0 * (a0 * a2) + 2.0 * a1) / den},
+                            {(2.0 * (a1 * a0) + 2.0 * a2) / den, (dg + 2.0 * (a1 * a1)) / den, (2.0 * (a1 * a2) - 2.0 * a0) / den},
+                            {(2.0 * (a2 * a0) - 2.0 * a1) / den, (2.0 * (a2 * a1) + 2.0 * a0) / den, (dg + 2.0 * (a2 * a2)) / den}};
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) N[4 * r + c] = (C[r][0] * E[c] + C[r][1] * E[4 + c]) + C[r][2] * E[8 + c];
+        N[4 * r + 3] = E[4 * r + 3] + e[3 + r];
+    }
+}
+
+__global__ __launch_bounds__(RS_THREADS) void rs_finish_kernel(RsArgs a) {
+    __shared__ double sm[RS_WAVES * 40];
+    __shared__ double bc[RS_WAVES];
+    __shared__ int bh[RS_WAVES];
+    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const double *nr = a.norm + 8 * (size_t)c;
+    const int n_use = (int)nr[4];
+    const double cx = nr[0], cy = nr[1], cz = nr[2], s = nr[3];
+    int lo, hi;
+    rs_range(a, c, lo, hi);
+    const double nan = __builtin_nan("");
+    int flags = nr[5] > 0.0 ? MM_RESECT_MALFORMED : 0;
+    double E[12], Pr[12];
+    bool prior = a.prior != nullptr;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        E[k] = nan;
+        Pr[k] = prior ? a.prior[12 * (size_t)c + k] : nan;
+    }
+#pragma unroll
+    for (int k = 0; k < 12; ++k) prior = prior && isfinite(Pr[k]);
+    double cost = nan;
+    int n_in = 0, best_h = -1, n_valid = 0, n_polish = 0;
+    bool model = false;
+
+    if (n_use < a.min_rows) {
+        flags |= MM_RESECT_TOO_FEW;
+    } else {
+        // lowest finite cost, ties to the lowest h; and the number of valid hypotheses
+        double c_best = __builtin_huge_val();
+        int h_best = INT32_MAX;
+        double nv[1] = {0.0};
+        for (int h = tid; h < a.n_hyp; h += RS_THREADS) {
+            const double ch = a.cost_h[(size_t)c * a.n_hyp + h];
+            nv[0] += isfinite(a.Eh[((size_t)c * a.n_hyp + h) * 12]) ? 1.0 : 0.0;
+            if (isfinite(ch) && ch < c_best) {
+                c_best = ch;
+                h_best = h;
+            }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const double oc = __shfl_xor(c_best, off, 64);
+            const int oh = __shfl_xor(h_best, off, 64);
+            if (oc < c_best || (oc == c_best && oh < h_best)) {
+                c_best = oc;
+                h_best = oh;
+            }
+        }
+        if (lane == 0) {
+            bc[wave] = c_best;
+            bh[wave] = h_best;
+        }
+        rs_block_sum<1>(nv, sm);      // (its barriers also publish bc / bh)
+        n_valid = (int)nv[0];
+        c_best = bc[0];
+        h_best = bh[0];
+#pragma unroll
+        for (int w = 1; w < RS_WAVES; ++w) {
+            if (bc[w] < c_best || (bc[w] == c_best && bh[w] < h_best)) {
+                c_best = bc[w];
+                h_best = bh[w];
+            }
+        }
+        if (h_best != INT32_MAX) {
+            model = true;
+            best_h = h_best;
+#pragma unroll
+            for (int k = 0; k < 12; ++k) E[k] = a.Eh[((size_t)c * a.n_hyp + h_best) * 12 + k];
+            rs_cost(a, lo, n_use, E, sm, cost, n_in);
+        }
+        if (prior) {      // hypothesis number n_hyp: it loses ties
+            double cp;
+            int np_in;
+            rs_cost(a, lo, n_use, Pr, sm, cp, np_in);
+            if (isfinite(cp) && (!model || cp < cost)) {
+                model = true;
+                best_h = a.n_hyp;
+                cost = cp;
+                n_in = np_in;
+#pragma unroll
+                for (int k = 0; k < 12; ++k) E[k] = Pr[k];
+            }
+        }
+        if (!model) flags |= MM_RESECT_NO_MODEL;
+    }
+
+    if (model) {
+        for (int it = 0; it < a.refit_iters; ++it) {
+            if (n_in < 6) break;      // (uniform: nothing changes any more)
+            double Q[12], acc[40];
+            rs_camera(a, E, Q);
+#pragma unroll
+            for (int k = 0; k < 40; ++k) acc[k] = 0.0;
+            for (int k = tid; k < n_use; k += RS_THREADS) {
+                double X, Y, Z, ox, oy, d2;
+                rs_load(a, lo, k, X, Y, Z, ox, oy);
+                if (rs_distance(Q, X, Y, Z, ox, oy, a.tau2, d2)) rs_accumulate(acc, a, cx, cy, cz, s, X, Y, Z, ox, oy);
+            }
+            rs_block_sum<40>(acc, sm);
+            double En[12], cn;
+            int nn_in;
+            const bool okE = rs_solve(acc, cx, cy, cz, s, En);
+            rs_cost(a, lo, n_use, En, sm, cn, nn_in);
+            if (okE && isfinite(cn) && cn < cost) {
+                cost = cn;
+                n_in = nn_in;
+#pragma unroll
+                for (int k = 0; k < 12; ++k) E[k] = En[k];
+            }
+        }
+        if (a.polish_iters > 0) {
+            // the set: the inliers of the model at entry (each thread writes and later reads its own rows)
+            double Q[12];
+            rs_camera(a, E, Q);
+            for (int k = tid; k < n_use; k += RS_THREADS) {
+                double X, Y, Z, ox, oy, d2;
+                rs_load(a, lo, k, X, Y, Z, ox, oy);
+                a.mask[lo + k] = rs_distance(Q, X, Y, Z, ox, oy, a.tau2, d2) ? 1 : 0;
+            }
+            double Ec[12], v[29], lam = 1e-3;
+#pragma unroll
+            for (int k = 0; k < 12; ++k) Ec[k] = E[k];
+            rs_polish_pass(a, lo, n_use, Ec, sm, v);
+            int accepted = 0;
+            for (int it = 0; it < a.polish_iters; ++it) {
+                double e[6], En[12], vn[29];
+                const bool ok = rs_lm_step(v, lam, e);
+                rs_update(Ec, e, En);
+                rs_polish_pass(a, lo, n_use, En, sm, vn);
+                const bool accept = ok && vn[1] == 0.0 && isfinite(vn[0]) && vn[0] < v[0];
+                if (accept) {
+                    ++accepted;
+#pragma unroll
+                    for (int k = 0; k < 12; ++k) Ec[k] = En[k];
+#pragma unroll
+                    for (int k = 0; k < 29; ++k) v[k] = vn[k];
+                }
+                lam = accept ? fmax(lam / 10.0, 1e-12) : lam * 10.0;
+            }
+            if (accepted > 0) {
+                double cn;
+                int nn_in;
+                bool fin = true;
+#pragma unroll
+                for (int k = 0; k < 12; ++k) fin = fin && isfinite(Ec[k]);
+                rs_cost(a, lo, n_use, Ec, sm, cn, nn_in);
+                if (fin && isfinite(cn) && cn < cost) {
+                    cost = cn;
+                    n_in = nn_in;
+                    n_polish = accepted;
+#pragma unroll
+                    for (int k = 0; k < 12; ++k) E[k] = Ec[k];
+                }
+            }
+        }
+        if (n_in < a.min_inliers) flags |= MM_RESECT_WEAK;
+        // the inliers of the final model (the prepare kernel has zeroed every row of a camera without one)
+        double Q[12];
+        rs_camera(a, E, Q);
+        for (int k = tid; k < n_use; k += RS_THREADS) {
+            double X, Y, Z, ox, oy, d2;
+            rs_load(a, lo, k, X, Y, Z, ox, oy);
+            a.inlier[a.rows[lo + k]] = rs_distance(Q, X, Y, Z, ox, oy, a.tau2, d2) ? 1 : 0;
+        }
+    }
+    if (tid == 0) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) a.ext[12 * (size_t)c + k] = model ? E[k] : Pr[k];      // (an absent prior is NaN)
+        a.cost[c] = cost;
+        int32_t *o = a.info + 6 * (size_t)c;
+        o[0] = flags;
+        o[1] = n_in;
+        o[2] = best_h;
+        o[3] = n_valid;
+        o[4] = n_use;
+        o[5] = n_polish;
+    }
+}
+
+size_t rs_region(size_t bytes) { return mm_align_up(bytes, 256); }
+
+}  // namespace
+
+extern "C" size_t mm_resect_workspace_bytes(int n_cams, int n_hyp, int64_t n_rows) {
+    const size_t nc = n_cams > 0 ? (size_t)n_cams : 0, nh = n_hyp > 0 ? (size_t)n_hyp : 0, nr = n_rows > 0 ? (size_t)n_rows : 0;
+    return rs_region(nc * 8 * sizeof(double)) + rs_region(nc * nh * 12 * sizeof(double)) + rs_region(nc * nh * sizeof(double)) +
+           rs_region(nr * sizeof(int32_t)) + rs_region(nr);
+}
+
+extern "C" int mm_resect_cameras(mm_ctx *ctx, const double *K, const double *X, int64_t P, const double *obs, const int32_t *pi,
+                                 int64_t O, const int32_t *cam_ptr, const int32_t *cam_obs, int64_t n_rows, int n_cams,
+                                 const uint8_t *pt_ok, const double *prior, const mm_resect_params *prm, double *extrinsics,
+                                 double *cost, uint8_t *inlier, int32_t *info, void *ws, size_t ws_bytes) {
+    // every argument is judged before the context is looked at: nothing below this block runs on a bad call
+    if (!prm || !K || n_cams < 0 || P < 0 || O < 0 || n_rows < 0 || P > INT32_MAX || O > INT32_MAX || n_rows > INT32_MAX)
+        return mm_fail(ctx, MM_ERR_ARG, "mm_resect_cameras: bad argument");
+    if (prm->n_hyp < 1 || prm->n_hyp > 4096) return mm_fail(ctx, MM_ERR_ARG, "mm_resect_cameras: n_hyp must be in 1 .. 4096");
+    if (!(prm->threshold_px >= 0.0))      // (negative or NaN)
+        return mm_fail(ctx, MM_ERR_ARG, "mm_resect_cameras: threshold_px must not be negative");
+    if (prm->refit_iters < 0 || prm->refit_iters > 1000 || prm->polish_iters < 0 || prm->polish_iters > 1000 || prm->min_inliers < 0)
+        return mm_fail(ctx, MM_ERR_ARG, "mm_resect_cameras: bad parameter");
+    bool k_ok = K[3] == 0.0 && K[6] == 0.0 && K[7] == 0.0 && K[8] == 1.0 && K[0] != 0.0 && K[4] != 0.0;
+    for (int k = 0; k < 9; ++k) k_ok = k_ok && std::isfinite(K[k]);
+    if (!k_ok)
+        return mm_fail(ctx, MM_ERR_ARG, "mm_resect_cameras: K must be finite and upper triangular with K[8] = 1 and non-zero focal lengths");
+    if (n_cams > 0 && (!cam_ptr || !extrinsics || !cost || !info || !ws))
+        return mm_fail(ctx, MM_ERR_ARG, "mm_resect_cameras: bad argument");
+    if (n_cams > 0 && n_rows > 0 && (!cam_obs || !inlier || (O > 0 && (!obs || !pi)) || (P > 0 && !X)))
+        return mm_fail(ctx, MM_ERR_ARG, "mm_resect_cameras: bad argument");
+    if (n_cams > 0 && ws_bytes < mm_resect_workspace_bytes(n_cams, prm->n_hyp, n_rows))
+        return mm_fail(ctx, MM_ERR_WORKSPACE, "mm_resect_cameras: workspace too small");
+    if (!ctx) return MM_ERR_ARG;
+    if (n_cams == 0) return MM_OK;
+    if (((uintptr_t)ws) & 7) return mm_fail(ctx, MM_ERR_ARG, "mm_resect_cameras: the workspace must be 8-byte aligned");
+    RsArgs a;
+    a.X = X;
+    a.obs = obs;
+    a.pi = pi;
+    a.cam_ptr = cam_ptr;
+    a.cam_obs = cam_obs;
+    a.pt_ok = pt_ok;
+    a.prior = prior;
+    a.P = P;
+    a.O = O;
+    a.n_rows = n_rows;
+    a.n_cams = n_cams;
+    a.n_hyp = prm->n_hyp;
+    a.min_rows = prm->min_rows < 12 ? 12 : prm->min_rows;
+    a.min_inliers = prm->min_inliers;
+    a.refit_iters = prm->refit_iters;
+    a.polish_iters = prm->polish_iters;
+    a.seed = prm->seed;
+    a.cam_base = prm->cam_base;
+    a.tau2 = prm->threshold_px * prm->threshold_px;
+    for (int k = 0; k < 9; ++k) a.K[k] = K[k];
+    const double fx = K[0], sk = K[1], cx = K[2], fy = K[4], cy = K[5];
+    a.Ki[0] = 1.0 / fx;
+    a.Ki[1] = -sk / (fx * fy);
+    a.Ki[2] = (sk * cy - cx * fy) / (fx * fy);
+    a.Ki[3] = 1.0 / fy;
+    a.Ki[4] = -cy / fy;
+    char *w = (char *)ws;
+    a.norm = (double *)w;
+    w += rs_region((size_t)n_cams * 8 * sizeof(double));
+    a.Eh = (double *)w;
+    w += rs_region((size_t)n_cams * a.n_hyp * 12 * sizeof(double));
+    a.cost_h = (double *)w;
+    w += rs_region((size_t)n_cams * a.n_hyp * sizeof(double));
+    a.rows = (int32_t *)w;
+    w += rs_region((size_t)n_rows * sizeof(int32_t));
+    a.mask = (uint8_t *)w;
+    a.ext = extrinsics;
+    a.cost = cost;
+    a.inlier = inlier;
+    a.info = info;
+    const dim3 per_hyp((unsigned)n_cams, (unsigned)((a.n_hyp + 63) / 64));
+    MM_LAUNCH(ctx, "rs_prepare_kernel", rs_prepare_kernel, dim3((unsigned)n_cams), dim3(RS_THREADS), 0, a);
+    MM_LAUNCH(ctx, "rs_hypothesis_kernel", rs_hypothesis_kernel, per_hyp, dim3(64), 0, a);
+    MM_LAUNCH(ctx, "rs_score_kernel", rs_score_kernel, per_hyp, dim3(64), 0, a);
+    MM_LAUNCH(ctx, "rs_finish_kernel", rs_finish_kernel, dim3((unsigned)n_cams), dim3(RS_THREADS), 0, a);
+    return MM_OK;
+}

@@ -214,6 +214,62 @@ def chain_poses(pairs, m, depth, R, t, info, E0=None, min_common=8, ctx=None):
     return ext, scale, rho, cinfo
 
 
+RESECT_TOO_FEW, RESECT_NO_MODEL, RESECT_WEAK, RESECT_MALFORMED = 1, 2, 4, 8      # MM_RESECT_* of include/meatmodeler.h
+
+
+def resect_cameras(K, X, obs, pi, cam_ptr, cam_obs, pt_ok=None, prior=None, n_hyp=256, threshold_px=2.0, min_rows=12,
+                   min_inliers=12, refit_iters=2, polish_iters=8, seed=0, cam_base=0, inlier=None, ctx=None):
+    """Every camera registered against the 3-D points it observes (mm_resect_cameras): K 3 x 3 on the host; X [P, 3] f64, obs
+    [O, 2] f64 pixels, pi [O] i32, the camera CSR cam_ptr [n_cams+1] / cam_obs [n_rows] i32 (what a BADevice carries), optional
+    pt_ok [P] u8 / bool (0: the point is not used) and prior [n_cams, 3, 4] or [n_cams, 12] f64 (a non-finite one counts as
+    absent) -- device tensors
+    -> (extrinsics [n_cams, 3, 4] f64, cost [n_cams] f64, inlier [O] u8 -- written for every usable or malformed row of a camera,
+    zero (or what `inlier` held) elsewhere --, info [n_cams, 6] i32 = (RESECT_* flags, n_inliers, best_h (n_hyp: the prior, -1:
+    none), valid hypotheses, usable rows, accepted polish steps))."""
+    Kh = _host_f64(K, 9, "resect_cameras: K")
+    if not np.isfinite(Kh).all() or Kh[3] != 0 or Kh[6] != 0 or Kh[7] != 0 or Kh[8] != 1 or Kh[0] == 0 or Kh[4] == 0:
+        raise ValueError("resect_cameras: K must be finite, upper triangular with K[2, 2] = 1 and non-zero focal lengths")
+    if not 1 <= int(n_hyp) <= 4096:
+        raise ValueError("resect_cameras: n_hyp must be in 1 .. 4096")
+    if not float(threshold_px) >= 0:
+        raise ValueError("resect_cameras: threshold_px must not be negative")
+    if not 0 <= int(refit_iters) <= 1000 or not 0 <= int(polish_iters) <= 1000 or int(min_inliers) < 0:
+        raise ValueError("resect_cameras: refit_iters and polish_iters must be in 0 .. 1000 and min_inliers not negative")
+    if X.dim() != 2 or X.shape[1] != 3 or obs.dim() != 2 or obs.shape[1] != 2 or tuple(pi.shape) != (obs.shape[0],) \
+            or cam_ptr.dim() != 1 or cam_ptr.shape[0] < 1 or cam_obs.dim() != 1:
+        raise ValueError("resect_cameras: X [P, 3], obs [O, 2], pi [O], cam_ptr [n_cams+1] and cam_obs [n_rows] expected")
+    n_cams, P, O, n_rows = cam_ptr.shape[0] - 1, X.shape[0], obs.shape[0], cam_obs.shape[0]
+    if pt_ok is not None:
+        if tuple(pt_ok.shape) != (P,):
+            raise ValueError("resect_cameras: pt_ok [P] expected")
+        pt_ok = pt_ok.to(torch.uint8).contiguous()
+    if prior is not None:
+        if prior.numel() != 12 * n_cams:
+            raise ValueError("resect_cameras: prior [n_cams, 3, 4] expected")
+        prior = prior.to(torch.float64).contiguous()
+    ctx = ctx or default_context()
+    d = X.device
+    ext = torch.full((n_cams, 3, 4), math.nan, dtype=torch.float64, device=d)
+    cost = torch.full((n_cams,), math.nan, dtype=torch.float64, device=d)
+    info = torch.zeros((n_cams, 6), dtype=torch.int32, device=d)
+    if inlier is None:
+        inlier = torch.zeros(O, dtype=torch.uint8, device=d)
+    elif inlier.dtype != torch.uint8 or tuple(inlier.shape) != (O,) or not inlier.is_contiguous():
+        raise ValueError("resect_cameras: inlier must be a contiguous u8 tensor [O]")
+    if n_cams == 0:
+        return ext, cost, inlier, info
+    assert X.dtype == torch.float64 and obs.dtype == torch.float64
+    prm = _lib.ResectParams(int(n_hyp), int(min_rows), int(min_inliers), int(refit_iters), int(polish_iters), 0,
+                            int(seed) & 0xFFFFFFFF, int(cam_base) & 0xFFFFFFFF, float(threshold_px))
+    wsb = lib.mm_resect_workspace_bytes(n_cams, int(n_hyp), n_rows)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=d)
+    ctx.check(lib.mm_resect_cameras(ctx.h, Kh.ctypes.data_as(_lib.c_f64p), ptr(X.contiguous()), P, ptr(obs.contiguous()),
+                                    ptr(_i32(pi.contiguous())), O, ptr(_i32(cam_ptr.contiguous())), ptr(_i32(cam_obs.contiguous())),
+                                    n_rows, n_cams, ptr(pt_ok), ptr(prior), C.byref(prm), ptr(ext), ptr(cost), ptr(inlier),
+                                    ptr(info), ptr(ws), wsb), "mm_resect_cameras")
+    return ext, cost, inlier, info
+
+
 # ------------------------------------------------------------------------------------------------ ORB
 
 def orb_params(nfeatures, nlevels=8, scale_factor=1.2, edge_threshold=31, fast_threshold=20):

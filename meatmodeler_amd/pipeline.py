@@ -5,7 +5,8 @@ and key points stay in HBM and each stage is a few large launches instead of one
 
 Keyframe gating, calibration and PnP are outside the scope: the caller provides K and one extrinsic
 per frame (the reference gets them from calibrate / poseEstimation / adjustPose, processor.py:422-448) -- or, with
-`run(verify={...}, poses={...})`, K alone: the extrinsics are then recovered from the verified matches.
+`run(verify={...}, poses={...})`, K alone: the extrinsics are then recovered from the verified matches; with
+`run(resect={...})` every frame is registered once more against the triangulated points (a RANSAC resection).
 """
 import ctypes as C
 import queue
@@ -51,6 +52,22 @@ def pose_options(poses):
     if unknown:
         raise ValueError(f"poses takes {', '.join(POSE_KEYS)}; not {sorted(unknown)}")
     return dict(poses)
+
+
+RESECT_KEYS = ("n_hyp", "threshold_px", "min_rows", "min_inliers", "refit_iters", "polish_iters", "seed")
+
+
+def resect_options(resect):
+    """`run(..., resect=)`: None (no resection) or a dict of the parameters of ops.resect_cameras -- the points, the prior,
+    cam_base and ctx are the pipeline's own.  Returns it as a dict; an unknown key raises ValueError."""
+    if resect is None:
+        return None
+    if not isinstance(resect, dict):
+        raise ValueError("resect must be None or a dict of " + ", ".join(RESECT_KEYS))
+    unknown = set(resect) - set(RESECT_KEYS)
+    if unknown:
+        raise ValueError(f"resect takes {', '.join(RESECT_KEYS)}; not {sorted(unknown)}")
+    return dict(resect)
 
 
 class ClipPipeline:
@@ -119,6 +136,26 @@ class ClipPipeline:
         R, t, sigma, depth, info = ops.recover_poses(det["xy"][:n + 1], pairs, m, F, K, ctx=self.ctx, **params)
         ext, scale, rho, cinfo = ops.chain_poses(pairs, m, depth, R, t, info, E0=E0, min_common=min_common, ctx=self.ctx)
         return dict(extrinsics=ext, R=R, t=t, sigma=sigma, info=info, depth=depth, scale=scale, rho=rho, chain_info=cinfo)
+
+    # ------------------------------------------------------------------------------------------- resect
+    def resect(self, K, points, track_ptr, obs_frame, obs_kp, kp_xy_dev, n_frames, pt_ok=None, prior=None, **params):
+        """Every frame registered against the 3-D points of the tracks it observes (ops.resect_cameras): points [T, 3] f64 (one
+        per track, as `triangulate` returns them), the linked tracks as `run` keeps them, pt_ok [T] (0: the track's point is
+        not used), prior [n_frames, 3, 4].  -> dict(extrinsics [n_frames, 3, 4] f64, cost [n_frames], info [n_frames, 6],
+        inliers_per_frame [n_frames] i64, inlier [O] u8 over the observations in track order), device tensors."""
+        d = self.device
+        coords, fi, pi = ops.flatten_tracks(track_ptr, obs_frame, obs_kp, kp_xy_dev, ctx=self.ctx)
+        # the camera CSR of the observations, stable (the order mm_ba_build_index gives)
+        fl = fi.long()
+        cam_obs = torch.argsort(fl, stable=True).to(torch.int32)
+        cam_ptr = torch.zeros(n_frames + 1, dtype=torch.int32, device=d)
+        cam_ptr[1:] = torch.cumsum(torch.bincount(fl, minlength=n_frames)[:n_frames], 0).to(torch.int32)
+        pr = None if prior is None else (prior if torch.is_tensor(prior) else
+                                         torch.as_tensor(np.ascontiguousarray(np.asarray(prior, np.float64)[:, :3, :]))).to(d)
+        ext, cost, inlier, info = ops.resect_cameras(K, points.contiguous(), coords, pi, cam_ptr, cam_obs, pt_ok=pt_ok, prior=pr,
+                                                     ctx=self.ctx, **params)
+        per_frame = torch.zeros(n_frames, dtype=torch.int64, device=d).index_add_(0, fl, inlier.long())
+        return dict(extrinsics=ext, cost=cost, info=info, inliers_per_frame=per_frame, inlier=inlier)
 
     # ------------------------------------------------------------------------------------------- link
     def link(self, kp_count, kp_xy, match_count, matches):
@@ -506,7 +543,7 @@ class ClipPipeline:
 
     # ------------------------------------------------------------------------------------------- whole clip
     def run(self, frames, K, extrinsics=None, ba=True, ftol=1e-4, verbose=0, dist=None, timers=None, max_nfev=None,
-            force_collectives=False, triangulation="two_view", cull=None, verify=None, poses=None):
+            force_collectives=False, triangulation="two_view", cull=None, verify=None, poses=None, resect=None):
         """frames [F,H,W] u8 (device).  With `dist` = torch.distributed (initialised), frames are the FULL clip on
         every rank (synthetic input is generated locally) and the work is sharded as described in parallel.py.
         `max_nfev`: evaluation budget of the adjustment (None = SciPy's default, as adjustPoints).
@@ -527,9 +564,15 @@ class ClipPipeline:
         ops.chain_poses ({} for the defaults; needs `verify`, which supplies each pair's F; one rank only -- the chain needs the
         neighbouring pair's depths across every rank boundary): the extrinsics are recovered from the verified matches and
         K, `extrinsics` may be None, and the result gains `poses` = dict(extrinsics [F,3,4], R, t, sigma, info, scale, rho,
-        chain_info); timer "poses".  The first baseline is the unit of length."""
+        chain_info); timer "poses".  The first baseline is the unit of length.
+        `resect`: None (default) or a dict of the parameters of ops.resect_cameras ({} for the defaults; one rank only): after
+        the triangulation every frame is resected against `points0` (under "multi_view" only against the tracks no test
+        flagged), with the extrinsics in use -- given or recovered -- as the prior, so no frame ends with a higher MSAC cost
+        than it came in with; the tracks are then triangulated again with the new poses and the adjustment starts from those.
+        The result gains `resect` = dict(extrinsics [F,3,4], cost [F], info [F,6], inliers_per_frame [F]); timer "resect"."""
         verify = verify_options(verify)
         poses = pose_options(poses)
+        resect = resect_options(resect)
         if poses is not None and verify is None:
             raise ValueError("poses needs verify (it supplies each pair's fundamental matrix): pass verify={} for the defaults")
         if poses is None and extrinsics is None:
@@ -546,6 +589,8 @@ class ClipPipeline:
         if poses is not None and world > 1:
             raise ValueError("poses is not supported with more than one rank: the chain needs the neighbouring pair's depths "
                              "across every rank boundary")
+        if resect is not None and world > 1:
+            raise ValueError("resect is not supported with more than one rank: every frame needs the whole point table")
         if cull is not None:
             tests = {"max_reproj_px", "min_angle_deg", "min_depth"}
             unknown = set(cull) - tests - {"refine_iters"}
@@ -631,6 +676,21 @@ class ClipPipeline:
         else:
             X = self.triangulate(track_ptr, obs_frame, obs_kp, xy_dev, proj)
         toc("triangulate")
+        resected = None
+        if resect is not None and track_ptr.shape[0] > 1:
+            tic("resect")
+            resected = self.resect(K, X, track_ptr, obs_frame, obs_kp, xy_dev, F,
+                                   pt_ok=(flags == 0) if triangulation == "multi_view" else None, prior=ext, **resect)
+            resected.pop("inlier")
+            ext = resected["extrinsics"].cpu().numpy()
+            toc("resect")
+            proj = np.einsum("ij,fjk->fik", np.asarray(K, float), ext)
+            tic("triangulate")
+            if triangulation == "multi_view":
+                X, quality, flags = self.triangulate_multi_view(track_ptr, obs_frame, obs_kp, xy_dev, proj, **(cull or {}))
+            else:
+                X = self.triangulate(track_ptr, obs_frame, obs_kp, xy_dev, proj)
+            toc("triangulate")
         P, O = track_ptr.shape[0] - 1, obs_frame.shape[0]
         out = dict(det=det, n_tracks=P, n_obs=O, points0=X, track_ptr_dev=track_ptr, obs_frame_dev=obs_frame,
                    obs_kp_dev=obs_kp, xy_dev=xy_dev, match_count=m_h, kp_count=n_h, pairs_local=int(p_hi - p_lo),
@@ -639,6 +699,8 @@ class ClipPipeline:
             out["verify"] = verified
         if recovered is not None:
             out["poses"] = recovered
+        if resected is not None:
+            out["resect"] = resected
         kept = None
         if triangulation == "multi_view":
             out.update(track_quality=quality, track_flags=flags)

@@ -359,6 +359,37 @@ def recoverPose(prev_matches, curr_matches, K, F, **params):
     return int(mask.sum()), R[0].cpu().numpy().reshape(3, 3), t[0].cpu().numpy(), mask
 
 
+def resectCameras(points_3D, points_2D, K, prior=None, **params):
+    """Camera registration against known 3-D points, the robust counterpart of the reference's cv2.solvePnP call
+    (processor.py:175): points_3D / points_2D are per-frame lists of [n_f, 3] object points and [n_f, 2] pixels (row i of one
+    belongs to row i of the other); prior: optional [n, 3, 4] starting poses (a non-finite one counts as absent)
+    -> (extrinsics [n, 3, 4] f64 -- [R|t] per frame, NaN where no pose was found --, masks: per frame the [n_f] bool inliers,
+    info [n, 6] i32 as ops.resect_cameras returns it).  `params` as ops.resect_cameras takes them (n_hyp, threshold_px,
+    min_rows, min_inliers, refit_iters, polish_iters, seed, cam_base)."""
+    if len(points_3D) != len(points_2D):
+        raise ValueError("resectCameras: points_3D and points_2D must have one entry per frame")
+    X3 = [np.asarray(a, np.float64).reshape(-1, 3) for a in points_3D]
+    x2 = [np.asarray(a, np.float64).reshape(-1, 2) for a in points_2D]
+    if any(len(a) != len(b) for a, b in zip(X3, x2)):
+        raise ValueError("resectCameras: a frame's points_3D and points_2D must have the same length")
+    n = len(X3)
+    if n == 0:
+        return np.zeros((0, 3, 4)), [], np.zeros((0, 6), np.int32)
+    dev = default_context().device
+    counts = np.array([len(a) for a in X3], np.int64)
+    cam_ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    total = int(cam_ptr[-1])
+    Xd = torch.as_tensor(np.ascontiguousarray(np.concatenate(X3).reshape(-1, 3))).to(dev)
+    od = torch.as_tensor(np.ascontiguousarray(np.concatenate(x2).reshape(-1, 2))).to(dev)
+    idx = torch.arange(total, dtype=torch.int32, device=dev)
+    pr = None
+    if prior is not None:
+        pr = torch.as_tensor(np.ascontiguousarray(np.asarray(prior, np.float64)[:, :3, :].reshape(n, 12))).to(dev)
+    ext, _, inlier, info = ops.resect_cameras(K, Xd, od, idx, torch.as_tensor(cam_ptr).to(dev), idx, prior=pr, **params)
+    mask = inlier.cpu().numpy().astype(bool)
+    return ext.cpu().numpy(), [mask[cam_ptr[f]:cam_ptr[f + 1]] for f in range(n)], info.cpu().numpy()
+
+
 # ----------------------------------------------------------------------------------------------- pointTracking
 
 def pointTracking(tracks, prev_keyframe_ID, feature_points, keyframe_ID, correspondents):

@@ -1,0 +1,766 @@
+"""CPU: the definition of mm_resect_cameras (include/meatmodeler.h) restated in NumPy, operation for operation, and checked
+against the truth and against the reference's own chessboard data; no device and no OpenCV.
+
+`resect_numpy` follows the header in the order the kernels of csrc/resect.hip take: every sum over the rows of a camera in
+per-thread strides of 256, xor butterflies inside a 64-lane wave and the four waves in order (`block_sum`), the hypothesis
+ranking over the rows ascending, every product-sum associated as the header writes it.  The kernels are built without FMA
+contraction, +, *, / and sqrt are correctly rounded on both sides, so the GPU file may compare integers exactly -- provided
+no decision of a fixture sits on a rounding: the margins asserted in `test_margins_of_the_exact_fixtures`.
+
+Measured here (NumPy, K = [[1500, 0, 960], [0, 1500, 540], [0, 0, 1]], points in a 2-unit cube 5 units away from the camera, the
+world's origin at the camera up to a small random motion):
+  noise-free six-point scenes, worst over 200: |R - R_true| 2.4e-11, |t - t_true| 1.1e-10 (asserted at 1e-9);
+  0.5 px noise, the linear fit alone, rotation error in degrees median / max over 60 scenes:
+  n = 12: 0.33 / 1.27, n = 200: 0.050 / 0.11, n = 2000: 0.013 / 0.032;
+  160 inliers at 0.3 px + 96 uniform outliers, n_hyp 256, tau 2, two refits, six seeds: 160 of 160 kept, 0 of 96 outliers
+  kept, rotation within 0.010 degrees.
+  g6 chessboard frames (planar): every sampled hypothesis invalid, the prior polished in 8 trials lands 7.4e-11 from the recorded
+  `result`, half the summed cost 2.00489 against the recorded 2.0049.
+The translation is t = b / sigma - R c (header): with the algebraically equal (b - A c) / sigma the same RANSAC case keeps 1 of
+160 inliers -- what the polar step removes from a noisy A is then multiplied by the points' distance from the origin.
+"""
+import ctypes as C
+import functools
+import math
+import os
+
+import numpy as np
+import pytest
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+K_SCENE = np.array([[1500.0, 0.0, 960.0], [0.0, 1500.0, 540.0], [0.0, 0.0, 1.0]])
+TOO_FEW, NO_MODEL, WEAK, MALFORMED = 1, 2, 4, 8
+EPS = 2.220446049250313e-16
+UNTOUCHED = 7      # what the inlier bytes hold before a call in these tests
+M32 = np.uint64(0xFFFFFFFF)
+
+
+# ------------------------------------------------------------------------------------------------ the restatement
+
+def pcg(v):
+    v = np.asarray(v, np.uint64) & M32
+    s = (v * np.uint64(747796405) + np.uint64(2891336453)) & M32
+    w = (((s >> ((s >> np.uint64(28)) + np.uint64(4))) ^ s) * np.uint64(277803737)) & M32
+    return ((w >> np.uint64(22)) ^ w) & M32
+
+
+def k_inverse(K):
+    K = np.asarray(K, float).reshape(3, 3)
+    fx, sk, cx, fy, cy = K[0, 0], K[0, 1], K[0, 2], K[1, 1], K[1, 2]
+    return np.array([1.0 / fx, -sk / (fx * fy), (sk * cy - cx * fy) / (fx * fy), 1.0 / fy, -cy / fy])
+
+
+def block_sum(vals):
+    """Sum of the rows of vals [n, N] in the workgroup's order: thread t takes rows t, t + 256, ...; xor butterfly over the 64
+    lanes of a wave; the four waves in order."""
+    vals = np.asarray(vals, float)
+    n, N = vals.shape
+    chunks = max(1, -(-n // 256))
+    pad = np.zeros((chunks * 256, N))
+    pad[:n] = vals
+    acc = np.zeros((256, N))
+    for ch in range(chunks):
+        acc = acc + pad[ch * 256:(ch + 1) * 256]
+    a = acc.reshape(4, 64, N)
+    lane = np.arange(64)
+    for off in (32, 16, 8, 4, 2, 1):
+        a = a + a[:, lane ^ off]
+    return ((a[0, 0] + a[1, 0]) + a[2, 0]) + a[3, 0]
+
+
+def jacobi(G, N):
+    """Cyclic Jacobi on the batch of symmetric matrices G[i][j] (arrays [B]): -> V[i][j]; eigenvalues on G's diagonal."""
+    B = G[0][0].shape
+    V = [[np.ones(B) if r == c else np.zeros(B) for c in range(N)] for r in range(N)]
+    for _ in range(30):
+        rotated = False
+        for p in range(N - 1):
+            for q in range(p + 1, N):
+                apq = G[p][q]
+                do = (np.abs(apq) > EPS * np.sqrt(np.abs(G[p][p] * G[q][q]))) & (apq != 0.0)
+                if not do.any():
+                    continue
+                rotated = True
+                zeta = (G[q][q] - G[p][p]) / (2.0 * apq)
+                tn = np.copysign(1.0, zeta) / (np.abs(zeta) + np.sqrt(1.0 + zeta * zeta))
+                cs = 1.0 / np.sqrt(1.0 + tn * tn)
+                sn = cs * tn
+                for k in range(N):
+                    akp, akq = G[k][p], G[k][q]
+                    G[k][p] = np.where(do, cs * akp - sn * akq, akp)
+                    G[k][q] = np.where(do, sn * akp + cs * akq, akq)
+                    vkp, vkq = V[k][p], V[k][q]
+                    V[k][p] = np.where(do, cs * vkp - sn * vkq, vkp)
+                    V[k][q] = np.where(do, sn * vkp + cs * vkq, vkq)
+                for k in range(N):
+                    apk, aqk = G[p][k], G[q][k]
+                    G[p][k] = np.where(do, cs * apk - sn * aqk, apk)
+                    G[q][k] = np.where(do, sn * apk + cs * aqk, aqk)
+                G[p][q] = np.where(do, 0.0, G[p][q])
+                G[q][p] = np.where(do, 0.0, G[q][p])
+        if not rotated:
+            break
+    return V
+
+
+def row_terms(Ki, c, s, X, obs):
+    """The 40 numbers one row adds to (S, Bu, Bv, C): X [n, 3], obs [n, 2] -> [n, 40]."""
+    x = [s * (X[:, 0] - c[0]), s * (X[:, 1] - c[1]), s * (X[:, 2] - c[2]), np.ones(len(X))]
+    u = (Ki[0] * obs[:, 0] + Ki[1] * obs[:, 1]) + Ki[2]
+    v = Ki[3] * obs[:, 1] + Ki[4]
+    r2 = u * u + v * v
+    out = np.zeros((len(X), 40))
+    k = 0
+    for i in range(4):
+        for j in range(i, 4):
+            w = x[i] * x[j]
+            out[:, k], out[:, 10 + k], out[:, 20 + k], out[:, 30 + k] = w, u * w, v * w, r2 * w
+            k += 1
+    return out
+
+
+def solve(acc, c, s):
+    """The reduced DLT on a batch of sums acc [B, 40] -> (E [B, 12], ok [B])."""
+    acc = np.asarray(acc, float)
+    B = acc.shape[0]
+    S, Bu, Bv, M = ([[None] * 4 for _ in range(4)] for _ in range(4))
+    k = 0
+    for i in range(4):
+        for j in range(i, 4):
+            S[i][j] = S[j][i] = acc[:, k]
+            Bu[i][j] = Bu[j][i] = acc[:, 10 + k]
+            Bv[i][j] = Bv[j][i] = acc[:, 20 + k]
+            M[i][j] = M[j][i] = acc[:, 30 + k]
+            k += 1
+    ok = np.ones(B, bool)
+    L = [[None] * 4 for _ in range(4)]
+    for j in range(4):
+        d = S[j][j]
+        for k in range(j):
+            d = d - L[j][k] * L[j][k]
+        ok &= np.isfinite(d) & (d > 1e-12 * S[j][j])
+        ljj = np.sqrt(d)
+        L[j][j] = ljj
+        for i in range(j + 1, 4):
+            v = S[i][j]
+            for k in range(j):
+                v = v - L[i][k] * L[j][k]
+            L[i][j] = v / ljj
+    Yu, Yv = [[None] * 4 for _ in range(4)], [[None] * 4 for _ in range(4)]
+    for i in range(4):
+        for cc in range(4):
+            vu, vv = Bu[i][cc], Bv[i][cc]
+            for k in range(i):
+                vu = vu - L[i][k] * Yu[k][cc]
+                vv = vv - L[i][k] * Yv[k][cc]
+            Yu[i][cc] = vu / L[i][i]
+            Yv[i][cc] = vv / L[i][i]
+    for i in range(4):
+        for j in range(i, 4):
+            tu = ((Yu[0][i] * Yu[0][j] + Yu[1][i] * Yu[1][j]) + Yu[2][i] * Yu[2][j]) + Yu[3][i] * Yu[3][j]
+            tv = ((Yv[0][i] * Yv[0][j] + Yv[1][i] * Yv[1][j]) + Yv[2][i] * Yv[2][j]) + Yv[3][i] * Yv[3][j]
+            M[i][j] = M[j][i] = (M[i][j] - tu) - tv
+    V4 = jacobi(M, 4)
+    ev = M[0][0]
+    p3 = [V4[r][0] for r in range(4)]
+    for cc in range(1, 4):
+        lower = M[cc][cc] < ev
+        ev = np.where(lower, M[cc][cc], ev)
+        p3 = [np.where(lower, V4[r][cc], p3[r]) for r in range(4)]
+    wu = [((Yu[i][0] * p3[0] + Yu[i][1] * p3[1]) + Yu[i][2] * p3[2]) + Yu[i][3] * p3[3] for i in range(4)]
+    wv = [((Yv[i][0] * p3[0] + Yv[i][1] * p3[1]) + Yv[i][2] * p3[2]) + Yv[i][3] * p3[3] for i in range(4)]
+    p1, p2 = [None] * 4, [None] * 4
+    for i in (3, 2, 1, 0):
+        vu, vv = wu[i], wv[i]
+        for k in range(i + 1, 4):
+            vu = vu - L[k][i] * p1[k]
+            vv = vv - L[k][i] * p2[k]
+        p1[i] = vu / L[i][i]
+        p2[i] = vv / L[i][i]
+    A = [[s * p1[cc] for cc in range(3)], [s * p2[cc] for cc in range(3)], [s * p3[cc] for cc in range(3)]]
+    last = [p1[3], p2[3], p3[3]]
+    b = last
+    det = (A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0])) + \
+        A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0])
+    neg = det < 0.0
+    A = [[np.where(neg, -A[r][cc], A[r][cc]) for cc in range(3)] for r in range(3)]
+    b = [np.where(neg, -b[r], b[r]) for r in range(3)]
+    G = [[(A[0][r] * A[0][cc] + A[1][r] * A[1][cc]) + A[2][r] * A[2][cc] for cc in range(3)] for r in range(3)]
+    V = jacobi(G, 3)
+    dk, sig = [], None
+    for k in range(3):
+        lam = G[k][k]
+        ok &= np.isfinite(lam) & (lam > 0.0)
+        rt = np.sqrt(lam)
+        dk.append(1.0 / rt)
+        sig = rt if k == 0 else sig + rt
+    sig = sig / 3.0
+    W = [[((V[i][0] * dk[0]) * V[j][0] + (V[i][1] * dk[1]) * V[j][1]) + (V[i][2] * dk[2]) * V[j][2] for j in range(3)]
+         for i in range(3)]
+    E = np.zeros((B, 12))
+    for r in range(3):
+        for cc in range(3):
+            E[:, 4 * r + cc] = (A[r][0] * W[0][cc] + A[r][1] * W[1][cc]) + A[r][2] * W[2][cc]
+        E[:, 4 * r + 3] = b[r] / sig - ((E[:, 4 * r] * c[0] + E[:, 4 * r + 1] * c[1]) + E[:, 4 * r + 2] * c[2])
+    ok &= np.isfinite(E).all(axis=1)
+    return E, ok
+
+
+def camera(K, E):
+    """Q = K [R|t] for a batch E [B, 12]."""
+    K = np.asarray(K, float).ravel()
+    Q = np.zeros_like(E)
+    for r in range(3):
+        for cc in range(4):
+            Q[:, 4 * r + cc] = (K[3 * r] * E[:, cc] + K[3 * r + 1] * E[:, 4 + cc]) + K[3 * r + 2] * E[:, 8 + cc]
+    return Q
+
+
+def distance(Q, X, obs, tau2):
+    """Q [B, 12], X [n, 3], obs [n, 2] -> (d2 [B, n], inlier [B, n], y2 [B, n])."""
+    q = [Q[:, k:k + 1] for k in range(12)]
+    x, y, z = X[None, :, 0], X[None, :, 1], X[None, :, 2]
+    y0 = ((q[0] * x + q[1] * y) + q[2] * z) + q[3]
+    y1 = ((q[4] * x + q[5] * y) + q[6] * z) + q[7]
+    y2 = ((q[8] * x + q[9] * y) + q[10] * z) + q[11]
+    ex, ey = y0 / y2 - obs[None, :, 0], y1 / y2 - obs[None, :, 1]
+    d2 = ex * ex + ey * ey
+    return d2, (y2 > 0.0) & np.isfinite(d2) & (d2 <= tau2), y2
+
+
+def polish_pass(K, E, X, obs, sel):
+    """(sum |r|^2, rows not in front, H (21), g (6)) over the rows in sel, in the workgroup's order."""
+    K = np.asarray(K, float).ravel()
+    fx, sk, pcx, fy, pcy = K[0], K[1], K[2], K[4], K[5]
+    x, y, z = X[:, 0], X[:, 1], X[:, 2]
+    D0 = (E[0] * x + E[1] * y) + E[2] * z
+    D1 = (E[4] * x + E[5] * y) + E[6] * z
+    D2 = (E[8] * x + E[9] * y) + E[10] * z
+    Y0, Y1, Y2 = D0 + E[3], D1 + E[7], D2 + E[11]
+    nu, nv = fx * Y0 + sk * Y1, fy * Y1
+    ru, rv = (nu / Y2 + pcx) - obs[:, 0], (nv / Y2 + pcy) - obs[:, 1]
+    a0, a1, a2, b1, b2 = fx / Y2, sk / Y2, -((nu / Y2) / Y2), fy / Y2, -((nv / Y2) / Y2)
+    Ju = [a2 * D1 - a1 * D2, a0 * D2 - a2 * D0, a1 * D0 - a0 * D1, a0, a1, a2]
+    Jv = [b2 * D1 - b1 * D2, -(b2 * D0), b1 * D0, np.zeros(len(X)), b1, b2]
+    t = np.zeros((len(X), 29))
+    t[:, 0] = ru * ru + rv * rv
+    t[:, 1] = np.where(Y2 > 0.0, 0.0, 1.0)
+    idx = 2
+    for i in range(6):
+        for j in range(i, 6):
+            t[:, idx] = Ju[i] * Ju[j] + Jv[i] * Jv[j]
+            idx += 1
+    for i in range(6):
+        t[:, 23 + i] = Ju[i] * ru + Jv[i] * rv
+    return block_sum(np.where(sel[:, None], t, 0.0))
+
+
+def lm_step(v, lam):
+    H = [[None] * 6 for _ in range(6)]
+    idx = 2
+    for i in range(6):
+        for j in range(i, 6):
+            H[i][j] = H[j][i] = np.float64(v[idx])
+            idx += 1
+    L = [[None] * 6 for _ in range(6)]
+    ok = True
+    for j in range(6):
+        d = H[j][j] + lam * H[j][j]
+        for k in range(j):
+            d = d - L[j][k] * L[j][k]
+        ok = ok and bool(d > 0.0)
+        ljj = np.sqrt(d)
+        L[j][j] = ljj
+        for i in range(j + 1, 6):
+            w = H[i][j]
+            for k in range(j):
+                w = w - L[i][k] * L[j][k]
+            L[i][j] = w / ljj
+    yv, e = [None] * 6, [None] * 6
+    for i in range(6):
+        w = -np.float64(v[23 + i])
+        for k in range(i):
+            w = w - L[i][k] * yv[k]
+        yv[i] = w / L[i][i]
+    for i in (5, 4, 3, 2, 1, 0):
+        w = yv[i]
+        for k in range(i + 1, 6):
+            w = w - L[k][i] * e[k]
+        e[i] = w / L[i][i]
+    return ok, e
+
+
+def cayley_update(E, e):
+    a0, a1, a2 = e[0] / 2.0, e[1] / 2.0, e[2] / 2.0
+    aa = (a0 * a0 + a1 * a1) + a2 * a2
+    den, dg = 1.0 + aa, 1.0 - aa
+    Cm = [[(dg + 2.0 * (a0 * a0)) / den, (2.0 * (a0 * a1) - 2.0 * a2) / den, (2.0 * (a0 * a2) + 2.0 * a1) / den],
+          [(2.0 * (a1 * a0) + 2.0 * a2) / den, (dg + 2.0 * (a1 * a1)) / den, (2.0 * (a1 * a2) - 2.0 * a0) / den],
+          [(2.0 * (a2 * a0) - 2.0 * a1) / den, (2.0 * (a2 * a1) + 2.0 * a0) / den, (dg + 2.0 * (a2 * a2)) / den]]
+    N = np.zeros(12)
+    for r in range(3):
+        for cc in range(3):
+            N[4 * r + cc] = (Cm[r][0] * E[cc] + Cm[r][1] * E[4 + cc]) + Cm[r][2] * E[8 + cc]
+        N[4 * r + 3] = E[4 * r + 3] + e[3 + r]
+    return N
+
+
+def rel_gap(a, b):
+    return abs(a - b) / max(abs(a), abs(b), 1e-300)
+
+
+def resect_numpy(K, X, obs, pi, cam_ptr, cam_obs, pt_ok=None, prior=None, n_hyp=256, threshold_px=2.0, min_rows=12,
+                 min_inliers=12, refit_iters=2, polish_iters=8, seed=0, cam_base=0):
+    """-> (extrinsics [n, 3, 4], cost [n], inlier [O] (UNTOUCHED where nothing is written), info [n, 6], margins): margins holds
+    per camera the smallest distance of a row to tau in pixels (px), the smallest |y2| (depth), the relative gap between the
+    best and the second-best hypothesis (best) and the smallest relative gap of an accept / reject decision (decision)."""
+    with np.errstate(all="ignore"):
+        return _resect(np.asarray(K, float), np.asarray(X, float).reshape(-1, 3), np.asarray(obs, float).reshape(-1, 2),
+                       np.asarray(pi), np.asarray(cam_ptr), np.asarray(cam_obs), pt_ok, prior, n_hyp, float(threshold_px),
+                       max(int(min_rows), 12), min_inliers, refit_iters, polish_iters, seed, cam_base)
+
+
+def _resect(K, X, obs, pi, cam_ptr, cam_obs, pt_ok, prior, n_hyp, tau, min_rows, min_inliers, refit_iters, polish_iters, seed,
+            cam_base):
+    n_cams, P, O, n_rows = len(cam_ptr) - 1, len(X), len(obs), len(cam_obs)
+    Ki, tau2 = k_inverse(K), tau * tau
+    ext = np.full((n_cams, 12), np.nan)
+    cost_out = np.full(n_cams, np.nan)
+    inlier = np.full(O, UNTOUCHED, np.uint8)
+    info = np.zeros((n_cams, 6), np.int32)
+    margins = []
+    for c in range(n_cams):
+        mg = dict(px=math.inf, depth=math.inf, best=math.inf, decision=math.inf)
+        margins.append(mg)
+        lo = min(max(int(cam_ptr[c]), 0), n_rows)
+        hi = min(max(int(cam_ptr[c + 1]), lo), n_rows)
+        rows, bad = [], 0
+        for q in range(lo, hi):
+            o = int(cam_obs[q])
+            if not 0 <= o < O:
+                bad += 1
+                continue
+            p = int(pi[o])
+            if not 0 <= p < P or not np.isfinite(obs[o]).all():
+                bad += 1
+                inlier[o] = 0
+                continue
+            if (pt_ok is None or pt_ok[p] != 0) and np.isfinite(X[p]).all():
+                rows.append(o)
+                inlier[o] = 0
+        rows = np.array(rows, np.int64)
+        n_use = len(rows)
+        Xc, oc = X[pi[rows]] if n_use else np.zeros((0, 3)), obs[rows] if n_use else np.zeros((0, 2))
+        cen = block_sum(Xc) / float(n_use)
+        dx, dy, dz = Xc[:, 0] - cen[0], Xc[:, 1] - cen[1], Xc[:, 2] - cen[2]
+        s = 1.7320508075688772 / (block_sum(np.sqrt((dx * dx + dy * dy) + dz * dz)[:, None])[0] / float(n_use))
+        flags = MALFORMED if bad else 0
+        Pr = None
+        if prior is not None and np.isfinite(np.asarray(prior[c], float)).all():
+            Pr = np.asarray(prior[c], float).reshape(12).copy()
+        E, cost, n_in, best_h, n_valid, n_polish = None, math.nan, 0, -1, 0, 0
+
+        def msac(Ecand):
+            d2, inl, y2 = distance(camera(K, Ecand[None]), Xc, oc, tau2)
+            v = block_sum(np.stack([np.where(inl[0], d2[0], tau2), inl[0].astype(float)], axis=1))
+            return v[0], int(v[1]), d2[0], inl[0], y2[0]
+
+        def note(d2, y2):
+            fin = np.isfinite(d2)
+            if fin.any():
+                mg["px"] = min(mg["px"], float(np.abs(np.sqrt(d2[fin]) - tau).min()))
+            mg["depth"] = min(mg["depth"], float(np.abs(y2).min()))
+
+        if n_use < min_rows:
+            flags |= TOO_FEW
+        else:
+            # hypotheses
+            h = np.arange(n_hyp, dtype=np.uint64)
+            base = pcg(pcg(np.uint64(seed & 0xFFFFFFFF) + pcg(np.uint64((cam_base + c) & 0xFFFFFFFF))) + h)
+            picks = np.zeros((n_hyp, 6), np.int64)
+            ok_pick = np.ones(n_hyp, bool)
+            for k in range(6):
+                chosen = np.full(n_hyp, -1, np.int64)
+                for t in range(8):
+                    i = ((pcg(base + np.uint64(8 * k + t)) * np.uint64(n_use)) >> np.uint64(32)).astype(np.int64)
+                    dup = (picks[:, :k] == i[:, None]).any(axis=1)
+                    chosen = np.where((chosen < 0) & ~dup, i, chosen)
+                ok_pick &= chosen >= 0
+                picks[:, k] = np.where(chosen < 0, 0, chosen)
+            acc = np.zeros((n_hyp, 40))
+            for k in range(6):
+                acc = acc + row_terms(Ki, cen, s, Xc[picks[:, k]], oc[picks[:, k]])
+            Eh, okh = solve(acc, cen, s)
+            okh &= ok_pick & bool(np.isfinite(s) and np.isfinite(cen).all())
+            Eh[~okh] = np.nan
+            n_valid = int(okh.sum())
+            d2, inl, _ = distance(camera(K, Eh), Xc, oc, tau2)
+            ch = np.zeros(n_hyp)
+            for j in range(n_use):
+                ch = ch + np.where(inl[:, j], d2[:, j], tau2)
+            ch[~okh] = np.inf
+            fin = np.isfinite(ch)
+            if fin.any():
+                best_h = int(np.flatnonzero(fin & (ch == ch[fin].min()))[0])
+                others = np.sort(ch[fin])
+                if len(others) > 1:
+                    mg["best"] = rel_gap(others[0], others[1])
+                E = Eh[best_h].copy()
+                cost, n_in, d2w, _, y2w = msac(E)
+                note(d2w, y2w)
+            if Pr is not None:
+                cp, np_in, d2p, _, y2p = msac(Pr)
+                if np.isfinite(cp):
+                    if E is not None:
+                        mg["decision"] = min(mg["decision"], rel_gap(cp, cost))
+                    if E is None or cp < cost:
+                        E, cost, n_in, best_h = Pr.copy(), cp, np_in, n_hyp
+                        note(d2p, y2p)
+            if E is None:
+                flags |= NO_MODEL
+        if E is not None:
+            for _ in range(refit_iters):
+                if n_in < 6:
+                    break
+                _, _, _, inl, _ = msac(E)
+                acc = block_sum(np.where(inl[:, None], row_terms(Ki, cen, s, Xc, oc), 0.0))
+                En, okE = solve(acc[None], cen, s)
+                cn, nn_in, d2n, _, y2n = msac(En[0])
+                if okE[0] and np.isfinite(cn) and not np.array_equal(En[0], E):      # (the same rows refit to the same bits)
+                    mg["decision"] = min(mg["decision"], rel_gap(cn, cost))
+                if okE[0] and np.isfinite(cn) and cn < cost:
+                    E, cost, n_in = En[0].copy(), cn, nn_in
+                    note(d2n, y2n)
+            if polish_iters > 0:
+                _, _, _, sel, _ = msac(E)
+                Ec, lam, accepted = E.copy(), 1e-3, 0
+                v = polish_pass(K, Ec, Xc, oc, sel)
+                for _ in range(polish_iters):
+                    ok, e = lm_step(v, lam)
+                    En = cayley_update(Ec, e)
+                    vn = polish_pass(K, En, Xc, oc, sel)
+                    if ok and vn[1] == 0.0 and np.isfinite(vn[0]) and vn[0] != 0.0:
+                        mg["decision"] = min(mg["decision"], rel_gap(vn[0], v[0]))
+                    accept = bool(ok and vn[1] == 0.0 and np.isfinite(vn[0]) and vn[0] < v[0])
+                    if accept:
+                        accepted += 1
+                        Ec, v = En, vn
+                    lam = max(lam / 10.0, 1e-12) if accept else lam * 10.0
+                if accepted > 0:
+                    cn, nn_in, d2n, _, y2n = msac(Ec)
+                    if np.isfinite(Ec).all() and np.isfinite(cn):
+                        mg["decision"] = min(mg["decision"], rel_gap(cn, cost))
+                        if cn < cost:
+                            E, cost, n_in, n_polish = Ec.copy(), cn, nn_in, accepted
+                            note(d2n, y2n)
+            if n_in < min_inliers:
+                flags |= WEAK
+            inlier[rows] = msac(E)[3].astype(np.uint8)
+            ext[c] = E
+            cost_out[c] = cost
+        elif Pr is not None:
+            ext[c] = Pr
+        info[c] = (flags, n_in, best_h, n_valid, n_use, n_polish)
+    return ext.reshape(n_cams, 3, 4), cost_out, inlier, info, margins
+
+
+# ------------------------------------------------------------------------------------------------ scenes
+
+def rodrigues(w):
+    th = np.linalg.norm(w)
+    if th == 0.0:
+        return np.eye(3)
+    k = w / th
+    Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + math.sin(th) * Kx + (1 - math.cos(th)) * Kx @ Kx
+
+
+def rot_err_deg(R, Rt):
+    return math.degrees(math.acos(max(-1.0, min(1.0, (np.trace(R @ Rt.T) - 1.0) / 2.0))))
+
+
+def scene(rng, n_in, n_out=0, noise=0.3, planar=False):
+    """One camera: -> dict(X [n, 3], obs [n, 2], R, t): points in a 2-unit cube 5 units away, inliers first."""
+    R = rodrigues(rng.uniform(-0.3, 0.3, 3))
+    n = n_in + n_out
+    Xcam = np.stack([rng.uniform(-1, 1, n), rng.uniform(-1, 1, n), rng.uniform(4, 6, n)], axis=1)
+    t = rng.uniform(-0.2, 0.2, 3)
+    Xw = (Xcam - t) @ R      # R^T (Xcam - t)
+    if planar:
+        Xw[:, 1] = 0.5
+    Y = Xw @ R.T + t
+    px = Y @ K_SCENE.T
+    obs = px[:, :2] / px[:, 2:3] + noise * rng.standard_normal((n, 2))
+    if n_out:
+        obs[n_in:] = np.stack([rng.uniform(0, 1920, n_out), rng.uniform(0, 1080, n_out)], axis=1)
+    return dict(X=Xw, obs=obs, R=R, t=t)
+
+
+def packed(scenes, shuffle_seed=None):
+    """Scenes -> (X, obs, pi, cam_ptr, cam_obs) with every camera's points in one table."""
+    X = np.concatenate([s["X"] for s in scenes]) if scenes else np.zeros((0, 3))
+    obs = np.concatenate([s["obs"] for s in scenes]) if scenes else np.zeros((0, 2))
+    counts = [len(s["X"]) for s in scenes]
+    cam_ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    pi = np.arange(len(X), dtype=np.int32)
+    cam_obs = np.arange(len(X), dtype=np.int32)
+    if shuffle_seed is not None:      # the rows of a camera in another order than its observations
+        rng = np.random.default_rng(shuffle_seed)
+        for c in range(len(scenes)):
+            rng.shuffle(cam_obs[cam_ptr[c]:cam_ptr[c + 1]])
+    return X, obs, pi, cam_ptr, cam_obs
+
+
+BOUNDARY_ROWS = (0, 5, 6, 11, 12, 13, 63, 64, 65, 255, 256, 257, 300)
+BOUNDARY_HYP = (1, 63, 64, 65, 256)
+HYP_SEED = 2      # sampling key of the n_hyp fixtures (its single hypothesis leaves no row within 0.02 px of tau)
+POLISH = 2      # trial steps of the fixtures that are compared exactly: a converged polish decides on roundings
+
+
+@functools.lru_cache(maxsize=None)
+def boundary_fixture(n):
+    """One camera with n usable rows and three that are not (a masked point, a NaN point, a point that is both)."""
+    rng = np.random.default_rng(1000 + n)
+    sc = scene(rng, n + 3)
+    X, obs, pi, cam_ptr, cam_obs = packed([sc], shuffle_seed=n)
+    pt_ok = np.ones(len(X), np.uint8)
+    pt_ok[[0, 2]] = 0
+    X[[1, 2]] = np.nan
+    return dict(args=(K_SCENE, X, obs, pi, cam_ptr, cam_obs), kw=dict(pt_ok=pt_ok, polish_iters=POLISH), scene=sc)
+
+
+@functools.lru_cache(maxsize=None)
+def five_cameras(with_prior):
+    """192 + 64 and 40 + 24 (inliers + outliers); 64 + 0 with half the points masked by pt_ok; a planar camera (with or without
+    a prior); a camera with a malformed row, a NaN point and a NaN pixel.  Four observations at the end belong to no camera."""
+    rng = np.random.default_rng(7)
+    scs = [scene(rng, 192, 64), scene(rng, 40, 24), scene(rng, 128), scene(rng, 48, planar=True), scene(rng, 80)]
+    X, obs, pi, cam_ptr, cam_obs = packed(scs, shuffle_seed=3)
+    pt_ok = np.ones(len(X) + 4, np.uint8)
+    pt_ok[cam_ptr[2]:cam_ptr[3]:2] = 0
+    X = np.concatenate([X, rng.uniform(-1, 1, (4, 3))])
+    obs = np.concatenate([obs, rng.uniform(0, 1000, (4, 2))])
+    pi = np.concatenate([pi, np.arange(len(X) - 4, len(X), dtype=np.int32)])
+    b = int(cam_ptr[4])
+    cam_obs = cam_obs.copy()
+    row_of = {int(o): q for q, o in enumerate(cam_obs)}
+    cam_obs[row_of[b + 3]] = len(obs) + 5       # an observation index out of range
+    cam_obs[row_of[b + 9]] = -1
+    pi[b + 17] = -2                             # a point index out of range
+    pi[b + 18] = len(X)
+    X[b + 30] = np.nan                          # a NaN point: skipped, no flag
+    obs[b + 41, 1] = np.nan                     # a NaN pixel: malformed
+    prior = None
+    if with_prior:
+        prior = np.full((5, 12), np.nan)
+        Rp = rodrigues(np.array([3e-4, -2e-4, 2.5e-4])) @ scs[3]["R"]
+        prior[3] = np.hstack([Rp, (scs[3]["t"] + np.array([1e-3, -5e-4, 2e-3]))[:, None]]).ravel()
+        prior[1, :11] = 1.0                     # (a prior with a NaN entry counts as absent)
+    return dict(args=(K_SCENE, X, obs, pi, cam_ptr, cam_obs), kw=dict(pt_ok=pt_ok, prior=prior, seed=11, polish_iters=POLISH), scenes=scs)
+
+
+@functools.lru_cache(maxsize=None)
+def five_reference(with_prior):
+    fx = five_cameras(with_prior)
+    return resect_numpy(*fx["args"], **fx["kw"])
+
+
+@functools.lru_cache(maxsize=None)
+def boundary_reference(n, n_hyp=64, seed=0):
+    fx = boundary_fixture(n)
+    return resect_numpy(*fx["args"], n_hyp=n_hyp, seed=seed, **fx["kw"])
+
+
+@functools.lru_cache(maxsize=None)
+def g6_fixture():
+    """Five frames of the 12 chessboard corners, object points as in bundleAdjuster.py:221-223 (planar, y = 0)."""
+    d = np.load(os.path.join(GOLDEN, "g6_adjust_pose.npz"))
+    grid = np.mgrid[0:4, 0:3].T.reshape(-1, 2) * 2
+    X = np.zeros((12, 3))
+    X[:, 0], X[:, 2] = grid[:, 0], grid[:, 1]
+    n = len(d["ext0"])
+    pi = np.tile(np.arange(12, dtype=np.int32), n)
+    cam_ptr = (12 * np.arange(n + 1)).astype(np.int32)
+    cam_obs = np.arange(12 * n, dtype=np.int32)
+    return dict(args=(d["K"], X, d["obs"], pi, cam_ptr, cam_obs), kw=dict(threshold_px=50.0, polish_iters=8, n_hyp=64),
+                ext0=d["ext0"][:, :3, :].reshape(n, 12), result=d["result"][:, :3, :])
+
+
+@functools.lru_cache(maxsize=None)
+def g6_reference(with_prior):
+    fx = g6_fixture()
+    return resect_numpy(*fx["args"], prior=fx["ext0"] if with_prior else None, **fx["kw"])
+
+
+# ------------------------------------------------------------------------------------------------ symbols and sizes
+
+def test_symbols_struct_size_and_workspace_without_a_device():
+    from meatmodeler_amd import _lib, ops
+    assert {"mm_resect_cameras", "mm_resect_workspace_bytes"} <= set(_lib.SIGNATURES)
+    assert C.sizeof(_lib.ResectParams) == 6 * 4 + 2 * 4 + 8      # sizeof(mm_resect_params)
+    assert callable(ops.resect_cameras)
+    assert (ops.RESECT_TOO_FEW, ops.RESECT_NO_MODEL, ops.RESECT_WEAK, ops.RESECT_MALFORMED) == (TOO_FEW, NO_MODEL, WEAK, MALFORMED)
+
+    def up(x):
+        return (x + 255) // 256 * 256
+    for n_cams, n_hyp, n_rows in ((1, 1, 0), (3, 64, 700), (200, 256, 600000), (5, 4096, 13)):
+        want = up(n_cams * 64) + up(n_cams * n_hyp * 96) + up(n_cams * n_hyp * 8) + up(n_rows * 4) + up(n_rows)
+        assert _lib.lib.mm_resect_workspace_bytes(n_cams, n_hyp, n_rows) == want
+    assert _lib.lib.mm_resect_workspace_bytes(0, 256, 0) == 0 and _lib.lib.mm_resect_workspace_bytes(-1, -1, -1) == 0
+    # argument errors come back before any device is needed: no context, null pointers
+    prm = _lib.ResectParams(256, 12, 12, 2, 8, 0, 0, 0, 2.0)
+    Kh = np.ascontiguousarray(K_SCENE.ravel())
+    call = _lib.lib.mm_resect_cameras
+    assert call(None, Kh.ctypes.data_as(_lib.c_f64p), None, 0, None, None, 0, None, None, 0, 1, None, None, C.byref(prm), None, None,
+                None, None, None, 0) == -1
+
+
+# ------------------------------------------------------------------------------------------------ against the truth
+
+def linear_fit(sc):
+    Ki = k_inverse(K_SCENE)
+    X, obs = sc["X"], sc["obs"]
+    cen = X.mean(axis=0)
+    s = math.sqrt(3.0) / np.sqrt(((X - cen) ** 2).sum(axis=1)).mean()
+    with np.errstate(all="ignore"):
+        E, ok = solve(row_terms(Ki, cen, s, X, obs).sum(axis=0)[None], cen, s)
+    return E[0].reshape(3, 4), bool(ok[0])
+
+
+def test_noise_free_six_points_recover_the_pose():
+    rng = np.random.default_rng(5)
+    worst_R = worst_t = 0.0
+    for _ in range(200):
+        sc = scene(rng, 6, noise=0.0)
+        E, ok = linear_fit(sc)
+        assert ok
+        worst_R, worst_t = max(worst_R, np.abs(E[:, :3] - sc["R"]).max()), max(worst_t, np.abs(E[:, 3] - sc["t"]).max())
+    print(f"noise-free six points, worst of 200: |R - R_true| {worst_R:.2e}, |t - t_true| {worst_t:.2e}")
+    assert worst_R < 1e-9 and worst_t < 1e-9
+
+
+@pytest.mark.parametrize("n,med_max,max_max", [(12, 0.65, 2.6), (200, 0.1, 0.22), (2000, 0.026, 0.065)])
+def test_linear_fit_under_half_a_pixel_of_noise(n, med_max, max_max):
+    """Bounds: about twice the figures of the module docstring (60 scenes are a small sample of a heavy-tailed error)."""
+    rng = np.random.default_rng(100 + n)
+    errs = []
+    for _ in range(60):
+        sc = scene(rng, n, noise=0.5)
+        E, ok = linear_fit(sc)
+        assert ok
+        errs.append(rot_err_deg(E[:, :3], sc["R"]))
+    print(f"n = {n}: rotation error median {np.median(errs):.3f} deg, max {max(errs):.3f} deg")
+    assert np.median(errs) < med_max and max(errs) < max_max
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_ransac_keeps_the_inliers_and_drops_the_outliers(seed):
+    sc = scene(np.random.default_rng(50), 160, 96, noise=0.3)
+    X, obs, pi, cam_ptr, cam_obs = packed([sc])
+    ext, cost, inlier, info, _ = resect_numpy(K_SCENE, X, obs, pi, cam_ptr, cam_obs, n_hyp=256, threshold_px=2.0, refit_iters=2,
+                                              seed=seed)
+    err = rot_err_deg(ext[0][:, :3], sc["R"])
+    print(f"seed {seed}: {int(inlier[:160].sum())} of 160 inliers, {int(inlier[160:].sum())} of 96 outliers kept, rotation off by "
+          f"{err:.4f} deg, info {info[0].tolist()}")
+    assert info[0, 0] == 0 and inlier[:160].sum() == 160 and inlier[160:].sum() == 0 and err < 0.04
+    assert info[0, 1] == 160 and info[0, 4] == 256 and 0 <= info[0, 2] < 256
+
+
+# ------------------------------------------------------------------------------------------------ the reference's own data
+
+def test_g6_chessboard_frames_with_the_prior():
+    fx = g6_fixture()
+    ext, cost, inlier, info, _ = g6_reference(True)
+    gap = np.abs(ext - fx["result"]).max()
+    print(f"g6: |polished - result| = {gap:.2e}, half the summed cost {0.5 * cost.sum():.5f}, info {info.tolist()}")
+    assert (info[:, 3] == 0).all() and (info[:, 2] == 64).all()      # every sampled hypothesis invalid; the prior is the model
+    assert (info[:, 0] == 0).all() and (info[:, 1] == 12).all() and (info[:, 4] == 12).all() and (inlier == 1).all()
+    assert gap <= 1e-8
+    assert abs(0.5 * cost.sum() - 2.0049) < 1e-4
+
+
+def test_g6_chessboard_frames_without_a_prior_have_no_model():
+    ext, cost, inlier, info, _ = g6_reference(False)
+    assert (info[:, 0] == NO_MODEL).all() and (info[:, 2] == -1).all() and (info[:, 3] == 0).all() and (info[:, 1] == 0).all()
+    assert np.isnan(ext).all() and np.isnan(cost).all() and (inlier == 0).all()
+
+
+# ------------------------------------------------------------------------------------------------ flags and the prior
+
+def test_five_camera_fixture_is_what_it_says():
+    for with_prior in (False, True):
+        fx = five_cameras(with_prior)
+        ext, cost, inlier, info, _ = five_reference(with_prior)
+        cam_ptr = fx["args"][4]
+        print(f"prior {with_prior}: info {info.tolist()}")
+        assert list(info[:3, 0]) == [0, 0, 0] and list(info[:3, 4]) == [256, 64, 64]
+        assert info[0, 1] >= 190 and info[1, 1] >= 38 and info[2, 1] >= 62
+        assert inlier[192:256].sum() == 0 and inlier[int(cam_ptr[1]) + 40:int(cam_ptr[2])].sum() == 0      # no outlier kept
+        # camera 2: the masked half is untouched
+        lo, hi = int(cam_ptr[2]), int(cam_ptr[3])
+        assert (inlier[lo:hi:2] == UNTOUCHED).all() and (inlier[lo + 1:hi:2] != UNTOUCHED).all()
+        # the planar camera: no valid hypothesis; a model only from a prior
+        assert info[3, 3] == 0 and info[3, 4] == 48
+        if with_prior:
+            assert info[3, 0] == 0 and info[3, 2] == 256 and info[3, 5] > 0 and info[3, 1] >= 46
+            assert rot_err_deg(ext[3][:, :3], fx["scenes"][3]["R"]) < 0.05
+            assert np.array_equal(ext[1], five_reference(False)[0][1])      # the prior with a NaN entry was absent
+        else:
+            assert info[3, 0] == NO_MODEL and np.isnan(ext[3]).all() and (inlier[int(cam_ptr[3]):int(cam_ptr[4])] == 0).all()
+        # the malformed camera: flagged, estimated from the 74 rows that are usable
+        b = int(cam_ptr[4])
+        assert info[4, 0] == MALFORMED and info[4, 4] == 80 - 6 and info[4, 1] >= 72
+        assert list(inlier[[b + 17, b + 18, b + 41]]) == [0, 0, 0] and list(inlier[[b + 3, b + 9, b + 30]]) == [UNTOUCHED] * 3
+        assert (inlier[-4:] == UNTOUCHED).all()
+        for c in (0, 1, 2, 4):
+            assert rot_err_deg(ext[c][:, :3], fx["scenes"][c]["R"]) < 0.3, c
+
+
+def test_the_prior_never_loses_to_a_worse_model_and_loses_ties():
+    fx = boundary_fixture(64)
+    ext, cost, _, info, _ = boundary_reference(64)
+    # the result as a prior: hypothesis best_h has the same or a higher cost, the prior wins only if strictly lower
+    again = resect_numpy(*fx["args"], n_hyp=64, prior=ext.reshape(1, 12), **fx["kw"])
+    assert again[1][0] <= cost[0]
+    # a far-off prior changes nothing
+    off = np.hstack([np.eye(3), np.array([[0.0], [0.0], [50.0]])]).reshape(1, 12)
+    far = resect_numpy(*fx["args"], n_hyp=64, prior=off, **fx["kw"])
+    assert np.array_equal(far[0], ext) and np.array_equal(far[3], info)
+    # too few rows: the prior passes through
+    few = boundary_fixture(11)
+    got = resect_numpy(*few["args"], n_hyp=64, prior=off, **few["kw"])
+    assert got[3][0, 0] == TOO_FEW and np.array_equal(got[0].reshape(1, 12), off) and np.isnan(got[1][0])
+    assert (got[2][np.flatnonzero(got[2] != UNTOUCHED)] == 0).all()
+
+
+def test_rows_of_a_block_equal_the_whole_call_with_cam_base():
+    fx = five_cameras(False)
+    K, X, obs, pi, cam_ptr, cam_obs = fx["args"]
+    whole = five_reference(False)
+    part = resect_numpy(K, X, obs, pi, cam_ptr[1:4], cam_obs, cam_base=1, **fx["kw"])
+    assert np.array_equal(part[0], whole[0][1:3], equal_nan=True) and np.array_equal(part[3], whole[3][1:3])
+
+
+# ------------------------------------------------------------------------------------------------ margins of the exact fixtures
+
+def exact_fixtures():
+    out = [("five", five_reference(False)), ("five+prior", five_reference(True)), ("g6+prior", g6_reference(True)),
+           ("g6", g6_reference(False))]
+    out += [(f"rows={n}", boundary_reference(n)) for n in BOUNDARY_ROWS]
+    out += [(f"n_hyp={h}", boundary_reference(65, h, HYP_SEED)) for h in BOUNDARY_HYP]
+    return out
+
+
+def test_margins_of_the_exact_fixtures():
+    """What makes exact comparison on the GPU legitimate: no row within 0.02 px of tau under the winning, refitted or polished
+    model, every y2 of those models at least 1e-3 from zero, best and second-best hypothesis at least 1e-9 apart relatively,
+    every accept / reject decision at least 1e-9 relatively from a tie."""
+    for name, ref in exact_fixtures():
+        for c, mg in enumerate(ref[4]):
+            print(f"{name} camera {c}: " + ", ".join(f"{k} {v:.3g}" for k, v in mg.items()))
+            assert mg["px"] >= 0.02, (name, c, mg)
+            assert mg["depth"] >= 1e-3, (name, c, mg)
+            assert mg["best"] >= 1e-9, (name, c, mg)
+            # (g6 runs the eight trial steps the issue sets, to convergence: its last trials decide on roundings, so the GPU
+            # file compares its accepted-step count and its pose with a tolerance, and everything else of it exactly)
+            assert mg["decision"] >= 1e-9 or name.startswith("g6"), (name, c, mg)
