@@ -1,0 +1,192 @@
+// The deterministic building blocks that the geometry stages share (verify.hip, pose.hip, resect.hip, triangulate.hip).
+//
+// include/meatmodeler.h states each of them once and lets the later stages refer back ("the integer scheme of
+// mm_verify_matches", "the 3 x 3 cyclic Jacobi of ..."); the stages promise results that repeat bit for bit, so every one of
+// these is a definition, written here once.  Header only, __forceinline__ templates: each is compiled under the flags of
+// the file that includes it (FMA contraction is off for pose.hip and resect.hip, on for verify.hip and triangulate.hip --
+// Makefile), so a stage's bits are those of its own build.  What belongs here: a definition the C header gives once and
+// several stages rely on.  What does not: one stage's model (its score kernel, its solver).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+constexpr double MM_F64_EPS = 2.220446049250313e-16;
+
+// workgroup shape of the mm_block_* helpers: 256 threads, four waves of 64 (callers static_assert their thread count)
+constexpr int MM_BLOCK_THREADS = 256;
+constexpr int MM_BLOCK_WAVES = MM_BLOCK_THREADS / 64;
+
+__host__ __device__ __forceinline__ uint32_t mm_pcg(uint32_t v) {
+    const uint32_t s = v * 747796405u + 2891336453u;
+    const uint32_t w = ((s >> ((s >> 28) + 4u)) ^ s) * 277803737u;
+    return (w >> 22) ^ w;
+}
+
+// K distinct indices in [0, n), integer arithmetic only: pick k is the first of the eight tries pcg(base + 8 k + t) * n >> 32
+// that is not an earlier pick.  false: some pick found all eight tries taken (that pick is 0).
+template <int K>
+__device__ __forceinline__ bool mm_sample_distinct(uint32_t base, int n, int (&pick)[K]) {
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        int chosen = -1;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const uint32_t r = mm_pcg(base + (uint32_t)(8 * k + t));
+            const int i = (int)(((uint64_t)r * (uint64_t)n) >> 32);
+            bool dup = false;
+#pragma unroll
+            for (int e = 0; e < k; ++e) dup = dup || pick[e] == i;
+            if (chosen < 0 && !dup) chosen = i;
+        }
+        ok = ok && chosen >= 0;
+        pick[k] = chosen < 0 ? 0 : chosen;
+    }
+    return ok;
+}
+
+// sum over the workgroup in a fixed order: xor butterfly inside a wave (addition commutes: every lane ends with the same
+// bits), then the waves' sums in wave order.  sm holds MM_BLOCK_WAVES * N doubles.  Every thread of the workgroup calls
+// it; it contains two barriers (the first also guards sm against the previous call's readers); every thread ends with the
+// same bits.
+template <int N>
+__device__ __forceinline__ void mm_block_sum(double (&v)[N], double *sm) {
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) v[i] += __shfl_xor(v[i], off, 64);
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    __syncthreads();
+    if (l == 0) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) sm[w * N + i] = v[i];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = ((sm[i] + sm[N + i]) + sm[2 * N + i]) + sm[3 * N + i];
+}
+
+template <int N>
+__device__ __forceinline__ void mm_identity(double (&V)[N][N]) {
+#pragma unroll
+    for (int r = 0; r < N; ++r)
+#pragma unroll
+        for (int c = 0; c < N; ++c) V[r][c] = (r == c) ? 1.0 : 0.0;
+}
+
+// Two-sided cyclic Jacobi in registers (every index static): the eigenvalues of the symmetric G end up on its diagonal, and
+// V, which the caller sets to the identity, is rotated along: its columns end up as the eigenvectors.  Pairs (p, q)
+// ascending, at most 30 sweeps; a rotation is skipped once |g_pq| <= eps sqrt(|g_pp g_qq|), the criterion that keeps the
+// small eigenvalues of a positive semi-definite matrix accurate relative to themselves.
+// Where V is set matters to the compiler, not to the mathematics: set inside a function (mm_identity) the sweeps are
+// arranged one way, set by loops in the caller's own body another.  verify.hip (FMA contraction on) sets V in its own
+// loop, where it always did; pose.hip and resect.hip (contraction off: one value either way) call mm_identity, and compile
+// to what they compiled to.  tri_tracks_kernel keeps a written-out copy of this loop (see there).
+// The callers then take the column of the smallest diagonal entry, ties to the lowest column; that selection is written
+// out at each call site (as a function here it turned the callers' branches into selects).
+template <int N>
+__device__ __forceinline__ void mm_jacobi(double (&G)[N][N], double (&V)[N][N]) {
+    for (int sweep = 0; sweep < 30; ++sweep) {
+        bool rotated = false;
+#pragma unroll
+        for (int p = 0; p < N - 1; ++p) {
+#pragma unroll
+            for (int q = p + 1; q < N; ++q) {
+                const double apq = G[p][q];
+                if (fabs(apq) > MM_F64_EPS * sqrt(fabs(G[p][p] * G[q][q])) && apq != 0.0) {
+                    rotated = true;
+                    const double zeta = (G[q][q] - G[p][p]) / (2.0 * apq);
+                    const double tn = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                    const double cs = 1.0 / sqrt(1.0 + tn * tn);
+                    const double sn = cs * tn;
+#pragma unroll
+                    for (int k = 0; k < N; ++k) {      // columns p, q of G and of V
+                        const double akp = G[k][p], akq = G[k][q];
+                        G[k][p] = cs * akp - sn * akq;
+                        G[k][q] = sn * akp + cs * akq;
+                        const double vkp = V[k][p], vkq = V[k][q];
+                        V[k][p] = cs * vkp - sn * vkq;
+                        V[k][q] = sn * vkp + cs * vkq;
+                    }
+#pragma unroll
+                    for (int k = 0; k < N; ++k) {      // rows p, q of G
+                        const double apk = G[p][k], aqk = G[q][k];
+                        G[p][k] = cs * apk - sn * aqk;
+                        G[q][k] = sn * apk + cs * aqk;
+                    }
+                    G[p][q] = G[q][p] = 0.0;
+                }
+            }
+        }
+        if (!rotated) break;
+    }
+}
+
+// Argmin over the n hypotheses of one workgroup's item: the lowest finite cost[h], ties to the lowest h (h_best stays
+// INT32_MAX when no cost is finite), and n_valid = the number of h whose probe[h * probe_stride] is finite.  Butterfly
+// inside a wave, then the waves in order through bc / bh (MM_BLOCK_WAVES entries each); sm as for mm_block_sum<1>.  Every
+// thread of the workgroup calls it and ends with the same values.
+__device__ __forceinline__ void mm_block_argmin_finite(const double *cost, int n, const double *probe, int probe_stride, double *bc,
+                                                       int *bh, double *sm, double &c_best, int &h_best, int &n_valid) {
+    c_best = __builtin_huge_val();
+    h_best = INT32_MAX;
+    double nv[1] = {0.0};
+    for (int h = threadIdx.x; h < n; h += MM_BLOCK_THREADS) {
+        const double ch = cost[h];
+        nv[0] += isfinite(probe[(size_t)h * probe_stride]) ? 1.0 : 0.0;
+        if (isfinite(ch) && ch < c_best) {
+            c_best = ch;
+            h_best = h;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double oc = __shfl_xor(c_best, off, 64);
+        const int oh = __shfl_xor(h_best, off, 64);
+        if (oc < c_best || (oc == c_best && oh < h_best)) {
+            c_best = oc;
+            h_best = oh;
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+        bc[threadIdx.x >> 6] = c_best;
+        bh[threadIdx.x >> 6] = h_best;
+    }
+    mm_block_sum<1>(nv, sm);      // (its barriers also publish bc / bh)
+    n_valid = (int)nv[0];
+    c_best = bc[0];
+    h_best = bh[0];
+#pragma unroll
+    for (int w = 1; w < MM_BLOCK_WAVES; ++w) {
+        if (bc[w] < c_best || (bc[w] == c_best && bh[w] < h_best)) {
+            c_best = bc[w];
+            h_best = bh[w];
+        }
+    }
+}
+
+// Order-preserving compaction, one round of MM_BLOCK_THREADS candidates: the slot of this thread's element among the kept
+// ones (ballot, popcount prefix, the waves' counts in wcount[MM_BLOCK_WAVES]), counted from `running`, which advances by
+// the round's total.  Contains two barriers: call it from loops whose trip count is uniform over the workgroup.
+__device__ __forceinline__ int mm_block_compact_slot(bool keep, int &running, int *wcount) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long bal = __ballot(keep);
+    __syncthreads();
+    if (lane == 0) wcount[wave] = __popcll(bal);
+    __syncthreads();
+    int at = running;
+    for (int w = 0; w < wave; ++w) at += wcount[w];
+    at += __popcll(bal & ((1ull << lane) - 1ull));
+    running += wcount[0] + wcount[1] + wcount[2] + wcount[3];
+    return at;
+}
+
+// K^-1 = [[Ki0, Ki1, Ki2], [0, Ki3, Ki4], [0, 0, 1]] of the upper triangular K with K[8] = 1, in closed form (host)
+inline void mm_k_inverse(const double K[9], double Ki[5]) {
+    const double fx = K[0], sk = K[1], cx = K[2], fy = K[4], cy = K[5];
+    Ki[0] = 1.0 / fx;
+    Ki[1] = -sk / (fx * fy);
+    Ki[2] = (sk * cy - cx * fy) / (fx * fy);
+    Ki[3] = 1.0 / fy;
+    Ki[4] = -cy / fy;
+}

@@ -15,12 +15,12 @@
 // every bit, and a product-sum then has one value whatever the compiler makes of its surroundings.  All counts are integers,
 // the only atomics are integer min / add in LDS: a pair's row does not depend on which other pairs share the call.
 #include "mm_common.h"
+#include "mm_geom.h"
 
 namespace {
 
 constexpr int POSE_THREADS = 256;
 constexpr int POSE_WAVES = POSE_THREADS / 64;
-constexpr double POSE_EPS = 2.220446049250313e-16;
 constexpr int CHAIN_MAX_CAP = 8192;
 
 struct PoseArgs {
@@ -34,49 +34,6 @@ struct PoseArgs {
     double *R, *t, *sigma, *depth;
     int32_t *info;
 };
-
-// eigenvectors of the symmetric G in the columns of V, eigenvalues on G's diagonal: the cyclic Jacobi of verify.hip's
-// vfy_rank2, same sweep order and same relative skip test
-__device__ __forceinline__ void pose_jacobi3(double (&G)[3][3], double (&V)[3][3]) {
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) V[r][c] = (r == c) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        bool rotated = false;
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-#pragma unroll
-            for (int q = p + 1; q < 3; ++q) {
-                const double apq = G[p][q];
-                if (fabs(apq) > POSE_EPS * sqrt(fabs(G[p][p] * G[q][q])) && apq != 0.0) {
-                    rotated = true;
-                    const double zeta = (G[q][q] - G[p][p]) / (2.0 * apq);
-                    const double tn = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                    const double cs = 1.0 / sqrt(1.0 + tn * tn);
-                    const double sn = cs * tn;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        const double akp = G[k][p], akq = G[k][q];
-                        G[k][p] = cs * akp - sn * akq;
-                        G[k][q] = sn * akp + cs * akq;
-                        const double vkp = V[k][p], vkq = V[k][q];
-                        V[k][p] = cs * vkp - sn * vkq;
-                        V[k][q] = sn * vkp + cs * vkq;
-                    }
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        const double apk = G[p][k], aqk = G[q][k];
-                        G[p][k] = cs * apk - sn * aqk;
-                        G[q][k] = sn * apk + cs * aqk;
-                    }
-                    G[p][q] = G[q][p] = 0.0;
-                }
-            }
-        }
-        if (!rotated) break;
-    }
-}
 
 struct Vec3 {
     double x, y, z;
@@ -167,7 +124,8 @@ __global__ __launch_bounds__(POSE_THREADS) void pose_pair_kernel(PoseArgs a) {
         for (int r = 0; r < 3; ++r)
 #pragma unroll
             for (int c = 0; c < 3; ++c) G[r][c] = (E[r] * E[c] + E[3 + r] * E[3 + c]) + E[6 + r] * E[6 + c];
-        pose_jacobi3(G, V);
+        mm_identity<3>(V);
+        mm_jacobi<3>(G, V);
         // v3: smallest eigenvalue, v1: largest, ties to the lowest column (selected without a runtime index)
         double lo = G[0][0], hi = G[0][0];
         Vec3 v3 = Vec3{V[0][0], V[1][0], V[2][0]}, v1 = v3;
@@ -487,12 +445,7 @@ extern "C" int mm_recover_poses(mm_ctx *ctx, const double *K, const float *kp_xy
     a.min_front_frac = prm->min_front_frac;
     a.ambiguous_frac = prm->ambiguous_frac;
     for (int k = 0; k < 9; ++k) a.K[k] = K[k];
-    const double fx = K[0], sk = K[1], cx = K[2], fy = K[4], cy = K[5];
-    a.Ki[0] = 1.0 / fx;
-    a.Ki[1] = -sk / (fx * fy);
-    a.Ki[2] = (sk * cy - cx * fy) / (fx * fy);
-    a.Ki[3] = 1.0 / fy;
-    a.Ki[4] = -cy / fy;
+    mm_k_inverse(K, a.Ki);
     a.R = R;
     a.t = t;
     a.sigma = sigma;

@@ -14,19 +14,14 @@
 // and the NumPy restatement of the tests can follow the header operation by operation.  Plain f64 VALU work; sums in an order
 // that depends on the camera alone (per-thread strides, xor butterflies, waves in order), no atomics.
 #include "mm_common.h"
+#include "mm_geom.h"
 
 namespace {
 
 constexpr int RS_THREADS = 256;      // prepare / finish: one workgroup per camera
 constexpr int RS_WAVES = RS_THREADS / 64;
 constexpr int RS_TILE = 256;         // rows per LDS tile of the score kernel
-constexpr double RS_EPS = 2.220446049250313e-16;
-
-__host__ __device__ __forceinline__ uint32_t rs_pcg(uint32_t v) {
-    const uint32_t s = v * 747796405u + 2891336453u;
-    const uint32_t w = ((s >> ((s >> 28) + 4u)) ^ s) * 277803737u;
-    return (w >> 22) ^ w;
-}
+static_assert(RS_THREADS == MM_BLOCK_THREADS, "the mm_block_* helpers are written for this workgroup");
 
 struct RsArgs {
     const double *X, *obs;
@@ -67,69 +62,6 @@ __device__ __forceinline__ void rs_load(const RsArgs &a, int lo, int k, double &
     Z = a.X[3 * (size_t)p + 2];
     ox = a.obs[2 * (size_t)o];
     oy = a.obs[2 * (size_t)o + 1];
-}
-
-// sum over the workgroup in a fixed order: xor butterfly inside a wave, then the waves' sums in wave order (verify.hip's
-// vfy_block_sum).  sm holds RS_WAVES * N doubles.  Every thread of the workgroup calls it and ends with the same bits.
-template <int N>
-__device__ __forceinline__ void rs_block_sum(double (&v)[N], double *sm) {
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v[i] += __shfl_xor(v[i], off, 64);
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    __syncthreads();
-    if (l == 0) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) sm[w * N + i] = v[i];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = ((sm[i] + sm[N + i]) + sm[2 * N + i]) + sm[3 * N + i];
-}
-
-// eigenvectors of the symmetric G in the columns of V, eigenvalues on G's diagonal: the cyclic Jacobi of verify.hip's
-// vfy_rank2 / pose.hip's pose_jacobi3 (a copy: those files compile to what they compiled to), for N = 3 and N = 4
-template <int N>
-__device__ __forceinline__ void rs_jacobi(double (&G)[N][N], double (&V)[N][N]) {
-#pragma unroll
-    for (int r = 0; r < N; ++r)
-#pragma unroll
-        for (int c = 0; c < N; ++c) V[r][c] = (r == c) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        bool rotated = false;
-#pragma unroll
-        for (int p = 0; p < N - 1; ++p) {
-#pragma unroll
-            for (int q = p + 1; q < N; ++q) {
-                const double apq = G[p][q];
-                if (fabs(apq) > RS_EPS * sqrt(fabs(G[p][p] * G[q][q])) && apq != 0.0) {
-                    rotated = true;
-                    const double zeta = (G[q][q] - G[p][p]) / (2.0 * apq);
-                    const double tn = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                    const double cs = 1.0 / sqrt(1.0 + tn * tn);
-                    const double sn = cs * tn;
-#pragma unroll
-                    for (int k = 0; k < N; ++k) {
-                        const double akp = G[k][p], akq = G[k][q];
-                        G[k][p] = cs * akp - sn * akq;
-                        G[k][q] = sn * akp + cs * akq;
-                        const double vkp = V[k][p], vkq = V[k][q];
-                        V[k][p] = cs * vkp - sn * vkq;
-                        V[k][q] = sn * vkp + cs * vkq;
-                    }
-#pragma unroll
-                    for (int k = 0; k < N; ++k) {
-                        const double apk = G[p][k], aqk = G[q][k];
-                        G[p][k] = cs * apk - sn * aqk;
-                        G[q][k] = sn * apk + cs * aqk;
-                    }
-                    G[p][q] = G[q][p] = 0.0;
-                }
-            }
-        }
-        if (!rotated) break;
-    }
 }
 
 // one row into the 40 sums: S, Bu, Bv, C, each the upper triangle of a 4 x 4, row-major
@@ -209,7 +141,8 @@ __device__ __forceinline__ bool rs_solve(const double (&acc)[40], double cx, dou
             M[i][j] = M[j][i] = (M[i][j] - tu) - tv;
         }
     double V4[4][4];
-    rs_jacobi<4>(M, V4);
+    mm_identity<4>(V4);
+    mm_jacobi<4>(M, V4);
     double ev = M[0][0], p3[4] = {V4[0][0], V4[1][0], V4[2][0], V4[3][0]};      // smallest eigenvalue, ties to the lowest column
 #pragma unroll
     for (int c = 1; c < 4; ++c) {
@@ -265,7 +198,8 @@ __device__ __forceinline__ bool rs_solve(const double (&acc)[40], double cx, dou
     for (int r = 0; r < 3; ++r)
 #pragma unroll
         for (int c = 0; c < 3; ++c) G[r][c] = (A[0][r] * A[0][c] + A[1][r] * A[1][c]) + A[2][r] * A[2][c];
-    rs_jacobi<3>(G, V);
+    mm_identity<3>(V);
+    mm_jacobi<3>(G, V);
     double dk[3], sig = 0.0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -336,15 +270,8 @@ __global__ __launch_bounds__(RS_THREADS) void rs_prepare_kernel(RsArgs a) {
             }
             bad += mal ? 1 : 0;
         }
-        const unsigned long long bal = __ballot(use);
-        __syncthreads();
-        if (lane == 0) wcount[wave] = __popcll(bal);
-        __syncthreads();
-        int at = n_use;
-        for (int w = 0; w < wave; ++w) at += wcount[w];
-        at += __popcll(bal & ((1ull << lane) - 1ull));
+        const int at = mm_block_compact_slot(use, n_use, wcount);
         if (use) a.rows[lo + at] = o;
-        n_use += wcount[0] + wcount[1] + wcount[2] + wcount[3];
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) bad += __shfl_xor(bad, off, 64);
@@ -359,7 +286,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_prepare_kernel(RsArgs a) {
         s3[1] += Y;
         s3[2] += Z;
     }
-    rs_block_sum<3>(s3, sm);
+    mm_block_sum<3>(s3, sm);
     const double n = (double)n_use, cx = s3[0] / n, cy = s3[1] / n, cz = s3[2] / n;
     double dd[1] = {0.0};
     for (int k = tid; k < n_use; k += RS_THREADS) {
@@ -367,7 +294,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_prepare_kernel(RsArgs a) {
         rs_load(a, lo, k, X, Y, Z, ox, oy);
         dd[0] += sqrt(((X - cx) * (X - cx) + (Y - cy) * (Y - cy)) + (Z - cz) * (Z - cz));
     }
-    rs_block_sum<1>(dd, sm);
+    mm_block_sum<1>(dd, sm);
     if (tid == 0) {
         double *o = a.norm + 8 * (size_t)c;
         o[0] = cx;
@@ -393,23 +320,9 @@ __global__ __launch_bounds__(64) void rs_hypothesis_kernel(RsArgs a) {
     const double cx = nr[0], cy = nr[1], cz = nr[2], s = nr[3];
     bool ok = isfinite(s) && isfinite(cx) && isfinite(cy) && isfinite(cz);
     // six distinct rows, integer arithmetic only
-    const uint32_t base = rs_pcg(rs_pcg(a.seed + rs_pcg(a.cam_base + (uint32_t)c)) + (uint32_t)h);
+    const uint32_t base = mm_pcg(mm_pcg(a.seed + mm_pcg(a.cam_base + (uint32_t)c)) + (uint32_t)h);
     int pick[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        int chosen = -1;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const uint32_t r = rs_pcg(base + (uint32_t)(8 * k + t));
-            const int i = (int)(((uint64_t)r * (uint64_t)n_use) >> 32);
-            bool dup = false;
-#pragma unroll
-            for (int e = 0; e < k; ++e) dup = dup || pick[e] == i;
-            if (chosen < 0 && !dup) chosen = i;
-        }
-        ok = ok && chosen >= 0;
-        pick[k] = chosen < 0 ? 0 : chosen;
-    }
+    ok = mm_sample_distinct<6>(base, n_use, pick) && ok;
     double acc[40];
 #pragma unroll
     for (int k = 0; k < 40; ++k) acc[k] = 0.0;
@@ -478,7 +391,7 @@ __device__ __forceinline__ void rs_cost(const RsArgs &a, int lo, int n_use, cons
         v[0] += in ? d2 : a.tau2;
         v[1] += in ? 1.0 : 0.0;
     }
-    rs_block_sum<2>(v, sm);
+    mm_block_sum<2>(v, sm);
     cost = v[0];
     n_in = (int)v[1];
 }
@@ -509,7 +422,7 @@ __device__ __forceinline__ void rs_polish_pass(const RsArgs &a, int lo, int n_us
 #pragma unroll
         for (int i = 0; i < 6; ++i) v[23 + i] += Ju[i] * ru + Jv[i] * rv;
     }
-    rs_block_sum<29>(v, sm);
+    mm_block_sum<29>(v, sm);
 }
 
 // (H + lam diag H) delta = -g by a 6 x 6 Cholesky; false: a pivot that is not positive
@@ -579,7 +492,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_finish_kernel(RsArgs a) {
     __shared__ double sm[RS_WAVES * 40];
     __shared__ double bc[RS_WAVES];
     __shared__ int bh[RS_WAVES];
-    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c = blockIdx.x, tid = threadIdx.x;
     const double *nr = a.norm + 8 * (size_t)c;
     const int n_use = (int)nr[4];
     const double cx = nr[0], cy = nr[1], cz = nr[2], s = nr[3];
@@ -604,41 +517,10 @@ __global__ __launch_bounds__(RS_THREADS) void rs_finish_kernel(RsArgs a) {
         flags |= MM_RESECT_TOO_FEW;
     } else {
         // lowest finite cost, ties to the lowest h; and the number of valid hypotheses
-        double c_best = __builtin_huge_val();
-        int h_best = INT32_MAX;
-        double nv[1] = {0.0};
-        for (int h = tid; h < a.n_hyp; h += RS_THREADS) {
-            const double ch = a.cost_h[(size_t)c * a.n_hyp + h];
-            nv[0] += isfinite(a.Eh[((size_t)c * a.n_hyp + h) * 12]) ? 1.0 : 0.0;
-            if (isfinite(ch) && ch < c_best) {
-                c_best = ch;
-                h_best = h;
-            }
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const double oc = __shfl_xor(c_best, off, 64);
-            const int oh = __shfl_xor(h_best, off, 64);
-            if (oc < c_best || (oc == c_best && oh < h_best)) {
-                c_best = oc;
-                h_best = oh;
-            }
-        }
-        if (lane == 0) {
-            bc[wave] = c_best;
-            bh[wave] = h_best;
-        }
-        rs_block_sum<1>(nv, sm);      // (its barriers also publish bc / bh)
-        n_valid = (int)nv[0];
-        c_best = bc[0];
-        h_best = bh[0];
-#pragma unroll
-        for (int w = 1; w < RS_WAVES; ++w) {
-            if (bc[w] < c_best || (bc[w] == c_best && bh[w] < h_best)) {
-                c_best = bc[w];
-                h_best = bh[w];
-            }
-        }
+        double c_best;
+        int h_best;
+        mm_block_argmin_finite(a.cost_h + (size_t)c * a.n_hyp, a.n_hyp, a.Eh + (size_t)c * a.n_hyp * 12, 12, bc, bh, sm, c_best, h_best,
+                               n_valid);
         if (h_best != INT32_MAX) {
             model = true;
             best_h = h_best;
@@ -674,7 +556,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_finish_kernel(RsArgs a) {
                 rs_load(a, lo, k, X, Y, Z, ox, oy);
                 if (rs_distance(Q, X, Y, Z, ox, oy, a.tau2, d2)) rs_accumulate(acc, a, cx, cy, cz, s, X, Y, Z, ox, oy);
             }
-            rs_block_sum<40>(acc, sm);
+            mm_block_sum<40>(acc, sm);
             double En[12], cn;
             int nn_in;
             const bool okE = rs_solve(acc, cx, cy, cz, s, En);
@@ -811,12 +693,7 @@ extern "C" int mm_resect_cameras(mm_ctx *ctx, const double *K, const double *X, 
     a.cam_base = prm->cam_base;
     a.tau2 = prm->threshold_px * prm->threshold_px;
     for (int k = 0; k < 9; ++k) a.K[k] = K[k];
-    const double fx = K[0], sk = K[1], cx = K[2], fy = K[4], cy = K[5];
-    a.Ki[0] = 1.0 / fx;
-    a.Ki[1] = -sk / (fx * fy);
-    a.Ki[2] = (sk * cy - cx * fy) / (fx * fy);
-    a.Ki[3] = 1.0 / fy;
-    a.Ki[4] = -cy / fy;
+    mm_k_inverse(K, a.Ki);
     char *w = (char *)ws;
     a.norm = (double *)w;
     w += rs_region((size_t)n_cams * 8 * sizeof(double));

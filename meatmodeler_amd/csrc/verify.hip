@@ -12,19 +12,14 @@
 // Plain f64 VALU work; sums in an order that depends on the pair alone (per-thread strides, xor butterflies, waves in order),
 // no atomics: a pair's row repeats bit for bit whatever else shares the call.
 #include "mm_common.h"
+#include "mm_geom.h"
 
 namespace {
 
 constexpr int VFY_THREADS = 256;      // normalise / refit: one workgroup per pair
 constexpr int VFY_WAVES = VFY_THREADS / 64;
 constexpr int VFY_TILE = 256;         // matches per LDS tile of the score kernel
-constexpr double VFY_EPS = 2.220446049250313e-16;
-
-__host__ __device__ __forceinline__ uint32_t vfy_pcg(uint32_t v) {
-    const uint32_t s = v * 747796405u + 2891336453u;
-    const uint32_t w = ((s >> ((s >> 28) + 4u)) ^ s) * 277803737u;
-    return (w >> 22) ^ w;
-}
+static_assert(VFY_THREADS == MM_BLOCK_THREADS, "the mm_block_* helpers are written for this workgroup");
 
 struct VfyArgs {
     const float *kp_xy;
@@ -67,25 +62,6 @@ __device__ __forceinline__ double vfy_sampson(const double (&F)[9], double x, do
 }
 __device__ __forceinline__ bool vfy_inlier(double d2, double tau2) { return isfinite(d2) && d2 <= tau2; }
 
-// sum over the workgroup in a fixed order: xor butterfly inside a wave (addition commutes: every lane ends with the same
-// bits), then the waves' sums in wave order.  sm holds VFY_WAVES * N doubles.  Every thread of the workgroup calls it.
-template <int N>
-__device__ __forceinline__ void vfy_block_sum(double (&v)[N], double *sm) {
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v[i] += __shfl_xor(v[i], off, 64);
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    __syncthreads();
-    if (l == 0) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) sm[w * N + i] = v[i];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = ((sm[i] + sm[N + i]) + sm[2 * N + i]) + sm[3 * N + i];
-}
-
 // F^ <- F^ - (F^ v3) v3^T, v3 the eigenvector of the smallest eigenvalue of F^^T F^ (3 x 3 cyclic Jacobi in registers)
 __device__ __forceinline__ void vfy_rank2(double (&F)[9]) {
     double G[3][3], V[3][3];
@@ -94,43 +70,10 @@ __device__ __forceinline__ void vfy_rank2(double (&F)[9]) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             G[r][c] = F[r] * F[c] + F[3 + r] * F[3 + c] + F[6 + r] * F[6 + c];
-            V[r][c] = (r == c) ? 1.0 : 0.0;
+            V[r][c] = (r == c) ? 1.0 : 0.0;      // (here, not by mm_identity: see mm_jacobi)
         }
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        bool rotated = false;
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-#pragma unroll
-            for (int q = p + 1; q < 3; ++q) {
-                const double apq = G[p][q];
-                if (fabs(apq) > VFY_EPS * sqrt(fabs(G[p][p] * G[q][q])) && apq != 0.0) {
-                    rotated = true;
-                    const double zeta = (G[q][q] - G[p][p]) / (2.0 * apq);
-                    const double tn = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                    const double cs = 1.0 / sqrt(1.0 + tn * tn);
-                    const double sn = cs * tn;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        const double akp = G[k][p], akq = G[k][q];
-                        G[k][p] = cs * akp - sn * akq;
-                        G[k][q] = sn * akp + cs * akq;
-                        const double vkp = V[k][p], vkq = V[k][q];
-                        V[k][p] = cs * vkp - sn * vkq;
-                        V[k][q] = sn * vkp + cs * vkq;
-                    }
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        const double apk = G[p][k], aqk = G[q][k];
-                        G[p][k] = cs * apk - sn * aqk;
-                        G[q][k] = sn * apk + cs * aqk;
-                    }
-                    G[p][q] = G[q][p] = 0.0;
-                }
-            }
-        }
-        if (!rotated) break;
-    }
-    double best = G[0][0], v0 = V[0][0], v1 = V[1][0], v2 = V[2][0];
+    mm_jacobi<3>(G, V);
+    double best = G[0][0], v0 = V[0][0], v1 = V[1][0], v2 = V[2][0];      // smallest eigenvalue, ties to the lowest column
 #pragma unroll
     for (int c = 1; c < 3; ++c) {
         if (G[c][c] < best) {
@@ -194,7 +137,7 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_normalise_kernel(VfyArgs a) {
             s5[4] += yp;
         }
     }
-    vfy_block_sum<5>(s5, sm);
+    mm_block_sum<5>(s5, sm);
     const double n = s5[0], cx = s5[1] / n, cy = s5[2] / n, cx2 = s5[3] / n, cy2 = s5[4] / n;
     double d2[2] = {0.0, 0.0};
     for (int j = tid; j < mm; j += VFY_THREADS) {
@@ -204,7 +147,7 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_normalise_kernel(VfyArgs a) {
             d2[1] += sqrt((xp - cx2) * (xp - cx2) + (yp - cy2) * (yp - cy2));
         }
     }
-    vfy_block_sum<2>(d2, sm);
+    mm_block_sum<2>(d2, sm);
     if (tid == 0) {
         double *o = a.norm + 8 * (size_t)p;
         o[0] = cx;
@@ -228,23 +171,9 @@ __global__ __launch_bounds__(64) void vfy_hypothesis_kernel(VfyArgs a) {
     const double cx = nr[0], cy = nr[1], s = nr[2], cx2 = nr[3], cy2 = nr[4], s2 = nr[5];
     bool ok = isfinite(s) && isfinite(s2);
     // eight distinct match indices, integer arithmetic only
-    const uint32_t base = vfy_pcg(vfy_pcg(a.seed + vfy_pcg(a.pair_base + (uint32_t)p)) + (uint32_t)h);
+    const uint32_t base = mm_pcg(mm_pcg(a.seed + mm_pcg(a.pair_base + (uint32_t)p)) + (uint32_t)h);
     int pick[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        int chosen = -1;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const uint32_t r = vfy_pcg(base + (uint32_t)(8 * k + t));
-            const int i = (int)(((uint64_t)r * (uint64_t)mm) >> 32);
-            bool dup = false;
-#pragma unroll
-            for (int e = 0; e < k; ++e) dup = dup || pick[e] == i;
-            if (chosen < 0 && !dup) chosen = i;
-        }
-        ok = ok && chosen >= 0;
-        pick[k] = chosen < 0 ? 0 : chosen;
-    }
+    ok = mm_sample_distinct<8>(base, mm, pick) && ok;
     double A[8][9];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -382,7 +311,7 @@ __device__ __forceinline__ void vfy_cost(const VfyArgs &a, int p, int mm, const 
         v[0] += in ? d2 : a.tau2;
         v[1] += in ? 1.0 : 0.0;
     }
-    vfy_block_sum<2>(v, sm);
+    mm_block_sum<2>(v, sm);
     cost = v[0];
     n_in = (int)v[1];
 }
@@ -394,7 +323,7 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_refit_kernel(VfyArgs a, int32
     __shared__ double M[9][9], V[9][9];
     __shared__ double bc[VFY_WAVES];
     __shared__ int bh[VFY_WAVES], wcount[VFY_WAVES];
-    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int p = blockIdx.x, tid = threadIdx.x;
     const int mm = vfy_count(a, p);
     const double nan = __builtin_nan("");
     int flags = a.norm[8 * (size_t)p + 6] > 0.0 ? MM_VERIFY_MALFORMED : 0;
@@ -409,41 +338,10 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_refit_kernel(VfyArgs a, int32
         flags |= MM_VERIFY_TOO_FEW;
     } else {
         // lowest finite cost, ties to the lowest h; and the number of valid hypotheses
-        double c_best = __builtin_huge_val();
-        int h_best = INT32_MAX;
-        double nv[1] = {0.0};
-        for (int h = tid; h < a.n_hyp; h += VFY_THREADS) {
-            const double c = a.cost_h[(size_t)p * a.n_hyp + h];
-            nv[0] += isfinite(a.Fh[((size_t)p * a.n_hyp + h) * 9]) ? 1.0 : 0.0;
-            if (isfinite(c) && c < c_best) {
-                c_best = c;
-                h_best = h;
-            }
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const double oc = __shfl_xor(c_best, off, 64);
-            const int oh = __shfl_xor(h_best, off, 64);
-            if (oc < c_best || (oc == c_best && oh < h_best)) {
-                c_best = oc;
-                h_best = oh;
-            }
-        }
-        if (lane == 0) {
-            bc[wave] = c_best;
-            bh[wave] = h_best;
-        }
-        vfy_block_sum<1>(nv, sm);      // (its barriers also publish bc / bh)
-        n_valid = (int)nv[0];
-        c_best = bc[0];
-        h_best = bh[0];
-#pragma unroll
-        for (int w = 1; w < VFY_WAVES; ++w) {
-            if (bc[w] < c_best || (bc[w] == c_best && bh[w] < h_best)) {
-                c_best = bc[w];
-                h_best = bh[w];
-            }
-        }
+        double c_best;
+        int h_best;
+        mm_block_argmin_finite(a.cost_h + (size_t)p * a.n_hyp, a.n_hyp, a.Fh + (size_t)p * a.n_hyp * 9, 9, bc, bh, sm, c_best, h_best,
+                               n_valid);
         if (h_best == INT32_MAX) {
             flags |= MM_VERIFY_NO_MODEL;
         } else {
@@ -471,7 +369,7 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_refit_kernel(VfyArgs a, int32
                     s5[4] += yp;
                 }
             }
-            vfy_block_sum<5>(s5, sm);
+            mm_block_sum<5>(s5, sm);
             const double n = s5[0], cx = s5[1] / n, cy = s5[2] / n, cx2 = s5[3] / n, cy2 = s5[4] / n;
             double dd[2] = {0.0, 0.0};
             for (int j = tid; j < mm; j += VFY_THREADS) {
@@ -482,7 +380,7 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_refit_kernel(VfyArgs a, int32
                     dd[1] += sqrt((xp - cx2) * (xp - cx2) + (yp - cy2) * (yp - cy2));
                 }
             }
-            vfy_block_sum<2>(dd, sm);
+            mm_block_sum<2>(dd, sm);
             const double s = 1.4142135623730951 / (dd[0] / n), s2 = 1.4142135623730951 / (dd[1] / n);
             // M = A^T A over the inliers: 45 sums (upper triangle, row-major)
             double acc[45];
@@ -504,7 +402,7 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_refit_kernel(VfyArgs a, int32
                         for (int c = i; c < 9; ++c) acc[k++] += r[i] * r[c];
                 }
             }
-            vfy_block_sum<45>(acc, sm);
+            mm_block_sum<45>(acc, sm);
             __syncthreads();
             if (tid == 0) {
                 int k = 0;
@@ -526,7 +424,7 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_refit_kernel(VfyArgs a, int32
                 for (int pp = 0; pp < 8; ++pp) {
                     for (int q = pp + 1; q < 9; ++q) {
                         const double apq = M[pp][q], app = M[pp][pp], aqq = M[q][q];
-                        if (fabs(apq) > VFY_EPS * sqrt(fabs(app * aqq)) && apq != 0.0) {      // (uniform)
+                        if (fabs(apq) > MM_F64_EPS * sqrt(fabs(app * aqq)) && apq != 0.0) {      // (uniform)
                             rotated = true;
                             const double zeta = (aqq - app) / (2.0 * apq);
                             const double tn = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
@@ -598,15 +496,8 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_refit_kernel(VfyArgs a, int32
                     keep = vfy_inlier(vfy_sampson(F, x, y, xp, yp), a.tau2);
                 }
             }
-            const unsigned long long bal = __ballot(keep);
-            __syncthreads();
-            if (lane == 0) wcount[wave] = __popcll(bal);
-            __syncthreads();
-            int at = kept;
-            for (int w = 0; w < wave; ++w) at += wcount[w];
-            at += __popcll(bal & ((1ull << lane) - 1ull));
+            const int at = mm_block_compact_slot(keep, kept, wcount);
             if (keep) reinterpret_cast<int2 *>(pairs_out)[(size_t)p * a.cap + at] = qt;
-            kept += wcount[0] + wcount[1] + wcount[2] + wcount[3];
         }
     }
     if (tid == 0) {
