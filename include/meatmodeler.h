@@ -403,6 +403,67 @@ int mm_resect_cameras(mm_ctx *ctx, const double *K /*host [9]*/, const double *X
                       const double *prior /*[n_cams,12] or NULL*/, const mm_resect_params *prm, double *extrinsics /*[n_cams,3,4]*/,
                       double *cost /*[n_cams]*/, uint8_t *inlier /*[O]*/, int32_t *info /*[n_cams,6]*/, void *ws, size_t ws_bytes);
 
+/* ---- a-2e: planar resection, the pose of a camera over coplanar points by a RANSAC homography ----------------------------------
+ * Reference counterpart: the same cv2.solvePnP(..., SOLVEPNP_ITERATIVE) at processor.py:175, on the data it is actually given: the
+ * corners of a flat chessboard, where the reduced DLT of mm_resect_cameras has no valid sample.  A camera whose usable points are
+ * coplanar is estimated from the homography between their plane and the calibrated image; any other camera is refused and left
+ * as it was, so that this call can be laid over a mm_resect_cameras call on the same buffers.
+ *   Inputs, usable rows, compaction, the calibrated image side (u, v), cam_base, the prior as hypothesis n_hyp, score, MSAC
+ *   ranking, polish and every argument check: exactly as in mm_resect_cameras.  min_rows is floored at 8 (four picks out of
+ *   n_use >= 8 with eight tries collide with chance at most (3/8)^8 < 1e-3 per pick).
+ *   Plane fit, per camera over its usable rows: centroid c (each coordinate sum / n_use); the six sums of (X - c)(X - c)^T (xx,
+ *   xy, xz, yy, yz, zz) in the workgroup's fixed order; 3 x 3 cyclic Jacobi (the one of mm_resect_cameras); the three eigenpairs
+ *   are ordered ascending, l0 <= l1 <= l2, by a stable exchange sort of the columns -- (0,1), (1,2), (0,1), each exchanged only
+ *   when the right eigenvalue is strictly smaller.  n = the eigenvector of l0, e1 = that of l2, e2 = n x e1: (e1, e2, n) is a
+ *   rotation whatever signs the Jacobi returns.
+ *   Verdicts, in this order.  n_use < max(min_rows, 8): TOO_FEW, refused.  Collinear: l2 is not finite and positive, or l1 is not
+ *   above 1e-12 l2: PLANAR | NO_MODEL.  Planar: l0 <= planar_tol^2 l1: PLANAR, the branch below runs.  Anything else is not
+ *   planar and refused (no flag but MALFORMED where that applies).
+ *   Plane coordinates: with d = X - c, a = (d0 e1_0 + d1 e1_1) + d2 e1_2, b likewise with e2; rbar the mean of sqrt(a a + b b),
+ *   s = sqrt(2) / rbar, m = (s a, s b, 1).
+ *   Sampling: the integer scheme of mm_resect_cameras with four picks (same base; pick k = 0 .. 3, tries 0 .. 7 on
+ *   pcg(base + 8 k + try)).  A sample is also invalid when any of its four triples (0,1,2), (0,1,3), (0,2,3), (1,2,3) is
+ *   near-collinear: with p = m_j - m_i, q = m_k - m_i, r = m_k - m_j the triple passes only if
+ *   |p_a q_b - p_b q_a| > collinear_tol * max(|p|^2, |q|^2, |r|^2) (a NaN does not pass).  Refits skip this test.
+ *   Hypothesis and refit -- one routine, the reduced DLT of mm_resect_cameras one dimension down.  Over the chosen rows, in
+ *   their order, four symmetric 3 x 3 sums (upper triangles, 24 numbers): with w_ij = m_i m_j, S += w, Bu += u w, Bv += v w,
+ *   C += (u u + v v) w.  Cholesky S = L L^T with the same pivot rule; Yu = L^-1 Bu, Yv = L^-1 Bv; M = (C - Yu^T Yu) - Yv^T Yv;
+ *   h3 = the eigenvector of the smallest eigenvalue of M, ties to the lowest column (3 x 3 Jacobi); h1 = L^-T (Yu h3),
+ *   h2 = L^-T (Yv h3).  H = [h1; h2; h3] (rows), negated when H[2][2] < 0 (the centroid in front).
+ *   Pose from H: columns g1, g2, g3; sigma = (|g1| + |g2|) / 2 with |g| = sqrt((g0 g0 + g1 g1) + g2 g2);
+ *   A = [g1, g2, (g1 x g2) / sigma] (columns); R' = A (V diag(lambda^-1/2) V^T) from the 3 x 3 Jacobi of A^T A (a lambda that is
+ *   not finite and positive is invalid, and so is an A whose smallest sqrt(lambda) is not above 1e-4 times its largest: a
+ *   homography of rank one or two, whose polar factor is no rotation); R = R' [e1 e2 n]^T; t = g3 / (sigma s) - R c, the about-the-centroid form of
+ *   mm_resect_cameras.  A non-finite entry is invalid.  det A = |g1 x g2|^2 / sigma > 0: R is a rotation.
+ *   Refit: over the inliers of the current model, at least 4 of them, accepted only when valid with a finite, strictly lower
+ *   cost over ALL usable rows.  The second (flipped) pose of a plane seen nearly fronto-parallel is not searched for.
+ *   Score, ranking, prior, polish: the code of mm_resect_cameras on Q = K [R|t] and the 3-D points; the polished pose is a
+ *   pose, not a homography.
+ *   Outputs.  extrinsics, cost, inlier, info as in mm_resect_cameras, and plane [n_cams, 6] f64 = (n, n . c,
+ *   thickness sqrt(max(l0, 0) / l1), aspect sqrt(l1 / l2)), written for every camera from the fit over its usable rows (NaN where
+ *   that has none).  Flags: the four of mm_resect_cameras and MM_RESECT_PLANAR: the camera's usable points passed the
+ *   coplanarity test (or are collinear, then with NO_MODEL).  A camera without that bit was refused: its extrinsic is the prior
+ *   when present, else NaN, its cost NaN, its info row (flags, 0, -1, 0, n_use, 0), and its inlier rows are left UNTOUCHED.  For
+ *   a camera with the bit the inlier rows are written as mm_resect_cameras writes them.
+ * The guarantees of mm_resect_cameras hold: a call repeats bit for bit, a camera's row does not depend on its neighbours, rows
+ * [a, b) equal a call on that block with cam_base + a; n_cams = 0 returns MM_OK without a launch.  ws holds
+ * mm_resect_planar_workspace_bytes(n_cams, n_hyp, n_rows) bytes.  Argument errors as in mm_resect_cameras, and a planar_tol or
+ * collinear_tol that is negative or not finite: MM_ERR_ARG, before the device is touched. */
+#define MM_RESECT_PLANAR 16
+typedef struct mm_resect_planar_params {
+    int32_t n_hyp, min_rows, min_inliers, refit_iters, polish_iters, reserved;      /* defaults 256, 8, 12, 2, 8 */
+    uint32_t seed, cam_base;
+    double threshold_px;                                                            /* default 2 */
+    double planar_tol, collinear_tol;                                               /* defaults 1e-2, 1e-3 */
+} mm_resect_planar_params;
+size_t mm_resect_planar_workspace_bytes(int n_cams, int n_hyp, int64_t n_rows);
+int mm_resect_planar(mm_ctx *ctx, const double *K /*host [9]*/, const double *X /*[P,3]*/, int64_t P, const double *obs /*[O,2]*/,
+                     const int32_t *pi /*[O]*/, int64_t O, const int32_t *cam_ptr /*[n_cams+1]*/,
+                     const int32_t *cam_obs /*[n_rows]*/, int64_t n_rows, int n_cams, const uint8_t *pt_ok /*[P] or NULL*/,
+                     const double *prior /*[n_cams,12] or NULL*/, const mm_resect_planar_params *prm,
+                     double *extrinsics /*[n_cams,3,4]*/, double *cost /*[n_cams]*/, uint8_t *inlier /*[O]*/,
+                     int32_t *info /*[n_cams,6]*/, double *plane /*[n_cams,6]*/, void *ws, size_t ws_bytes);
+
 /* ---- a-4: two-view DLT triangulation ------------------------------------------------------------
  * Replaces the per-track cv2.triangulatePoints + dehomogenise loop, processor.py:254-261.
  * proj [F,3,4] f64; track i uses views f0[i], f1[i] with pixels x0[i], x1[i]; X [n,3]. */

@@ -87,6 +87,12 @@ class ResectParams(C.Structure):
                 ("threshold_px", C.c_double)]
 
 
+class ResectPlanarParams(C.Structure):
+    """mm_resect_planar_params: the fields of mm_resect_params, then the coplanarity and the sample-collinearity tolerance of
+    mm_resect_planar."""
+    _fields_ = ResectParams._fields_ + [("planar_tol", C.c_double), ("collinear_tol", C.c_double)]
+
+
 ALLREDUCE_FN =C.CFUNCTYPE(C.c_int, vp, vp, C.c_int64)
 
 
@@ -145,6 +151,9 @@ SIGNATURES = {
     "mm_resect_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int64]),
     "mm_resect_cameras": (C.c_int, [vp, c_f64p, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int, vp, vp,
                                     C.POINTER(ResectParams), vp, vp, vp, vp, vp, C.c_size_t]),
+    "mm_resect_planar_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int64]),
+    "mm_resect_planar": (C.c_int, [vp, c_f64p, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int, vp, vp,
+                                   C.POINTER(ResectPlanarParams), vp, vp, vp, vp, vp, vp, C.c_size_t]),
     "mm_triangulate_dlt": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int64, vp]),
     "mm_triangulate_tracks_workspace_bytes": (C.c_size_t, [C.c_int]),
     "mm_triangulate_tracks": (C.c_int, [vp, vp, C.c_int, vp, C.c_int64, vp, vp, C.POINTER(TriParams), vp, vp, vp, vp, C.c_size_t]),

@@ -122,6 +122,69 @@ __device__ __forceinline__ void mm_jacobi(double (&G)[N][N], double (&V)[N][N]) 
     }
 }
 
+// c = a x b, each component one difference of two products
+__device__ __forceinline__ void mm_cross3(const double (&a)[3], const double (&b)[3], double (&c)[3]) {
+    c[0] = a[1] * b[2] - a[2] * b[1];
+    c[1] = a[2] * b[0] - a[0] * b[2];
+    c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// Cholesky S = L L^T of a small symmetric matrix in registers, column by column, each entry reduced by its products left to
+// right.  false: some pivot was not finite or <= 1e-12 times the diagonal entry it started from (the factor is then
+// unusable; every entry is still written).  Only the lower triangle of L is set.
+template <int N>
+__device__ __forceinline__ bool mm_cholesky_pivot(const double (&S)[N][N], double (&L)[N][N]) {
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        double d = S[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
+        ok = ok && isfinite(d) && d > 1e-12 * S[j][j];
+        const double ljj = sqrt(d);
+        L[j][j] = ljj;
+#pragma unroll
+        for (int i = j + 1; i < N; ++i) {
+            double v = S[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
+            L[i][j] = v / ljj;
+        }
+    }
+    return ok;
+}
+
+// Polar factor of a 3 x 3 A: R = A (V diag(lambda^-1/2) V^T) with lambda, V from the cyclic Jacobi of A^T A; rt receives
+// sqrt(lambda) in the Jacobi's order.  false: a lambda that is not finite and positive.  det R has the sign of det A.
+__device__ __forceinline__ bool mm_polar3(const double (&A)[3][3], double (&R)[3][3], double (&rt)[3]) {
+    double G[3][3], V[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) G[r][c] = (A[0][r] * A[0][c] + A[1][r] * A[1][c]) + A[2][r] * A[2][c];
+    mm_identity<3>(V);
+    mm_jacobi<3>(G, V);
+    bool ok = true;
+    double dk[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double lam = G[k][k];
+        ok = ok && isfinite(lam) && lam > 0.0;
+        rt[k] = sqrt(lam);
+        dk[k] = 1.0 / rt[k];
+    }
+    double W[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) W[i][j] = ((V[i][0] * dk[0]) * V[j][0] + (V[i][1] * dk[1]) * V[j][1]) + (V[i][2] * dk[2]) * V[j][2];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) R[r][c] = (A[r][0] * W[0][c] + A[r][1] * W[1][c]) + A[r][2] * W[2][c];
+    return ok;
+}
+
 // Argmin over the n hypotheses of one workgroup's item: the lowest finite cost[h], ties to the lowest h (h_best stays
 // INT32_MAX when no cost is finite), and n_valid = the number of h whose probe[h * probe_stride] is finite.  Butterfly
 // inside a wave, then the waves in order through bc / bh (MM_BLOCK_WAVES entries each); sm as for mm_block_sum<1>.  Every

@@ -10,6 +10,13 @@
 //   rs_score_kernel       lane = hypothesis, K [R|t] in twelve registers; the camera's rows go through LDS in tiles and every
 //                         lane reads the same address (broadcast), summing min(d^2, tau^2) over the rows ascending
 //   rs_finish_kernel      one workgroup per camera: argmin, the prior, refit rounds, Levenberg-Marquardt polish, mask, outputs
+// and the planar branch (mm_resect_planar: coplanar points, where the reduced DLT above has no valid sample), which shares the
+// score kernel, the workspace slots and the finish stage:
+//   rp_prepare_kernel     one workgroup per camera: the same compaction, then the plane through the points (six sums, 3 x 3
+//                         Jacobi), the verdict -- planar, collinear, refused -- and the camera's frame e1, e2, n
+//   rp_hypothesis_kernel  one lane per (camera, hypothesis): four sampled rows in plane coordinates, near-collinear triples
+//                         rejected, the 24 sums of the same DLT one dimension down, the pose from the homography
+//   rs_finish_kernel<true>  the finish stage with the verdict in front and the homography refit in the place of the DLT's
 // Built without FMA contraction (Makefile): a product-sum then has one value whatever the compiler makes of its surroundings,
 // and the NumPy restatement of the tests can follow the header operation by operation.  Plain f64 VALU work; sums in an order
 // that depends on the camera alone (per-thread strides, xor butterflies, waves in order), no atomics.
@@ -35,6 +42,10 @@ struct RsArgs {
     double K[9];
     double Ki[5];      // K^-1 = [[Ki0, Ki1, Ki2], [0, Ki3, Ki4], [0, 0, 1]]
     double *norm;      // [n_cams, 8]: cx, cy, cz, s, n_use, number of malformed rows, -, -
+                       // (mm_resect_planar: slot 4 is n_use where the homography branch runs, else 0; 6: n_use; 7: verdict flags)
+    double *frame;     // mm_resect_planar only, [n_cams, 9]: e1, e2, n of the fitted plane
+    double *plane;     // mm_resect_planar only, the output [n_cams, 6]
+    double planar_tol2, collinear_tol;
     double *Eh;        // [n_cams, n_hyp, 12] (NaN: invalid hypothesis)
     double *cost_h;    // [n_cams, n_hyp] (+inf: invalid hypothesis)
     int32_t *rows;     // [n_rows]: the usable observations of camera c at cam_ptr[c] .. + n_use, in order
@@ -245,34 +256,198 @@ __device__ __forceinline__ bool rs_distance(const double (&Q)[12], double X, dou
     return y2 > 0.0 && isfinite(d2) && d2 <= tau2;
 }
 
+// ---- the planar branch (mm_resect_planar): the reduced DLT one dimension down ----------------------------------------------
+// plane coordinates (ma, mb) = s ((X - c) . e1, (X - c) . e2) of a point and the calibrated pixel (u, v); fr = e1, e2, n
+__device__ __forceinline__ void rp_row(const RsArgs &a, const double (&fr)[9], double cx, double cy, double cz, double s, double X,
+                                       double Y, double Z, double ox, double oy, double &ma, double &mb, double &u, double &v) {
+    const double dx = X - cx, dy = Y - cy, dz = Z - cz;
+    ma = s * ((dx * fr[0] + dy * fr[1]) + dz * fr[2]);
+    mb = s * ((dx * fr[3] + dy * fr[4]) + dz * fr[5]);
+    u = (a.Ki[0] * ox + a.Ki[1] * oy) + a.Ki[2];
+    v = a.Ki[3] * oy + a.Ki[4];
+}
+
+// one row into the 24 sums: S, Bu, Bv, C, each the upper triangle of a 3 x 3, row-major, over m = (ma, mb, 1)
+__device__ __forceinline__ void rp_accumulate(double (&acc)[24], double ma, double mb, double u, double v) {
+    const double m[3] = {ma, mb, 1.0};
+    const double r2 = u * u + v * v;
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = i; j < 3; ++j) {
+            const double w = m[i] * m[j];
+            acc[k] += w;
+            acc[6 + k] += u * w;
+            acc[12 + k] += v * w;
+            acc[18 + k] += r2 * w;
+            ++k;
+        }
+}
+
+// true: the triangle (i, j, k) of plane points is not near-collinear: |cross| > tol x its longest squared side (NaN: false)
+__device__ __forceinline__ bool rp_triple_ok(double ai, double bi, double aj, double bj, double ak, double bk, double tol) {
+    const double pa = aj - ai, pb = bj - bi, qa = ak - ai, qb = bk - bi, ra = ak - aj, rb = bk - bj;
+    const double cr = pa * qb - pb * qa;
+    const double d0 = pa * pa + pb * pb, d1 = qa * qa + qb * qb, d2 = ra * ra + rb * rb;
+    double lng = d0 > d1 ? d0 : d1;
+    lng = lng > d2 ? lng : d2;
+    return fabs(cr) > tol * lng;
+}
+
+// [R|t] from the 24 sums: the homography H = [h1; h2; h3] by the reduced DLT, then the pose of the plane's frame fr = e1, e2, n
+// about the centroid.  false: a failed pivot, a non-positive eigenvalue or a non-finite result.
+__device__ __forceinline__ bool rp_solve(const double (&acc)[24], const double (&fr)[9], double cx, double cy, double cz, double s,
+                                         double (&E)[12]) {
+    double S[3][3], Bu[3][3], Bv[3][3], M[3][3];
+    {
+        int k = 0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = i; j < 3; ++j) {
+                S[i][j] = S[j][i] = acc[k];
+                Bu[i][j] = Bu[j][i] = acc[6 + k];
+                Bv[i][j] = Bv[j][i] = acc[12 + k];
+                M[i][j] = M[j][i] = acc[18 + k];
+                ++k;
+            }
+    }
+    double L[3][3];
+    bool ok = mm_cholesky_pivot<3>(S, L);
+    double Yu[3][3], Yv[3][3];      // L^-1 Bu, L^-1 Bv
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            double vu = Bu[i][c], vv = Bv[i][c];
+#pragma unroll
+            for (int k = 0; k < i; ++k) {
+                vu -= L[i][k] * Yu[k][c];
+                vv -= L[i][k] * Yv[k][c];
+            }
+            Yu[i][c] = vu / L[i][i];
+            Yv[i][c] = vv / L[i][i];
+        }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = i; j < 3; ++j) {
+            const double tu = (Yu[0][i] * Yu[0][j] + Yu[1][i] * Yu[1][j]) + Yu[2][i] * Yu[2][j];
+            const double tv = (Yv[0][i] * Yv[0][j] + Yv[1][i] * Yv[1][j]) + Yv[2][i] * Yv[2][j];
+            M[i][j] = M[j][i] = (M[i][j] - tu) - tv;
+        }
+    double V3[3][3];
+    mm_identity<3>(V3);
+    mm_jacobi<3>(M, V3);
+    double ev = M[0][0], h3[3] = {V3[0][0], V3[1][0], V3[2][0]};      // smallest eigenvalue, ties to the lowest column
+#pragma unroll
+    for (int c = 1; c < 3; ++c) {
+        if (M[c][c] < ev) {
+            ev = M[c][c];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) h3[r] = V3[r][c];
+        }
+    }
+    double h1[3], h2[3];      // S^-1 Bu h3 = L^-T (Yu h3), S^-1 Bv h3
+    {
+        double wu[3], wv[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            wu[i] = (Yu[i][0] * h3[0] + Yu[i][1] * h3[1]) + Yu[i][2] * h3[2];
+            wv[i] = (Yv[i][0] * h3[0] + Yv[i][1] * h3[1]) + Yv[i][2] * h3[2];
+        }
+#pragma unroll
+        for (int i = 2; i >= 0; --i) {
+            double vu = wu[i], vv = wv[i];
+#pragma unroll
+            for (int k = i + 1; k < 3; ++k) {
+                vu -= L[k][i] * h1[k];
+                vv -= L[k][i] * h2[k];
+            }
+            h1[i] = vu / L[i][i];
+            h2[i] = vv / L[i][i];
+        }
+    }
+    const double sg = h3[2] < 0.0 ? -1.0 : 1.0;      // H[2][2] >= 0: the centroid in front
+    const double g1[3] = {sg * h1[0], sg * h2[0], sg * h3[0]}, g2[3] = {sg * h1[1], sg * h2[1], sg * h3[1]};
+    const double g3[3] = {sg * h1[2], sg * h2[2], sg * h3[2]};
+    const double sigma = (sqrt((g1[0] * g1[0] + g1[1] * g1[1]) + g1[2] * g1[2]) + sqrt((g2[0] * g2[0] + g2[1] * g2[1]) + g2[2] * g2[2])) / 2.0;
+    double g12[3];
+    mm_cross3(g1, g2, g12);
+    double A[3][3], Rp[3][3], rt[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        A[r][0] = g1[r];
+        A[r][1] = g2[r];
+        A[r][2] = g12[r] / sigma;
+    }
+    ok = mm_polar3(A, Rp, rt) && ok;
+    {   // a homography of rank one or two (every pixel the same, or on a line) has no pose: its polar factor is no rotation
+        double lo_ = rt[0] < rt[1] ? rt[0] : rt[1], hi_ = rt[0] > rt[1] ? rt[0] : rt[1];
+        lo_ = lo_ < rt[2] ? lo_ : rt[2];
+        hi_ = hi_ > rt[2] ? hi_ : rt[2];
+        ok = ok && lo_ > 1e-4 * hi_;
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) E[4 * r + c] = (Rp[r][0] * fr[c] + Rp[r][1] * fr[3 + c]) + Rp[r][2] * fr[6 + c];
+        E[4 * r + 3] = g3[r] / (sigma * s) - ((E[4 * r] * cx + E[4 * r + 1] * cy) + E[4 * r + 2] * cz);
+    }
+#pragma unroll
+    for (int k = 0; k < 12; ++k) ok = ok && isfinite(E[k]);
+    return ok;
+}
+
 // ---- usable rows, centroid and scale ----------------------------------------------------------------------------------------
+// row q of a camera: its observation o; mal: an index out of range or a non-finite pixel; use: a usable row; mark: o is in
+// range and the row is usable or malformed (the rows whose inlier byte a call writes).  Nothing is read through a bad index.
+__device__ __forceinline__ void rs_classify(const RsArgs &a, int q, int &o, bool &mal, bool &mark, bool &use) {
+    o = a.cam_obs[q];
+    mal = !(o >= 0 && (long long)o < a.O);
+    use = false;
+    mark = false;
+    if (!mal) {
+        const int p = a.pi[o];
+        const double ox = a.obs[2 * (size_t)o], oy = a.obs[2 * (size_t)o + 1];
+        mal = !(p >= 0 && (long long)p < a.P) || !(isfinite(ox) && isfinite(oy));
+        if (!mal && (a.pt_ok == nullptr || a.pt_ok[p] != 0))
+            use = isfinite(a.X[3 * (size_t)p]) && isfinite(a.X[3 * (size_t)p + 1]) && isfinite(a.X[3 * (size_t)p + 2]);
+        mark = mal || use;
+    }
+}
+
+// the usable rows of the camera compacted in order into a.rows[lo ..]; n_use: their number (uniform), bad: this thread's
+// malformed rows.  MARK: the inlier byte of every usable or malformed row is zeroed on the way.
+template <bool MARK>
+__device__ __forceinline__ void rs_compact_rows(const RsArgs &a, int lo, int hi, int *wcount, int &n_use, int &bad) {
+    const int tid = threadIdx.x;
+    n_use = 0;
+    bad = 0;
+    for (int q0 = lo; q0 < hi; q0 += RS_THREADS) {
+        const int q = q0 + tid;
+        bool use = false;
+        int o = 0;
+        if (q < hi) {
+            bool mal, mark;
+            rs_classify(a, q, o, mal, mark, use);
+            if (MARK && mark) a.inlier[o] = 0;
+            bad += mal ? 1 : 0;
+        }
+        const int at = mm_block_compact_slot(use, n_use, wcount);
+        if (use) a.rows[lo + at] = o;
+    }
+}
+
 __global__ __launch_bounds__(RS_THREADS) void rs_prepare_kernel(RsArgs a) {
     __shared__ double sm[RS_WAVES * 3];
     __shared__ int wcount[RS_WAVES], wbad[RS_WAVES];
     const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int lo, hi;
     rs_range(a, c, lo, hi);
-    int n_use = 0, bad = 0;
-    for (int q0 = lo; q0 < hi; q0 += RS_THREADS) {
-        const int q = q0 + tid;
-        bool use = false;
-        int o = 0;
-        if (q < hi) {
-            o = a.cam_obs[q];
-            bool mal = !(o >= 0 && (long long)o < a.O);
-            if (!mal) {
-                const int p = a.pi[o];
-                const double ox = a.obs[2 * (size_t)o], oy = a.obs[2 * (size_t)o + 1];
-                mal = !(p >= 0 && (long long)p < a.P) || !(isfinite(ox) && isfinite(oy));
-                if (!mal && (a.pt_ok == nullptr || a.pt_ok[p] != 0))
-                    use = isfinite(a.X[3 * (size_t)p]) && isfinite(a.X[3 * (size_t)p + 1]) && isfinite(a.X[3 * (size_t)p + 2]);
-                if (mal || use) a.inlier[o] = 0;
-            }
-            bad += mal ? 1 : 0;
-        }
-        const int at = mm_block_compact_slot(use, n_use, wcount);
-        if (use) a.rows[lo + at] = o;
-    }
+    int n_use, bad;
+    rs_compact_rows<true>(a, lo, hi, wcount, n_use, bad);
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) bad += __shfl_xor(bad, off, 64);
     if (lane == 0) wbad[wave] = bad;
@@ -308,6 +483,118 @@ __global__ __launch_bounds__(RS_THREADS) void rs_prepare_kernel(RsArgs a) {
     }
 }
 
+// mm_resect_planar: the usable rows, the plane through them, the verdict and the header (norm, frame) of the camera
+__global__ __launch_bounds__(RS_THREADS) void rp_prepare_kernel(RsArgs a) {
+    __shared__ double sm[RS_WAVES * 6];
+    __shared__ int wcount[RS_WAVES], wbad[RS_WAVES];
+    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int lo, hi;
+    rs_range(a, c, lo, hi);
+    int n_use, bad;
+    rs_compact_rows<false>(a, lo, hi, wcount, n_use, bad);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) bad += __shfl_xor(bad, off, 64);
+    if (lane == 0) wbad[wave] = bad;
+    __syncthreads();      // (also publishes rows to the whole workgroup)
+    bad = wbad[0] + wbad[1] + wbad[2] + wbad[3];
+    double s3[3] = {0.0, 0.0, 0.0};
+    for (int k = tid; k < n_use; k += RS_THREADS) {
+        double X, Y, Z, ox, oy;
+        rs_load(a, lo, k, X, Y, Z, ox, oy);
+        s3[0] += X;
+        s3[1] += Y;
+        s3[2] += Z;
+    }
+    mm_block_sum<3>(s3, sm);
+    const double n = (double)n_use, cx = s3[0] / n, cy = s3[1] / n, cz = s3[2] / n;
+    double cv[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};      // (X - c)(X - c)^T, upper triangle row-major
+    for (int k = tid; k < n_use; k += RS_THREADS) {
+        double X, Y, Z, ox, oy;
+        rs_load(a, lo, k, X, Y, Z, ox, oy);
+        const double dx = X - cx, dy = Y - cy, dz = Z - cz;
+        cv[0] += dx * dx;
+        cv[1] += dx * dy;
+        cv[2] += dx * dz;
+        cv[3] += dy * dy;
+        cv[4] += dy * dz;
+        cv[5] += dz * dz;
+    }
+    mm_block_sum<6>(cv, sm);
+    double G[3][3] = {{cv[0], cv[1], cv[2]}, {cv[1], cv[3], cv[4]}, {cv[2], cv[4], cv[5]}}, V[3][3];
+    mm_identity<3>(V);
+    mm_jacobi<3>(G, V);
+    // eigenpairs ascending by a stable exchange sort of the three columns: (0, 1), (1, 2), (0, 1), each only on a strictly
+    // smaller right neighbour
+    double l[3] = {G[0][0], G[1][1], G[2][2]};
+#define RP_EXCHANGE(i, j)                     \
+    if (l[j] < l[i]) {                        \
+        const double t_ = l[i];               \
+        l[i] = l[j];                          \
+        l[j] = t_;                            \
+        _Pragma("unroll") for (int r = 0; r < 3; ++r) { \
+            const double w_ = V[r][i];        \
+            V[r][i] = V[r][j];                \
+            V[r][j] = w_;                     \
+        }                                     \
+    }
+    RP_EXCHANGE(0, 1)
+    RP_EXCHANGE(1, 2)
+    RP_EXCHANGE(0, 1)
+#undef RP_EXCHANGE
+    const double nrm[3] = {V[0][0], V[1][0], V[2][0]}, e1[3] = {V[0][2], V[1][2], V[2][2]};
+    double e2[3];
+    mm_cross3(nrm, e1, e2);
+    int verdict = 0;
+    bool runs = false;
+    if (n_use < a.min_rows) {
+        verdict = MM_RESECT_TOO_FEW;
+    } else if (!(isfinite(l[2]) && l[2] > 0.0) || !(l[1] > 1e-12 * l[2])) {
+        verdict = MM_RESECT_PLANAR | MM_RESECT_NO_MODEL;      // collinear (or no finite extent at all)
+    } else if (l[0] <= a.planar_tol2 * l[1]) {
+        verdict = MM_RESECT_PLANAR;
+        runs = true;
+    }
+    double dd[1] = {0.0};
+    for (int k = tid; k < n_use; k += RS_THREADS) {
+        double X, Y, Z, ox, oy;
+        rs_load(a, lo, k, X, Y, Z, ox, oy);
+        const double dx = X - cx, dy = Y - cy, dz = Z - cz;
+        const double pa = (dx * e1[0] + dy * e1[1]) + dz * e1[2], pb = (dx * e2[0] + dy * e2[1]) + dz * e2[2];
+        dd[0] += sqrt(pa * pa + pb * pb);
+    }
+    mm_block_sum<1>(dd, sm);
+    if (verdict & MM_RESECT_PLANAR) {      // the rows this call writes: as rs_prepare_kernel does for every camera
+        for (int q = lo + tid; q < hi; q += RS_THREADS) {
+            int o;
+            bool mal, mark, use;
+            rs_classify(a, q, o, mal, mark, use);
+            if (mark) a.inlier[o] = 0;
+        }
+    }
+    if (tid == 0) {
+        double *o = a.norm + 8 * (size_t)c;
+        o[0] = cx;
+        o[1] = cy;
+        o[2] = cz;
+        o[3] = 1.4142135623730951 / (dd[0] / n);
+        o[4] = runs ? n : 0.0;
+        o[5] = (double)bad;
+        o[6] = n;
+        o[7] = (double)verdict;
+        double *f = a.frame + 9 * (size_t)c, *p = a.plane + 6 * (size_t)c;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            f[k] = e1[k];
+            f[3 + k] = e2[k];
+            f[6 + k] = nrm[k];
+            p[k] = nrm[k];
+        }
+        p[3] = (nrm[0] * cx + nrm[1] * cy) + nrm[2] * cz;
+        p[4] = sqrt((l[0] > 0.0 ? l[0] : 0.0) / l[1]);
+        p[5] = sqrt(l[1] / l[2]);
+    }
+}
+
 // ---- one hypothesis per lane --------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void rs_hypothesis_kernel(RsArgs a) {
     const int c = blockIdx.x;
@@ -334,6 +621,45 @@ __global__ __launch_bounds__(64) void rs_hypothesis_kernel(RsArgs a) {
     }
     double E[12];
     ok = rs_solve(acc, cx, cy, cz, s, E) && ok;
+    double *o = a.Eh + ((size_t)c * a.n_hyp + h) * 12;
+    const double nan = __builtin_nan("");
+#pragma unroll
+    for (int k = 0; k < 12; ++k) o[k] = ok ? E[k] : nan;
+}
+
+// mm_resect_planar: four sampled rows, the near-collinear triples rejected, the 24 sums and the pose from the homography
+__global__ __launch_bounds__(64) void rp_hypothesis_kernel(RsArgs a) {
+    const int c = blockIdx.x;
+    const int h = blockIdx.y * 64 + threadIdx.x;
+    const double *nr = a.norm + 8 * (size_t)c;
+    const int n_use = (int)nr[4];
+    if (h >= a.n_hyp || n_use < a.min_rows) return;      // (a refused camera is never scored either)
+    int lo, hi;
+    rs_range(a, c, lo, hi);
+    const double cx = nr[0], cy = nr[1], cz = nr[2], s = nr[3];
+    double fr[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) fr[k] = a.frame[9 * (size_t)c + k];
+    bool ok = isfinite(s) && isfinite(cx) && isfinite(cy) && isfinite(cz);
+    const uint32_t base = mm_pcg(mm_pcg(a.seed + mm_pcg(a.cam_base + (uint32_t)c)) + (uint32_t)h);
+    int pick[4];
+    ok = mm_sample_distinct<4>(base, n_use, pick) && ok;
+    double ma[4], mb[4], acc[24];
+#pragma unroll
+    for (int k = 0; k < 24; ++k) acc[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        double X, Y, Z, ox, oy, u, v;
+        rs_load(a, lo, pick[k], X, Y, Z, ox, oy);
+        rp_row(a, fr, cx, cy, cz, s, X, Y, Z, ox, oy, ma[k], mb[k], u, v);
+        rp_accumulate(acc, ma[k], mb[k], u, v);
+    }
+    ok = rp_triple_ok(ma[0], mb[0], ma[1], mb[1], ma[2], mb[2], a.collinear_tol) && ok;
+    ok = rp_triple_ok(ma[0], mb[0], ma[1], mb[1], ma[3], mb[3], a.collinear_tol) && ok;
+    ok = rp_triple_ok(ma[0], mb[0], ma[2], mb[2], ma[3], mb[3], a.collinear_tol) && ok;
+    ok = rp_triple_ok(ma[1], mb[1], ma[2], mb[2], ma[3], mb[3], a.collinear_tol) && ok;
+    double E[12];
+    ok = rp_solve(acc, fr, cx, cy, cz, s, E) && ok;
     double *o = a.Eh + ((size_t)c * a.n_hyp + h) * 12;
     const double nan = __builtin_nan("");
 #pragma unroll
@@ -488,13 +814,16 @@ __device__ __forceinline__ void rs_update(const double (&E)[12], const double (&
     }
 }
 
+// PLANAR: the finish stage of mm_resect_planar -- the verdict of rp_prepare_kernel decides whether anything runs, and the refit
+// is the homography's.  A separate instantiation: the general one compiles from the source it always had.
+template <bool PLANAR>
 __global__ __launch_bounds__(RS_THREADS) void rs_finish_kernel(RsArgs a) {
     __shared__ double sm[RS_WAVES * 40];
     __shared__ double bc[RS_WAVES];
     __shared__ int bh[RS_WAVES];
     const int c = blockIdx.x, tid = threadIdx.x;
     const double *nr = a.norm + 8 * (size_t)c;
-    const int n_use = (int)nr[4];
+    const int n_use = (int)nr[4];      // (PLANAR: 0 for a camera the homography branch does not run on)
     const double cx = nr[0], cy = nr[1], cz = nr[2], s = nr[3];
     int lo, hi;
     rs_range(a, c, lo, hi);
@@ -514,8 +843,13 @@ __global__ __launch_bounds__(RS_THREADS) void rs_finish_kernel(RsArgs a) {
     bool model = false;
 
     if (n_use < a.min_rows) {
-        flags |= MM_RESECT_TOO_FEW;
+        if constexpr (PLANAR) {
+            flags |= (int)nr[7];      // TOO_FEW, nothing (refused) or PLANAR | NO_MODEL (collinear)
+        } else {
+            flags |= MM_RESECT_TOO_FEW;
+        }
     } else {
+        if constexpr (PLANAR) flags |= MM_RESECT_PLANAR;
         // lowest finite cost, ties to the lowest h; and the number of valid hypotheses
         double c_best;
         int h_best;
@@ -546,20 +880,47 @@ __global__ __launch_bounds__(RS_THREADS) void rs_finish_kernel(RsArgs a) {
 
     if (model) {
         for (int it = 0; it < a.refit_iters; ++it) {
-            if (n_in < 6) break;      // (uniform: nothing changes any more)
-            double Q[12], acc[40];
+            if (n_in < (PLANAR ? 4 : 6)) break;      // (uniform: nothing changes any more)
+            double Q[12], En[12];
             rs_camera(a, E, Q);
+            bool okE;
+            if constexpr (PLANAR) {
+                // the plane's frame goes through LDS: read from there it lives in vector registers for this block only (as
+                // nine uniform loads it sat in scalar registers over the whole kernel, which has none to spare)
+                __shared__ double sfr[9];
+                __syncthreads();
+                if (tid < 9) sfr[tid] = a.frame[9 * (size_t)c + tid];
+                __syncthreads();
+                double fr[9], acc[24];
 #pragma unroll
-            for (int k = 0; k < 40; ++k) acc[k] = 0.0;
-            for (int k = tid; k < n_use; k += RS_THREADS) {
-                double X, Y, Z, ox, oy, d2;
-                rs_load(a, lo, k, X, Y, Z, ox, oy);
-                if (rs_distance(Q, X, Y, Z, ox, oy, a.tau2, d2)) rs_accumulate(acc, a, cx, cy, cz, s, X, Y, Z, ox, oy);
+                for (int k = 0; k < 9; ++k) fr[k] = sfr[k];
+#pragma unroll
+                for (int k = 0; k < 24; ++k) acc[k] = 0.0;
+                for (int k = tid; k < n_use; k += RS_THREADS) {
+                    double X, Y, Z, ox, oy, d2;
+                    rs_load(a, lo, k, X, Y, Z, ox, oy);
+                    if (rs_distance(Q, X, Y, Z, ox, oy, a.tau2, d2)) {
+                        double ma, mb, u, v;
+                        rp_row(a, fr, cx, cy, cz, s, X, Y, Z, ox, oy, ma, mb, u, v);
+                        rp_accumulate(acc, ma, mb, u, v);
+                    }
+                }
+                mm_block_sum<24>(acc, sm);
+                okE = rp_solve(acc, fr, cx, cy, cz, s, En);
+            } else {
+                double acc[40];
+#pragma unroll
+                for (int k = 0; k < 40; ++k) acc[k] = 0.0;
+                for (int k = tid; k < n_use; k += RS_THREADS) {
+                    double X, Y, Z, ox, oy, d2;
+                    rs_load(a, lo, k, X, Y, Z, ox, oy);
+                    if (rs_distance(Q, X, Y, Z, ox, oy, a.tau2, d2)) rs_accumulate(acc, a, cx, cy, cz, s, X, Y, Z, ox, oy);
+                }
+                mm_block_sum<40>(acc, sm);
+                okE = rs_solve(acc, cx, cy, cz, s, En);
             }
-            mm_block_sum<40>(acc, sm);
-            double En[12], cn;
+            double cn;
             int nn_in;
-            const bool okE = rs_solve(acc, cx, cy, cz, s, En);
             rs_cost(a, lo, n_use, En, sm, cn, nn_in);
             if (okE && isfinite(cn) && cn < cost) {
                 cost = cn;
@@ -614,7 +975,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_finish_kernel(RsArgs a) {
             }
         }
         if (n_in < a.min_inliers) flags |= MM_RESECT_WEAK;
-        // the inliers of the final model (the prepare kernel has zeroed every row of a camera without one)
+        // the inliers of the final model (the prepare kernel has zeroed every row the call writes)
         double Q[12];
         rs_camera(a, E, Q);
         for (int k = tid; k < n_use; k += RS_THREADS) {
@@ -632,7 +993,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_finish_kernel(RsArgs a) {
         o[1] = n_in;
         o[2] = best_h;
         o[3] = n_valid;
-        o[4] = n_use;
+        o[4] = PLANAR ? (int)nr[6] : n_use;
         o[5] = n_polish;
     }
 }
@@ -647,32 +1008,36 @@ extern "C" size_t mm_resect_workspace_bytes(int n_cams, int n_hyp, int64_t n_row
            rs_region(nr * sizeof(int32_t)) + rs_region(nr);
 }
 
-extern "C" int mm_resect_cameras(mm_ctx *ctx, const double *K, const double *X, int64_t P, const double *obs, const int32_t *pi,
-                                 int64_t O, const int32_t *cam_ptr, const int32_t *cam_obs, int64_t n_rows, int n_cams,
-                                 const uint8_t *pt_ok, const double *prior, const mm_resect_params *prm, double *extrinsics,
-                                 double *cost, uint8_t *inlier, int32_t *info, void *ws, size_t ws_bytes) {
+namespace {
+
+// Every argument of the two entry points judged, then RsArgs filled and the general workspace carved (`extra` bytes may follow
+// it).  MM_OK with launch = false: n_cams = 0.  Nothing here touches the device.
+int rs_setup(mm_ctx *ctx, const char *fn, const double *K, const double *X, int64_t P, const double *obs, const int32_t *pi, int64_t O,
+             const int32_t *cam_ptr, const int32_t *cam_obs, int64_t n_rows, int n_cams, const uint8_t *pt_ok, const double *prior,
+             const mm_resect_params *prm, int row_floor, double *extrinsics, double *cost, uint8_t *inlier, int32_t *info, void *ws,
+             size_t ws_bytes, size_t extra, bool extra_ok, RsArgs &a, char *&ws_end, bool &launch) {
+    launch = false;
     // every argument is judged before the context is looked at: nothing below this block runs on a bad call
     if (!prm || !K || n_cams < 0 || P < 0 || O < 0 || n_rows < 0 || P > INT32_MAX || O > INT32_MAX || n_rows > INT32_MAX)
-        return mm_fail(ctx, MM_ERR_ARG, "mm_resect_cameras: bad argument");
-    if (prm->n_hyp < 1 || prm->n_hyp > 4096) return mm_fail(ctx, MM_ERR_ARG, "mm_resect_cameras: n_hyp must be in 1 .. 4096");
+        return mm_fail(ctx, MM_ERR_ARG, "%s: bad argument", fn);
+    if (prm->n_hyp < 1 || prm->n_hyp > 4096) return mm_fail(ctx, MM_ERR_ARG, "%s: n_hyp must be in 1 .. 4096", fn);
     if (!(prm->threshold_px >= 0.0))      // (negative or NaN)
-        return mm_fail(ctx, MM_ERR_ARG, "mm_resect_cameras: threshold_px must not be negative");
+        return mm_fail(ctx, MM_ERR_ARG, "%s: threshold_px must not be negative", fn);
     if (prm->refit_iters < 0 || prm->refit_iters > 1000 || prm->polish_iters < 0 || prm->polish_iters > 1000 || prm->min_inliers < 0)
-        return mm_fail(ctx, MM_ERR_ARG, "mm_resect_cameras: bad parameter");
+        return mm_fail(ctx, MM_ERR_ARG, "%s: bad parameter", fn);
+    if (!extra_ok) return mm_fail(ctx, MM_ERR_ARG, "%s: planar_tol and collinear_tol must not be negative", fn);
     bool k_ok = K[3] == 0.0 && K[6] == 0.0 && K[7] == 0.0 && K[8] == 1.0 && K[0] != 0.0 && K[4] != 0.0;
     for (int k = 0; k < 9; ++k) k_ok = k_ok && std::isfinite(K[k]);
     if (!k_ok)
-        return mm_fail(ctx, MM_ERR_ARG, "mm_resect_cameras: K must be finite and upper triangular with K[8] = 1 and non-zero focal lengths");
-    if (n_cams > 0 && (!cam_ptr || !extrinsics || !cost || !info || !ws))
-        return mm_fail(ctx, MM_ERR_ARG, "mm_resect_cameras: bad argument");
+        return mm_fail(ctx, MM_ERR_ARG, "%s: K must be finite and upper triangular with K[8] = 1 and non-zero focal lengths", fn);
+    if (n_cams > 0 && (!cam_ptr || !extrinsics || !cost || !info || !ws)) return mm_fail(ctx, MM_ERR_ARG, "%s: bad argument", fn);
     if (n_cams > 0 && n_rows > 0 && (!cam_obs || !inlier || (O > 0 && (!obs || !pi)) || (P > 0 && !X)))
-        return mm_fail(ctx, MM_ERR_ARG, "mm_resect_cameras: bad argument");
-    if (n_cams > 0 && ws_bytes < mm_resect_workspace_bytes(n_cams, prm->n_hyp, n_rows))
-        return mm_fail(ctx, MM_ERR_WORKSPACE, "mm_resect_cameras: workspace too small");
+        return mm_fail(ctx, MM_ERR_ARG, "%s: bad argument", fn);
+    if (n_cams > 0 && ws_bytes < mm_resect_workspace_bytes(n_cams, prm->n_hyp, n_rows) + extra)
+        return mm_fail(ctx, MM_ERR_WORKSPACE, "%s: workspace too small", fn);
     if (!ctx) return MM_ERR_ARG;
     if (n_cams == 0) return MM_OK;
-    if (((uintptr_t)ws) & 7) return mm_fail(ctx, MM_ERR_ARG, "mm_resect_cameras: the workspace must be 8-byte aligned");
-    RsArgs a;
+    if (((uintptr_t)ws) & 7) return mm_fail(ctx, MM_ERR_ARG, "%s: the workspace must be 8-byte aligned", fn);
     a.X = X;
     a.obs = obs;
     a.pi = pi;
@@ -685,7 +1050,7 @@ extern "C" int mm_resect_cameras(mm_ctx *ctx, const double *K, const double *X, 
     a.n_rows = n_rows;
     a.n_cams = n_cams;
     a.n_hyp = prm->n_hyp;
-    a.min_rows = prm->min_rows < 12 ? 12 : prm->min_rows;
+    a.min_rows = prm->min_rows < row_floor ? row_floor : prm->min_rows;
     a.min_inliers = prm->min_inliers;
     a.refit_iters = prm->refit_iters;
     a.polish_iters = prm->polish_iters;
@@ -704,14 +1069,79 @@ extern "C" int mm_resect_cameras(mm_ctx *ctx, const double *K, const double *X, 
     a.rows = (int32_t *)w;
     w += rs_region((size_t)n_rows * sizeof(int32_t));
     a.mask = (uint8_t *)w;
+    w += rs_region((size_t)n_rows);
+    ws_end = w;
+    a.frame = nullptr;
+    a.plane = nullptr;
+    a.planar_tol2 = 0.0;
+    a.collinear_tol = 0.0;
     a.ext = extrinsics;
     a.cost = cost;
     a.inlier = inlier;
     a.info = info;
+    launch = true;
+    return MM_OK;
+}
+
+}  // namespace
+
+extern "C" int mm_resect_cameras(mm_ctx *ctx, const double *K, const double *X, int64_t P, const double *obs, const int32_t *pi,
+                                 int64_t O, const int32_t *cam_ptr, const int32_t *cam_obs, int64_t n_rows, int n_cams,
+                                 const uint8_t *pt_ok, const double *prior, const mm_resect_params *prm, double *extrinsics,
+                                 double *cost, uint8_t *inlier, int32_t *info, void *ws, size_t ws_bytes) {
+    RsArgs a;
+    char *ws_end;
+    bool launch;
+    const int rc = rs_setup(ctx, "mm_resect_cameras", K, X, P, obs, pi, O, cam_ptr, cam_obs, n_rows, n_cams, pt_ok, prior, prm, 12,
+                            extrinsics, cost, inlier, info, ws, ws_bytes, 0, true, a, ws_end, launch);
+    if (rc != MM_OK || !launch) return rc;
     const dim3 per_hyp((unsigned)n_cams, (unsigned)((a.n_hyp + 63) / 64));
     MM_LAUNCH(ctx, "rs_prepare_kernel", rs_prepare_kernel, dim3((unsigned)n_cams), dim3(RS_THREADS), 0, a);
     MM_LAUNCH(ctx, "rs_hypothesis_kernel", rs_hypothesis_kernel, per_hyp, dim3(64), 0, a);
     MM_LAUNCH(ctx, "rs_score_kernel", rs_score_kernel, per_hyp, dim3(64), 0, a);
-    MM_LAUNCH(ctx, "rs_finish_kernel", rs_finish_kernel, dim3((unsigned)n_cams), dim3(RS_THREADS), 0, a);
+    MM_LAUNCH(ctx, "rs_finish_kernel", rs_finish_kernel<false>, dim3((unsigned)n_cams), dim3(RS_THREADS), 0, a);
+    return MM_OK;
+}
+
+extern "C" size_t mm_resect_planar_workspace_bytes(int n_cams, int n_hyp, int64_t n_rows) {
+    const size_t nc = n_cams > 0 ? (size_t)n_cams : 0;
+    return mm_resect_workspace_bytes(n_cams, n_hyp, n_rows) + rs_region(nc * 9 * sizeof(double));
+}
+
+extern "C" int mm_resect_planar(mm_ctx *ctx, const double *K, const double *X, int64_t P, const double *obs, const int32_t *pi,
+                                int64_t O, const int32_t *cam_ptr, const int32_t *cam_obs, int64_t n_rows, int n_cams,
+                                const uint8_t *pt_ok, const double *prior, const mm_resect_planar_params *prm, double *extrinsics,
+                                double *cost, uint8_t *inlier, int32_t *info, double *plane, void *ws, size_t ws_bytes) {
+    mm_resect_params base;
+    bool tol_ok = false;
+    if (prm) {
+        base.n_hyp = prm->n_hyp;
+        base.min_rows = prm->min_rows;
+        base.min_inliers = prm->min_inliers;
+        base.refit_iters = prm->refit_iters;
+        base.polish_iters = prm->polish_iters;
+        base.reserved = 0;
+        base.seed = prm->seed;
+        base.cam_base = prm->cam_base;
+        base.threshold_px = prm->threshold_px;
+        tol_ok = prm->planar_tol >= 0.0 && prm->collinear_tol >= 0.0 && std::isfinite(prm->planar_tol) && std::isfinite(prm->collinear_tol);
+    }
+    if (n_cams > 0 && !plane) return mm_fail(ctx, MM_ERR_ARG, "mm_resect_planar: bad argument");
+    RsArgs a;
+    char *ws_end;
+    bool launch;
+    const size_t extra = rs_region((size_t)(n_cams > 0 ? n_cams : 0) * 9 * sizeof(double));
+    const int rc = rs_setup(ctx, "mm_resect_planar", K, X, P, obs, pi, O, cam_ptr, cam_obs, n_rows, n_cams, pt_ok, prior,
+                            prm ? &base : nullptr, 8, extrinsics, cost, inlier, info, ws, ws_bytes, extra, !prm || tol_ok, a, ws_end, launch);
+    if (rc != MM_OK || !launch) return rc;
+    a.frame = (double *)ws_end;
+    a.plane = plane;
+    a.planar_tol2 = prm->planar_tol * prm->planar_tol;
+    a.collinear_tol = prm->collinear_tol;
+    const dim3 per_hyp((unsigned)n_cams, (unsigned)((a.n_hyp + 63) / 64));
+    MM_LAUNCH(ctx, "rp_prepare_kernel", rp_prepare_kernel, dim3((unsigned)n_cams), dim3(RS_THREADS), 0, a);
+    MM_LAUNCH(ctx, "rp_hypothesis_kernel", rp_hypothesis_kernel, per_hyp, dim3(64), 0, a);
+    MM_LAUNCH(ctx, "rs_score_kernel", rs_score_kernel, per_hyp, dim3(64), 0, a);
+    MM_LAUNCH(ctx, "rp_finish_kernel", rs_finish_kernel<true>, dim3((unsigned)n_cams), dim3(RS_THREADS), 0, a);
     return MM_OK;
 }

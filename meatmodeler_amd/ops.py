@@ -215,39 +215,34 @@ def chain_poses(pairs, m, depth, R, t, info, E0=None, min_common=8, ctx=None):
 
 
 RESECT_TOO_FEW, RESECT_NO_MODEL, RESECT_WEAK, RESECT_MALFORMED = 1, 2, 4, 8      # MM_RESECT_* of include/meatmodeler.h
+RESECT_PLANAR = 16
 
 
-def resect_cameras(K, X, obs, pi, cam_ptr, cam_obs, pt_ok=None, prior=None, n_hyp=256, threshold_px=2.0, min_rows=12,
-                   min_inliers=12, refit_iters=2, polish_iters=8, seed=0, cam_base=0, inlier=None, ctx=None):
-    """Every camera registered against the 3-D points it observes (mm_resect_cameras): K 3 x 3 on the host; X [P, 3] f64, obs
-    [O, 2] f64 pixels, pi [O] i32, the camera CSR cam_ptr [n_cams+1] / cam_obs [n_rows] i32 (what a BADevice carries), optional
-    pt_ok [P] u8 / bool (0: the point is not used) and prior [n_cams, 3, 4] or [n_cams, 12] f64 (a non-finite one counts as
-    absent) -- device tensors
-    -> (extrinsics [n_cams, 3, 4] f64, cost [n_cams] f64, inlier [O] u8 -- written for every usable or malformed row of a camera,
-    zero (or what `inlier` held) elsewhere --, info [n_cams, 6] i32 = (RESECT_* flags, n_inliers, best_h (n_hyp: the prior, -1:
-    none), valid hypotheses, usable rows, accepted polish steps))."""
-    Kh = _host_f64(K, 9, "resect_cameras: K")
+def _resect_args(name, K, X, obs, pi, cam_ptr, cam_obs, pt_ok, prior, n_hyp, threshold_px, min_inliers, refit_iters, polish_iters,
+                 inlier):
+    """The argument checks and output buffers that resect_cameras and resect_planar share
+    -> (Kh, pt_ok, prior, ext, cost, inlier, info, (n_cams, P, O, n_rows))."""
+    Kh = _host_f64(K, 9, f"{name}: K")
     if not np.isfinite(Kh).all() or Kh[3] != 0 or Kh[6] != 0 or Kh[7] != 0 or Kh[8] != 1 or Kh[0] == 0 or Kh[4] == 0:
-        raise ValueError("resect_cameras: K must be finite, upper triangular with K[2, 2] = 1 and non-zero focal lengths")
+        raise ValueError(f"{name}: K must be finite, upper triangular with K[2, 2] = 1 and non-zero focal lengths")
     if not 1 <= int(n_hyp) <= 4096:
-        raise ValueError("resect_cameras: n_hyp must be in 1 .. 4096")
+        raise ValueError(f"{name}: n_hyp must be in 1 .. 4096")
     if not float(threshold_px) >= 0:
-        raise ValueError("resect_cameras: threshold_px must not be negative")
+        raise ValueError(f"{name}: threshold_px must not be negative")
     if not 0 <= int(refit_iters) <= 1000 or not 0 <= int(polish_iters) <= 1000 or int(min_inliers) < 0:
-        raise ValueError("resect_cameras: refit_iters and polish_iters must be in 0 .. 1000 and min_inliers not negative")
+        raise ValueError(f"{name}: refit_iters and polish_iters must be in 0 .. 1000 and min_inliers not negative")
     if X.dim() != 2 or X.shape[1] != 3 or obs.dim() != 2 or obs.shape[1] != 2 or tuple(pi.shape) != (obs.shape[0],) \
             or cam_ptr.dim() != 1 or cam_ptr.shape[0] < 1 or cam_obs.dim() != 1:
-        raise ValueError("resect_cameras: X [P, 3], obs [O, 2], pi [O], cam_ptr [n_cams+1] and cam_obs [n_rows] expected")
+        raise ValueError(f"{name}: X [P, 3], obs [O, 2], pi [O], cam_ptr [n_cams+1] and cam_obs [n_rows] expected")
     n_cams, P, O, n_rows = cam_ptr.shape[0] - 1, X.shape[0], obs.shape[0], cam_obs.shape[0]
     if pt_ok is not None:
         if tuple(pt_ok.shape) != (P,):
-            raise ValueError("resect_cameras: pt_ok [P] expected")
+            raise ValueError(f"{name}: pt_ok [P] expected")
         pt_ok = pt_ok.to(torch.uint8).contiguous()
     if prior is not None:
         if prior.numel() != 12 * n_cams:
-            raise ValueError("resect_cameras: prior [n_cams, 3, 4] expected")
+            raise ValueError(f"{name}: prior [n_cams, 3, 4] expected")
         prior = prior.to(torch.float64).contiguous()
-    ctx = ctx or default_context()
     d = X.device
     ext = torch.full((n_cams, 3, 4), math.nan, dtype=torch.float64, device=d)
     cost = torch.full((n_cams,), math.nan, dtype=torch.float64, device=d)
@@ -255,19 +250,87 @@ def resect_cameras(K, X, obs, pi, cam_ptr, cam_obs, pt_ok=None, prior=None, n_hy
     if inlier is None:
         inlier = torch.zeros(O, dtype=torch.uint8, device=d)
     elif inlier.dtype != torch.uint8 or tuple(inlier.shape) != (O,) or not inlier.is_contiguous():
-        raise ValueError("resect_cameras: inlier must be a contiguous u8 tensor [O]")
+        raise ValueError(f"{name}: inlier must be a contiguous u8 tensor [O]")
+    return Kh, pt_ok, prior, ext, cost, inlier, info, (n_cams, P, O, n_rows)
+
+
+def resect_cameras(K, X, obs, pi, cam_ptr, cam_obs, pt_ok=None, prior=None, n_hyp=256, threshold_px=2.0, min_rows=12,
+                   min_inliers=12, refit_iters=2, polish_iters=8, seed=0, cam_base=0, inlier=None, ctx=None, planar=None,
+                   planar_tol=1e-2, collinear_tol=1e-3):
+    """Every camera registered against the 3-D points it observes (mm_resect_cameras): K 3 x 3 on the host; X [P, 3] f64, obs
+    [O, 2] f64 pixels, pi [O] i32, the camera CSR cam_ptr [n_cams+1] / cam_obs [n_rows] i32 (what a BADevice carries), optional
+    pt_ok [P] u8 / bool (0: the point is not used) and prior [n_cams, 3, 4] or [n_cams, 12] f64 (a non-finite one counts as
+    absent) -- device tensors
+    -> (extrinsics [n_cams, 3, 4] f64, cost [n_cams] f64, inlier [O] u8 -- written for every usable or malformed row of a camera,
+    zero (or what `inlier` held) elsewhere --, info [n_cams, 6] i32 = (RESECT_* flags, n_inliers, best_h (n_hyp: the prior, -1:
+    none), valid hypotheses, usable rows, accepted polish steps)).
+    `planar`: None (default) -- that call alone; "auto" -- that call, then resect_planar on the same inlier buffer: a camera
+    whose points are coplanar (RESECT_PLANAR in the planar call's flags) takes the planar call's extrinsic, cost and info row,
+    every other camera keeps its own (selected on the device, nothing is read back); "only" -- the planar call alone, its
+    `plane` dropped.  planar_tol and collinear_tol go to resect_planar; min_rows goes to both calls, each with its own floor."""
+    if planar not in (None, "auto", "only"):
+        raise ValueError('resect_cameras: planar must be None, "auto" or "only"')
+    common = dict(pt_ok=pt_ok, prior=prior, n_hyp=n_hyp, threshold_px=threshold_px, min_rows=min_rows, min_inliers=min_inliers,
+                  refit_iters=refit_iters, polish_iters=polish_iters, seed=seed, cam_base=cam_base, ctx=ctx)
+    if planar == "only":
+        return resect_planar(K, X, obs, pi, cam_ptr, cam_obs, planar_tol=planar_tol, collinear_tol=collinear_tol, inlier=inlier,
+                             **common)[:4]
+    Kh, pt_ok, prior, ext, cost, inlier, info, (n_cams, P, O, n_rows) = _resect_args(
+        "resect_cameras", K, X, obs, pi, cam_ptr, cam_obs, pt_ok, prior, n_hyp, threshold_px, min_inliers, refit_iters, polish_iters,
+        inlier)
+    ctx = ctx or default_context()
     if n_cams == 0:
         return ext, cost, inlier, info
     assert X.dtype == torch.float64 and obs.dtype == torch.float64
     prm = _lib.ResectParams(int(n_hyp), int(min_rows), int(min_inliers), int(refit_iters), int(polish_iters), 0,
                             int(seed) & 0xFFFFFFFF, int(cam_base) & 0xFFFFFFFF, float(threshold_px))
     wsb = lib.mm_resect_workspace_bytes(n_cams, int(n_hyp), n_rows)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=d)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=X.device)
     ctx.check(lib.mm_resect_cameras(ctx.h, Kh.ctypes.data_as(_lib.c_f64p), ptr(X.contiguous()), P, ptr(obs.contiguous()),
                                     ptr(_i32(pi.contiguous())), O, ptr(_i32(cam_ptr.contiguous())), ptr(_i32(cam_obs.contiguous())),
                                     n_rows, n_cams, ptr(pt_ok), ptr(prior), C.byref(prm), ptr(ext), ptr(cost), ptr(inlier),
                                     ptr(info), ptr(ws), wsb), "mm_resect_cameras")
+    if planar == "auto":
+        common["ctx"] = ctx
+        pext, pcost, _, pinfo, _ = resect_planar(K, X, obs, pi, cam_ptr, cam_obs, planar_tol=planar_tol, collinear_tol=collinear_tol,
+                                                 inlier=inlier, **common)
+        took = (pinfo[:, 0] & RESECT_PLANAR) != 0
+        ext = torch.where(took[:, None, None], pext, ext)
+        cost = torch.where(took, pcost, cost)
+        info = torch.where(took[:, None], pinfo, info)
     return ext, cost, inlier, info
+
+
+def resect_planar(K, X, obs, pi, cam_ptr, cam_obs, pt_ok=None, prior=None, n_hyp=256, threshold_px=2.0, min_rows=8,
+                  min_inliers=12, refit_iters=2, polish_iters=8, seed=0, cam_base=0, planar_tol=1e-2, collinear_tol=1e-3,
+                  inlier=None, ctx=None):
+    """Every camera whose usable points are coplanar registered by a RANSAC homography between their plane and the calibrated
+    image (mm_resect_planar); arguments as resect_cameras takes them, planar_tol the largest thickness sqrt(l0 / l1) of a point
+    set that counts as a plane, collinear_tol the near-collinearity bound of a sampled triple
+    -> (extrinsics, cost, inlier, info, plane [n_cams, 6] f64 = (unit normal, normal . centroid, thickness, aspect)).  A camera
+    without RESECT_PLANAR in its flags was refused: extrinsic = the prior or NaN, cost NaN, and its bytes of `inlier` are left
+    as they were -- so a buffer that resect_cameras has filled can be handed on."""
+    Kh, pt_ok, prior, ext, cost, inlier, info, (n_cams, P, O, n_rows) = _resect_args(
+        "resect_planar", K, X, obs, pi, cam_ptr, cam_obs, pt_ok, prior, n_hyp, threshold_px, min_inliers, refit_iters, polish_iters,
+        inlier)
+    if not (float(planar_tol) >= 0 and math.isfinite(float(planar_tol)) and float(collinear_tol) >= 0
+            and math.isfinite(float(collinear_tol))):
+        raise ValueError("resect_planar: planar_tol and collinear_tol must be finite and not negative")
+    ctx = ctx or default_context()
+    plane = torch.full((n_cams, 6), math.nan, dtype=torch.float64, device=X.device)
+    if n_cams == 0:
+        return ext, cost, inlier, info, plane
+    assert X.dtype == torch.float64 and obs.dtype == torch.float64
+    prm = _lib.ResectPlanarParams(int(n_hyp), int(min_rows), int(min_inliers), int(refit_iters), int(polish_iters), 0,
+                                  int(seed) & 0xFFFFFFFF, int(cam_base) & 0xFFFFFFFF, float(threshold_px), float(planar_tol),
+                                  float(collinear_tol))
+    wsb = lib.mm_resect_planar_workspace_bytes(n_cams, int(n_hyp), n_rows)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=X.device)
+    ctx.check(lib.mm_resect_planar(ctx.h, Kh.ctypes.data_as(_lib.c_f64p), ptr(X.contiguous()), P, ptr(obs.contiguous()),
+                                   ptr(_i32(pi.contiguous())), O, ptr(_i32(cam_ptr.contiguous())), ptr(_i32(cam_obs.contiguous())),
+                                   n_rows, n_cams, ptr(pt_ok), ptr(prior), C.byref(prm), ptr(ext), ptr(cost), ptr(inlier),
+                                   ptr(info), ptr(plane), ptr(ws), wsb), "mm_resect_planar")
+    return ext, cost, inlier, info, plane
 
 
 # ------------------------------------------------------------------------------------------------ ORB

@@ -6,7 +6,8 @@ and key points stay in HBM and each stage is a few large launches instead of one
 Keyframe gating, calibration and PnP are outside the scope: the caller provides K and one extrinsic
 per frame (the reference gets them from calibrate / poseEstimation / adjustPose, processor.py:422-448) -- or, with
 `run(verify={...}, poses={...})`, K alone: the extrinsics are then recovered from the verified matches; with
-`run(resect={...})` every frame is registered once more against the triangulated points (a RANSAC resection).
+`run(resect={...})` every frame is registered once more against the triangulated points (a RANSAC resection, DESIGN.md 6f;
+`planar="auto"` adds the homography branch for coplanar points, 6g).
 """
 import ctypes as C
 import queue
@@ -54,7 +55,8 @@ def pose_options(poses):
     return dict(poses)
 
 
-RESECT_KEYS = ("n_hyp", "threshold_px", "min_rows", "min_inliers", "refit_iters", "polish_iters", "seed")
+RESECT_KEYS = ("n_hyp", "threshold_px", "min_rows", "min_inliers", "refit_iters", "polish_iters", "seed", "planar", "planar_tol",
+               "collinear_tol")
 
 
 def resect_options(resect):
@@ -569,7 +571,8 @@ class ClipPipeline:
         the triangulation every frame is resected against `points0` (under "multi_view" only against the tracks no test
         flagged), with the extrinsics in use -- given or recovered -- as the prior, so no frame ends with a higher MSAC cost
         than it came in with; the tracks are then triangulated again with the new poses and the adjustment starts from those.
-        The result gains `resect` = dict(extrinsics [F,3,4], cost [F], info [F,6], inliers_per_frame [F]); timer "resect"."""
+        Its key `planar` ("auto" / "only", with planar_tol and collinear_tol) sends frames whose points are coplanar through
+        the homography branch; without it exactly the one call of 6f is launched.  The result gains `resect` = dict(extrinsics [F,3,4], cost [F], info [F,6], inliers_per_frame [F]); timer "resect"."""
         verify = verify_options(verify)
         poses = pose_options(poses)
         resect = resect_options(resect)

@@ -365,7 +365,8 @@ def resectCameras(points_3D, points_2D, K, prior=None, **params):
     belongs to row i of the other); prior: optional [n, 3, 4] starting poses (a non-finite one counts as absent)
     -> (extrinsics [n, 3, 4] f64 -- [R|t] per frame, NaN where no pose was found --, masks: per frame the [n_f] bool inliers,
     info [n, 6] i32 as ops.resect_cameras returns it).  `params` as ops.resect_cameras takes them (n_hyp, threshold_px,
-    min_rows, min_inliers, refit_iters, polish_iters, seed, cam_base)."""
+    min_rows, min_inliers, refit_iters, polish_iters, seed, cam_base, and planar = None / "auto" / "only" with planar_tol and
+    collinear_tol: frames whose object points are coplanar, a chessboard's, need "auto" or "only")."""
     if len(points_3D) != len(points_2D):
         raise ValueError("resectCameras: points_3D and points_2D must have one entry per frame")
     X3 = [np.asarray(a, np.float64).reshape(-1, 3) for a in points_3D]
@@ -388,6 +389,56 @@ def resectCameras(points_3D, points_2D, K, prior=None, **params):
     ext, _, inlier, info = ops.resect_cameras(K, Xd, od, idx, torch.as_tensor(cam_ptr).to(dev), idx, prior=pr, **params)
     mask = inlier.cpu().numpy().astype(bool)
     return ext.cpu().numpy(), [mask[cam_ptr[f]:cam_ptr[f + 1]] for f in range(n)], info.cpu().numpy()
+
+
+def rotation_vector(R):
+    """The rotation vector (axis times angle, what cv2.Rodrigues returns for a matrix) of a 3 x 3 rotation, on the host."""
+    R = np.asarray(R, np.float64).reshape(3, 3)
+    w = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    sn, cs = 0.5 * np.linalg.norm(w), 0.5 * (np.trace(R) - 1.0)
+    th = math.atan2(sn, cs)
+    if sn > 1e-8:
+        return w * (th / (2.0 * sn))
+    if cs > 0.0:      # near the identity: R - R^T = 2 [w]x to first order
+        return 0.5 * w
+    # near a half turn: R + I = 2 a a^T; the largest column gives the axis, its sign does not matter at exactly pi
+    B = 0.5 * (R + np.eye(3))
+    k = int(np.argmax(np.diag(B)))
+    ax = B[:, k] / math.sqrt(max(B[k, k], 1e-300))
+    if w @ ax < 0.0:
+        ax = -ax
+    return ax * th
+
+
+def poseEstimationFromCorners(corners, pattern_shape, side_length, camera_intrinsic_matrix, **params):
+    """The part of the reference's poseEstimation (processor.py:145-187) that follows cv2.cornerSubPix: the pose of the camera
+    over a flat chessboard from its refined corners [x * y, 2] (any shape cv2 returns them in), pattern_shape = (x, y) and the
+    square's side_length, with the object points the reference builds (x along X, y along Z, Y = 0)
+    -> (rvec [3, 1], tvec [3, 1], extrinsic_matrix [3, 4], projection_matrix [3, 4]) or None when no pose was found: no
+    model at all, or one that fewer than min_inliers corners (default: half of them) agree with.  A list of corner arrays gives
+    a list of such results from one call.  The pose is a RANSAC homography polished on the reprojection error
+    (ops.resect_planar; `params` as it takes them).  It takes NO distortion coefficients: undistort the corners first
+    (cv2.undistortPoints with P = K) when the lens needs it."""
+    many = isinstance(corners, (list, tuple))
+    frames = [np.asarray(c, np.float64).reshape(-1, 2) for c in (corners if many else [corners])]
+    x, y = pattern_shape
+    objp = np.zeros((x * y, 3), np.float32)
+    grid = np.mgrid[0:x, 0:y].T.reshape(-1, 2) * side_length
+    objp[:, 0] = grid[:, 0]
+    objp[:, 2] = grid[:, 1]
+    if any(len(f) != x * y for f in frames):
+        raise ValueError("poseEstimationFromCorners: every frame needs pattern_shape[0] * pattern_shape[1] corners")
+    K = np.asarray(camera_intrinsic_matrix, np.float64).reshape(3, 3)
+    params.setdefault("min_inliers", (x * y + 1) // 2)
+    ext, _, info = resectCameras([objp.astype(np.float64)] * len(frames), frames, K, planar="only", **params)
+    refuse = ops.RESECT_TOO_FEW | ops.RESECT_NO_MODEL | ops.RESECT_WEAK
+    out = []
+    for E, row in zip(ext, info):
+        if not np.isfinite(E).all() or (row[0] & refuse) or not (row[0] & ops.RESECT_PLANAR):
+            out.append(None)
+            continue
+        out.append((rotation_vector(E[:, :3]).reshape(3, 1), E[:, 3].reshape(3, 1).copy(), E.copy(), K @ E))
+    return out if many else out[0]
 
 
 # ----------------------------------------------------------------------------------------------- pointTracking

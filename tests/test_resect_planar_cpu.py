@@ -1,0 +1,752 @@
+"""CPU: the definition of mm_resect_planar (include/meatmodeler.h) restated in NumPy, operation for operation, and checked
+against the truth and against the reference's own chessboard data; no device and no OpenCV.
+
+`resect_planar_numpy` follows the header in the order the kernels of csrc/resect.hip take (see test_resect_cameras_cpu, whose
+pieces it imports): the plane fit and every sum over the rows of a camera in the workgroup's order (`block_sum`), the hypothesis
+ranking over the rows ascending, every product-sum associated as the header writes it.  The GPU file compares integers exactly,
+provided no decision of a fixture sits on a rounding: the margins asserted by the tests at the end of this file.
+
+Measured here (NumPy, K = [[1500, 0, 960], [0, 1500, 540], [0, 0, 1]], the planar scene of test_resect_cameras_cpu -- a plane
+half a unit beside the optical axis, 5 units away, seen about 6 degrees above grazing -- as it is and rotated / shifted 104
+units away from the origin, alternating):
+  noise-free scenes, worst over 200: four points (samples that pass the collinearity rule) |R - R_true| 1.0e-08,
+  |t - t_true| 2.6e-07 (asserted at 2e-7, 5e-6); eight points 2.8e-13, 6.5e-12 (asserted at 1e-9);
+  0.5 px noise, the linear fit alone, rotation error in degrees median / max over 60 scenes:
+  n = 8: 0.30 / 4.4, n = 200: 0.039 / 0.13, n = 2000: 0.013 / 0.039;
+  160 inliers at 0.3 px + 96 uniform outliers, n_hyp 256, tau 2, two refits, eight polish trials, six seeds: 160 of 160 kept,
+  0 of 96 outliers kept, rotation within 0.0080 degrees;
+  g6 chessboard frames WITHOUT a prior: flags PLANAR, 12 inliers, the polished pose 8.2e-11 from the recorded `result`, half
+  the summed cost 2.00489 against the recorded 2.0049 (mm_resect_cameras gives NO_MODEL and NaN on this input).
+"""
+import ctypes as C
+import functools
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from test_resect_cameras_cpu import (K_SCENE, MALFORMED, NO_MODEL, TOO_FEW, UNTOUCHED, WEAK, block_sum, camera,  # noqa: E402
+                                     cayley_update, distance, g6_fixture, jacobi, k_inverse, lm_step, packed, pcg, polish_pass,
+                                     rel_gap, rodrigues, rot_err_deg, scene)
+
+PLANAR = 16
+PLANAR_TOL, COLLINEAR_TOL = 1e-2, 1e-3
+TRIPLES = ((0, 1, 2), (0, 1, 3), (0, 2, 3), (1, 2, 3))
+
+
+# ------------------------------------------------------------------------------------------------ the restatement
+
+def plane_fit(Xc):
+    """The prepare stage's arithmetic over the usable points Xc [n, 3] -> dict(cen, l [3] ascending, e1, e2, n, s)."""
+    n_use = len(Xc)
+    cen = block_sum(Xc) / float(n_use)
+    dx, dy, dz = Xc[:, 0] - cen[0], Xc[:, 1] - cen[1], Xc[:, 2] - cen[2]
+    cv = block_sum(np.stack([dx * dx, dx * dy, dx * dz, dy * dy, dy * dz, dz * dz], axis=1))
+    idx = [[0, 1, 2], [1, 3, 4], [2, 4, 5]]
+    G = [[np.array([cv[idx[r][c]]]) for c in range(3)] for r in range(3)]
+    V = jacobi(G, 3)
+    lam = [float(G[k][k][0]) for k in range(3)]
+    cols = [[float(V[r][k][0]) for r in range(3)] for k in range(3)]
+    for i, j in ((0, 1), (1, 2), (0, 1)):      # the stable exchange sort of the header
+        if lam[j] < lam[i]:
+            lam[i], lam[j] = lam[j], lam[i]
+            cols[i], cols[j] = cols[j], cols[i]
+    nrm, e1 = np.array(cols[0]), np.array(cols[2])
+    e2 = np.array([nrm[1] * e1[2] - nrm[2] * e1[1], nrm[2] * e1[0] - nrm[0] * e1[2], nrm[0] * e1[1] - nrm[1] * e1[0]])
+    pa = (dx * e1[0] + dy * e1[1]) + dz * e1[2]
+    pb = (dx * e2[0] + dy * e2[1]) + dz * e2[2]
+    s = 1.4142135623730951 / (block_sum(np.sqrt(pa * pa + pb * pb)[:, None])[0] / float(n_use))
+    return dict(cen=cen, l=np.array(lam), e1=e1, e2=e2, n=nrm, s=s)
+
+
+def plane_rows(Ki, pf, X, obs):
+    """(ma, mb, u, v) of the rows: the plane coordinates scaled by s and the calibrated pixel."""
+    cen, e1, e2, s = pf["cen"], pf["e1"], pf["e2"], pf["s"]
+    dx, dy, dz = X[:, 0] - cen[0], X[:, 1] - cen[1], X[:, 2] - cen[2]
+    ma = s * ((dx * e1[0] + dy * e1[1]) + dz * e1[2])
+    mb = s * ((dx * e2[0] + dy * e2[1]) + dz * e2[2])
+    u = (Ki[0] * obs[:, 0] + Ki[1] * obs[:, 1]) + Ki[2]
+    v = Ki[3] * obs[:, 1] + Ki[4]
+    return ma, mb, u, v
+
+
+def plane_terms(ma, mb, u, v):
+    """The 24 numbers one row adds to (S, Bu, Bv, C) -> [n, 24]."""
+    m = [ma, mb, np.ones(len(ma))]
+    r2 = u * u + v * v
+    out = np.zeros((len(ma), 24))
+    k = 0
+    for i in range(3):
+        for j in range(i, 3):
+            w = m[i] * m[j]
+            out[:, k], out[:, 6 + k], out[:, 12 + k], out[:, 18 + k] = w, u * w, v * w, r2 * w
+            k += 1
+    return out
+
+
+def triple_measure(ai, bi, aj, bj, ak, bk):
+    """(|cross|, longest squared side) of the triangle (i, j, k)."""
+    pa, pb, qa, qb, ra, rb = aj - ai, bj - bi, ak - ai, bk - bi, ak - aj, bk - bj
+    cr = pa * qb - pb * qa
+    d0, d1, d2 = pa * pa + pb * pb, qa * qa + qb * qb, ra * ra + rb * rb
+    lng = np.where(d0 > d1, d0, d1)
+    lng = np.where(lng > d2, lng, d2)
+    return np.abs(cr), lng
+
+
+def solve_planar(acc, pf):
+    """The reduced DLT one dimension down on a batch of sums acc [B, 24] -> (E [B, 12], ok [B])."""
+    acc = np.asarray(acc, float)
+    B = acc.shape[0]
+    cen, s = pf["cen"], pf["s"]
+    fr = [pf["e1"], pf["e2"], pf["n"]]
+    S, Bu, Bv, M = ([[None] * 3 for _ in range(3)] for _ in range(4))
+    k = 0
+    for i in range(3):
+        for j in range(i, 3):
+            S[i][j] = S[j][i] = acc[:, k]
+            Bu[i][j] = Bu[j][i] = acc[:, 6 + k]
+            Bv[i][j] = Bv[j][i] = acc[:, 12 + k]
+            M[i][j] = M[j][i] = acc[:, 18 + k]
+            k += 1
+    ok = np.ones(B, bool)
+    L = [[None] * 3 for _ in range(3)]
+    for j in range(3):
+        d = S[j][j]
+        for k in range(j):
+            d = d - L[j][k] * L[j][k]
+        ok &= np.isfinite(d) & (d > 1e-12 * S[j][j])
+        ljj = np.sqrt(d)
+        L[j][j] = ljj
+        for i in range(j + 1, 3):
+            v = S[i][j]
+            for k in range(j):
+                v = v - L[i][k] * L[j][k]
+            L[i][j] = v / ljj
+    Yu, Yv = [[None] * 3 for _ in range(3)], [[None] * 3 for _ in range(3)]
+    for i in range(3):
+        for cc in range(3):
+            vu, vv = Bu[i][cc], Bv[i][cc]
+            for k in range(i):
+                vu = vu - L[i][k] * Yu[k][cc]
+                vv = vv - L[i][k] * Yv[k][cc]
+            Yu[i][cc] = vu / L[i][i]
+            Yv[i][cc] = vv / L[i][i]
+    for i in range(3):
+        for j in range(i, 3):
+            tu = (Yu[0][i] * Yu[0][j] + Yu[1][i] * Yu[1][j]) + Yu[2][i] * Yu[2][j]
+            tv = (Yv[0][i] * Yv[0][j] + Yv[1][i] * Yv[1][j]) + Yv[2][i] * Yv[2][j]
+            M[i][j] = M[j][i] = (M[i][j] - tu) - tv
+    V3 = jacobi(M, 3)
+    ev = M[0][0]
+    h3 = [V3[r][0] for r in range(3)]
+    for cc in range(1, 3):
+        lower = M[cc][cc] < ev
+        ev = np.where(lower, M[cc][cc], ev)
+        h3 = [np.where(lower, V3[r][cc], h3[r]) for r in range(3)]
+    wu = [(Yu[i][0] * h3[0] + Yu[i][1] * h3[1]) + Yu[i][2] * h3[2] for i in range(3)]
+    wv = [(Yv[i][0] * h3[0] + Yv[i][1] * h3[1]) + Yv[i][2] * h3[2] for i in range(3)]
+    h1, h2 = [None] * 3, [None] * 3
+    for i in (2, 1, 0):
+        vu, vv = wu[i], wv[i]
+        for k in range(i + 1, 3):
+            vu = vu - L[k][i] * h1[k]
+            vv = vv - L[k][i] * h2[k]
+        h1[i] = vu / L[i][i]
+        h2[i] = vv / L[i][i]
+    sg = np.where(h3[2] < 0.0, -1.0, 1.0)
+    g = [[sg * h1[cc], sg * h2[cc], sg * h3[cc]] for cc in range(3)]      # g[cc] = column cc of H
+    g1, g2, g3 = g
+    sigma = (np.sqrt((g1[0] * g1[0] + g1[1] * g1[1]) + g1[2] * g1[2]) + np.sqrt((g2[0] * g2[0] + g2[1] * g2[1]) + g2[2] * g2[2])) / 2.0
+    g12 = [g1[1] * g2[2] - g1[2] * g2[1], g1[2] * g2[0] - g1[0] * g2[2], g1[0] * g2[1] - g1[1] * g2[0]]
+    A = [[g1[r], g2[r], g12[r] / sigma] for r in range(3)]
+    G = [[(A[0][r] * A[0][cc] + A[1][r] * A[1][cc]) + A[2][r] * A[2][cc] for cc in range(3)] for r in range(3)]
+    V = jacobi(G, 3)
+    dk, rt = [], []
+    for k in range(3):
+        lam = G[k][k]
+        ok &= np.isfinite(lam) & (lam > 0.0)
+        rt.append(np.sqrt(lam))
+        dk.append(1.0 / rt[k])
+    lo_, hi_ = np.where(rt[0] < rt[1], rt[0], rt[1]), np.where(rt[0] > rt[1], rt[0], rt[1])
+    lo_, hi_ = np.where(lo_ < rt[2], lo_, rt[2]), np.where(hi_ > rt[2], hi_, rt[2])
+    ok &= lo_ > 1e-4 * hi_
+    W = [[((V[i][0] * dk[0]) * V[j][0] + (V[i][1] * dk[1]) * V[j][1]) + (V[i][2] * dk[2]) * V[j][2] for j in range(3)]
+         for i in range(3)]
+    Rp = [[(A[r][0] * W[0][cc] + A[r][1] * W[1][cc]) + A[r][2] * W[2][cc] for cc in range(3)] for r in range(3)]
+    E = np.zeros((B, 12))
+    for r in range(3):
+        for cc in range(3):
+            E[:, 4 * r + cc] = (Rp[r][0] * fr[0][cc] + Rp[r][1] * fr[1][cc]) + Rp[r][2] * fr[2][cc]
+        E[:, 4 * r + 3] = g3[r] / (sigma * s) - ((E[:, 4 * r] * cen[0] + E[:, 4 * r + 1] * cen[1]) + E[:, 4 * r + 2] * cen[2])
+    ok &= np.isfinite(E).all(axis=1)
+    return E, ok
+
+
+def factor_from(x, tol):
+    """How many times x is away from tol, in either direction (inf for x = 0 against a positive tol)."""
+    if x == tol:
+        return 1.0
+    if x == 0.0 or tol == 0.0:
+        return math.inf
+    return max(x / tol, tol / x)
+
+
+def resect_planar_numpy(K, X, obs, pi, cam_ptr, cam_obs, pt_ok=None, prior=None, n_hyp=256, threshold_px=2.0, min_rows=8,
+                        min_inliers=12, refit_iters=2, polish_iters=8, seed=0, cam_base=0, planar_tol=PLANAR_TOL,
+                        collinear_tol=COLLINEAR_TOL, inlier=None):
+    """-> (extrinsics [n, 3, 4], cost [n], inlier [O] (UNTOUCHED, or what `inlier` held, where nothing is written), info [n, 6],
+    margins, plane [n, 6]): margins as resect_numpy gives them, and per camera `thickness`, the factor between the thickness and
+    planar_tol, and `collinear`, the smallest factor between a sampled triple's collinearity measure and collinear_tol."""
+    with np.errstate(all="ignore"):
+        return _resect_planar(np.asarray(K, float), np.asarray(X, float).reshape(-1, 3), np.asarray(obs, float).reshape(-1, 2),
+                              np.asarray(pi), np.asarray(cam_ptr), np.asarray(cam_obs), pt_ok, prior, n_hyp, float(threshold_px),
+                              max(int(min_rows), 8), min_inliers, refit_iters, polish_iters, seed, cam_base, float(planar_tol),
+                              float(collinear_tol), inlier)
+
+
+def _resect_planar(K, X, obs, pi, cam_ptr, cam_obs, pt_ok, prior, n_hyp, tau, min_rows, min_inliers, refit_iters, polish_iters,
+                   seed, cam_base, planar_tol, collinear_tol, inlier_in):
+    n_cams, P, O, n_rows = len(cam_ptr) - 1, len(X), len(obs), len(cam_obs)
+    Ki, tau2 = k_inverse(K), tau * tau
+    ext = np.full((n_cams, 12), np.nan)
+    cost_out = np.full(n_cams, np.nan)
+    inlier = np.full(O, UNTOUCHED, np.uint8) if inlier_in is None else np.array(inlier_in, np.uint8)
+    info = np.zeros((n_cams, 6), np.int32)
+    plane = np.full((n_cams, 6), np.nan)
+    margins = []
+    for c in range(n_cams):
+        mg = dict(px=math.inf, depth=math.inf, best=math.inf, decision=math.inf, thickness=math.inf, collinear=math.inf)
+        margins.append(mg)
+        lo = min(max(int(cam_ptr[c]), 0), n_rows)
+        hi = min(max(int(cam_ptr[c + 1]), lo), n_rows)
+        rows, marked, bad = [], [], 0
+        for q in range(lo, hi):
+            o = int(cam_obs[q])
+            if not 0 <= o < O:
+                bad += 1
+                continue
+            p = int(pi[o])
+            if not 0 <= p < P or not np.isfinite(obs[o]).all():
+                bad += 1
+                marked.append(o)
+                continue
+            if (pt_ok is None or pt_ok[p] != 0) and np.isfinite(X[p]).all():
+                rows.append(o)
+                marked.append(o)
+        rows = np.array(rows, np.int64)
+        n_use = len(rows)
+        Xc, oc = X[pi[rows]] if n_use else np.zeros((0, 3)), obs[rows] if n_use else np.zeros((0, 2))
+        pf = plane_fit(Xc)
+        cen, s, lam = pf["cen"], pf["s"], pf["l"]
+        plane[c, :3] = pf["n"]
+        plane[c, 3] = (pf["n"][0] * cen[0] + pf["n"][1] * cen[1]) + pf["n"][2] * cen[2]
+        plane[c, 4] = np.sqrt(np.where(lam[0] > 0.0, lam[0], 0.0) / lam[1])
+        plane[c, 5] = np.sqrt(lam[1] / lam[2])
+        flags = MALFORMED if bad else 0
+        runs = False
+        if n_use < min_rows:
+            flags |= TOO_FEW
+        elif not (np.isfinite(lam[2]) and lam[2] > 0.0) or not (lam[1] > 1e-12 * lam[2]):
+            flags |= PLANAR | NO_MODEL
+        else:
+            mg["thickness"] = factor_from(float(plane[c, 4]), planar_tol)
+            if lam[0] <= (planar_tol * planar_tol) * lam[1]:
+                flags |= PLANAR
+                runs = True
+        if flags & PLANAR:
+            inlier[np.array(marked, np.int64)] = 0
+        Pr = None
+        if prior is not None and np.isfinite(np.asarray(prior[c], float)).all():
+            Pr = np.asarray(prior[c], float).reshape(12).copy()
+        E, cost, n_in, best_h, n_valid, n_polish = None, math.nan, 0, -1, 0, 0
+
+        def msac(Ecand):
+            d2, inl, y2 = distance(camera(K, Ecand[None]), Xc, oc, tau2)
+            v = block_sum(np.stack([np.where(inl[0], d2[0], tau2), inl[0].astype(float)], axis=1))
+            return v[0], int(v[1]), d2[0], inl[0], y2[0]
+
+        def note(d2, y2):
+            fin = np.isfinite(d2)
+            if fin.any():
+                mg["px"] = min(mg["px"], float(np.abs(np.sqrt(d2[fin]) - tau).min()))
+            mg["depth"] = min(mg["depth"], float(np.abs(y2).min()))
+
+        if runs:
+            ma, mb, u, v = plane_rows(Ki, pf, Xc, oc)
+            terms = plane_terms(ma, mb, u, v)
+            h = np.arange(n_hyp, dtype=np.uint64)
+            base = pcg(pcg(np.uint64(seed & 0xFFFFFFFF) + pcg(np.uint64((cam_base + c) & 0xFFFFFFFF))) + h)
+            picks = np.zeros((n_hyp, 4), np.int64)
+            ok_pick = np.ones(n_hyp, bool)
+            for k in range(4):
+                chosen = np.full(n_hyp, -1, np.int64)
+                for t in range(8):
+                    i = ((pcg(base + np.uint64(8 * k + t)) * np.uint64(n_use)) >> np.uint64(32)).astype(np.int64)
+                    dup = (picks[:, :k] == i[:, None]).any(axis=1)
+                    chosen = np.where((chosen < 0) & ~dup, i, chosen)
+                ok_pick &= chosen >= 0
+                picks[:, k] = np.where(chosen < 0, 0, chosen)
+            acc = np.zeros((n_hyp, 24))
+            for k in range(4):
+                acc = acc + terms[picks[:, k]]
+            ok_tri = np.ones(n_hyp, bool)
+            for (i, j, k) in TRIPLES:
+                cr, lng = triple_measure(ma[picks[:, i]], mb[picks[:, i]], ma[picks[:, j]], mb[picks[:, j]], ma[picks[:, k]],
+                                         mb[picks[:, k]])
+                ok_tri &= cr > collinear_tol * lng
+                for hh in np.flatnonzero(ok_pick):
+                    if lng[hh] > 0.0:
+                        mg["collinear"] = min(mg["collinear"], factor_from(float(cr[hh] / lng[hh]), collinear_tol))
+            Eh, okh = solve_planar(acc, pf)
+            okh &= ok_pick & ok_tri & bool(np.isfinite(s) and np.isfinite(cen).all())
+            Eh[~okh] = np.nan
+            n_valid = int(okh.sum())
+            d2, inl, _ = distance(camera(K, Eh), Xc, oc, tau2)
+            ch = np.zeros(n_hyp)
+            for j in range(n_use):
+                ch = ch + np.where(inl[:, j], d2[:, j], tau2)
+            ch[~okh] = np.inf
+            fin = np.isfinite(ch)
+            if fin.any():
+                best_h = int(np.flatnonzero(fin & (ch == ch[fin].min()))[0])
+                others = np.sort(ch[fin])
+                if len(others) > 1:
+                    mg["best"] = rel_gap(others[0], others[1])
+                E = Eh[best_h].copy()
+                cost, n_in, d2w, _, y2w = msac(E)
+                note(d2w, y2w)
+            if Pr is not None:
+                cp, np_in, d2p, _, y2p = msac(Pr)
+                if np.isfinite(cp):
+                    if E is not None:
+                        mg["decision"] = min(mg["decision"], rel_gap(cp, cost))
+                    if E is None or cp < cost:
+                        E, cost, n_in, best_h = Pr.copy(), cp, np_in, n_hyp
+                        note(d2p, y2p)
+            if E is None:
+                flags |= NO_MODEL
+        if E is not None:
+            for _ in range(refit_iters):
+                if n_in < 4:
+                    break
+                _, _, _, inl, _ = msac(E)
+                acc = block_sum(np.where(inl[:, None], terms, 0.0))
+                En, okE = solve_planar(acc[None], pf)
+                cn, nn_in, d2n, _, y2n = msac(En[0])
+                if okE[0] and np.isfinite(cn) and not np.array_equal(En[0], E):      # (the same rows refit to the same bits)
+                    mg["decision"] = min(mg["decision"], rel_gap(cn, cost))
+                if okE[0] and np.isfinite(cn) and cn < cost:
+                    E, cost, n_in = En[0].copy(), cn, nn_in
+                    note(d2n, y2n)
+            if polish_iters > 0:
+                _, _, _, sel, _ = msac(E)
+                Ec, lam_, accepted = E.copy(), 1e-3, 0
+                v = polish_pass(K, Ec, Xc, oc, sel)
+                for _ in range(polish_iters):
+                    ok, e = lm_step(v, lam_)
+                    En = cayley_update(Ec, e)
+                    vn = polish_pass(K, En, Xc, oc, sel)
+                    if ok and vn[1] == 0.0 and np.isfinite(vn[0]) and vn[0] != 0.0:
+                        mg["decision"] = min(mg["decision"], rel_gap(vn[0], v[0]))
+                    accept = bool(ok and vn[1] == 0.0 and np.isfinite(vn[0]) and vn[0] < v[0])
+                    if accept:
+                        accepted += 1
+                        Ec, v = En, vn
+                    lam_ = max(lam_ / 10.0, 1e-12) if accept else lam_ * 10.0
+                if accepted > 0:
+                    cn, nn_in, d2n, _, y2n = msac(Ec)
+                    if np.isfinite(Ec).all() and np.isfinite(cn):
+                        mg["decision"] = min(mg["decision"], rel_gap(cn, cost))
+                        if cn < cost:
+                            E, cost, n_in, n_polish = Ec.copy(), cn, nn_in, accepted
+                            note(d2n, y2n)
+            if n_in < min_inliers:
+                flags |= WEAK
+            inlier[rows] = msac(E)[3].astype(np.uint8)
+            ext[c] = E
+            cost_out[c] = cost
+        elif Pr is not None:
+            ext[c] = Pr
+        info[c] = (flags, n_in, best_h, n_valid, n_use, n_polish)
+    return ext.reshape(n_cams, 3, 4), cost_out, inlier, info, margins, plane
+
+
+# ------------------------------------------------------------------------------------------------ scenes
+
+def moved(sc, w, shift):
+    """The scene with its world rotated by rodrigues(w) and shifted: X' = Rw X + shift, so R' = R Rw^T, t' = t - R' shift."""
+    Rw = rodrigues(np.asarray(w, float))
+    R2 = sc["R"] @ Rw.T
+    return dict(X=sc["X"] @ Rw.T + np.asarray(shift, float), obs=sc["obs"], R=R2, t=sc["t"] - R2 @ np.asarray(shift, float))
+
+
+FAR = ((0.7, -0.4, 0.5), (60.0, -80.0, 30.0))      # the tilted plane far from the origin: |shift| = 104
+
+
+def planar_scene(rng, n_in, n_out=0, noise=0.3, far=False):
+    sc = scene(rng, n_in, n_out, noise=noise, planar=True)
+    return moved(sc, *FAR) if far else sc
+
+
+def cube_scene(rng, n):
+    return scene(rng, n)
+
+
+def collinear_scene(rng, n):
+    sc = planar_scene(rng, n, far=True)
+    p0, d = sc["X"][0].copy(), sc["X"][1] - sc["X"][0]
+    sc["X"] = p0 + np.linspace(-1.0, 1.0, n)[:, None] * d
+    return sc
+
+
+def slab_scene(rng, n, thickness):
+    """The planar scene with its points spread uniformly over `thickness` times its width (2 units) along the normal."""
+    sc = scene(rng, n, planar=True)
+    sc["X"][:, 1] += thickness * 2.0 * rng.uniform(-0.5, 0.5, n)
+    Y = sc["X"] @ sc["R"].T + sc["t"]
+    px = Y @ K_SCENE.T
+    sc["obs"] = px[:, :2] / px[:, 2:3]
+    return sc
+
+
+POLISH = 2      # trial steps of the fixtures that are compared exactly: a converged polish decides on roundings
+BOUNDARY_ROWS = (0, 3, 4, 7, 8, 9, 63, 64, 65, 255, 256, 257, 300)
+BOUNDARY_HYP = (1, 63, 64, 65, 256)
+# Sampling keys chosen on the CPU so that the margins asserted at the end of this file hold for the restatement alone.
+ROW_SEED = {8: 1, 64: 1, 65: 2, 257: 8, 300: 3}      # by usable rows; 0 where not listed
+HYP_SEED = 2
+FIVE_SEED = 2
+G6_SEED = 4
+# A call with 256 hypotheses samples a thousand triples; under the default collinear_tol = 1e-3 some of them always lie within
+# a factor 10 of it, under 1e-6 none does for the keys above.  The random fixtures that are compared exactly run with that
+# value; the chessboard grid (exactly collinear or far from it) and the tests against the truth run with the default.
+FIXTURE_COLLINEAR_TOL = 1e-6
+DEFAULT_TOL_SEED = 258      # the one key in 0 .. 599 under which the 64-row fixture keeps the margins at the default 1e-3 too
+
+
+@functools.lru_cache(maxsize=None)
+def boundary_fixture(n):
+    """One camera over a far, tilted plane with n usable rows and three that are not (a masked point, a NaN point, both)."""
+    rng = np.random.default_rng(2000 + n)
+    sc = planar_scene(rng, n + 3, far=True)
+    X, obs, pi, cam_ptr, cam_obs = packed([sc], shuffle_seed=n)
+    pt_ok = np.ones(len(X), np.uint8)
+    pt_ok[[0, 2]] = 0
+    X[[1, 2]] = np.nan
+    return dict(args=(K_SCENE, X, obs, pi, cam_ptr, cam_obs), kw=dict(pt_ok=pt_ok, polish_iters=POLISH, collinear_tol=FIXTURE_COLLINEAR_TOL),
+                scene=sc)
+
+
+@functools.lru_cache(maxsize=None)
+def boundary_reference(n, n_hyp=64, seed=None):
+    fx = boundary_fixture(n)
+    return resect_planar_numpy(*fx["args"], n_hyp=n_hyp, seed=ROW_SEED.get(n, 0) if seed is None else seed, **fx["kw"])
+
+
+@functools.lru_cache(maxsize=None)
+def default_tol_reference():
+    """The 64-row fixture under the default collinear_tol, 64 hypotheses."""
+    fx = boundary_fixture(64)
+    return resect_planar_numpy(*fx["args"], n_hyp=64, seed=DEFAULT_TOL_SEED, **dict(fx["kw"], collinear_tol=COLLINEAR_TOL))
+
+
+@functools.lru_cache(maxsize=None)
+def five_cameras(with_prior):
+    """A planar camera with outliers (160 + 48); a cube camera (refused); a collinear one; a planar one with 7 usable rows of 9
+    (TOO_FEW); a planar one (far, tilted) with malformed rows and a masked point.  Four observations belong to no camera."""
+    rng = np.random.default_rng(17)
+    scs = [planar_scene(rng, 160, 48), cube_scene(rng, 40), collinear_scene(rng, 30), planar_scene(rng, 9), planar_scene(rng, 80, far=True)]
+    X, obs, pi, cam_ptr, cam_obs = packed(scs, shuffle_seed=5)
+    pt_ok = np.ones(len(X) + 4, np.uint8)
+    pt_ok[int(cam_ptr[3]) + 2] = 0                # camera 3: 9 rows, one masked, one NaN point -> 7 usable
+    X = np.concatenate([X, rng.uniform(-1, 1, (4, 3))])
+    X[int(cam_ptr[3]) + 5] = np.nan
+    obs = np.concatenate([obs, rng.uniform(0, 1000, (4, 2))])
+    pi = np.concatenate([pi, np.arange(len(X) - 4, len(X), dtype=np.int32)])
+    b = int(cam_ptr[4])
+    cam_obs = cam_obs.copy()
+    row_of = {int(o): q for q, o in enumerate(cam_obs)}
+    cam_obs[row_of[b + 3]] = len(obs) + 5         # an observation index out of range
+    cam_obs[row_of[b + 9]] = -1
+    pi[b + 17] = -2                               # a point index out of range
+    pi[b + 18] = len(X)
+    pt_ok[b + 30] = 0                             # a masked point: skipped, no flag
+    obs[b + 41, 1] = np.nan                       # a NaN pixel: malformed
+    prior = None
+    if with_prior:
+        prior = np.full((5, 12), np.nan)
+        for c in (0, 1, 3):
+            Rp = rodrigues(np.array([3e-4, -2e-4, 2.5e-4])) @ scs[c]["R"]
+            prior[c] = np.hstack([Rp, (scs[c]["t"] + np.array([1e-3, -5e-4, 2e-3]))[:, None]]).ravel()
+        prior[4, :11] = 1.0                       # (a prior with a NaN entry counts as absent)
+    return dict(args=(K_SCENE, X, obs, pi, cam_ptr, cam_obs), kw=dict(pt_ok=pt_ok, prior=prior, seed=FIVE_SEED, polish_iters=POLISH,
+                                                                     collinear_tol=FIXTURE_COLLINEAR_TOL), scenes=scs)
+
+
+@functools.lru_cache(maxsize=None)
+def five_reference(with_prior):
+    fx = five_cameras(with_prior)
+    return resect_planar_numpy(*fx["args"], **fx["kw"])
+
+
+@functools.lru_cache(maxsize=None)
+def g6_reference():
+    """The g6 chessboard frames WITHOUT a prior."""
+    fx = g6_fixture()
+    return resect_planar_numpy(*fx["args"], seed=G6_SEED, **fx["kw"])
+
+
+# ------------------------------------------------------------------------------------------------ symbols and sizes
+
+def test_symbols_struct_size_and_workspace_without_a_device():
+    from meatmodeler_amd import _lib, ops
+    assert {"mm_resect_planar", "mm_resect_planar_workspace_bytes"} <= set(_lib.SIGNATURES)
+    assert C.sizeof(_lib.ResectPlanarParams) == C.sizeof(_lib.ResectParams) + 16 == 56      # sizeof(mm_resect_planar_params)
+    assert callable(ops.resect_planar) and ops.RESECT_PLANAR == PLANAR
+
+    def up(x):
+        return (x + 255) // 256 * 256
+    for n_cams, n_hyp, n_rows in ((1, 1, 0), (3, 64, 700), (200, 256, 600000), (5, 4096, 13)):
+        want = _lib.lib.mm_resect_workspace_bytes(n_cams, n_hyp, n_rows) + up(n_cams * 72)
+        assert _lib.lib.mm_resect_planar_workspace_bytes(n_cams, n_hyp, n_rows) == want
+    assert _lib.lib.mm_resect_planar_workspace_bytes(0, 256, 0) == 0 and _lib.lib.mm_resect_planar_workspace_bytes(-1, -1, -1) == 0
+    # argument errors come back before any device is needed: no context, null pointers
+    prm = _lib.ResectPlanarParams(256, 8, 12, 2, 8, 0, 0, 0, 2.0, 1e-2, 1e-3)
+    Kh = np.ascontiguousarray(K_SCENE.ravel())
+    call = _lib.lib.mm_resect_planar
+    assert call(None, Kh.ctypes.data_as(_lib.c_f64p), None, 0, None, None, 0, None, None, 0, 1, None, None, C.byref(prm), None, None,
+                None, None, None, None, 0) == -1
+    assert call(None, Kh.ctypes.data_as(_lib.c_f64p), None, 0, None, None, 0, None, None, 0, 0, None, None, C.byref(prm), None, None,
+                None, None, None, None, 0) == -1      # (n_cams = 0 is a good call, but there is no context)
+    bad = _lib.ResectPlanarParams(256, 8, 12, 2, 8, 0, 0, 0, 2.0, -1.0, 1e-3)
+    assert call(None, Kh.ctypes.data_as(_lib.c_f64p), None, 0, None, None, 0, None, None, 0, 0, None, None, C.byref(bad), None, None,
+                None, None, None, None, 0) == -1
+
+
+# ------------------------------------------------------------------------------------------------ against the truth
+
+def linear_fit(sc, check_sample=False):
+    Ki = k_inverse(K_SCENE)
+    with np.errstate(all="ignore"):
+        pf = plane_fit(sc["X"])
+        ma, mb, u, v = plane_rows(Ki, pf, sc["X"], sc["obs"])
+        E, ok = solve_planar(block_sum(plane_terms(ma, mb, u, v))[None], pf)
+        good = True
+        if check_sample:
+            for (i, j, k) in TRIPLES:
+                cr, lng = triple_measure(ma[i], mb[i], ma[j], mb[j], ma[k], mb[k])
+                good = good and bool(cr > COLLINEAR_TOL * lng)
+    return E[0].reshape(3, 4), bool(ok[0]), good
+
+
+@pytest.mark.parametrize("n,bound_R,bound_t", [(4, 2e-7, 5e-6), (8, 1e-9, 1e-9)])
+def test_noise_free_points_recover_the_pose(n, bound_R, bound_t):
+    """Bounds: started at 1e-9, which eight points keep (worst of 200: 2.8e-13 on R, 6.5e-12 on t).  Four points measured 1.0e-8
+    on R and 2.6e-7 on t: a minimal sample may sit a factor 1e3 inside the collinearity rule and loses that much of what a
+    well-spread one reaches, and t is 100 units long in the shifted scenes; committed with a margin of 20 (2e-7, 5e-6).  A
+    four-point scene that the estimator's own collinearity rule rejects as a sample is redrawn: the estimator never fits one."""
+    rng = np.random.default_rng(5 + n)
+    worst_R = worst_t = 0.0
+    done = 0
+    while done < 200:
+        sc = planar_scene(rng, n, noise=0.0, far=bool(done % 2))
+        E, ok, good = linear_fit(sc, check_sample=(n == 4))
+        if not good:
+            continue
+        done += 1
+        assert ok
+        worst_R, worst_t = max(worst_R, np.abs(E[:, :3] - sc["R"]).max()), max(worst_t, np.abs(E[:, 3] - sc["t"]).max())
+    print(f"noise-free {n} points, worst of 200: |R - R_true| {worst_R:.2e}, |t - t_true| {worst_t:.2e}")
+    assert worst_R < bound_R and worst_t < bound_t
+
+
+@pytest.mark.parametrize("n,med_max,max_max", [(8, 0.6, 9.0), (200, 0.08, 0.26), (2000, 0.026, 0.08)])
+def test_linear_fit_under_half_a_pixel_of_noise(n, med_max, max_max):
+    """Bounds: about twice the figures of the module docstring (60 scenes are a small sample of a heavy-tailed error).  The
+    scene's plane is seen at a grazing angle of about six degrees, which is what makes eight noisy points a weak fit."""
+    rng = np.random.default_rng(100 + n)
+    errs = []
+    for k in range(60):
+        sc = planar_scene(rng, n, noise=0.5, far=bool(k % 2))
+        E, ok, _ = linear_fit(sc)
+        assert ok
+        errs.append(rot_err_deg(E[:, :3], sc["R"]))
+    print(f"n = {n}: rotation error median {np.median(errs):.3f} deg, max {max(errs):.3f} deg")
+    assert np.median(errs) < med_max and max(errs) < max_max
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_ransac_keeps_the_inliers_and_drops_the_outliers(seed):
+    """The rotation bound is about twice the worst of the six seeds (module docstring)."""
+    sc = planar_scene(np.random.default_rng(50), 160, 96, noise=0.3, far=bool(seed % 2))
+    X, obs, pi, cam_ptr, cam_obs = packed([sc])
+    ext, cost, inlier, info, _, plane = resect_planar_numpy(K_SCENE, X, obs, pi, cam_ptr, cam_obs, n_hyp=256, threshold_px=2.0,
+                                                            refit_iters=2, seed=seed)
+    err = rot_err_deg(ext[0][:, :3], sc["R"])
+    print(f"seed {seed}: {int(inlier[:160].sum())} of 160 inliers, {int(inlier[160:].sum())} of 96 outliers kept, rotation off by "
+          f"{err:.4f} deg, info {info[0].tolist()}, plane {plane[0].tolist()}")
+    assert info[0, 0] == PLANAR and inlier[:160].sum() == 160 and inlier[160:].sum() == 0 and err < 0.016
+    assert info[0, 1] == 160 and info[0, 4] == 256 and 0 <= info[0, 2] < 256
+
+
+# ------------------------------------------------------------------------------------------------ the reference's own data
+
+def test_g6_chessboard_frames_without_a_prior():
+    """The test that fails without the planar branch: mm_resect_cameras gives NO_MODEL and NaN on this input."""
+    fx = g6_fixture()
+    ext, cost, inlier, info, _, plane = g6_reference()
+    gap = np.abs(ext - fx["result"]).max()
+    print(f"g6 without a prior: |polished - result| = {gap:.2e}, half the summed cost {0.5 * cost.sum():.5f}, info {info.tolist()}")
+    assert (info[:, 0] == PLANAR).all() and (info[:, 1] == 12).all() and (info[:, 4] == 12).all() and (inlier == 1).all()
+    assert (info[:, 2] >= 0).all() and (info[:, 2] < 64).all()
+    assert gap <= 1e-8
+    assert abs(0.5 * cost.sum() - 2.0049) < 1e-4
+    # the board: y = 0, so the normal is the y axis (either sign), the offset 0, no thickness, sqrt(32 / 60) long
+    assert np.array_equal(np.abs(plane[:, :3]), np.tile([0.0, 1.0, 0.0], (5, 1))) and (plane[:, 3:5] == 0.0).all()
+    assert np.abs(plane[:, 5] - math.sqrt(32.0 / 60.0)).max() < 1e-15
+
+
+# ------------------------------------------------------------------------------------------------ verdicts, flags, the prior
+
+def one_camera(sc, **kw):
+    X, obs, pi, cam_ptr, cam_obs = packed([sc])
+    return resect_planar_numpy(K_SCENE, X, obs, pi, cam_ptr, cam_obs, n_hyp=64, **kw)
+
+
+def test_verdicts_one_camera_of_each_kind():
+    rng = np.random.default_rng(9)
+    ext, cost, inlier, info, _, plane = one_camera(cube_scene(rng, 40))
+    assert info[0].tolist() == [0, 0, -1, 0, 40, 0] and np.isnan(ext).all() and np.isnan(cost[0]) and (inlier == UNTOUCHED).all()
+    assert plane[0, 4] > 0.1
+    ext, cost, inlier, info, _, plane = one_camera(collinear_scene(rng, 30))
+    assert info[0].tolist() == [PLANAR | NO_MODEL, 0, -1, 0, 30, 0] and np.isnan(ext).all() and (inlier == 0).all()
+    sc = slab_scene(rng, 60, 0.1)
+    ext, cost, inlier, info, _, plane = one_camera(sc)
+    print(f"slab 0.1: thickness {plane[0, 4]:.4f}, aspect {plane[0, 5]:.3f}")
+    assert info[0, 0] == 0 and 0.02 < plane[0, 4] < 0.2 and (inlier == UNTOUCHED).all()
+    sc = slab_scene(rng, 60, 1e-6)
+    ext, cost, inlier, info, _, plane = one_camera(sc)
+    print(f"slab 1e-6: thickness {plane[0, 4]:.3e}, rotation off by {rot_err_deg(ext[0][:, :3], sc['R']):.2e} deg, info {info[0].tolist()}")
+    assert info[0, 0] == PLANAR and info[0, 1] == 60 and 1e-7 < plane[0, 4] < 1e-5 and rot_err_deg(ext[0][:, :3], sc["R"]) < 1e-3
+    # a unit normal, the offset of the plane y = 0.5 (thin slab around it)
+    assert abs(np.linalg.norm(plane[0, :3]) - 1.0) < 1e-14 and abs(abs(plane[0, 3]) - 0.5) < 1e-5
+    # planar_tol is the knob: the thick slab passes at 0.5
+    assert one_camera(slab_scene(np.random.default_rng(3), 60, 0.1), planar_tol=0.5)[3][0, 0] & PLANAR
+
+
+def test_five_camera_fixture_is_what_it_says():
+    for with_prior in (False, True):
+        fx = five_cameras(with_prior)
+        ext, cost, inlier, info, _, plane = five_reference(with_prior)
+        cam_ptr = fx["args"][4]
+        print(f"prior {with_prior}: info {info.tolist()}")
+        assert info[:, 0].tolist() == [PLANAR, 0, PLANAR | NO_MODEL, TOO_FEW, PLANAR | MALFORMED]
+        assert info[:, 4].tolist() == [208, 40, 30, 7, 80 - 6]
+        assert info[0, 1] == 160 and inlier[:160].sum() == 160 and inlier[160:208].sum() == 0 and info[4, 1] >= 72
+        for c in (0, 4):
+            assert rot_err_deg(ext[c][:, :3], fx["scenes"][c]["R"]) < 0.3, c
+        # refused cameras: nothing written; the collinear one: zeros
+        assert (inlier[int(cam_ptr[1]):int(cam_ptr[2])] == UNTOUCHED).all() and (inlier[int(cam_ptr[3]):int(cam_ptr[4])] == UNTOUCHED).all()
+        assert (inlier[int(cam_ptr[2]):int(cam_ptr[3])] == 0).all()
+        b = int(cam_ptr[4])
+        assert list(inlier[[b + 17, b + 18, b + 41]]) == [0, 0, 0] and list(inlier[[b + 3, b + 9, b + 30]]) == [UNTOUCHED] * 3
+        assert (inlier[-4:] == UNTOUCHED).all()
+        for c in (1, 2, 3):
+            assert np.isnan(cost[c]) and info[c, 1:4].tolist() == [0, -1, 0] and info[c, 5] == 0
+            if with_prior and c != 2:
+                assert np.array_equal(ext[c].ravel(), fx["kw"]["prior"][c])
+            else:
+                assert np.isnan(ext[c]).all()
+        if with_prior:
+            assert np.array_equal(ext[4], five_reference(False)[0][4])      # the prior with a NaN entry was absent
+
+
+def test_the_prior_never_loses_to_a_worse_model_and_loses_ties():
+    fx = boundary_fixture(64)
+    ext, cost, _, info, _, _ = boundary_reference(64)
+    kw = dict(fx["kw"], n_hyp=64, seed=ROW_SEED.get(64, 0))
+    again = resect_planar_numpy(*fx["args"], prior=ext.reshape(1, 12), **kw)
+    assert again[1][0] <= cost[0]
+    # the winning hypothesis itself as the prior ties and loses: best_h stays
+    raw = resect_planar_numpy(*fx["args"], **dict(kw, refit_iters=0, polish_iters=0))
+    tie = resect_planar_numpy(*fx["args"], prior=raw[0].reshape(1, 12), **dict(kw, refit_iters=0, polish_iters=0))
+    assert tie[3][0, 2] == raw[3][0, 2] < 64 and np.array_equal(tie[0], raw[0]) and tie[1][0] == raw[1][0]
+    # a far-off prior changes nothing
+    off = np.hstack([np.eye(3), np.array([[0.0], [0.0], [50.0]])]).reshape(1, 12)
+    far = resect_planar_numpy(*fx["args"], prior=off, **kw)
+    assert np.array_equal(far[0], ext) and np.array_equal(far[3], info)
+    # too few rows: the prior passes through, nothing is written
+    few = boundary_fixture(7)
+    got = resect_planar_numpy(*few["args"], n_hyp=64, prior=off, **few["kw"])
+    assert got[3][0, 0] == TOO_FEW and np.array_equal(got[0].reshape(1, 12), off) and np.isnan(got[1][0])
+    assert (got[2] == UNTOUCHED).all()
+
+
+def test_a_refused_camera_leaves_its_inlier_bytes_untouched():
+    fx = five_cameras(False)
+    O = len(fx["args"][2])
+    before = (np.arange(O) % 5 + 2).astype(np.uint8)
+    got = resect_planar_numpy(*fx["args"], inlier=before, **fx["kw"])
+    cam_ptr = fx["args"][4]
+    for c in (1, 3):
+        lo, hi = int(cam_ptr[c]), int(cam_ptr[c + 1])
+        assert np.array_equal(got[2][lo:hi], before[lo:hi])
+    assert np.array_equal(got[2][-4:], before[-4:])
+    assert (got[2][:int(cam_ptr[1])] <= 1).all()
+
+
+def test_rows_of_a_block_equal_the_whole_call_with_cam_base():
+    fx = five_cameras(False)
+    K, X, obs, pi, cam_ptr, cam_obs = fx["args"]
+    whole = five_reference(False)
+    part = resect_planar_numpy(K, X, obs, pi, cam_ptr[1:5], cam_obs, cam_base=1, **fx["kw"])
+    assert np.array_equal(part[0], whole[0][1:4], equal_nan=True) and np.array_equal(part[3], whole[3][1:4])
+    assert np.array_equal(part[5], whole[5][1:4], equal_nan=True)
+    last = resect_planar_numpy(K, X, obs, pi, cam_ptr[4:6], cam_obs, cam_base=4, **fx["kw"])
+    assert np.array_equal(last[0], whole[0][4:5]) and np.array_equal(last[3], whole[3][4:5]) and np.array_equal(last[1], whole[1][4:5])
+
+
+# ------------------------------------------------------------------------------------------------ margins of the exact fixtures
+
+def check_margins(name, ref, decisions=True):
+    for c, mg in enumerate(ref[4]):
+        print(f"{name} camera {c}: " + ", ".join(f"{k} {v:.3g}" for k, v in mg.items()))
+        assert mg["px"] >= 0.02, (name, c, mg)
+        assert mg["depth"] >= 1e-3, (name, c, mg)
+        assert mg["best"] >= 1e-9, (name, c, mg)
+        assert mg["decision"] >= 1e-9 or not decisions, (name, c, mg)
+        assert mg["thickness"] >= 10.0, (name, c, mg)
+        assert mg["collinear"] >= 10.0, (name, c, mg)
+
+
+@pytest.mark.parametrize("with_prior", (False, True))
+def test_margins_of_the_five_camera_fixture(with_prior):
+    """What makes exact comparison on the GPU legitimate: no row within 0.02 px of tau under the winning, refitted or polished
+    model, every y2 at least 1e-3 from zero, best and second-best hypothesis at least 1e-9 apart relatively, every accept /
+    reject decision at least 1e-9 relatively from a tie, every thickness a factor 10 from planar_tol, every sampled triple's
+    collinearity measure a factor 10 from collinear_tol."""
+    check_margins(f"five prior={with_prior}", five_reference(with_prior))
+
+
+def test_margins_of_the_g6_fixture():
+    """(g6 runs the eight trial steps to convergence: its last trials decide on roundings, so the GPU file compares its
+    accepted-step count and its pose with a tolerance, and everything else of it exactly.)"""
+    check_margins("g6", g6_reference(), decisions=False)
+
+
+@pytest.mark.parametrize("n", BOUNDARY_ROWS)
+def test_margins_of_the_row_fixtures(n):
+    check_margins(f"rows={n}", boundary_reference(n))
+
+
+def test_margins_of_the_default_tolerance_fixture():
+    check_margins("default collinear_tol", default_tol_reference())
+
+
+@pytest.mark.parametrize("n_hyp", BOUNDARY_HYP)
+def test_margins_of_the_hypothesis_count_fixtures(n_hyp):
+    check_margins(f"n_hyp={n_hyp}", boundary_reference(65, n_hyp, HYP_SEED))
