@@ -24,52 +24,40 @@ from .orb_pattern import brief_pattern
 
 
 VERIFY_KEYS = ("n_hyp", "threshold_px", "min_matches", "min_inliers", "refit_iters", "seed", "on_fail")
+POSE_KEYS = ("min_matches", "min_front_frac", "ambiguous_frac", "min_common", "E0")
+RESECT_KEYS = ("n_hyp", "threshold_px", "min_rows", "min_inliers", "refit_iters", "polish_iters", "seed", "planar", "planar_tol",
+               "collinear_tol")
+
+
+def _stage_options(stage, value, keys):
+    """An option of `run` that is None (the stage is off) or a dict with keys out of `keys`.  Returns it as a dict; anything
+    else, or an unknown key, raises ValueError."""
+    if value is None:
+        return None
+    if not isinstance(value, dict):
+        raise ValueError(f"{stage} must be None or a dict of " + ", ".join(keys))
+    unknown = set(value) - set(keys)
+    if unknown:
+        raise ValueError(f"{stage} takes {', '.join(keys)}; not {sorted(unknown)}")
+    return dict(value)
 
 
 def verify_options(verify):
     """`run(..., verify=)`: None (no verification) or a dict of the parameters of ops.verify_matches -- pair_base and ctx are
     the pipeline's own.  Returns it as a dict; an unknown key raises ValueError."""
-    if verify is None:
-        return None
-    if not isinstance(verify, dict):
-        raise ValueError("verify must be None or a dict of " + ", ".join(VERIFY_KEYS))
-    unknown = set(verify) - set(VERIFY_KEYS)
-    if unknown:
-        raise ValueError(f"verify takes {', '.join(VERIFY_KEYS)}; not {sorted(unknown)}")
-    return dict(verify)
-
-
-POSE_KEYS = ("min_matches", "min_front_frac", "ambiguous_frac", "min_common", "E0")
+    return _stage_options("verify", verify, VERIFY_KEYS)
 
 
 def pose_options(poses):
     """`run(..., poses=)`: None (the caller provides the extrinsics) or a dict of the parameters of ops.recover_poses and
     ops.chain_poses.  Returns it as a dict; an unknown key raises ValueError."""
-    if poses is None:
-        return None
-    if not isinstance(poses, dict):
-        raise ValueError("poses must be None or a dict of " + ", ".join(POSE_KEYS))
-    unknown = set(poses) - set(POSE_KEYS)
-    if unknown:
-        raise ValueError(f"poses takes {', '.join(POSE_KEYS)}; not {sorted(unknown)}")
-    return dict(poses)
-
-
-RESECT_KEYS = ("n_hyp", "threshold_px", "min_rows", "min_inliers", "refit_iters", "polish_iters", "seed", "planar", "planar_tol",
-               "collinear_tol")
+    return _stage_options("poses", poses, POSE_KEYS)
 
 
 def resect_options(resect):
     """`run(..., resect=)`: None (no resection) or a dict of the parameters of ops.resect_cameras -- the points, the prior,
     cam_base and ctx are the pipeline's own.  Returns it as a dict; an unknown key raises ValueError."""
-    if resect is None:
-        return None
-    if not isinstance(resect, dict):
-        raise ValueError("resect must be None or a dict of " + ", ".join(RESECT_KEYS))
-    unknown = set(resect) - set(RESECT_KEYS)
-    if unknown:
-        raise ValueError(f"resect takes {', '.join(RESECT_KEYS)}; not {sorted(unknown)}")
-    return dict(resect)
+    return _stage_options("resect", resect, RESECT_KEYS)
 
 
 class ClipPipeline:
@@ -257,8 +245,9 @@ class ClipPipeline:
         all-reduces the camera-side blocks exactly as the global adjustment does ("C5 sliding
         window: same, with F replaced by W"); the adjusted points of a window are re-assembled on every rank.
 
-        order = "wavefront": the windows are coloured so that windows of one colour share no camera (two colours for
-        stride >= window / 2: the even windows, then the odd ones, which start from both neighbours' results) and each
+        order = "wavefront": the windows (`window_schedule`, which every schedule takes them from) are coloured so that
+        windows of one colour share no camera (two colours for stride >= window / 2: the even windows, then the odd ones,
+        which start from both neighbours' results; a last window that ends off the stride grid may take a third) and each
         colour is one pass in which every window is solved WHOLE by one rank (round robin), the results of a pass being
         exchanged with one all-reduce of the touched cameras / points.  Windows of a pass are independent, so this
         scales with the number of GPUs instead of paying a collective per trust-region iteration of a 300-unknown
@@ -293,161 +282,125 @@ class ClipPipeline:
             raise ValueError("order must be 'sequential' or 'wavefront'")
         if boundary not in ("inside", "anchored"):
             raise ValueError("boundary must be 'inside' or 'anchored'")
-        if boundary == "anchored":
-            if order != "sequential" or batched or int(streams) > 1 or dist is not None:
-                raise ValueError("boundary='anchored' needs order='sequential' on one rank and one stream (no batched): "
-                                 "its windows read the cameras earlier windows settled")
-            return self._adjust_windows_anchored(out, K, extrinsics, window, stride, ftol, verbose, timers, max_nfev)
+        if boundary == "anchored" and (order != "sequential" or batched or int(streams) > 1 or dist is not None):
+            raise ValueError("boundary='anchored' needs order='sequential' on one rank and one stream (no batched): "
+                             "its windows read the cameras earlier windows settled")
         allreduce = parallel.AllReduce() if world > 1 else None
-        if order == "wavefront":
-            return self._adjust_windows_wavefront(out, K, extrinsics, window, stride, ftol, verbose, timers, allreduce,
-                                                  world, rank, streams, batched, max_nfev)
         F = int(np.asarray(extrinsics).shape[0])
-        tp, of_, ok = out["track_ptr_dev"], out["obs_frame_dev"], out["obs_kp_dev"]
-        xy = out["xy_dev"]
-        T = tp.shape[0] - 1
-        with np.errstate(all="ignore"):
-            cams = torch.as_tensor(frameParameters(np.asarray(extrinsics, float)[:, :3, :]).reshape(F, 6)).to(d)
-        pts = out["points0"].clone()
-        stats = []
-        if T == 0:
-            return dict(cams=cams, points=pts, windows=stats)
-        tp64 = tp.long()
-        first_f, last_f = of_[tp64[:-1]], of_[tp64[1:] - 1]
-        lens_all = tp64[1:] - tp64[:-1]
-        window = max(2, min(int(window), F))
-        his = list(range(window, F, max(1, int(stride)))) + [F]
-        t0 = time.perf_counter()
-        for hi in his:
-            lo = max(0, hi - window)
-            sel = torch.nonzero(self.window_selection(first_f, last_f, lo, hi, F)).reshape(-1)
-            P = int(sel.numel())
-            if P == 0:
-                continue
-            lens = lens_all[sel]
-            P_all, p_lo, p_hi = P, 0, P
-            if world > 1 and P >= 4 * world:
-                # this rank's contiguous share of the window's points (balanced by observations); tiny windows are
-                # solved redundantly on every rank (identical, deterministic) rather than with empty shards
-                cum = torch.cat([torch.zeros(1, dtype=torch.int64, device=d), torch.cumsum(lens, 0)])
-                bounds = parallel.split_by_weight(cum, world)
-                p_lo, p_hi = bounds[rank], bounds[rank + 1]
-                sel_all, sel = sel, sel[p_lo:p_hi]
-                lens = lens[p_lo:p_hi]
-                P = p_hi - p_lo
-            sharded = world > 1 and P_all >= 4 * world
-            # the selected tracks' observations, point-major (managePoints order; mm_flatten_tracks)
-            coords, fi, pi = ops.flatten_tracks(tp, of_, ok, xy, sel=sel, frame_offset=lo, ctx=self.ctx)
-            O = int(fi.numel())
-            pb = ops.BADevice(K, fi, pi, coords, hi - lo, P, d, self.ctx)
-            res = SchurTRF(pb, allreduce=allreduce if sharded else None).solve(
-                cams[lo:hi].contiguous(), pts[sel].contiguous(), ftol=ftol, max_nfev=max_nfev, verbose=verbose if rank == 0 else 0)
-            cams[lo:hi] = res.cams
-            if sharded:
-                buf = torch.zeros((P_all, 3), dtype=torch.float64, device=d)
-                buf[p_lo:p_hi] = res.pts
-                allreduce(buf)                                  # disjoint shards: the sum re-assembles the window
-                pts[sel_all] = buf
-                O_all = torch.tensor([float(O)], dtype=torch.float64, device=d)
-                allreduce(O_all)
-                O = int(O_all.item())
-            else:
-                pts[sel] = res.pts
-            stats.append(dict(lo=lo, hi=hi, points=P_all, observations=O, nfev=res.nfev, cost=res.cost,
-                              status=res.status))
-        self.ctx.sync()
-        if timers is not None:
-            timers["ba_windows"] = timers.get("ba_windows", 0.0) + (time.perf_counter() - t0) * 1e3
-        return dict(cams=cams, points=pts, windows=stats)
-
-    def _adjust_windows_anchored(self, out, K, extrinsics, window, stride, ftol, verbose, timers, max_nfev):
-        """adjust_windows(boundary="anchored"): free cameras lo .. hi - 1 (indices f - lo), fixed cameras 0 .. lo - 1
-        (indices W + f, the current values), the finished tracks last observed at or after lo."""
-        d = self.device
-        F = int(np.asarray(extrinsics).shape[0])
-        tp, of_, ok = out["track_ptr_dev"], out["obs_frame_dev"], out["obs_kp_dev"]
-        xy = out["xy_dev"]
-        T = tp.shape[0] - 1
-        with np.errstate(all="ignore"):
-            cams = torch.as_tensor(frameParameters(np.asarray(extrinsics, float)[:, :3, :]).reshape(F, 6)).to(d)
-        pts = out["points0"].clone()
-        stats = []
-        if T == 0:
-            return dict(cams=cams, points=pts, windows=stats)
-        tp64 = tp.long()
-        first_f, last_f = of_[tp64[:-1]], of_[tp64[1:] - 1]
-        window = max(2, min(int(window), F))
-        his = list(range(window, F, max(1, int(stride)))) + [F]
-        t0 = time.perf_counter()
-        for hi in his:
-            lo = max(0, hi - window)
-            W = hi - lo
-            sel = torch.nonzero(self.window_selection_anchored(first_f, last_f, lo, hi, F)).reshape(-1)
-            P = int(sel.numel())
-            if P == 0:
-                continue
-            # managePoints order; frame indices come back as obs_frame - lo: the cameras before the window (negative)
-            # become fixed camera W + f
-            coords, fi, pi = ops.flatten_tracks(tp, of_, ok, xy, sel=sel, frame_offset=lo, ctx=self.ctx)
-            O = int(fi.numel())
-            n_fixed = 0
-            if lo > 0:
-                fi = torch.where(fi < 0, fi + (lo + W), fi).contiguous()
-                n_fixed = int(torch.unique(fi[fi >= W]).numel())
-                pb = ops.BADevice(K, fi, pi, coords, W, P, d, self.ctx, fixed_cams=cams[:lo].clone())
-            else:
-                pb = ops.BADevice(K, fi, pi, coords, W, P, d, self.ctx)
-            res = SchurTRF(pb).solve(cams[lo:hi].contiguous(), pts[sel].contiguous(), ftol=ftol, max_nfev=max_nfev,
-                                     verbose=verbose)
-            cams[lo:hi] = res.cams
-            pts[sel] = res.pts
-            stats.append(dict(lo=lo, hi=hi, points=P, observations=O, fixed_cameras=n_fixed, nfev=res.nfev, cost=res.cost,
-                              status=res.status))
-        self.ctx.sync()
-        if timers is not None:
-            timers["ba_windows"] = timers.get("ba_windows", 0.0) + (time.perf_counter() - t0) * 1e3
-        return dict(cams=cams, points=pts, windows=stats)
-
-    def _window_problem(self, out, first_f, last_f, lens_all, tp64, lo, hi, F, ctx=None):
-        """Selection + managePoints-order flattening of one window on the device -> (sel, fi, pi, coords, P, O)."""
-        d = self.device
-        of_, ok, xy = out["obs_frame_dev"], out["obs_kp_dev"], out["xy_dev"]
-        sel = torch.nonzero(self.window_selection(first_f, last_f, lo, hi, F)).reshape(-1)
-        P = int(sel.numel())
-        if P == 0:
-            return sel, None, None, None, 0, 0
-        # (mm_flatten_offsets + mm_flatten_tracks: the window's tracks, frame indices relative to the window)
-        coords, fi, pi = ops.flatten_tracks(out["track_ptr_dev"], of_, ok, xy, sel=sel, frame_offset=lo, ctx=ctx or self.ctx)
-        return sel, fi, pi, coords, P, int(fi.numel())
-
-    def _adjust_windows_wavefront(self, out, K, extrinsics, window, stride, ftol, verbose, timers, allreduce, world, rank,
-                                  streams=1, batched=False, max_nfev=None):
-        d = self.device
-        F = int(np.asarray(extrinsics).shape[0])
-        tp, of_ = out["track_ptr_dev"], out["obs_frame_dev"]
-        T = tp.shape[0] - 1
-        with np.errstate(all="ignore"):
-            cams = torch.as_tensor(frameParameters(np.asarray(extrinsics, float)[:, :3, :]).reshape(F, 6)).to(d)
-        pts = out["points0"].clone()
+        cams, pts, first_f, last_f, lens_all, T = self._windows_prologue(out, extrinsics, F)
         if T == 0:
             return dict(cams=cams, points=pts, windows=[])
-        tp64 = tp.long()
-        first_f, last_f = of_[tp64[:-1]], of_[tp64[1:] - 1]
-        lens_all = tp64[1:] - tp64[:-1]
-        window = max(2, min(int(window), F))
-        his = list(range(window, F, max(1, int(stride)))) + [F]
-        wins = [(max(0, hi - window), hi) for hi in his]
-        # greedy colouring in window order: a colour's windows share no camera
+        wins, colours = self.window_schedule(F, window, stride)
+        t0 = time.perf_counter()
+        if order == "wavefront":
+            cams, pts, table = self._windows_wavefront(out, K, cams, pts, first_f, last_f, wins, colours, ftol, verbose,
+                                                       allreduce, world, rank, streams, batched, max_nfev)
+        else:
+            stats = []
+            for lo, hi in wins:
+                sel = sel_all = self._window_tracks(first_f, last_f, lo, hi, F, boundary)
+                P_all = int(sel.numel())
+                if P_all == 0:
+                    continue
+                sharded = world > 1 and P_all >= 4 * world
+                if sharded:
+                    # this rank's contiguous share of the window's points (balanced by observations); tiny windows are
+                    # solved redundantly on every rank (identical, deterministic) rather than with empty shards
+                    cum = torch.cat([torch.zeros(1, dtype=torch.int64, device=d), torch.cumsum(lens_all[sel], 0)])
+                    bounds = parallel.split_by_weight(cum, world)
+                    p_lo, p_hi = bounds[rank], bounds[rank + 1]
+                    sel = sel[p_lo:p_hi]
+                pb, n_fixed = self._window_problem(out, K, cams, sel, lo, hi, boundary, self.ctx)
+                O = pb.O
+                res = SchurTRF(pb, allreduce=allreduce if sharded else None).solve(
+                    cams[lo:hi].contiguous(), pts[sel].contiguous(), ftol=ftol, max_nfev=max_nfev,
+                    verbose=verbose if rank == 0 else 0)
+                cams[lo:hi] = res.cams
+                if sharded:
+                    buf = torch.zeros((P_all, 3), dtype=torch.float64, device=d)
+                    buf[p_lo:p_hi] = res.pts
+                    allreduce(buf)                                  # disjoint shards: the sum re-assembles the window
+                    pts[sel_all] = buf
+                    O_all = torch.tensor([float(O)], dtype=torch.float64, device=d)
+                    allreduce(O_all)
+                    O = int(O_all.item())
+                else:
+                    pts[sel] = res.pts
+                st = dict(lo=lo, hi=hi, points=P_all, observations=O)
+                if boundary == "anchored":
+                    st["fixed_cameras"] = n_fixed
+                stats.append(dict(st, nfev=res.nfev, cost=res.cost, status=res.status))
+        self.ctx.sync()
+        if timers is not None:
+            timers["ba_windows"] = timers.get("ba_windows", 0.0) + (time.perf_counter() - t0) * 1e3
+        if order == "wavefront":
+            stats = [dict(lo=wins[k][0], hi=wins[k][1], points=int(r[0]), observations=int(r[1]), nfev=int(r[2]),
+                          status=int(r[3]), cost=float(r[4]), colour=colours[k])
+                     for k, r in enumerate(table.cpu().numpy()) if r[0] > 0]
+        return dict(cams=cams, points=pts, windows=stats)
+
+    @staticmethod
+    def window_schedule(n_frames, window, stride):
+        """The windows of `adjust_windows`, on the host -> (wins, colours).  wins: (lo, hi) for hi = window, window + stride,
+        ..., n_frames with lo = max(0, hi - window); the window is clamped to 2 .. n_frames keyframes, the stride to at least
+        1, and the last window ends at n_frames.  colours: greedy colouring in window order -- a window takes the first
+        colour whose last window ended at or before its lo -- so a colour's windows share no camera (read by the wavefront
+        schedule only)."""
+        window = max(2, min(int(window), n_frames))
+        wins = [(max(0, hi - window), hi) for hi in list(range(window, n_frames, max(1, int(stride)))) + [n_frames]]
         colour_end, colours = [], []
         for lo, hi in wins:
             c = next((k for k, e in enumerate(colour_end) if e <= lo), len(colour_end))
-            if c == len(colour_end):
-                colour_end.append(hi)
-            else:
-                colour_end[c] = hi
+            colour_end[c:c + 1] = [hi]                # (a new colour when c == len(colour_end))
             colours.append(c)
-        t0 = time.perf_counter()
-        table = torch.zeros((len(wins), 5), dtype=torch.float64, device=d)      # points, observations, nfev, status, cost
+        return wins, colours
+
+    def _windows_prologue(self, out, extrinsics, F):
+        """What every schedule starts from -> (cams [F,6], pts [T,3] (a copy of points0), first_f, last_f (first / last frame
+        of every track), lens_all (observations per track), T); without tracks the last four are None, None, None, 0."""
+        tp, of_ = out["track_ptr_dev"], out["obs_frame_dev"]
+        with np.errstate(all="ignore"):
+            cams = torch.as_tensor(frameParameters(np.asarray(extrinsics, float)[:, :3, :]).reshape(F, 6)).to(self.device)
+        pts = out["points0"].clone()
+        T = tp.shape[0] - 1
+        if T == 0:
+            return cams, pts, None, None, None, 0
+        tp64 = tp.long()
+        return cams, pts, of_[tp64[:-1]], of_[tp64[1:] - 1], tp64[1:] - tp64[:-1], T
+
+    def _window_tracks(self, first_f, last_f, lo, hi, F, boundary="inside"):
+        """Indices of the tracks the window [lo, hi) adjusts (`window_selection` / `window_selection_anchored`)."""
+        select = self.window_selection_anchored if boundary == "anchored" else self.window_selection
+        return torch.nonzero(select(first_f, last_f, lo, hi, F)).reshape(-1)
+
+    def _window_flatten(self, out, sel, lo, hi, boundary="inside", ctx=None):
+        """The observations of the tracks `sel`, point-major (managePoints order; mm_flatten_offsets + mm_flatten_tracks), frame
+        indices relative to the window -> (fi, pi, coords, n_fixed).  Anchored: the cameras before the window (negative
+        indices) become the fixed cameras W + f, and n_fixed counts the distinct ones observed."""
+        coords, fi, pi = ops.flatten_tracks(out["track_ptr_dev"], out["obs_frame_dev"], out["obs_kp_dev"], out["xy_dev"], sel=sel,
+                                            frame_offset=lo, ctx=ctx or self.ctx)
+        n_fixed = 0
+        if boundary == "anchored" and lo > 0:
+            W = hi - lo
+            fi = torch.where(fi < 0, fi + (lo + W), fi).contiguous()
+            n_fixed = int(torch.unique(fi[fi >= W]).numel())
+        return fi, pi, coords, n_fixed
+
+    def _window_problem(self, out, K, cams, sel, lo, hi, boundary="inside", ctx=None):
+        """The bundle adjustment problem of the tracks `sel` in the window [lo, hi) -> (BADevice, n_fixed): free
+        cameras lo .. hi - 1 (indices f - lo); anchored, and lo > 0: fixed cameras 0 .. lo - 1 at their current values."""
+        ctx = ctx or self.ctx
+        fi, pi, coords, n_fixed = self._window_flatten(out, sel, lo, hi, boundary, ctx)
+        fixed = dict(fixed_cams=cams[:lo].clone()) if boundary == "anchored" and lo > 0 else {}
+        return ops.BADevice(K, fi, pi, coords, hi - lo, int(sel.numel()), self.device, ctx, **fixed), n_fixed
+
+    def _windows_wavefront(self, out, K, cams, pts, first_f, last_f, wins, colours, ftol, verbose, allreduce, world, rank,
+                           streams, batched, max_nfev):
+        """adjust_windows(order="wavefront") between the prologue and the epilogue -> (cams, pts, table [windows, 5]: points,
+        observations, nfev, status, cost of every window, all-reduced)."""
+        d = self.device
+        F, T = cams.shape[0], pts.shape[0]
+        table = torch.zeros((len(wins), 5), dtype=torch.float64, device=d)
         # Windows of a pass are independent AND small (a 300-unknown reduced system keeps 16 workgroups busy): this rank
         # solves up to `streams` of them at once, each on its own HIP stream with its own library context, driven by its
         # own host thread (mm_ba_trf blocks in C with the GIL released).  Every window still runs the same code on the
@@ -459,19 +412,25 @@ class ClipPipeline:
                 st = torch.cuda.Stream(device=d)
                 slots.put((st, _lib.Context(d, st)))
 
+        def window_problem(k, ctx):         # -> (sel, BADevice; None for an empty window); the boundary is "inside"
+            lo, hi = wins[k]
+            sel = self._window_tracks(first_f, last_f, lo, hi, F)
+            if int(sel.numel()) == 0:
+                return sel, None
+            return sel, self._window_problem(out, K, None, sel, lo, hi, ctx=ctx)[0]
+
         def solve_window(k, ctx, cams, pts, cams_upd, cam_mask, pts_upd, pt_mask):
             lo, hi = wins[k]
-            sel, fi, pi, coords, P, O = self._window_problem(out, first_f, last_f, lens_all, tp64, lo, hi, F, ctx)
-            if P == 0:
+            sel, pb = window_problem(k, ctx)
+            if pb is None:
                 return
-            pb = ops.BADevice(K, fi, pi, coords, hi - lo, P, d, ctx)
             res = SchurTRF(pb).solve(cams[lo:hi].contiguous(), pts[sel].contiguous(), ftol=ftol, max_nfev=max_nfev,
                                      verbose=verbose if rank == 0 and n_streams == 1 else 0)
             cams_upd[lo:hi] = res.cams
             cam_mask[lo:hi] = 1.0
             pts_upd[sel] = res.pts
             pt_mask[sel] = 1.0
-            table[k] = torch.tensor([P, O, res.nfev, res.status, res.cost], dtype=torch.float64, device=d)
+            table[k] = torch.tensor([pb.P, pb.O, res.nfev, res.status, res.cost], dtype=torch.float64, device=d)
 
         def solve_window_on_slot(k, *state):
             slot = slots.get()
@@ -482,7 +441,7 @@ class ClipPipeline:
             finally:
                 slots.put(slot)
 
-        for c in range(len(colour_end)):
+        for c in range(max(colours) + 1):
             mine = [k for j, k in enumerate(k for k, cc in enumerate(colours) if cc == c) if j % world == rank]
             cams_upd, pts_upd = torch.zeros_like(cams), torch.zeros_like(pts)
             cam_mask = torch.zeros(F, dtype=torch.float64, device=d)
@@ -493,21 +452,19 @@ class ClipPipeline:
                 items = []
                 for k in mine:
                     lo, hi = wins[k]
-                    sel, fi, pi, coords, P, O = self._window_problem(out, first_f, last_f, lens_all, tp64, lo, hi, F)
-                    if P == 0:
-                        continue
-                    pb = ops.BADevice(K, fi, pi, coords, hi - lo, P, d, self.ctx)
-                    items.append((k, sel, pb, cams[lo:hi].contiguous(), pts[sel].contiguous(), P, O))
+                    sel, pb = window_problem(k, self.ctx)
+                    if pb is not None:
+                        items.append((k, sel, pb, cams[lo:hi].contiguous(), pts[sel].contiguous()))
                 reps, _ = ops.trf_solve_batched([it[2] for it in items], [it[3] for it in items], [it[4] for it in items],
                                                 ftol, 1e-8, 1e-8, max_nfev=max_nfev, ctx=self.ctx)
                 rows, ks = [], []
-                for (k, sel, pb, cw, pw, P, O), rep in zip(items, reps):
+                for (k, sel, pb, cw, pw), rep in zip(items, reps):
                     lo, hi = wins[k]
                     cams_upd[lo:hi] = cw
                     cam_mask[lo:hi] = 1.0
                     pts_upd[sel] = pw
                     pt_mask[sel] = 1.0
-                    rows.append([P, O, rep.nfev, rep.status, rep.cost])
+                    rows.append([pb.P, pb.O, rep.nfev, rep.status, rep.cost])
                     ks.append(k)
                 if ks:
                     table[torch.tensor(ks, device=d)] = torch.tensor(rows, dtype=torch.float64, device=d)
@@ -526,13 +483,7 @@ class ClipPipeline:
             pts = torch.where(pt_mask[:, None] > 0, pts_upd, pts)
         if allreduce is not None:
             allreduce(table)
-        self.ctx.sync()
-        if timers is not None:
-            timers["ba_windows"] = timers.get("ba_windows", 0.0) + (time.perf_counter() - t0) * 1e3
-        tab = table.cpu().numpy()
-        stats = [dict(lo=wins[k][0], hi=wins[k][1], points=int(r[0]), observations=int(r[1]), nfev=int(r[2]), status=int(r[3]),
-                      cost=float(r[4]), colour=colours[k]) for k, r in enumerate(tab) if r[0] > 0]
-        return dict(cams=cams, points=pts, windows=stats)
+        return cams, pts, table
 
     @staticmethod
     def tracks_to_host(out):
@@ -672,13 +623,19 @@ class ClipPipeline:
             toc("poses")
         else:
             ext = np.asarray(extrinsics, float)[:, :3, :]
-        proj = np.einsum("ij,fjk->fik", np.asarray(K, float), ext)   # K [R|t], processor.py:184,448
-        tic("triangulate")
-        if triangulation == "multi_view":
-            X, quality, flags = self.triangulate_multi_view(track_ptr, obs_frame, obs_kp, xy_dev, proj, **(cull or {}))
-        else:
-            X = self.triangulate(track_ptr, obs_frame, obs_kp, xy_dev, proj)
-        toc("triangulate")
+
+        def triangulated(ext):
+            """(points, quality, flags) of the linked tracks under the extrinsics `ext`; two-view has no quality or flags."""
+            proj = np.einsum("ij,fjk->fik", np.asarray(K, float), ext)   # K [R|t], processor.py:184,448
+            tic("triangulate")
+            if triangulation == "multi_view":
+                res = self.triangulate_multi_view(track_ptr, obs_frame, obs_kp, xy_dev, proj, **(cull or {}))
+            else:
+                res = self.triangulate(track_ptr, obs_frame, obs_kp, xy_dev, proj), None, None
+            toc("triangulate")
+            return res
+
+        X, quality, flags = triangulated(ext)
         resected = None
         if resect is not None and track_ptr.shape[0] > 1:
             tic("resect")
@@ -687,13 +644,7 @@ class ClipPipeline:
             resected.pop("inlier")
             ext = resected["extrinsics"].cpu().numpy()
             toc("resect")
-            proj = np.einsum("ij,fjk->fik", np.asarray(K, float), ext)
-            tic("triangulate")
-            if triangulation == "multi_view":
-                X, quality, flags = self.triangulate_multi_view(track_ptr, obs_frame, obs_kp, xy_dev, proj, **(cull or {}))
-            else:
-                X = self.triangulate(track_ptr, obs_frame, obs_kp, xy_dev, proj)
-            toc("triangulate")
+            X, quality, flags = triangulated(ext)
         P, O = track_ptr.shape[0] - 1, obs_frame.shape[0]
         out = dict(det=det, n_tracks=P, n_obs=O, points0=X, track_ptr_dev=track_ptr, obs_frame_dev=obs_frame,
                    obs_kp_dev=obs_kp, xy_dev=xy_dev, match_count=m_h, kp_count=n_h, pairs_local=int(p_hi - p_lo),

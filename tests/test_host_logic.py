@@ -251,6 +251,57 @@ def test_partitions_cover_everything_once():
     assert p_hi == 499 and f_hi == 500 and f_lo == p_lo
 
 
+def test_window_schedule_windows_and_colours_equal_a_plain_restatement():
+    """ClipPipeline.window_schedule (the windows of every adjust_windows schedule and the wavefront's colours) against a
+    plain restatement, over every small shape.  For stride >= window / 2 the windows on the stride grid alternate between
+    two colours, and the schedule has exactly two whenever the clip ends on the grid and the windows overlap.  Two cases
+    keep "exactly two" from holding for every such shape, so the count is pinned to what the windows force instead: with
+    a stride of at least the window the windows can all be disjoint (12 frames, window 3, stride 5: 0-3, 5-8, 9-12; one
+    colour), and the last window, which ends at the clip's end off the grid, can share cameras with both its
+    predecessors (7 frames, window 4, stride 2: 0-4, 2-6, 3-7; it alone takes a third)."""
+    for F in range(1, 13):
+        for window in range(0, 15):
+            for stride in range(0, 9):
+                wins, colours = ClipPipeline.window_schedule(F, window, stride)
+                w, s = max(2, min(window, F)), max(1, stride)
+                # the restatement: ends window, window + s, ... below F, then F; colour = first one free at lo
+                want, hi = [], w
+                while hi < F:
+                    want.append((max(0, hi - w), hi))
+                    hi += s
+                want.append((max(0, F - w), F))
+                want_colours, last_hi = [], []
+                for lo, hi in want:
+                    for c in range(len(last_hi)):
+                        if last_hi[c] <= lo:
+                            break
+                    else:
+                        c = len(last_hi)
+                        last_hi.append(None)
+                    last_hi[c] = hi
+                    want_colours.append(c)
+                case = (F, window, stride)
+                assert wins == want and colours == want_colours, case
+                assert all(type(v) is int for win in wins for v in win), case
+                assert all(hi - lo == w or lo == 0 for lo, hi in wins), case
+                assert all(0 <= lo < hi <= F for lo, hi in wins), case
+                assert wins[-1][1] == F, case
+                his = [hi for _, hi in wins]
+                assert all(b - a == s for a, b in zip(his[:-2], his[1:-1])), case
+                assert len(his) < 2 or 1 <= his[-1] - his[-2] <= s, case
+                for c in set(colours):
+                    own = [set(range(*win)) for win, cc in zip(wins, colours) if cc == c]
+                    assert sum(len(o) for o in own) == len(set().union(*own)), case     # pairwise disjoint in cameras
+                assert sorted(set(colours)) == list(range(max(colours) + 1)), case
+                if len(wins) >= 2 and 2 * s >= w:
+                    touching = any(b[0] < a[1] for a, b in zip(wins[:-1], wins[1:]))
+                    last_meets_two = len(wins) >= 3 and wins[-1][0] < wins[-3][1]
+                    assert len(set(colours)) == 1 + touching + last_meets_two, case
+                    assert set(colours[:-1]) <= {0, 1}, case
+                    if s < w and (F - w) % s == 0:
+                        assert len(set(colours)) == 2, case
+
+
 def test_brief_pattern_is_fixed_and_inside_the_disc():
     from meatmodeler_amd.orb_pattern import brief_pattern
     p = brief_pattern().astype(int)
