@@ -464,6 +464,114 @@ int mm_resect_planar(mm_ctx *ctx, const double *K /*host [9]*/, const double *X 
                      double *extrinsics /*[n_cams,3,4]*/, double *cost /*[n_cams]*/, uint8_t *inlier /*[O]*/,
                      int32_t *info /*[n_cams,6]*/, double *plane /*[n_cams,6]*/, void *ws, size_t ws_bytes);
 
+/* ---- a-2f: a homography per consecutive frame pair -- the planar / rotation-only verdict and the motion (no reference
+ * counterpart) ----------------------------------------------------------------------------------------------------------------
+ * A fundamental matrix is not determined when the camera only turns or when the scene is a plane: mm_verify_matches then
+ * returns WEAK or an arbitrary F of the pencil, and mm_recover_poses flags AMBIGUOUS.  A homography explains exactly those
+ * pairs.  mm_verify_homography estimates one per pair on the same raw matches mm_verify_matches reads (not on its inliers)
+ * and compares the two inlier counts; mm_recover_poses_homography turns H and the calibration into R, t, depths and an info
+ * row in the layouts mm_chain_poses consumes.
+ *   Inputs, malformed matches, Hartley normalisation per image over all well-formed matches, the MSAC score and its tie rule:
+ *   exactly as in mm_verify_matches.
+ *   Convention.  x' ~ H x on homogeneous pixels, H row-major with unit Frobenius norm, negated when (H c)_2 < 0 with
+ *   (H c)_2 = (H6 c_x + H7 c_y) + H8 and c the image-1 centroid of the normalisation the fit ran under.
+ *   Distance.  Symmetric transfer: y = H (x, 1) with y_i = (H_i0 x + H_i1 y) + H_i2, z = adj(H) (x', 1) likewise, adj the
+ *   adjugate written out (A00 = H4 H8 - H5 H7, A01 = H2 H7 - H1 H8, A02 = H1 H5 - H2 H4, A10 = H5 H6 - H3 H8,
+ *   A11 = H0 H8 - H2 H6, A12 = H2 H3 - H0 H5, A20 = H3 H7 - H4 H6, A21 = H1 H6 - H0 H7, A22 = H0 H4 - H1 H3: no division by
+ *   the determinant); d^2 = (((x' - y0/y2)^2 + (y' - y1/y2)^2) + ((x - z0/z2)^2 + (y - z1/z2)^2)) * 0.5.  A match is an inlier
+ *   iff d^2 is finite and <= tau^2, tau = threshold_px.
+ *   Sampling: the integer scheme of mm_resect_planar with four picks: base = pcg(pcg(seed + pcg(pair_base + p)) + h); pick
+ *   k = 0 .. 3 tries a = 0 .. 7: i = (uint64(pcg(base + 8 k + a)) * m) >> 32, the first i that is not an earlier pick; eight
+ *   collisions make the hypothesis invalid (at most (3/8)^8 < 1e-3 per pick for m >= 8: why min_matches is floored at 8).
+ *   A sample is also invalid when any of its four triples (0,1,2), (0,1,3), (0,2,3), (1,2,3) is near-collinear in either
+ *   image's normalised coordinates -- the rule of mm_resect_planar with collinear_tol; a NaN does not pass.
+ *   Hypothesis and refit -- one routine, the reduced DLT of mm_resect_planar with m = (s (x - c), 1) in the place of the plane
+ *   coordinates and (u, v) = s' (x' - c'): the 24 sums over the chosen matches in their order, Cholesky S = L L^T with the same
+ *   pivot rule, Yu, Yv, M = (C - Yu^T Yu) - Yv^T Yv, h3 = the eigenvector of the smallest eigenvalue of M (3 x 3 Jacobi, ties to
+ *   the lowest column), h1 = L^-T (Yu h3), h2 = L^-T (Yv h3), H^ = [h1; h2; h3].  Rank guard: the hypothesis is invalid unless
+ *   the smallest eigenvalue of H^^T H^ (3 x 3 Jacobi; entry (r, c) = (H^0r H^0c + H^1r H^1c) + H^2r H^2c) is above 1e-8 times
+ *   the largest (the guard of mm_resect_planar, squared).  Denormalise: A = H^ T with A_r0 = s H^_r0, A_r1 = s H^_r1,
+ *   A_r2 = (H^_r2 - (s c_x) H^_r0) - (s c_y) H^_r1; H = T'^-1 A with H_0c = A_0c / s' + c'_x A_2c, H_1c = A_1c / s' + c'_y A_2c,
+ *   H_2c = A_2c; then unit norm (the nine squares summed in order) and the sign rule.  A non-finite H is invalid.
+ *   Refit.  refit_iters rounds (a fixed count) over the inliers of the current H -- fewer than 4: nothing changes any more --
+ *   renormalised over them; a refit skips the collinearity test and replaces H only when it is valid and its cost over ALL
+ *   matches is finite and strictly lower.
+ *   Outputs.  pairs_out [n_pairs, cap, 2] (must not alias pairs) / m_out [n_pairs]: the inliers of the final H in input order,
+ *   rows at or beyond m_out[p] untouched; a failed pair (any of the first three flags) has m_out = 0.  Hm [n_pairs, 9] and
+ *   cost [n_pairs] f64, NaN without a model.  info [n_pairs, 6] i32 = (flags, n_inliers, best_h or -1, valid hypotheses,
+ *   n_F or -1, 0).
+ *   Flags.  MM_HOMOG_TOO_FEW m < max(min_matches, 8) | MM_HOMOG_NO_MODEL no hypothesis with a finite cost | MM_HOMOG_WEAK
+ *   n_inliers < min_inliers | MM_HOMOG_MALFORMED | MM_HOMOG_DEGENERATE: verify_info [n_pairs, 4] (the info of
+ *   mm_verify_matches on the same matches) is given, the pair has none of the first three flags, and either
+ *   verify_info[p, 0] & 7 is non-zero (the fundamental matrix failed where the homography did not) or
+ *   double(n_inliers) >= degenerate_frac * double(n_F) with n_F = verify_info[p, 1]: the homography explains nearly everything
+ *   the fundamental matrix does, so the pair is planar or rotation-only and its F is one of a pencil.  With verify_info NULL
+ *   the bit is never set, info[4] = -1 and every other output is the same.
+ * Four launches (normalise, hypothesis, score, finish) with the shapes of mm_verify_matches; the guarantees are the same: a
+ * call repeats bit for bit, a pair's row does not depend on its neighbours, rows [a, b) equal a call on that block with
+ * pair_base + a, n_pairs = 0 returns MM_OK without a launch.  All pointers are DEVICE pointers except prm; kp_xy, pairs and
+ * pairs_out 8-byte aligned; ws holds mm_homography_workspace_bytes(n_pairs, n_hyp) bytes (normalisations, every hypothesis' H
+ * and cost).  Argument errors -- n_hyp outside 1 .. 4096, a negative or NaN threshold_px or collinear_tol, degenerate_frac
+ * outside [0, 1], null pointers other than verify_info: MM_ERR_ARG; a workspace that is too small: MM_ERR_WORKSPACE -- are
+ * returned before the device is touched. */
+#define MM_HOMOG_TOO_FEW 1
+#define MM_HOMOG_NO_MODEL 2
+#define MM_HOMOG_WEAK 4
+#define MM_HOMOG_MALFORMED 8
+#define MM_HOMOG_DEGENERATE 16
+typedef struct mm_homography_params {
+    int32_t n_hyp, min_matches, min_inliers, refit_iters;      /* defaults 256, 8, 16, 2 */
+    uint32_t seed, pair_base;
+    double threshold_px, collinear_tol, degenerate_frac;       /* defaults 2, 1e-3, 0.8 */
+} mm_homography_params;
+size_t mm_homography_workspace_bytes(int n_pairs, int n_hyp);
+int mm_verify_homography(mm_ctx *ctx, const float *kp_xy /*[n_pairs+1,cap,2]*/, const int32_t *pairs /*[n_pairs,cap,2]*/,
+                         const int32_t *m /*[n_pairs]*/, int n_pairs, int cap, const mm_homography_params *prm,
+                         const int32_t *verify_info /*[n_pairs,4] or NULL*/, int32_t *pairs_out /*[n_pairs,cap,2]*/,
+                         int32_t *m_out /*[n_pairs]*/, double *Hm /*[n_pairs,9]*/, double *cost /*[n_pairs]*/,
+                         int32_t *info /*[n_pairs,6]*/, void *ws, size_t ws_bytes);
+/* The motion a homography implies.  K, kp_xy, pairs, m, the rays a = K^-1 (x, y, 1), b = K^-1 (x', y', 1), the convention
+ * X2 = R X1 + t with |t| = 1 and the layouts of R, t, depth [n_pairs, cap, 2] and info [n_pairs, 8] = (flags, winner or -1,
+ * votes[0 .. 3], m used, 0) are those of mm_recover_poses; pairs and m are what mm_verify_homography wrote to pairs_out /
+ * m_out, Hm its homographies; normal_hint [n_pairs, 3] f64 or NULL.  The flag values 1, 2, 4, 8 mean what MM_POSE_* mean, so
+ * mm_chain_poses reads the rows unchanged; MM_HPOSE_ROTATION is new.
+ *   Setup.  G = K^-1 (H K), every entry summed left to right; M = G^T G; eigenpairs by the 3 x 3 Jacobi, ordered
+ *   l1 >= l2 >= l3 by a stable exchange sort of the columns -- (0,1), (1,2), (0,1), each exchanged only when the right
+ *   eigenvalue is strictly larger.  NO_MODEL when H or an eigenvalue is not finite or l3 <= 0.  sigma = (sqrt l1, sqrt l2,
+ *   sqrt l3); G <- G / sqrt l2 (every entry divided); v1, v3 the eigenvectors of l1, l3 and v2 = v3 x v1.  G is negated when
+ *   more of the pair's well-formed matches have b . (G a) < 0 than > 0.
+ *   Rotation only: sqrt(l1 / l3) - 1 <= rotation_tol.  R = the polar factor of G (A (V diag(lambda^-1/2) V^T) from the Jacobi
+ *   of A^T A, as in mm_resect_cameras; NO_MODEL when a lambda is not finite and positive or R is not finite), t = 0, normal
+ *   and every depth row NaN, winner -1, no votes, flag MM_HPOSE_ROTATION.  mm_chain_poses composes the rotation, finds no
+ *   common depths and carries the previous scale (FEW_COMMON on this pair and the next).
+ *   Planar otherwise (Ma, Soatto, Kosecka, Sastry, An Invitation to 3-D Vision, section 5.3).  With n1 = l1 / l2 and
+ *   n3 = l3 / l2: u+- = (sqrt(1 - n3) v1 +- sqrt(n1 - 1) v3) / sqrt(n1 - n3), each component one sum and one division;
+ *   U = [v2, u, v2 x u] and W = [G v2, G u, (G v2) x (G u)] by columns; R = W U^T, n = v2 x u, t = (G - R) n.  Candidates
+ *   c = 0: (R+, t+, n+), 1: (R+, -t+, -n+), 2: (R-, t-, n-), 3: (R-, -t-, -n-).  NO_MODEL when |t+| or |t-| is not finite and
+ *   positive or an entry of R+ or R- is not finite.  n is a unit vector; with the plane n . X = d in camera 1, t comes out
+ *   as t / d and the depths below in units of d.
+ *   Depths and votes.  l1 = 1 / (n . a), l2 = l1 (R a)_z + t_z; a well-formed match votes for c when both are finite and > 0.
+ *   After the vote t and the depths of the winner are divided by |t|.
+ *   Winner.  The contenders are the candidates with double(votes) >= ambiguous_frac * double(largest count).  With a finite
+ *   normal_hint[p] the winner is the contender with the largest n . hint, ties to the lowest c; without one the largest
+ *   count, ties to the lowest c.  MM_POSE_AMBIGUOUS: votes[winner] < min_front_frac m, or several contenders and no hint (the
+ *   twofold ambiguity of a plane seen by two cameras: both solutions put every point in front).
+ *   Outputs.  R, t of the winner (NaN: no model); sigma [n_pairs, 3]; normal [n_pairs, 3] the winner's n (NaN without one);
+ *   depth = (l1, l2) / |t| for the rows that voted for the winner, NaN elsewhere, rows at or beyond m[p] included; info.
+ * One 256-thread workgroup per pair, integer counts; the depth pass repeats the vote pass's expression bit for bit.  The
+ * guarantees and the argument checks of mm_recover_poses apply; a rotation_tol that is negative or NaN is MM_ERR_ARG. */
+#define MM_HPOSE_ROTATION 16
+typedef struct mm_hpose_params {
+    int32_t min_matches, reserved;                              /* default 8 */
+    double min_front_frac, ambiguous_frac, rotation_tol;        /* defaults 0.5, 0.9, 1e-2 */
+} mm_hpose_params;
+int mm_recover_poses_homography(mm_ctx *ctx, const double *K /*host [9]*/, const float *kp_xy /*[n_pairs+1,cap,2]*/,
+                                const int32_t *pairs /*[n_pairs,cap,2]*/, const int32_t *m /*[n_pairs]*/,
+                                const double *Hm /*[n_pairs,9]*/, const double *normal_hint /*[n_pairs,3] or NULL*/, int n_pairs,
+                                int cap, const mm_hpose_params *prm, double *R /*[n_pairs,9]*/, double *t /*[n_pairs,3]*/,
+                                double *sigma /*[n_pairs,3]*/, double *normal /*[n_pairs,3]*/, double *depth /*[n_pairs,cap,2]*/,
+                                int32_t *info /*[n_pairs,8]*/);
+
 /* ---- a-4: two-view DLT triangulation ------------------------------------------------------------
  * Replaces the per-track cv2.triangulatePoints + dehomogenise loop, processor.py:254-261.
  * proj [F,3,4] f64; track i uses views f0[i], f1[i] with pixels x0[i], x1[i]; X [n,3]. */

@@ -79,6 +79,20 @@ class PoseParams(C.Structure):
                 ("ambiguous_frac", C.c_double)]
 
 
+class HomographyParams(C.Structure):
+    """mm_homography_params: hypotheses, floors, refit count, sampling key, threshold, sample-collinearity tolerance and the
+    inlier ratio of the verdict of mm_verify_homography."""
+    _fields_ = [("n_hyp", C.c_int32), ("min_matches", C.c_int32), ("min_inliers", C.c_int32), ("refit_iters", C.c_int32),
+                ("seed", C.c_uint32), ("pair_base", C.c_uint32), ("threshold_px", C.c_double), ("collinear_tol", C.c_double),
+                ("degenerate_frac", C.c_double)]
+
+
+class HPoseParams(C.Structure):
+    """mm_hpose_params: match floor, the two vote fractions and the rotation-only tolerance of mm_recover_poses_homography."""
+    _fields_ = [("min_matches", C.c_int32), ("reserved", C.c_int32), ("min_front_frac", C.c_double),
+                ("ambiguous_frac", C.c_double), ("rotation_tol", C.c_double)]
+
+
 class ResectParams(C.Structure):
     """mm_resect_params: hypotheses, row and inlier floors, refit and polish counts, sampling key and threshold of
     mm_resect_cameras."""
@@ -148,6 +162,11 @@ SIGNATURES = {
     "mm_verify_matches": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(VerifyParams), vp, vp, vp, vp, vp, vp, C.c_size_t]),
     "mm_recover_poses": (C.c_int, [vp, c_f64p, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(PoseParams), vp, vp, vp, vp, vp]),
     "mm_chain_poses": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, c_f64p, C.c_int, vp, vp, vp, vp]),
+    "mm_homography_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "mm_verify_homography": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(HomographyParams), vp, vp, vp, vp, vp, vp, vp,
+                                       C.c_size_t]),
+    "mm_recover_poses_homography": (C.c_int, [vp, c_f64p, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(HPoseParams), vp, vp, vp,
+                                              vp, vp, vp]),
     "mm_resect_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int64]),
     "mm_resect_cameras": (C.c_int, [vp, c_f64p, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int, vp, vp,
                                     C.POINTER(ResectParams), vp, vp, vp, vp, vp, C.c_size_t]),

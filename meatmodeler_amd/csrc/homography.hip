@@ -1,0 +1,950 @@
+// A homography per consecutive frame pair: the planar / rotation-only verdict beside mm_verify_matches, and the motion a
+// homography implies beside mm_recover_poses (gfx950, f64).
+//
+// No reference counterpart: the reference takes its poses from a chessboard.  A fundamental matrix is not determined when the
+// camera only turns or when the scene is a plane; a homography explains exactly those pairs.  The definition -- sampling,
+// the reduced DLT, the symmetric transfer distance, MSAC, refit, the verdict, the decomposition into four motions, the depth
+// vote -- is in include/meatmodeler.h (mm_verify_homography, mm_recover_poses_homography); this file maps it:
+//   hg_normalise_kernel   one workgroup per pair: Hartley centroid / scale of both images over the well-formed matches
+//   hg_hypothesis_kernel  one lane per (pair, hypothesis): four sampled matches, near-collinear triples rejected in both
+//                         images, the 24 sums and the reduced DLT in registers (every index static), rank guard, denormalise
+//   hg_score_kernel       lane = hypothesis, H and its adjugate in registers; the pair's matches go through LDS in tiles and
+//                         every lane reads the same address (broadcast), summing min(d^2, tau^2) over j ascending
+//   hg_finish_kernel      one workgroup per pair: argmin, refit rounds (24 sums over the inliers, the same solve), the verdict
+//                         against the fundamental matrix's inlier count, order-preserving compaction, outputs
+//   hp_pair_kernel        one workgroup per pair: G = K^-1 H K, its eigenpairs, the sign from the matches, then either the
+//                         polar factor (rotation only) or the four plane motions, integer votes, the winner's depths
+// Built without FMA contraction (Makefile): the inlier test is evaluated in several passes that must agree on every bit, the
+// depth pass repeats the vote pass, and the NumPy restatement of the tests follows the header operation by operation.
+// Plain f64 VALU work; sums in an order that depends on the pair alone (per-thread strides, xor butterflies, waves in order),
+// no float atomics: a pair's row repeats bit for bit whatever else shares the call.
+#include "mm_common.h"
+#include "mm_geom.h"
+
+namespace {
+
+constexpr int HG_THREADS = 256;      // normalise / finish / pose: one workgroup per pair
+constexpr int HG_WAVES = HG_THREADS / 64;
+constexpr int HG_TILE = 256;         // matches per LDS tile of the score kernel
+static_assert(HG_THREADS == MM_BLOCK_THREADS, "the mm_block_* helpers are written for this workgroup");
+
+struct HgArgs {
+    const float *kp_xy;
+    const int32_t *pairs, *m, *verify_info;
+    int n_pairs, cap, n_hyp, min_matches, min_inliers, refit_iters;
+    uint32_t seed, pair_base;
+    double tau2, collinear_tol, degenerate_frac;
+    double *norm;      // [n_pairs, 8]: cx, cy, s, cx', cy', s', number of malformed matches, -
+    double *Hh;        // [n_pairs, n_hyp, 9] (NaN: invalid hypothesis)
+    double *cost_h;    // [n_pairs, n_hyp] (+inf: invalid hypothesis)
+};
+
+__device__ __forceinline__ int hg_count(const int32_t *m, int cap, int p) {
+    const int mm = m[p];
+    return mm < 0 ? 0 : (mm > cap ? cap : mm);
+}
+
+// match j of pair p, widened; false (and NaN coordinates) for a malformed match -- nothing is read through a bad index
+__device__ __forceinline__ bool hg_load(const float *kp_xy, const int32_t *pairs, int cap, int p, int j, double &x, double &y,
+                                        double &xp, double &yp) {
+    const int2 qt = reinterpret_cast<const int2 *>(pairs)[(size_t)p * cap + j];
+    const bool wf = (unsigned)qt.x < (unsigned)cap && (unsigned)qt.y < (unsigned)cap;
+    const double nan = __builtin_nan("");
+    x = y = xp = yp = nan;
+    if (wf) {
+        const float2 u = reinterpret_cast<const float2 *>(kp_xy)[(size_t)p * cap + qt.x];
+        const float2 v = reinterpret_cast<const float2 *>(kp_xy)[(size_t)(p + 1) * cap + qt.y];
+        x = (double)u.x;
+        y = (double)u.y;
+        xp = (double)v.x;
+        yp = (double)v.y;
+    }
+    return wf;
+}
+__device__ __forceinline__ bool hg_load(const HgArgs &a, int p, int j, double &x, double &y, double &xp, double &yp) {
+    return hg_load(a.kp_xy, a.pairs, a.cap, p, j, x, y, xp, yp);
+}
+
+// adj(H), written out: every entry one difference of two products, no division by the determinant
+__device__ __forceinline__ void hg_adjugate(const double (&H)[9], double (&A)[9]) {
+    A[0] = H[4] * H[8] - H[5] * H[7];
+    A[1] = H[2] * H[7] - H[1] * H[8];
+    A[2] = H[1] * H[5] - H[2] * H[4];
+    A[3] = H[5] * H[6] - H[3] * H[8];
+    A[4] = H[0] * H[8] - H[2] * H[6];
+    A[5] = H[2] * H[3] - H[0] * H[5];
+    A[6] = H[3] * H[7] - H[4] * H[6];
+    A[7] = H[1] * H[6] - H[0] * H[7];
+    A[8] = H[0] * H[4] - H[1] * H[3];
+}
+
+// symmetric transfer distance d^2 = (|x' - pi(H x)|^2 + |x - pi(adj(H) x')|^2) / 2
+__device__ __forceinline__ double hg_transfer(const double (&H)[9], const double (&A)[9], double x, double y, double xp, double yp) {
+    const double y0 = (H[0] * x + H[1] * y) + H[2], y1 = (H[3] * x + H[4] * y) + H[5], y2 = (H[6] * x + H[7] * y) + H[8];
+    const double z0 = (A[0] * xp + A[1] * yp) + A[2], z1 = (A[3] * xp + A[4] * yp) + A[5], z2 = (A[6] * xp + A[7] * yp) + A[8];
+    const double ex = xp - y0 / y2, ey = yp - y1 / y2, fx = x - z0 / z2, fy = y - z1 / z2;
+    return ((ex * ex + ey * ey) + (fx * fx + fy * fy)) * 0.5;
+}
+__device__ __forceinline__ bool hg_inlier(double d2, double tau2) { return isfinite(d2) && d2 <= tau2; }
+
+// one normalised match into the 24 sums: S, Bu, Bv, C, each the upper triangle of a 3 x 3, row-major, over m = (x, y, 1)
+// with (u, v) = the normalised x'
+__device__ __forceinline__ void hg_accumulate(double (&acc)[24], double xn, double yn, double u, double v) {
+    const double m[3] = {xn, yn, 1.0};
+    const double r2 = u * u + v * v;
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = i; j < 3; ++j) {
+            const double w = m[i] * m[j];
+            acc[k] += w;
+            acc[6 + k] += u * w;
+            acc[12 + k] += v * w;
+            acc[18 + k] += r2 * w;
+            ++k;
+        }
+}
+
+// true: the triangle (i, j, k) is not near-collinear: |cross| > tol x its longest squared side (NaN: false) -- the rule of
+// mm_resect_planar
+__device__ __forceinline__ bool hg_triple_ok(double ai, double bi, double aj, double bj, double ak, double bk, double tol) {
+    const double pa = aj - ai, pb = bj - bi, qa = ak - ai, qb = bk - bi, ra = ak - aj, rb = bk - bj;
+    const double cr = pa * qb - pb * qa;
+    const double d0 = pa * pa + pb * pb, d1 = qa * qa + qb * qb, d2 = ra * ra + rb * rb;
+    double lng = d0 > d1 ? d0 : d1;
+    lng = lng > d2 ? lng : d2;
+    return fabs(cr) > tol * lng;
+}
+
+// H from the 24 sums: the reduced DLT of mm_resect_planar (Cholesky of S, h3 by the 3 x 3 Jacobi, h1 and h2 by back
+// substitution), the rank guard on the normalised matrix, H = T'^-1 H^ T, unit Frobenius norm, (H c)_2 >= 0.
+// false: a failed pivot, a rank below three or a non-finite entry.
+__device__ __forceinline__ bool hg_solve(const double (&acc)[24], double cx, double cy, double s, double cx2, double cy2, double s2,
+                                         double (&H)[9]) {
+    double S[3][3], Bu[3][3], Bv[3][3], M[3][3];
+    {
+        int k = 0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = i; j < 3; ++j) {
+                S[i][j] = S[j][i] = acc[k];
+                Bu[i][j] = Bu[j][i] = acc[6 + k];
+                Bv[i][j] = Bv[j][i] = acc[12 + k];
+                M[i][j] = M[j][i] = acc[18 + k];
+                ++k;
+            }
+    }
+    double L[3][3];
+    bool ok = mm_cholesky_pivot<3>(S, L);
+    double Yu[3][3], Yv[3][3];      // L^-1 Bu, L^-1 Bv
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            double vu = Bu[i][c], vv = Bv[i][c];
+#pragma unroll
+            for (int k = 0; k < i; ++k) {
+                vu -= L[i][k] * Yu[k][c];
+                vv -= L[i][k] * Yv[k][c];
+            }
+            Yu[i][c] = vu / L[i][i];
+            Yv[i][c] = vv / L[i][i];
+        }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = i; j < 3; ++j) {
+            const double tu = (Yu[0][i] * Yu[0][j] + Yu[1][i] * Yu[1][j]) + Yu[2][i] * Yu[2][j];
+            const double tv = (Yv[0][i] * Yv[0][j] + Yv[1][i] * Yv[1][j]) + Yv[2][i] * Yv[2][j];
+            M[i][j] = M[j][i] = (M[i][j] - tu) - tv;
+        }
+    double V3[3][3];
+    mm_identity<3>(V3);
+    mm_jacobi<3>(M, V3);
+    double ev = M[0][0], h3[3] = {V3[0][0], V3[1][0], V3[2][0]};      // smallest eigenvalue, ties to the lowest column
+#pragma unroll
+    for (int c = 1; c < 3; ++c) {
+        if (M[c][c] < ev) {
+            ev = M[c][c];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) h3[r] = V3[r][c];
+        }
+    }
+    double h1[3], h2[3];      // S^-1 Bu h3 = L^-T (Yu h3), S^-1 Bv h3
+    {
+        double wu[3], wv[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            wu[i] = (Yu[i][0] * h3[0] + Yu[i][1] * h3[1]) + Yu[i][2] * h3[2];
+            wv[i] = (Yv[i][0] * h3[0] + Yv[i][1] * h3[1]) + Yv[i][2] * h3[2];
+        }
+#pragma unroll
+        for (int i = 2; i >= 0; --i) {
+            double vu = wu[i], vv = wv[i];
+#pragma unroll
+            for (int k = i + 1; k < 3; ++k) {
+                vu -= L[k][i] * h1[k];
+                vv -= L[k][i] * h2[k];
+            }
+            h1[i] = vu / L[i][i];
+            h2[i] = vv / L[i][i];
+        }
+    }
+    const double Hn[9] = {h1[0], h1[1], h1[2], h2[0], h2[1], h2[2], h3[0], h3[1], h3[2]};
+    {   // rank guard: the smallest eigenvalue of H^^T H^ must be above 1e-8 of the largest (a NaN does not pass)
+        double G[3][3], V[3][3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) G[r][c] = (Hn[r] * Hn[c] + Hn[3 + r] * Hn[3 + c]) + Hn[6 + r] * Hn[6 + c];
+        mm_identity<3>(V);
+        mm_jacobi<3>(G, V);
+        double lo = G[0][0] < G[1][1] ? G[0][0] : G[1][1], hi = G[0][0] > G[1][1] ? G[0][0] : G[1][1];
+        lo = lo < G[2][2] ? lo : G[2][2];
+        hi = hi > G[2][2] ? hi : G[2][2];
+        ok = ok && lo > 1e-8 * hi;
+    }
+    double A[9];      // A = H^ T with T = [[s, 0, -s cx], [0, s, -s cy], [0, 0, 1]]
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        A[3 * r] = s * Hn[3 * r];
+        A[3 * r + 1] = s * Hn[3 * r + 1];
+        A[3 * r + 2] = (Hn[3 * r + 2] - (s * cx) * Hn[3 * r]) - (s * cy) * Hn[3 * r + 1];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {      // H = T'^-1 A with T'^-1 = [[1/s', 0, cx'], [0, 1/s', cy'], [0, 0, 1]]
+        H[c] = A[c] / s2 + cx2 * A[6 + c];
+        H[3 + c] = A[3 + c] / s2 + cy2 * A[6 + c];
+        H[6 + c] = A[6 + c];
+    }
+    double nn = 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) nn += H[k] * H[k];
+    const double w = (H[6] * cx + H[7] * cy) + H[8];
+    const double inv = (w < 0.0 ? -1.0 : 1.0) / sqrt(nn);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        H[k] *= inv;
+        ok = ok && isfinite(H[k]);
+    }
+    return ok;
+}
+
+// ---- normalisation over all well-formed matches of the pair -----------------------------------------------------------------
+__global__ __launch_bounds__(HG_THREADS) void hg_normalise_kernel(HgArgs a) {
+    __shared__ double sm[HG_WAVES * 5];
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int mm = hg_count(a.m, a.cap, p);
+    double s5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int j = tid; j < mm; j += HG_THREADS) {
+        double x, y, xp, yp;
+        if (hg_load(a, p, j, x, y, xp, yp)) {
+            s5[0] += 1.0;
+            s5[1] += x;
+            s5[2] += y;
+            s5[3] += xp;
+            s5[4] += yp;
+        }
+    }
+    mm_block_sum<5>(s5, sm);
+    const double n = s5[0], cx = s5[1] / n, cy = s5[2] / n, cx2 = s5[3] / n, cy2 = s5[4] / n;
+    double d2[2] = {0.0, 0.0};
+    for (int j = tid; j < mm; j += HG_THREADS) {
+        double x, y, xp, yp;
+        if (hg_load(a, p, j, x, y, xp, yp)) {
+            d2[0] += sqrt((x - cx) * (x - cx) + (y - cy) * (y - cy));
+            d2[1] += sqrt((xp - cx2) * (xp - cx2) + (yp - cy2) * (yp - cy2));
+        }
+    }
+    mm_block_sum<2>(d2, sm);
+    if (tid == 0) {
+        double *o = a.norm + 8 * (size_t)p;
+        o[0] = cx;
+        o[1] = cy;
+        o[2] = 1.4142135623730951 / (d2[0] / n);
+        o[3] = cx2;
+        o[4] = cy2;
+        o[5] = 1.4142135623730951 / (d2[1] / n);
+        o[6] = (double)mm - n;
+        o[7] = 0.0;
+    }
+}
+
+// ---- one hypothesis per lane --------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void hg_hypothesis_kernel(HgArgs a) {
+    const int p = blockIdx.x;
+    const int h = blockIdx.y * 64 + threadIdx.x;
+    const int mm = hg_count(a.m, a.cap, p);
+    if (h >= a.n_hyp || mm < a.min_matches) return;      // (a pair with too few matches is never scored either)
+    const double *nr = a.norm + 8 * (size_t)p;
+    const double cx = nr[0], cy = nr[1], s = nr[2], cx2 = nr[3], cy2 = nr[4], s2 = nr[5];
+    bool ok = isfinite(s) && isfinite(s2);
+    const uint32_t base = mm_pcg(mm_pcg(a.seed + mm_pcg(a.pair_base + (uint32_t)p)) + (uint32_t)h);
+    int pick[4];
+    ok = mm_sample_distinct<4>(base, mm, pick) && ok;
+    double xa[4], ya[4], xb[4], yb[4], acc[24];
+#pragma unroll
+    for (int k = 0; k < 24; ++k) acc[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        double x, y, xp, yp;
+        ok = hg_load(a, p, pick[k], x, y, xp, yp) && ok;
+        xa[k] = s * (x - cx);
+        ya[k] = s * (y - cy);
+        xb[k] = s2 * (xp - cx2);
+        yb[k] = s2 * (yp - cy2);
+        hg_accumulate(acc, xa[k], ya[k], xb[k], yb[k]);
+    }
+    ok = hg_triple_ok(xa[0], ya[0], xa[1], ya[1], xa[2], ya[2], a.collinear_tol) && ok;
+    ok = hg_triple_ok(xa[0], ya[0], xa[1], ya[1], xa[3], ya[3], a.collinear_tol) && ok;
+    ok = hg_triple_ok(xa[0], ya[0], xa[2], ya[2], xa[3], ya[3], a.collinear_tol) && ok;
+    ok = hg_triple_ok(xa[1], ya[1], xa[2], ya[2], xa[3], ya[3], a.collinear_tol) && ok;
+    ok = hg_triple_ok(xb[0], yb[0], xb[1], yb[1], xb[2], yb[2], a.collinear_tol) && ok;
+    ok = hg_triple_ok(xb[0], yb[0], xb[1], yb[1], xb[3], yb[3], a.collinear_tol) && ok;
+    ok = hg_triple_ok(xb[0], yb[0], xb[2], yb[2], xb[3], yb[3], a.collinear_tol) && ok;
+    ok = hg_triple_ok(xb[1], yb[1], xb[2], yb[2], xb[3], yb[3], a.collinear_tol) && ok;
+    double H[9];
+    ok = hg_solve(acc, cx, cy, s, cx2, cy2, s2, H) && ok;
+    double *o = a.Hh + ((size_t)p * a.n_hyp + h) * 9;
+    const double nan = __builtin_nan("");
+#pragma unroll
+    for (int c = 0; c < 9; ++c) o[c] = ok ? H[c] : nan;
+}
+
+// ---- MSAC cost of every hypothesis --------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void hg_score_kernel(HgArgs a) {
+    __shared__ double tile[HG_TILE * 4];
+    const int p = blockIdx.x;
+    const int h = blockIdx.y * 64 + threadIdx.x;
+    const int mm = hg_count(a.m, a.cap, p);
+    if (mm < a.min_matches) return;      // (uniform over the workgroup)
+    const bool live = h < a.n_hyp;
+    double H[9], A[9];
+    const double *src = a.Hh + ((size_t)p * a.n_hyp + (live ? h : 0)) * 9;
+#pragma unroll
+    for (int c = 0; c < 9; ++c) H[c] = src[c];
+    hg_adjugate(H, A);
+    double cost = 0.0;
+    for (int j0 = 0; j0 < mm; j0 += HG_TILE) {
+        const int nt = min(HG_TILE, mm - j0);
+        __syncthreads();
+        for (int j = threadIdx.x; j < nt; j += 64) {
+            double x, y, xp, yp;
+            hg_load(a, p, j0 + j, x, y, xp, yp);
+            tile[4 * j] = x;
+            tile[4 * j + 1] = y;
+            tile[4 * j + 2] = xp;
+            tile[4 * j + 3] = yp;
+        }
+        __syncthreads();
+        for (int j = 0; j < nt; ++j) {
+            const double d2 = hg_transfer(H, A, tile[4 * j], tile[4 * j + 1], tile[4 * j + 2], tile[4 * j + 3]);
+            cost += hg_inlier(d2, a.tau2) ? d2 : a.tau2;
+        }
+    }
+    if (live) a.cost_h[(size_t)p * a.n_hyp + h] = isfinite(H[0]) ? cost : __builtin_huge_val();
+}
+
+// ---- winner, refit, verdict, compaction -----------------------------------------------------------------------------------
+// MSAC cost and inlier count of H over all matches of the pair (every thread returns the same bits)
+__device__ __forceinline__ void hg_cost(const HgArgs &a, int p, int mm, const double (&H)[9], double *sm, double &cost, int &n_in) {
+    double A[9];
+    hg_adjugate(H, A);
+    double v[2] = {0.0, 0.0};
+    for (int j = threadIdx.x; j < mm; j += HG_THREADS) {
+        double x, y, xp, yp;
+        hg_load(a, p, j, x, y, xp, yp);
+        const double d2 = hg_transfer(H, A, x, y, xp, yp);
+        const bool in = hg_inlier(d2, a.tau2);
+        v[0] += in ? d2 : a.tau2;
+        v[1] += in ? 1.0 : 0.0;
+    }
+    mm_block_sum<2>(v, sm);
+    cost = v[0];
+    n_in = (int)v[1];
+}
+
+__global__ __launch_bounds__(HG_THREADS) void hg_finish_kernel(HgArgs a, int32_t *__restrict__ pairs_out, int32_t *__restrict__ m_out,
+                                                               double *__restrict__ Hm, double *__restrict__ cost_out,
+                                                               int32_t *__restrict__ info) {
+    __shared__ double sm[HG_WAVES * 24];
+    __shared__ double bc[HG_WAVES];
+    __shared__ int bh[HG_WAVES], wcount[HG_WAVES];
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int mm = hg_count(a.m, a.cap, p);
+    const double nan = __builtin_nan("");
+    int flags = a.norm[8 * (size_t)p + 6] > 0.0 ? MM_HOMOG_MALFORMED : 0;
+    double H[9], A[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) H[c] = nan;
+    double cost = nan;
+    int n_in = 0, best_h = -1, n_valid = 0;
+    bool model = false;
+
+    if (mm < a.min_matches) {
+        flags |= MM_HOMOG_TOO_FEW;
+    } else {
+        double c_best;
+        int h_best;
+        mm_block_argmin_finite(a.cost_h + (size_t)p * a.n_hyp, a.n_hyp, a.Hh + (size_t)p * a.n_hyp * 9, 9, bc, bh, sm, c_best, h_best,
+                               n_valid);
+        if (h_best == INT32_MAX) {
+            flags |= MM_HOMOG_NO_MODEL;
+        } else {
+            model = true;
+            best_h = h_best;
+#pragma unroll
+            for (int c = 0; c < 9; ++c) H[c] = a.Hh[((size_t)p * a.n_hyp + h_best) * 9 + c];
+            hg_cost(a, p, mm, H, sm, cost, n_in);
+        }
+    }
+
+    if (model) {
+        for (int it = 0; it < a.refit_iters; ++it) {
+            if (n_in < 4) break;      // (uniform: nothing changes any more)
+            hg_adjugate(H, A);
+            // Hartley normalisation over the inliers of the current H
+            double s5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+            for (int j = tid; j < mm; j += HG_THREADS) {
+                double x, y, xp, yp;
+                hg_load(a, p, j, x, y, xp, yp);
+                if (hg_inlier(hg_transfer(H, A, x, y, xp, yp), a.tau2)) {
+                    s5[0] += 1.0;
+                    s5[1] += x;
+                    s5[2] += y;
+                    s5[3] += xp;
+                    s5[4] += yp;
+                }
+            }
+            mm_block_sum<5>(s5, sm);
+            const double n = s5[0], cx = s5[1] / n, cy = s5[2] / n, cx2 = s5[3] / n, cy2 = s5[4] / n;
+            double dd[2] = {0.0, 0.0};
+            for (int j = tid; j < mm; j += HG_THREADS) {
+                double x, y, xp, yp;
+                hg_load(a, p, j, x, y, xp, yp);
+                if (hg_inlier(hg_transfer(H, A, x, y, xp, yp), a.tau2)) {
+                    dd[0] += sqrt((x - cx) * (x - cx) + (y - cy) * (y - cy));
+                    dd[1] += sqrt((xp - cx2) * (xp - cx2) + (yp - cy2) * (yp - cy2));
+                }
+            }
+            mm_block_sum<2>(dd, sm);
+            const double s = 1.4142135623730951 / (dd[0] / n), s2 = 1.4142135623730951 / (dd[1] / n);
+            double acc[24];
+#pragma unroll
+            for (int k = 0; k < 24; ++k) acc[k] = 0.0;
+            for (int j = tid; j < mm; j += HG_THREADS) {
+                double x, y, xp, yp;
+                hg_load(a, p, j, x, y, xp, yp);
+                if (hg_inlier(hg_transfer(H, A, x, y, xp, yp), a.tau2))
+                    hg_accumulate(acc, s * (x - cx), s * (y - cy), s2 * (xp - cx2), s2 * (yp - cy2));
+            }
+            mm_block_sum<24>(acc, sm);
+            double Hn[9];
+            const bool okH = hg_solve(acc, cx, cy, s, cx2, cy2, s2, Hn);
+            double cn;
+            int nn_in;
+            hg_cost(a, p, mm, Hn, sm, cn, nn_in);
+            if (okH && isfinite(cn) && cn < cost) {
+                cost = cn;
+                n_in = nn_in;
+#pragma unroll
+                for (int c = 0; c < 9; ++c) H[c] = Hn[c];
+            }
+        }
+        if (n_in < a.min_inliers) flags |= MM_HOMOG_WEAK;
+    }
+
+    const bool failed = (flags & (MM_HOMOG_TOO_FEW | MM_HOMOG_NO_MODEL | MM_HOMOG_WEAK)) != 0;
+    int n_f = -1;
+    if (a.verify_info != nullptr) {
+        const int vflags = a.verify_info[4 * (size_t)p];
+        n_f = a.verify_info[4 * (size_t)p + 1];
+        if (!failed && ((vflags & 7) != 0 || (double)n_in >= a.degenerate_frac * (double)n_f)) flags |= MM_HOMOG_DEGENERATE;
+    }
+    // the inliers of H in their input order; a failed pair keeps none
+    int kept = 0;
+    if (!failed) {
+        hg_adjugate(H, A);
+        for (int j0 = 0; j0 < mm; j0 += HG_THREADS) {
+            const int j = j0 + tid;
+            bool keep = false;
+            int2 qt = make_int2(0, 0);
+            if (j < mm) {
+                qt = reinterpret_cast<const int2 *>(a.pairs)[(size_t)p * a.cap + j];
+                double x, y, xp, yp;
+                hg_load(a, p, j, x, y, xp, yp);
+                keep = hg_inlier(hg_transfer(H, A, x, y, xp, yp), a.tau2);
+            }
+            const int at = mm_block_compact_slot(keep, kept, wcount);
+            if (keep) reinterpret_cast<int2 *>(pairs_out)[(size_t)p * a.cap + at] = qt;
+        }
+    }
+    if (tid == 0) {
+        m_out[p] = kept;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) Hm[9 * (size_t)p + c] = H[c];
+        cost_out[p] = cost;
+        int32_t *o = info + 6 * (size_t)p;
+        o[0] = flags;
+        o[1] = n_in;
+        o[2] = best_h;
+        o[3] = n_valid;
+        o[4] = n_f;
+        o[5] = 0;
+    }
+}
+
+// ---- the motion a homography implies --------------------------------------------------------------------------------------
+struct HpArgs {
+    const float *kp_xy;
+    const int32_t *pairs, *m;
+    const double *Hm, *hint;
+    int n_pairs, cap, min_matches;
+    double min_front_frac, ambiguous_frac, rotation_tol;
+    double K[9];
+    double Ki[5];      // K^-1 = [[Ki0, Ki1, Ki2], [0, Ki3, Ki4], [0, 0, 1]]
+    double *R, *t, *sigma, *normal, *depth;
+    int32_t *info;
+};
+
+struct Vec3 {
+    double x, y, z;
+};
+__device__ __forceinline__ double dot3(Vec3 a, Vec3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ __forceinline__ Vec3 cross3(Vec3 a, Vec3 b) {
+    return Vec3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
+__device__ __forceinline__ Vec3 mat3(const double (&M)[9], Vec3 v) {
+    return Vec3{(M[0] * v.x + M[1] * v.y) + M[2] * v.z, (M[3] * v.x + M[4] * v.y) + M[5] * v.z, (M[6] * v.x + M[7] * v.y) + M[8] * v.z};
+}
+
+// rays of match j of pair p (mm_recover_poses); false for a malformed match -- nothing is read through a bad index
+__device__ __forceinline__ bool hp_rays(const HpArgs &a, int p, int j, Vec3 &ra, Vec3 &rb) {
+    double x, y, xp, yp;
+    const bool wf = hg_load(a.kp_xy, a.pairs, a.cap, p, j, x, y, xp, yp);
+    ra = rb = Vec3{0.0, 0.0, 1.0};
+    if (wf) {
+        ra = Vec3{(a.Ki[0] * x + a.Ki[1] * y) + a.Ki[2], a.Ki[3] * y + a.Ki[4], 1.0};
+        rb = Vec3{(a.Ki[0] * xp + a.Ki[1] * yp) + a.Ki[2], a.Ki[3] * yp + a.Ki[4], 1.0};
+    }
+    return wf;
+}
+
+// depths of a match on the plane n . X = 1 seen from camera 1: l1 = 1 / (n . a), l2 = (l1 R a + t)_z; true: both > 0
+__device__ __forceinline__ bool hp_depths(const double (&R)[9], Vec3 t, Vec3 n, Vec3 ra, double &l1, double &l2) {
+    l1 = 1.0 / dot3(n, ra);
+    l2 = l1 * ((R[6] * ra.x + R[7] * ra.y) + R[8] * ra.z) + t.z;
+    return isfinite(l1) && isfinite(l2) && l1 > 0.0 && l2 > 0.0;
+}
+
+// one of the two solutions: u = (a1 v1 + sg a3 v3) / den; U = [v2, u, v2 x u], W = [G v2, G u, G v2 x G u]; R = W U^T,
+// n = v2 x u, t = (G - R) n
+__device__ __forceinline__ void hp_solution(const double (&G)[9], Vec3 v1, Vec3 v2, Vec3 v3, double a1, double a3, double den,
+                                            double (&R)[9], Vec3 &t, Vec3 &n) {
+    const Vec3 u = Vec3{(a1 * v1.x + a3 * v3.x) / den, (a1 * v1.y + a3 * v3.y) / den, (a1 * v1.z + a3 * v3.z) / den};
+    n = cross3(v2, u);
+    const Vec3 w0 = mat3(G, v2), w1 = mat3(G, u);
+    const Vec3 w2 = cross3(w0, w1);
+    R[0] = (w0.x * v2.x + w1.x * u.x) + w2.x * n.x;
+    R[1] = (w0.x * v2.y + w1.x * u.y) + w2.x * n.y;
+    R[2] = (w0.x * v2.z + w1.x * u.z) + w2.x * n.z;
+    R[3] = (w0.y * v2.x + w1.y * u.x) + w2.y * n.x;
+    R[4] = (w0.y * v2.y + w1.y * u.y) + w2.y * n.y;
+    R[5] = (w0.y * v2.z + w1.y * u.z) + w2.y * n.z;
+    R[6] = (w0.z * v2.x + w1.z * u.x) + w2.z * n.x;
+    R[7] = (w0.z * v2.y + w1.z * u.y) + w2.z * n.y;
+    R[8] = (w0.z * v2.z + w1.z * u.z) + w2.z * n.z;
+    t = Vec3{((G[0] - R[0]) * n.x + (G[1] - R[1]) * n.y) + (G[2] - R[2]) * n.z,
+             ((G[3] - R[3]) * n.x + (G[4] - R[4]) * n.y) + (G[5] - R[5]) * n.z,
+             ((G[6] - R[6]) * n.x + (G[7] - R[7]) * n.y) + (G[8] - R[8]) * n.z};
+}
+
+__device__ __forceinline__ int hp_block_count(int slot, int (*cnt)[5]) {      // (after the caller's barrier)
+    return cnt[0][slot] + cnt[1][slot] + cnt[2][slot] + cnt[3][slot];
+}
+
+__global__ __launch_bounds__(HG_THREADS) void hp_pair_kernel(HpArgs a) {
+    __shared__ int cnt[HG_WAVES][5];
+    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int mm = hg_count(a.m, a.cap, p);
+    const double nan = __builtin_nan("");
+    int flags = 0;
+    double G[9], Rp[9], Rm[9];
+    Vec3 tpl = Vec3{nan, nan, nan}, tmi = tpl, npl = tpl, nmi = tpl;
+    double sg1 = nan, sg2 = nan, sg3 = nan;
+    bool model = false, rotation = false;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) G[k] = Rp[k] = Rm[k] = nan;
+    Vec3 v1 = tpl, v2 = tpl, v3 = tpl;
+    double a1 = nan, a3 = nan, den = nan;
+
+    if (mm < a.min_matches) {
+        flags |= MM_POSE_TOO_FEW;
+    } else {
+        double H[9];
+        bool finite = true;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            H[k] = a.Hm[9 * (size_t)p + k];
+            finite = finite && isfinite(H[k]);
+        }
+        // G = K^-1 (H K), M = G^T G
+        double HK[9], M[3][3], V[3][3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) HK[3 * r + c] = (H[3 * r] * a.K[c] + H[3 * r + 1] * a.K[3 + c]) + H[3 * r + 2] * a.K[6 + c];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            G[c] = (a.Ki[0] * HK[c] + a.Ki[1] * HK[3 + c]) + a.Ki[2] * HK[6 + c];
+            G[3 + c] = a.Ki[3] * HK[3 + c] + a.Ki[4] * HK[6 + c];
+            G[6 + c] = HK[6 + c];
+        }
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) M[r][c] = (G[r] * G[c] + G[3 + r] * G[3 + c]) + G[6 + r] * G[6 + c];
+        mm_identity<3>(V);
+        mm_jacobi<3>(M, V);
+        // l1 >= l2 >= l3 by a stable exchange sort of the columns -- (0,1), (1,2), (0,1), each exchanged only when the right
+        // eigenvalue is strictly larger (every index static)
+        double l[3] = {M[0][0], M[1][1], M[2][2]};
+        Vec3 col[3] = {Vec3{V[0][0], V[1][0], V[2][0]}, Vec3{V[0][1], V[1][1], V[2][1]}, Vec3{V[0][2], V[1][2], V[2][2]}};
+#define HP_EXCHANGE(i, j)            \
+    if (l[j] > l[i]) {               \
+        const double tl = l[i];      \
+        l[i] = l[j];                 \
+        l[j] = tl;                   \
+        const Vec3 tc = col[i];      \
+        col[i] = col[j];             \
+        col[j] = tc;                 \
+    }
+        HP_EXCHANGE(0, 1)
+        HP_EXCHANGE(1, 2)
+        HP_EXCHANGE(0, 1)
+#undef HP_EXCHANGE
+        model = finite && isfinite(l[0]) && isfinite(l[1]) && isfinite(l[2]) && l[2] > 0.0;
+        if (model) {
+            sg1 = sqrt(l[0]);
+            sg2 = sqrt(l[1]);
+            sg3 = sqrt(l[2]);
+#pragma unroll
+            for (int k = 0; k < 9; ++k) G[k] = G[k] / sg2;
+            v1 = col[0];
+            v3 = col[2];
+            v2 = cross3(v3, v1);
+            rotation = sqrt(l[0] / l[2]) - 1.0 <= a.rotation_tol;
+            const double n1 = l[0] / l[1], n3 = l[2] / l[1];      // the normalised eigenvalues (the middle one is 1)
+            a1 = sqrt(1.0 - n3);
+            a3 = sqrt(n1 - 1.0);
+            den = sqrt(n1 - n3);
+        }
+    }
+
+    // the sign of G from the well-formed matches: b . (G a) should be positive; and the malformed rows
+    int neg = 0, pos = 0, bad = 0;
+    for (int j = tid; j < mm; j += HG_THREADS) {
+        Vec3 ra, rb;
+        const bool wf = hp_rays(a, p, j, ra, rb);
+        bad += wf ? 0 : 1;
+        if (model && wf) {
+            const double d = dot3(rb, mat3(G, ra));
+            neg += d < 0.0 ? 1 : 0;
+            pos += d > 0.0 ? 1 : 0;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        neg += __shfl_xor(neg, off, 64);
+        pos += __shfl_xor(pos, off, 64);
+        bad += __shfl_xor(bad, off, 64);
+    }
+    if (lane == 0) {
+        cnt[wave][0] = neg;
+        cnt[wave][1] = pos;
+        cnt[wave][2] = bad;
+    }
+    __syncthreads();
+    neg = hp_block_count(0, cnt);
+    pos = hp_block_count(1, cnt);
+    bad = hp_block_count(2, cnt);
+    __syncthreads();      // (cnt is rewritten by the vote)
+    if (bad > 0) flags |= MM_POSE_MALFORMED;
+    if (model && neg > pos) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) G[k] = -G[k];
+    }
+
+    double Rw[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Rw[k] = nan;
+    Vec3 tw = Vec3{nan, nan, nan}, nw = tw;
+    double tnorm = nan;
+    int winner = -1, v0 = 0, v1c = 0, v2c = 0, v3c = 0;
+
+    if (model && rotation) {
+        double Gm[3][3], Rr[3][3], rt[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) Gm[r][c] = G[3 * r + c];
+        bool okR = mm_polar3(Gm, Rr, rt);
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) okR = okR && isfinite(Rr[r][c]);
+        if (okR) {
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) Rw[3 * r + c] = Rr[r][c];
+            tw = Vec3{0.0, 0.0, 0.0};
+            flags |= MM_HPOSE_ROTATION;
+        } else {
+            model = false;
+        }
+    } else if (model) {
+        hp_solution(G, v1, v2, v3, a1, a3, den, Rp, tpl, npl);
+        hp_solution(G, v1, v2, v3, a1, -a3, den, Rm, tmi, nmi);
+        const double np_ = sqrt(dot3(tpl, tpl)), nm_ = sqrt(dot3(tmi, tmi));
+        model = isfinite(np_) && isfinite(nm_) && np_ > 0.0 && nm_ > 0.0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) model = model && isfinite(Rp[k]) && isfinite(Rm[k]);
+    }
+    if (!model && !(flags & MM_POSE_TOO_FEW)) flags |= MM_POSE_NO_MODEL;
+    const bool planar = model && !rotation;
+
+    if (planar) {      // (uniform over the workgroup)
+        const Vec3 tpn = Vec3{-tpl.x, -tpl.y, -tpl.z}, npn = Vec3{-npl.x, -npl.y, -npl.z};
+        const Vec3 tmn = Vec3{-tmi.x, -tmi.y, -tmi.z}, nmn = Vec3{-nmi.x, -nmi.y, -nmi.z};
+        for (int j = tid; j < mm; j += HG_THREADS) {
+            Vec3 ra, rb;
+            if (hp_rays(a, p, j, ra, rb)) {
+                double l1, l2;
+                v0 += hp_depths(Rp, tpl, npl, ra, l1, l2) ? 1 : 0;
+                v1c += hp_depths(Rp, tpn, npn, ra, l1, l2) ? 1 : 0;
+                v2c += hp_depths(Rm, tmi, nmi, ra, l1, l2) ? 1 : 0;
+                v3c += hp_depths(Rm, tmn, nmn, ra, l1, l2) ? 1 : 0;
+            }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            v0 += __shfl_xor(v0, off, 64);
+            v1c += __shfl_xor(v1c, off, 64);
+            v2c += __shfl_xor(v2c, off, 64);
+            v3c += __shfl_xor(v3c, off, 64);
+        }
+        if (lane == 0) {
+            cnt[wave][0] = v0;
+            cnt[wave][1] = v1c;
+            cnt[wave][2] = v2c;
+            cnt[wave][3] = v3c;
+        }
+        __syncthreads();
+        v0 = hp_block_count(0, cnt);
+        v1c = hp_block_count(1, cnt);
+        v2c = hp_block_count(2, cnt);
+        v3c = hp_block_count(3, cnt);
+
+        int vmax = v0 > v1c ? v0 : v1c;
+        vmax = vmax > v2c ? vmax : v2c;
+        vmax = vmax > v3c ? vmax : v3c;
+        const double bar = a.ambiguous_frac * (double)vmax;
+        const bool c0 = (double)v0 >= bar, c1 = (double)v1c >= bar, c2 = (double)v2c >= bar, c3 = (double)v3c >= bar;
+        const int n_cont = (c0 ? 1 : 0) + (c1 ? 1 : 0) + (c2 ? 1 : 0) + (c3 ? 1 : 0);
+        bool hinted = false;
+        Vec3 hv = Vec3{0.0, 0.0, 0.0};
+        if (a.hint != nullptr) {
+            hv = Vec3{a.hint[3 * (size_t)p], a.hint[3 * (size_t)p + 1], a.hint[3 * (size_t)p + 2]};
+            hinted = isfinite(hv.x) && isfinite(hv.y) && isfinite(hv.z);
+        }
+        if (hinted) {      // the contender whose normal agrees best with the hint, ties to the lowest c
+            const double dp = dot3(npl, hv), dm = dot3(nmi, hv);
+            const double d0 = dp, d1 = -dp, d2 = dm, d3 = -dm;
+            double best = 0.0;
+            if (c0) {
+                winner = 0;
+                best = d0;
+            }
+            if (c1 && (winner < 0 || d1 > best)) {
+                winner = 1;
+                best = d1;
+            }
+            if (c2 && (winner < 0 || d2 > best)) {
+                winner = 2;
+                best = d2;
+            }
+            if (c3 && (winner < 0 || d3 > best)) {
+                winner = 3;
+                best = d3;
+            }
+        } else {           // the largest count, ties to the lowest c
+            int wv = v0;
+            winner = 0;
+            if (v1c > wv) {
+                wv = v1c;
+                winner = 1;
+            }
+            if (v2c > wv) {
+                wv = v2c;
+                winner = 2;
+            }
+            if (v3c > wv) {
+                wv = v3c;
+                winner = 3;
+            }
+        }
+        const int wv = winner == 0 ? v0 : (winner == 1 ? v1c : (winner == 2 ? v2c : v3c));
+        if ((double)wv < a.min_front_frac * (double)mm || (n_cont > 1 && !hinted)) flags |= MM_POSE_AMBIGUOUS;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Rw[k] = winner < 2 ? Rp[k] : Rm[k];
+        tw = winner == 0 ? tpl : (winner == 1 ? tpn : (winner == 2 ? tmi : tmn));
+        nw = winner == 0 ? npl : (winner == 1 ? npn : (winner == 2 ? nmi : nmn));
+        tnorm = sqrt(dot3(tw, tw));
+    }
+
+    // the winner's depths of the rows that voted for it, over |t|; NaN everywhere else, rows at or beyond m included
+    for (int j = tid; j < a.cap; j += HG_THREADS) {
+        double l1 = nan, l2 = nan;
+        if (planar && j < mm) {
+            Vec3 ra, rb;
+            if (hp_rays(a, p, j, ra, rb)) {
+                double d1, d2;
+                if (hp_depths(Rw, tw, nw, ra, d1, d2)) {
+                    l1 = d1 / tnorm;
+                    l2 = d2 / tnorm;
+                }
+            }
+        }
+        reinterpret_cast<double2 *>(a.depth)[(size_t)p * a.cap + j] = make_double2(l1, l2);
+    }
+    if (tid == 0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) a.R[9 * (size_t)p + k] = Rw[k];
+        a.t[3 * (size_t)p] = planar ? tw.x / tnorm : tw.x;
+        a.t[3 * (size_t)p + 1] = planar ? tw.y / tnorm : tw.y;
+        a.t[3 * (size_t)p + 2] = planar ? tw.z / tnorm : tw.z;
+        a.sigma[3 * (size_t)p] = sg1;
+        a.sigma[3 * (size_t)p + 1] = sg2;
+        a.sigma[3 * (size_t)p + 2] = sg3;
+        a.normal[3 * (size_t)p] = nw.x;
+        a.normal[3 * (size_t)p + 1] = nw.y;
+        a.normal[3 * (size_t)p + 2] = nw.z;
+        int32_t *o = a.info + 8 * (size_t)p;
+        o[0] = flags;
+        o[1] = winner;
+        o[2] = v0;
+        o[3] = v1c;
+        o[4] = v2c;
+        o[5] = v3c;
+        o[6] = mm;
+        o[7] = 0;
+    }
+}
+
+size_t hg_workspace(size_t np, size_t nh) {
+    return mm_align_up(np * 8 * sizeof(double), 256) + mm_align_up(np * nh * 9 * sizeof(double), 256) +
+           mm_align_up(np * nh * sizeof(double), 256);
+}
+
+}  // namespace
+
+extern "C" size_t mm_homography_workspace_bytes(int n_pairs, int n_hyp) {
+    return hg_workspace(n_pairs > 0 ? (size_t)n_pairs : 0, n_hyp > 0 ? (size_t)n_hyp : 0);
+}
+
+extern "C" int mm_verify_homography(mm_ctx *ctx, const float *kp_xy, const int32_t *pairs, const int32_t *m, int n_pairs, int cap,
+                                    const mm_homography_params *prm, const int32_t *verify_info, int32_t *pairs_out, int32_t *m_out,
+                                    double *Hm, double *cost, int32_t *info, void *ws, size_t ws_bytes) {
+    // every argument is judged before the context is looked at: nothing below this block runs on a bad call
+    if (!prm || n_pairs < 0) return mm_fail(ctx, MM_ERR_ARG, "mm_verify_homography: bad argument");
+    if (prm->n_hyp < 1 || prm->n_hyp > 4096) return mm_fail(ctx, MM_ERR_ARG, "mm_verify_homography: n_hyp must be in 1 .. 4096");
+    if (!(prm->threshold_px >= 0.0) || !(prm->collinear_tol >= 0.0))      // (negative or NaN; +inf keeps every well-formed match)
+        return mm_fail(ctx, MM_ERR_ARG, "mm_verify_homography: threshold_px and collinear_tol must not be negative");
+    if (!(prm->degenerate_frac >= 0.0 && prm->degenerate_frac <= 1.0))
+        return mm_fail(ctx, MM_ERR_ARG, "mm_verify_homography: degenerate_frac must be in [0, 1]");
+    if (prm->refit_iters < 0 || prm->refit_iters > 1000 || prm->min_inliers < 0)
+        return mm_fail(ctx, MM_ERR_ARG, "mm_verify_homography: bad parameter");
+    if (n_pairs > 0 && (!kp_xy || !pairs || !m || !pairs_out || !m_out || !Hm || !cost || !info || !ws || cap <= 0 || pairs == pairs_out))
+        return mm_fail(ctx, MM_ERR_ARG, "mm_verify_homography: bad argument");
+    if (n_pairs > 0 && ws_bytes < mm_homography_workspace_bytes(n_pairs, prm->n_hyp))
+        return mm_fail(ctx, MM_ERR_WORKSPACE, "mm_verify_homography: workspace too small");
+    if (!ctx) return MM_ERR_ARG;
+    if (n_pairs == 0) return MM_OK;
+    if (((uintptr_t)kp_xy | (uintptr_t)pairs | (uintptr_t)pairs_out) & 7)
+        return mm_fail(ctx, MM_ERR_ARG, "mm_verify_homography: kp_xy, pairs and pairs_out must be 8-byte aligned");
+    HgArgs a;
+    a.kp_xy = kp_xy;
+    a.pairs = pairs;
+    a.m = m;
+    a.verify_info = verify_info;
+    a.n_pairs = n_pairs;
+    a.cap = cap;
+    a.n_hyp = prm->n_hyp;
+    a.min_matches = prm->min_matches < 8 ? 8 : prm->min_matches;
+    a.min_inliers = prm->min_inliers;
+    a.refit_iters = prm->refit_iters;
+    a.seed = prm->seed;
+    a.pair_base = prm->pair_base;
+    a.tau2 = prm->threshold_px * prm->threshold_px;
+    a.collinear_tol = prm->collinear_tol;
+    a.degenerate_frac = prm->degenerate_frac;
+    char *w = (char *)ws;
+    a.norm = (double *)w;
+    w += mm_align_up((size_t)n_pairs * 8 * sizeof(double), 256);
+    a.Hh = (double *)w;
+    w += mm_align_up((size_t)n_pairs * a.n_hyp * 9 * sizeof(double), 256);
+    a.cost_h = (double *)w;
+    const dim3 per_hyp((unsigned)n_pairs, (unsigned)((a.n_hyp + 63) / 64));
+    MM_LAUNCH(ctx, "hg_normalise_kernel", hg_normalise_kernel, dim3((unsigned)n_pairs), dim3(HG_THREADS), 0, a);
+    MM_LAUNCH(ctx, "hg_hypothesis_kernel", hg_hypothesis_kernel, per_hyp, dim3(64), 0, a);
+    MM_LAUNCH(ctx, "hg_score_kernel", hg_score_kernel, per_hyp, dim3(64), 0, a);
+    MM_LAUNCH(ctx, "hg_finish_kernel", hg_finish_kernel, dim3((unsigned)n_pairs), dim3(HG_THREADS), 0, a, pairs_out, m_out, Hm, cost, info);
+    return MM_OK;
+}
+
+extern "C" int mm_recover_poses_homography(mm_ctx *ctx, const double *K, const float *kp_xy, const int32_t *pairs, const int32_t *m,
+                                           const double *Hm, const double *normal_hint, int n_pairs, int cap,
+                                           const mm_hpose_params *prm, double *R, double *t, double *sigma, double *normal,
+                                           double *depth, int32_t *info) {
+    // every argument is judged before the context is looked at: nothing below this block runs on a bad call
+    if (!prm || !K || n_pairs < 0 || cap <= 0) return mm_fail(ctx, MM_ERR_ARG, "mm_recover_poses_homography: bad argument");
+    if (!(prm->min_front_frac >= 0.0 && prm->min_front_frac <= 1.0) || !(prm->ambiguous_frac >= 0.0 && prm->ambiguous_frac <= 1.0))
+        return mm_fail(ctx, MM_ERR_ARG, "mm_recover_poses_homography: min_front_frac and ambiguous_frac must be in [0, 1]");
+    if (!(prm->rotation_tol >= 0.0)) return mm_fail(ctx, MM_ERR_ARG, "mm_recover_poses_homography: rotation_tol must not be negative");
+    bool k_ok = K[3] == 0.0 && K[6] == 0.0 && K[7] == 0.0 && K[8] == 1.0 && K[0] != 0.0 && K[4] != 0.0;
+    for (int k = 0; k < 9; ++k) k_ok = k_ok && std::isfinite(K[k]);
+    if (!k_ok)
+        return mm_fail(ctx, MM_ERR_ARG,
+                       "mm_recover_poses_homography: K must be finite and upper triangular with K[8] = 1 and non-zero focal lengths");
+    if (n_pairs > 0 && (!kp_xy || !pairs || !m || !Hm || !R || !t || !sigma || !normal || !depth || !info))
+        return mm_fail(ctx, MM_ERR_ARG, "mm_recover_poses_homography: bad argument");
+    if (!ctx) return MM_ERR_ARG;
+    if (n_pairs == 0) return MM_OK;
+    if (((uintptr_t)kp_xy | (uintptr_t)pairs) & 7 || ((uintptr_t)depth & 15))
+        return mm_fail(ctx, MM_ERR_ARG, "mm_recover_poses_homography: kp_xy and pairs must be 8-byte aligned, depth 16-byte aligned");
+    HpArgs a;
+    a.kp_xy = kp_xy;
+    a.pairs = pairs;
+    a.m = m;
+    a.Hm = Hm;
+    a.hint = normal_hint;
+    a.n_pairs = n_pairs;
+    a.cap = cap;
+    a.min_matches = prm->min_matches < 8 ? 8 : prm->min_matches;
+    a.min_front_frac = prm->min_front_frac;
+    a.ambiguous_frac = prm->ambiguous_frac;
+    a.rotation_tol = prm->rotation_tol;
+    for (int k = 0; k < 9; ++k) a.K[k] = K[k];
+    mm_k_inverse(K, a.Ki);
+    a.R = R;
+    a.t = t;
+    a.sigma = sigma;
+    a.normal = normal;
+    a.depth = depth;
+    a.info = info;
+    MM_LAUNCH(ctx, "hp_pair_kernel", hp_pair_kernel, dim3((unsigned)n_pairs), dim3(HG_THREADS), 0, a);
+    return MM_OK;
+}

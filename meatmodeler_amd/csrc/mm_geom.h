@@ -1,9 +1,10 @@
-// The deterministic building blocks that the geometry stages share (verify.hip, pose.hip, resect.hip, triangulate.hip).
+// The deterministic building blocks that the geometry stages share (verify.hip, pose.hip, resect.hip, homography.hip,
+// triangulate.hip).
 //
 // include/meatmodeler.h states each of them once and lets the later stages refer back ("the integer scheme of
 // mm_verify_matches", "the 3 x 3 cyclic Jacobi of ..."); the stages promise results that repeat bit for bit, so every one of
 // these is a definition, written here once.  Header only, __forceinline__ templates: each is compiled under the flags of
-// the file that includes it (FMA contraction is off for pose.hip and resect.hip, on for verify.hip and triangulate.hip --
+// the file that includes it (FMA contraction is off for pose.hip, resect.hip and homography.hip, on for verify.hip and triangulate.hip --
 // Makefile), so a stage's bits are those of its own build.  What belongs here: a definition the C header gives once and
 // several stages rely on.  What does not: one stage's model (its score kernel, its solver).
 #pragma once

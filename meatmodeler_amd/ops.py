@@ -214,6 +214,99 @@ def chain_poses(pairs, m, depth, R, t, info, E0=None, min_common=8, ctx=None):
     return ext, scale, rho, cinfo
 
 
+HOMOG_TOO_FEW, HOMOG_NO_MODEL, HOMOG_WEAK, HOMOG_MALFORMED, HOMOG_DEGENERATE = 1, 2, 4, 8, 16      # MM_HOMOG_*
+HPOSE_ROTATION = 16                                                                             # MM_HPOSE_ROTATION
+
+
+def _pair_shapes(name, kp_xy, pairs, m):
+    if pairs.dim() != 3 or pairs.shape[2] != 2 or kp_xy.dim() != 3 or tuple(kp_xy.shape) != (pairs.shape[0] + 1, pairs.shape[1], 2) \
+            or tuple(m.shape) != (pairs.shape[0],):
+        raise ValueError(f"{name}: kp_xy [n_pairs+1, cap, 2], pairs [n_pairs, cap, 2] and m [n_pairs] expected")
+
+
+def verify_homography(kp_xy, pairs, m, verify_info=None, n_hyp=256, threshold_px=2.0, min_matches=8, min_inliers=16, refit_iters=2,
+                      seed=0, pair_base=0, collinear_tol=1e-3, degenerate_frac=0.8, ctx=None):
+    """A RANSAC homography per consecutive frame pair (mm_verify_homography) on the matches verify_matches reads: kp_xy
+    [n_pairs+1, cap, 2] f32, pairs [n_pairs, cap, 2] i32, m [n_pairs] i32 (device tensors); verify_info [n_pairs, 4] i32 the
+    info of verify_matches on the same matches, or None (no verdict)
+    -> (pairs_out [n_pairs, cap, 2] i32 -- the inliers of each pair's homography in input order, -1 beyond m_out; nothing for
+    a failed pair --, m_out [n_pairs] i32, H [n_pairs, 9] f64 (x' ~ H x, unit norm, NaN without a model), cost [n_pairs] f64,
+    info [n_pairs, 6] i32 = (HOMOG_* flags, n_inliers, best_h, valid hypotheses, n_F or -1, 0)).  HOMOG_DEGENERATE: the pair
+    is planar or rotation-only, its fundamental matrix one of a pencil."""
+    if not 1 <= int(n_hyp) <= 4096:
+        raise ValueError("verify_homography: n_hyp must be in 1 .. 4096")
+    if not float(threshold_px) >= 0 or not float(collinear_tol) >= 0:
+        raise ValueError("verify_homography: threshold_px and collinear_tol must not be negative")
+    if not 0.0 <= float(degenerate_frac) <= 1.0:
+        raise ValueError("verify_homography: degenerate_frac must be in [0, 1]")
+    if not 0 <= int(refit_iters) <= 1000 or int(min_inliers) < 0:
+        raise ValueError("verify_homography: refit_iters must be in 0 .. 1000 and min_inliers not negative")
+    _pair_shapes("verify_homography", kp_xy, pairs, m)
+    if verify_info is not None and tuple(verify_info.shape) != (pairs.shape[0], 4):
+        raise ValueError("verify_homography: verify_info [n_pairs, 4] expected")
+    ctx = ctx or default_context()
+    d = pairs.device
+    n_pairs, cap = pairs.shape[0], pairs.shape[1]
+    pairs_out = torch.full((n_pairs, cap, 2), -1, dtype=torch.int32, device=d)
+    m_out = torch.zeros(n_pairs, dtype=torch.int32, device=d)
+    H = torch.full((n_pairs, 9), math.nan, dtype=torch.float64, device=d)
+    cost = torch.full((n_pairs,), math.nan, dtype=torch.float64, device=d)
+    info = torch.zeros((n_pairs, 6), dtype=torch.int32, device=d)
+    if n_pairs == 0 or cap == 0:
+        return pairs_out, m_out, H, cost, info
+    prm = _lib.HomographyParams(int(n_hyp), int(min_matches), int(min_inliers), int(refit_iters), int(seed) & 0xFFFFFFFF,
+                                int(pair_base) & 0xFFFFFFFF, float(threshold_px), float(collinear_tol), float(degenerate_frac))
+    wsb = lib.mm_homography_workspace_bytes(n_pairs, int(n_hyp))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=d)
+    assert kp_xy.dtype == torch.float32
+    vi = None if verify_info is None else _i32(verify_info.contiguous())
+    ctx.check(lib.mm_verify_homography(ctx.h, ptr(kp_xy.contiguous()), ptr(_i32(pairs.contiguous())), ptr(_i32(m.contiguous())),
+                                       n_pairs, cap, C.byref(prm), ptr(vi), ptr(pairs_out), ptr(m_out), ptr(H), ptr(cost),
+                                       ptr(info), ptr(ws), wsb), "mm_verify_homography")
+    return pairs_out, m_out, H, cost, info
+
+
+def recover_poses_homography(kp_xy, pairs, m, H, K, normal_hint=None, min_matches=8, min_front_frac=0.5, ambiguous_frac=0.9,
+                             rotation_tol=1e-2, ctx=None):
+    """The motion each pair's homography implies (mm_recover_poses_homography): kp_xy, pairs, m and H [n_pairs, 9] f64 as
+    verify_homography returns them (device tensors), K 3 x 3 on the host, normal_hint [n_pairs, 3] f64 or None
+    -> (R [n_pairs, 9], t [n_pairs, 3] with X2 = R X1 + t -- |t| = 1 for a plane, t = 0 with HPOSE_ROTATION --, sigma
+    [n_pairs, 3], normal [n_pairs, 3] (the plane n . X = d in camera 1; NaN for a rotation), depth [n_pairs, cap, 2], info
+    [n_pairs, 8] i32 = (POSE_* flags | HPOSE_ROTATION, winner or -1, votes[0..3], m used, 0)): the rows chain_poses reads."""
+    Kh = _host_f64(K, 9, "recover_poses_homography: K")
+    if not np.isfinite(Kh).all() or Kh[3] != 0 or Kh[6] != 0 or Kh[7] != 0 or Kh[8] != 1 or Kh[0] == 0 or Kh[4] == 0:
+        raise ValueError("recover_poses_homography: K must be finite, upper triangular with K[2, 2] = 1 and non-zero focal lengths")
+    if not (0.0 <= float(min_front_frac) <= 1.0 and 0.0 <= float(ambiguous_frac) <= 1.0):
+        raise ValueError("recover_poses_homography: min_front_frac and ambiguous_frac must be in [0, 1]")
+    if not float(rotation_tol) >= 0:
+        raise ValueError("recover_poses_homography: rotation_tol must not be negative")
+    _pair_shapes("recover_poses_homography", kp_xy, pairs, m)
+    if tuple(H.shape) != (pairs.shape[0], 9) or (normal_hint is not None and tuple(normal_hint.shape) != (pairs.shape[0], 3)):
+        raise ValueError("recover_poses_homography: H [n_pairs, 9] and normal_hint [n_pairs, 3] expected")
+    ctx = ctx or default_context()
+    d = pairs.device
+    n_pairs, cap = pairs.shape[0], pairs.shape[1]
+    R = torch.full((n_pairs, 9), math.nan, dtype=torch.float64, device=d)
+    t = torch.full((n_pairs, 3), math.nan, dtype=torch.float64, device=d)
+    sigma = torch.full((n_pairs, 3), math.nan, dtype=torch.float64, device=d)
+    normal = torch.full((n_pairs, 3), math.nan, dtype=torch.float64, device=d)
+    depth = torch.empty((n_pairs, cap, 2), dtype=torch.float64, device=d)      # (every element is written by the kernel)
+    info = torch.zeros((n_pairs, 8), dtype=torch.int32, device=d)
+    if n_pairs == 0 or cap == 0:
+        return R, t, sigma, normal, depth, info
+    assert kp_xy.dtype == torch.float32 and H.dtype == torch.float64
+    hint = None
+    if normal_hint is not None:
+        assert normal_hint.dtype == torch.float64
+        hint = normal_hint.contiguous()
+    prm = _lib.HPoseParams(int(min_matches), 0, float(min_front_frac), float(ambiguous_frac), float(rotation_tol))
+    ctx.check(lib.mm_recover_poses_homography(ctx.h, Kh.ctypes.data_as(_lib.c_f64p), ptr(kp_xy.contiguous()),
+                                              ptr(_i32(pairs.contiguous())), ptr(_i32(m.contiguous())), ptr(H.contiguous()),
+                                              ptr(hint), n_pairs, cap, C.byref(prm), ptr(R), ptr(t), ptr(sigma), ptr(normal),
+                                              ptr(depth), ptr(info)), "mm_recover_poses_homography")
+    return R, t, sigma, normal, depth, info
+
+
 RESECT_TOO_FEW, RESECT_NO_MODEL, RESECT_WEAK, RESECT_MALFORMED = 1, 2, 4, 8      # MM_RESECT_* of include/meatmodeler.h
 RESECT_PLANAR = 16
 

@@ -25,6 +25,10 @@ from .orb_pattern import brief_pattern
 
 VERIFY_KEYS = ("n_hyp", "threshold_px", "min_matches", "min_inliers", "refit_iters", "seed", "on_fail")
 POSE_KEYS = ("min_matches", "min_front_frac", "ambiguous_frac", "min_common", "E0")
+DEGENERACY_HOMOGRAPHY_KEYS = ("n_hyp", "threshold_px", "min_matches", "min_inliers", "refit_iters", "seed", "collinear_tol",
+                              "degenerate_frac")
+DEGENERACY_POSE_KEYS = ("min_front_frac", "ambiguous_frac", "rotation_tol")
+DEGENERACY_KEYS = DEGENERACY_HOMOGRAPHY_KEYS + DEGENERACY_POSE_KEYS
 RESECT_KEYS = ("n_hyp", "threshold_px", "min_rows", "min_inliers", "refit_iters", "polish_iters", "seed", "planar", "planar_tol",
                "collinear_tol")
 
@@ -52,6 +56,13 @@ def pose_options(poses):
     """`run(..., poses=)`: None (the caller provides the extrinsics) or a dict of the parameters of ops.recover_poses and
     ops.chain_poses.  Returns it as a dict; an unknown key raises ValueError."""
     return _stage_options("poses", poses, POSE_KEYS)
+
+
+def degeneracy_options(degeneracy):
+    """`run(..., degeneracy=)`: None (no homography stage) or a dict of the parameters of ops.verify_homography and of
+    ops.recover_poses_homography (min_front_frac, ambiguous_frac, rotation_tol) -- verify_info, pair_base, the hint and ctx are
+    the pipeline's own.  Returns it as a dict; an unknown key raises ValueError."""
+    return _stage_options("degeneracy", degeneracy, DEGENERACY_KEYS)
 
 
 def resect_options(resect):
@@ -115,6 +126,14 @@ class ClipPipeline:
         block gives the rows the whole clip would.  -> (pairs_out, m_out, F [n,9], cost [n], info [n,4]), device tensors."""
         n = pairs.shape[0]
         return ops.verify_matches(det["xy"][:n + 1], pairs, m, pair_base=pair_lo, ctx=self.ctx, **params)
+
+    # ------------------------------------------------------------------------------------------- homography
+    def homography(self, det, pairs, m, verify_info=None, pair_lo=0, **params):
+        """A RANSAC homography per pair on the matches `match` returned for the frames in `det` (ops.verify_homography) -- the
+        same input `verify` takes, not its output; verify_info = the info `verify` returned for them, which the planar /
+        rotation-only verdict needs; pair_lo as in `verify`.  -> (pairs_out, m_out, H [n,9], cost [n], info [n,6])."""
+        n = pairs.shape[0]
+        return ops.verify_homography(det["xy"][:n + 1], pairs, m, verify_info=verify_info, pair_base=pair_lo, ctx=self.ctx, **params)
 
     # ------------------------------------------------------------------------------------------- poses
     def recover_poses(self, det, pairs, m, F, K, E0=None, min_common=8, **params):
@@ -496,7 +515,7 @@ class ClipPipeline:
 
     # ------------------------------------------------------------------------------------------- whole clip
     def run(self, frames, K, extrinsics=None, ba=True, ftol=1e-4, verbose=0, dist=None, timers=None, max_nfev=None,
-            force_collectives=False, triangulation="two_view", cull=None, verify=None, poses=None, resect=None):
+            force_collectives=False, triangulation="two_view", cull=None, verify=None, poses=None, resect=None, degeneracy=None):
         """frames [F,H,W] u8 (device).  With `dist` = torch.distributed (initialised), frames are the FULL clip on
         every rank (synthetic input is generated locally) and the work is sharded as described in parallel.py.
         `max_nfev`: evaluation budget of the adjustment (None = SciPy's default, as adjustPoints).
@@ -518,6 +537,13 @@ class ClipPipeline:
         neighbouring pair's depths across every rank boundary): the extrinsics are recovered from the verified matches and
         K, `extrinsics` may be None, and the result gains `poses` = dict(extrinsics [F,3,4], R, t, sigma, info, scale, rho,
         chain_info); timer "poses".  The first baseline is the unit of length.
+        `degeneracy`: None (default: nothing below runs) or a dict of the parameters of ops.verify_homography and the
+        fractions / rotation_tol of ops.recover_poses_homography ({} for the defaults; needs `verify`): every rank fits a
+        homography per pair on the matches `verify` read, and a pair the homography explains as well as the fundamental matrix
+        (HOMOG_DEGENERATE: a planar scene or a camera that only turns) is linked by the homography's inliers; with
+        `poses` its relative pose comes from the homography -- a pure rotation is chained with t = 0 and the scale carried --
+        before the one chain call.  The selection is a torch.where on the device, no host read.  The result gains `degeneracy`
+        = dict(H [n,9], cost [n], info [n,6], and with `poses` pose_info [n,8], sigma [n,3], normal [n,3]); timer "degeneracy".
         `resect`: None (default) or a dict of the parameters of ops.resect_cameras ({} for the defaults; one rank only): after
         the triangulation every frame is resected against `points0` (under "multi_view" only against the tracks no test
         flagged), with the extrinsics in use -- given or recovered -- as the prior, so no frame ends with a higher MSAC cost
@@ -527,6 +553,10 @@ class ClipPipeline:
         verify = verify_options(verify)
         poses = pose_options(poses)
         resect = resect_options(resect)
+        degeneracy = degeneracy_options(degeneracy)
+        if degeneracy is not None and verify is None:
+            raise ValueError("degeneracy needs verify (the verdict compares the homography with each pair's fundamental matrix): "
+                             "pass verify={} for the defaults")
         if poses is not None and verify is None:
             raise ValueError("poses needs verify (it supplies each pair's fundamental matrix): pass verify={} for the defaults")
         if poses is None and extrinsics is None:
@@ -576,7 +606,7 @@ class ClipPipeline:
         verified = None
         if verify is not None:
             tic("verify")
-            matches_in = m
+            pairs_in, matches_in = pairs, m
             if det is not None:
                 pairs, m, F_v, cost_v, info_v = self.verify(det, pairs, m, pair_lo=p_lo, **verify)
             else:
@@ -585,6 +615,22 @@ class ClipPipeline:
                 info_v = torch.zeros((0, 4), dtype=torch.int32, device=self.device)
             verified = dict(info=info_v, cost=cost_v, F=F_v, matches_in=matches_in)
             toc("verify")
+        degenerate = None
+        if degeneracy is not None:
+            tic("degeneracy")
+            if det is not None:
+                hparams = {k: v for k, v in degeneracy.items() if k in DEGENERACY_HOMOGRAPHY_KEYS}
+                pairs_h, m_hg, H_d, cost_d, info_d = self.homography(det, pairs_in, matches_in, verify_info=info_v, pair_lo=p_lo,
+                                                                     **hparams)
+                is_deg = (info_d[:, 0] & ops.HOMOG_DEGENERATE) != 0
+                pairs = torch.where(is_deg[:, None, None], pairs_h, pairs)
+                m = torch.where(is_deg, m_hg, m)
+            else:
+                H_d = torch.zeros((0, 9), dtype=torch.float64, device=self.device)
+                cost_d = torch.zeros(0, dtype=torch.float64, device=self.device)
+                info_d = torch.zeros((0, 6), dtype=torch.int32, device=self.device)
+            degenerate = dict(H=H_d, cost=cost_d, info=info_d)
+            toc("degeneracy")
         tic("link")
         if sharded:
             # every rank needs every frame's key points and every pair's matches to link identical tracks.  The block
@@ -617,7 +663,30 @@ class ClipPipeline:
         recovered = None
         if poses is not None:
             tic("poses")
-            recovered = self.recover_poses(det, pairs, m, F_v, K, **poses)
+            if degenerate is None:
+                recovered = self.recover_poses(det, pairs, m, F_v, K, **poses)
+            else:
+                # both pose calls on the linked matches, the homography's rows where the verdict says so, then one chain
+                kw = {k: v for k, v in poses.items() if k not in ("E0", "min_common")}
+                R_p, t_p, sigma_p, depth_p, info_p = ops.recover_poses(det["xy"], pairs, m, F_v, K, ctx=self.ctx, **kw)
+                toc("poses")
+                tic("degeneracy")
+                hkw = {k: v for k, v in degeneracy.items() if k in DEGENERACY_POSE_KEYS}
+                if "min_matches" in kw:
+                    hkw["min_matches"] = kw["min_matches"]
+                R_h, t_h, sigma_h, normal_h, depth_h, info_h = ops.recover_poses_homography(det["xy"], pairs, m, H_d, K,
+                                                                                            ctx=self.ctx, **hkw)
+                R_p = torch.where(is_deg[:, None], R_h, R_p)
+                t_p = torch.where(is_deg[:, None], t_h, t_p)
+                depth_p = torch.where(is_deg[:, None, None], depth_h, depth_p)
+                info_p = torch.where(is_deg[:, None], info_h, info_p)
+                degenerate.update(pose_info=info_h, sigma=sigma_h, normal=normal_h)
+                toc("degeneracy")
+                tic("poses")
+                ext_d, scale_d, rho_d, cinfo_d = ops.chain_poses(pairs, m, depth_p, R_p, t_p, info_p, E0=poses.get("E0"),
+                                                                 min_common=poses.get("min_common", 8), ctx=self.ctx)
+                recovered = dict(extrinsics=ext_d, R=R_p, t=t_p, sigma=sigma_p, info=info_p, depth=depth_p, scale=scale_d,
+                                 rho=rho_d, chain_info=cinfo_d)
             recovered.pop("depth")
             ext = recovered["extrinsics"].cpu().numpy()
             toc("poses")
@@ -653,6 +722,8 @@ class ClipPipeline:
             out["verify"] = verified
         if recovered is not None:
             out["poses"] = recovered
+        if degenerate is not None:
+            out["degeneracy"] = degenerate
         if resected is not None:
             out["resect"] = resected
         kept = None

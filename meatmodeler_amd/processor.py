@@ -6,6 +6,7 @@ return order, HIP kernels underneath (no CPU fallback: a missing extension or GP
     cv2.ORB_create(nfeatures=...)  processor.py:308  ORB_create(nfeatures=...) -> ORB (detectAndCompute on device)
     featureTracking                processor.py:113  featureTracking     (mm_orb_detect_compute + mm_bf_knn2_* + ratio)
     (no counterpart)                                 verifyMatches       (mm_verify_matches: RANSAC fundamental matrix, inlier mask)
+    (no counterpart)                                 verifyHomography    (mm_verify_homography: RANSAC homography, planar / rotation-only verdict)
     pointTracking                  processor.py:190  pointTracking       (hash join; same list semantics)
     triangulatePoints              processor.py:246  triangulatePoints   (mm_triangulate_dlt, batched over tracks)
     (no counterpart)                                 triangulateTracks   (mm_triangulate_tracks: all views, quality, flags)
@@ -357,6 +358,54 @@ def recoverPose(prev_matches, curr_matches, K, F, **params):
     R, t, _, depth, _ = ops.recover_poses(kp, pairs, m, Fd, K, **params)
     mask = torch.isfinite(depth[0, :, 0]).cpu().numpy()
     return int(mask.sum()), R[0].cpu().numpy().reshape(3, 3), t[0].cpu().numpy(), mask
+
+
+def _one_pair(name, prev_matches, curr_matches):
+    """The two coordinate lists of a wrapper as the one-pair call of the ops: (n, kp_xy [2,n,2], pairs [1,n,2], m [1])."""
+    prev = np.asarray(prev_matches, np.float32).reshape(-1, 2)
+    curr = np.asarray(curr_matches, np.float32).reshape(-1, 2)
+    if prev.shape != curr.shape:
+        raise ValueError(f"{name}: prev_matches and curr_matches must have the same length")
+    n = prev.shape[0]
+    if n == 0:
+        return 0, None, None, None
+    dev = default_context().device
+    kp = torch.as_tensor(np.stack([prev, curr])).to(dev)
+    idx = torch.arange(n, dtype=torch.int32, device=dev)
+    pairs = torch.stack([idx, idx], dim=1).unsqueeze(0).contiguous()
+    return n, kp, pairs, torch.full((1,), n, dtype=torch.int32, device=dev)
+
+
+def verifyHomography(prev_matches, curr_matches, **params):
+    """A RANSAC homography between two keyframes on what `featureTracking` returns (the input of `verifyMatches`, not its
+    output): -> (mask [n] bool, H [3,3] f64 with curr ~ H prev, NaN if no model was found, flags -- the HOMOG_* bits of
+    ops.verify_homography).  `params` as ops.verify_homography takes them; with verify_info = the [1,4] info row of
+    ops.verify_matches on the same matches the flags carry the planar / rotation-only verdict HOMOG_DEGENERATE."""
+    n, kp, pairs, m = _one_pair("verifyHomography", prev_matches, curr_matches)
+    if n == 0:
+        return np.zeros(0, bool), np.full((3, 3), np.nan), ops.HOMOG_TOO_FEW
+    pairs_out, m_out, H, _, info = ops.verify_homography(kp, pairs, m, **params)
+    mask = np.zeros(n, bool)
+    mask[pairs_out[0, :int(m_out[0].item()), 0].cpu().numpy()] = True
+    return mask, H[0].cpu().numpy().reshape(3, 3), int(info[0, 0].item())
+
+
+def recoverPoseFromHomography(prev_matches, curr_matches, K, H, **params):
+    """The motion a homography between two keyframes implies (curr ~ H prev, as `verifyHomography` returns it):
+    -> (n_front, R [3,3], t [3], mask [n] bool, normal [3], flags) with X_curr = R X_prev + t.  A plane: |t| = 1, normal its
+    unit-distance normal in the previous camera, mask the matches in front of both cameras; a camera that only turned
+    (flags & HPOSE_ROTATION): t = 0, normal NaN, no depths.  `params` as ops.recover_poses_homography takes them
+    (normal_hint [1,3], min_matches, min_front_frac, ambiguous_frac, rotation_tol)."""
+    n, kp, pairs, m = _one_pair("recoverPoseFromHomography", prev_matches, curr_matches)
+    if n == 0:
+        return 0, np.full((3, 3), np.nan), np.full(3, np.nan), np.zeros(0, bool), np.full(3, np.nan), ops.POSE_TOO_FEW
+    Hd = torch.as_tensor(np.ascontiguousarray(np.asarray(H, np.float64).reshape(1, 9))).to(kp.device)
+    if params.get("normal_hint") is not None:
+        params = dict(params, normal_hint=torch.as_tensor(np.asarray(params["normal_hint"], np.float64).reshape(1, 3)).to(kp.device))
+    R, t, _, normal, depth, info = ops.recover_poses_homography(kp, pairs, m, Hd, K, **params)
+    mask = torch.isfinite(depth[0, :, 0]).cpu().numpy()
+    return (int(mask.sum()), R[0].cpu().numpy().reshape(3, 3), t[0].cpu().numpy(), mask, normal[0].cpu().numpy(),
+            int(info[0, 0].item()))
 
 
 def resectCameras(points_3D, points_2D, K, prior=None, **params):
