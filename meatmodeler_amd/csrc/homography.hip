@@ -14,56 +14,24 @@
 //                         against the fundamental matrix's inlier count, order-preserving compaction, outputs
 //   hp_pair_kernel        one workgroup per pair: G = K^-1 H K, its eigenpairs, the sign from the matches, then either the
 //                         polar factor (rotation only) or the four plane motions, integer votes, the winner's depths
+// The reduced DLT and the triple rule are mm_geom.h's (shared with resect.hip); how a match is read, the normalisation and the
+// MSAC skeleton are mm_pairs.h's (shared with verify.hip); here is the model: HgModel, hg_solve's own tail, the verdict.
 // Built without FMA contraction (Makefile): the inlier test is evaluated in several passes that must agree on every bit, the
 // depth pass repeats the vote pass, and the NumPy restatement of the tests follows the header operation by operation.
 // Plain f64 VALU work; sums in an order that depends on the pair alone (per-thread strides, xor butterflies, waves in order),
 // no float atomics: a pair's row repeats bit for bit whatever else shares the call.
-#include "mm_common.h"
-#include "mm_geom.h"
+#include "mm_pairs.h"
 
 namespace {
 
 constexpr int HG_THREADS = 256;      // normalise / finish / pose: one workgroup per pair
 constexpr int HG_WAVES = HG_THREADS / 64;
-constexpr int HG_TILE = 256;         // matches per LDS tile of the score kernel
 static_assert(HG_THREADS == MM_BLOCK_THREADS, "the mm_block_* helpers are written for this workgroup");
 
-struct HgArgs {
-    const float *kp_xy;
-    const int32_t *pairs, *m, *verify_info;
-    int n_pairs, cap, n_hyp, min_matches, min_inliers, refit_iters;
-    uint32_t seed, pair_base;
-    double tau2, collinear_tol, degenerate_frac;
-    double *norm;      // [n_pairs, 8]: cx, cy, s, cx', cy', s', number of malformed matches, -
-    double *Hh;        // [n_pairs, n_hyp, 9] (NaN: invalid hypothesis)
-    double *cost_h;    // [n_pairs, n_hyp] (+inf: invalid hypothesis)
+struct HgArgs : MmPairArgs {      // (model_h: the hypotheses' H)
+    const int32_t *verify_info;
+    double collinear_tol, degenerate_frac;
 };
-
-__device__ __forceinline__ int hg_count(const int32_t *m, int cap, int p) {
-    const int mm = m[p];
-    return mm < 0 ? 0 : (mm > cap ? cap : mm);
-}
-
-// match j of pair p, widened; false (and NaN coordinates) for a malformed match -- nothing is read through a bad index
-__device__ __forceinline__ bool hg_load(const float *kp_xy, const int32_t *pairs, int cap, int p, int j, double &x, double &y,
-                                        double &xp, double &yp) {
-    const int2 qt = reinterpret_cast<const int2 *>(pairs)[(size_t)p * cap + j];
-    const bool wf = (unsigned)qt.x < (unsigned)cap && (unsigned)qt.y < (unsigned)cap;
-    const double nan = __builtin_nan("");
-    x = y = xp = yp = nan;
-    if (wf) {
-        const float2 u = reinterpret_cast<const float2 *>(kp_xy)[(size_t)p * cap + qt.x];
-        const float2 v = reinterpret_cast<const float2 *>(kp_xy)[(size_t)(p + 1) * cap + qt.y];
-        x = (double)u.x;
-        y = (double)u.y;
-        xp = (double)v.x;
-        yp = (double)v.y;
-    }
-    return wf;
-}
-__device__ __forceinline__ bool hg_load(const HgArgs &a, int p, int j, double &x, double &y, double &xp, double &yp) {
-    return hg_load(a.kp_xy, a.pairs, a.cap, p, j, x, y, xp, yp);
-}
 
 // adj(H), written out: every entry one difference of two products, no division by the determinant
 __device__ __forceinline__ void hg_adjugate(const double (&H)[9], double (&A)[9]) {
@@ -85,113 +53,25 @@ __device__ __forceinline__ double hg_transfer(const double (&H)[9], const double
     const double ex = xp - y0 / y2, ey = yp - y1 / y2, fx = x - z0 / z2, fy = y - z1 / z2;
     return ((ex * ex + ey * ey) + (fx * fx + fy * fy)) * 0.5;
 }
-__device__ __forceinline__ bool hg_inlier(double d2, double tau2) { return isfinite(d2) && d2 <= tau2; }
 
-// one normalised match into the 24 sums: S, Bu, Bv, C, each the upper triangle of a 3 x 3, row-major, over m = (x, y, 1)
-// with (u, v) = the normalised x'
-__device__ __forceinline__ void hg_accumulate(double (&acc)[24], double xn, double yn, double u, double v) {
-    const double m[3] = {xn, yn, 1.0};
-    const double r2 = u * u + v * v;
-    int k = 0;
+// the model of the MSAC skeleton (mm_pairs.h): H with its adjugate prepared once
+struct HgModel {
+    double H[9], A[9];
+    __device__ __forceinline__ explicit HgModel(const double (&h)[9]) {
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = i; j < 3; ++j) {
-            const double w = m[i] * m[j];
-            acc[k] += w;
-            acc[6 + k] += u * w;
-            acc[12 + k] += v * w;
-            acc[18 + k] += r2 * w;
-            ++k;
-        }
-}
+        for (int c = 0; c < 9; ++c) H[c] = h[c];
+        hg_adjugate(H, A);
+    }
+    __device__ __forceinline__ double distance(double x, double y, double xp, double yp) const { return hg_transfer(H, A, x, y, xp, yp); }
+};
 
-// true: the triangle (i, j, k) is not near-collinear: |cross| > tol x its longest squared side (NaN: false) -- the rule of
-// mm_resect_planar
-__device__ __forceinline__ bool hg_triple_ok(double ai, double bi, double aj, double bj, double ak, double bk, double tol) {
-    const double pa = aj - ai, pb = bj - bi, qa = ak - ai, qb = bk - bi, ra = ak - aj, rb = bk - bj;
-    const double cr = pa * qb - pb * qa;
-    const double d0 = pa * pa + pb * pb, d1 = qa * qa + qb * qb, d2 = ra * ra + rb * rb;
-    double lng = d0 > d1 ? d0 : d1;
-    lng = lng > d2 ? lng : d2;
-    return fabs(cr) > tol * lng;
-}
-
-// H from the 24 sums: the reduced DLT of mm_resect_planar (Cholesky of S, h3 by the 3 x 3 Jacobi, h1 and h2 by back
-// substitution), the rank guard on the normalised matrix, H = T'^-1 H^ T, unit Frobenius norm, (H c)_2 >= 0.
+// H from the 24 sums: the reduced DLT (mm_plane_dlt), the rank guard on the normalised matrix, H = T'^-1 H^ T, unit Frobenius
+// norm, (H c)_2 >= 0.
 // false: a failed pivot, a rank below three or a non-finite entry.
 __device__ __forceinline__ bool hg_solve(const double (&acc)[24], double cx, double cy, double s, double cx2, double cy2, double s2,
                                          double (&H)[9]) {
-    double S[3][3], Bu[3][3], Bv[3][3], M[3][3];
-    {
-        int k = 0;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = i; j < 3; ++j) {
-                S[i][j] = S[j][i] = acc[k];
-                Bu[i][j] = Bu[j][i] = acc[6 + k];
-                Bv[i][j] = Bv[j][i] = acc[12 + k];
-                M[i][j] = M[j][i] = acc[18 + k];
-                ++k;
-            }
-    }
-    double L[3][3];
-    bool ok = mm_cholesky_pivot<3>(S, L);
-    double Yu[3][3], Yv[3][3];      // L^-1 Bu, L^-1 Bv
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            double vu = Bu[i][c], vv = Bv[i][c];
-#pragma unroll
-            for (int k = 0; k < i; ++k) {
-                vu -= L[i][k] * Yu[k][c];
-                vv -= L[i][k] * Yv[k][c];
-            }
-            Yu[i][c] = vu / L[i][i];
-            Yv[i][c] = vv / L[i][i];
-        }
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = i; j < 3; ++j) {
-            const double tu = (Yu[0][i] * Yu[0][j] + Yu[1][i] * Yu[1][j]) + Yu[2][i] * Yu[2][j];
-            const double tv = (Yv[0][i] * Yv[0][j] + Yv[1][i] * Yv[1][j]) + Yv[2][i] * Yv[2][j];
-            M[i][j] = M[j][i] = (M[i][j] - tu) - tv;
-        }
-    double V3[3][3];
-    mm_identity<3>(V3);
-    mm_jacobi<3>(M, V3);
-    double ev = M[0][0], h3[3] = {V3[0][0], V3[1][0], V3[2][0]};      // smallest eigenvalue, ties to the lowest column
-#pragma unroll
-    for (int c = 1; c < 3; ++c) {
-        if (M[c][c] < ev) {
-            ev = M[c][c];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) h3[r] = V3[r][c];
-        }
-    }
-    double h1[3], h2[3];      // S^-1 Bu h3 = L^-T (Yu h3), S^-1 Bv h3
-    {
-        double wu[3], wv[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            wu[i] = (Yu[i][0] * h3[0] + Yu[i][1] * h3[1]) + Yu[i][2] * h3[2];
-            wv[i] = (Yv[i][0] * h3[0] + Yv[i][1] * h3[1]) + Yv[i][2] * h3[2];
-        }
-#pragma unroll
-        for (int i = 2; i >= 0; --i) {
-            double vu = wu[i], vv = wv[i];
-#pragma unroll
-            for (int k = i + 1; k < 3; ++k) {
-                vu -= L[k][i] * h1[k];
-                vv -= L[k][i] * h2[k];
-            }
-            h1[i] = vu / L[i][i];
-            h2[i] = vv / L[i][i];
-        }
-    }
+    double h1[3], h2[3], h3[3];
+    bool ok = mm_plane_dlt(acc, h1, h2, h3);
     const double Hn[9] = {h1[0], h1[1], h1[2], h2[0], h2[1], h2[2], h3[0], h3[1], h3[2]};
     {   // rank guard: the smallest eigenvalue of H^^T H^ must be above 1e-8 of the largest (a NaN does not pass)
         double G[3][3], V[3][3];
@@ -233,50 +113,13 @@ __device__ __forceinline__ bool hg_solve(const double (&acc)[24], double cx, dou
 }
 
 // ---- normalisation over all well-formed matches of the pair -----------------------------------------------------------------
-__global__ __launch_bounds__(HG_THREADS) void hg_normalise_kernel(HgArgs a) {
-    __shared__ double sm[HG_WAVES * 5];
-    const int p = blockIdx.x, tid = threadIdx.x;
-    const int mm = hg_count(a.m, a.cap, p);
-    double s5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int j = tid; j < mm; j += HG_THREADS) {
-        double x, y, xp, yp;
-        if (hg_load(a, p, j, x, y, xp, yp)) {
-            s5[0] += 1.0;
-            s5[1] += x;
-            s5[2] += y;
-            s5[3] += xp;
-            s5[4] += yp;
-        }
-    }
-    mm_block_sum<5>(s5, sm);
-    const double n = s5[0], cx = s5[1] / n, cy = s5[2] / n, cx2 = s5[3] / n, cy2 = s5[4] / n;
-    double d2[2] = {0.0, 0.0};
-    for (int j = tid; j < mm; j += HG_THREADS) {
-        double x, y, xp, yp;
-        if (hg_load(a, p, j, x, y, xp, yp)) {
-            d2[0] += sqrt((x - cx) * (x - cx) + (y - cy) * (y - cy));
-            d2[1] += sqrt((xp - cx2) * (xp - cx2) + (yp - cy2) * (yp - cy2));
-        }
-    }
-    mm_block_sum<2>(d2, sm);
-    if (tid == 0) {
-        double *o = a.norm + 8 * (size_t)p;
-        o[0] = cx;
-        o[1] = cy;
-        o[2] = 1.4142135623730951 / (d2[0] / n);
-        o[3] = cx2;
-        o[4] = cy2;
-        o[5] = 1.4142135623730951 / (d2[1] / n);
-        o[6] = (double)mm - n;
-        o[7] = 0.0;
-    }
-}
+__global__ __launch_bounds__(HG_THREADS) void hg_normalise_kernel(HgArgs a) { mm_pairs_normalise(a); }
 
 // ---- one hypothesis per lane --------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void hg_hypothesis_kernel(HgArgs a) {
     const int p = blockIdx.x;
     const int h = blockIdx.y * 64 + threadIdx.x;
-    const int mm = hg_count(a.m, a.cap, p);
+    const int mm = mm_pair_count(a.m, a.cap, p);
     if (h >= a.n_hyp || mm < a.min_matches) return;      // (a pair with too few matches is never scored either)
     const double *nr = a.norm + 8 * (size_t)p;
     const double cx = nr[0], cy = nr[1], s = nr[2], cx2 = nr[3], cy2 = nr[4], s2 = nr[5];
@@ -290,82 +133,27 @@ __global__ __launch_bounds__(64) void hg_hypothesis_kernel(HgArgs a) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         double x, y, xp, yp;
-        ok = hg_load(a, p, pick[k], x, y, xp, yp) && ok;
+        ok = mm_pair_load(a, p, pick[k], x, y, xp, yp) && ok;
         xa[k] = s * (x - cx);
         ya[k] = s * (y - cy);
         xb[k] = s2 * (xp - cx2);
         yb[k] = s2 * (yp - cy2);
-        hg_accumulate(acc, xa[k], ya[k], xb[k], yb[k]);
+        mm_plane_accumulate(acc, xa[k], ya[k], xb[k], yb[k]);
     }
-    ok = hg_triple_ok(xa[0], ya[0], xa[1], ya[1], xa[2], ya[2], a.collinear_tol) && ok;
-    ok = hg_triple_ok(xa[0], ya[0], xa[1], ya[1], xa[3], ya[3], a.collinear_tol) && ok;
-    ok = hg_triple_ok(xa[0], ya[0], xa[2], ya[2], xa[3], ya[3], a.collinear_tol) && ok;
-    ok = hg_triple_ok(xa[1], ya[1], xa[2], ya[2], xa[3], ya[3], a.collinear_tol) && ok;
-    ok = hg_triple_ok(xb[0], yb[0], xb[1], yb[1], xb[2], yb[2], a.collinear_tol) && ok;
-    ok = hg_triple_ok(xb[0], yb[0], xb[1], yb[1], xb[3], yb[3], a.collinear_tol) && ok;
-    ok = hg_triple_ok(xb[0], yb[0], xb[2], yb[2], xb[3], yb[3], a.collinear_tol) && ok;
-    ok = hg_triple_ok(xb[1], yb[1], xb[2], yb[2], xb[3], yb[3], a.collinear_tol) && ok;
+    ok = mm_triples_ok(xa, ya, a.collinear_tol) && ok;
+    ok = mm_triples_ok(xb, yb, a.collinear_tol) && ok;
     double H[9];
     ok = hg_solve(acc, cx, cy, s, cx2, cy2, s2, H) && ok;
-    double *o = a.Hh + ((size_t)p * a.n_hyp + h) * 9;
+    double *o = a.model_h + ((size_t)p * a.n_hyp + h) * 9;
     const double nan = __builtin_nan("");
 #pragma unroll
     for (int c = 0; c < 9; ++c) o[c] = ok ? H[c] : nan;
 }
 
 // ---- MSAC cost of every hypothesis --------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void hg_score_kernel(HgArgs a) {
-    __shared__ double tile[HG_TILE * 4];
-    const int p = blockIdx.x;
-    const int h = blockIdx.y * 64 + threadIdx.x;
-    const int mm = hg_count(a.m, a.cap, p);
-    if (mm < a.min_matches) return;      // (uniform over the workgroup)
-    const bool live = h < a.n_hyp;
-    double H[9], A[9];
-    const double *src = a.Hh + ((size_t)p * a.n_hyp + (live ? h : 0)) * 9;
-#pragma unroll
-    for (int c = 0; c < 9; ++c) H[c] = src[c];
-    hg_adjugate(H, A);
-    double cost = 0.0;
-    for (int j0 = 0; j0 < mm; j0 += HG_TILE) {
-        const int nt = min(HG_TILE, mm - j0);
-        __syncthreads();
-        for (int j = threadIdx.x; j < nt; j += 64) {
-            double x, y, xp, yp;
-            hg_load(a, p, j0 + j, x, y, xp, yp);
-            tile[4 * j] = x;
-            tile[4 * j + 1] = y;
-            tile[4 * j + 2] = xp;
-            tile[4 * j + 3] = yp;
-        }
-        __syncthreads();
-        for (int j = 0; j < nt; ++j) {
-            const double d2 = hg_transfer(H, A, tile[4 * j], tile[4 * j + 1], tile[4 * j + 2], tile[4 * j + 3]);
-            cost += hg_inlier(d2, a.tau2) ? d2 : a.tau2;
-        }
-    }
-    if (live) a.cost_h[(size_t)p * a.n_hyp + h] = isfinite(H[0]) ? cost : __builtin_huge_val();
-}
+__global__ __launch_bounds__(64) void hg_score_kernel(HgArgs a) { mm_pairs_score<HgModel>(a); }
 
 // ---- winner, refit, verdict, compaction -----------------------------------------------------------------------------------
-// MSAC cost and inlier count of H over all matches of the pair (every thread returns the same bits)
-__device__ __forceinline__ void hg_cost(const HgArgs &a, int p, int mm, const double (&H)[9], double *sm, double &cost, int &n_in) {
-    double A[9];
-    hg_adjugate(H, A);
-    double v[2] = {0.0, 0.0};
-    for (int j = threadIdx.x; j < mm; j += HG_THREADS) {
-        double x, y, xp, yp;
-        hg_load(a, p, j, x, y, xp, yp);
-        const double d2 = hg_transfer(H, A, x, y, xp, yp);
-        const bool in = hg_inlier(d2, a.tau2);
-        v[0] += in ? d2 : a.tau2;
-        v[1] += in ? 1.0 : 0.0;
-    }
-    mm_block_sum<2>(v, sm);
-    cost = v[0];
-    n_in = (int)v[1];
-}
-
 __global__ __launch_bounds__(HG_THREADS) void hg_finish_kernel(HgArgs a, int32_t *__restrict__ pairs_out, int32_t *__restrict__ m_out,
                                                                double *__restrict__ Hm, double *__restrict__ cost_out,
                                                                int32_t *__restrict__ info) {
@@ -373,88 +161,32 @@ __global__ __launch_bounds__(HG_THREADS) void hg_finish_kernel(HgArgs a, int32_t
     __shared__ double bc[HG_WAVES];
     __shared__ int bh[HG_WAVES], wcount[HG_WAVES];
     const int p = blockIdx.x, tid = threadIdx.x;
-    const int mm = hg_count(a.m, a.cap, p);
+    const int mm = mm_pair_count(a.m, a.cap, p);
     const double nan = __builtin_nan("");
     int flags = a.norm[8 * (size_t)p + 6] > 0.0 ? MM_HOMOG_MALFORMED : 0;
-    double H[9], A[9];
+    double H[9];
 #pragma unroll
     for (int c = 0; c < 9; ++c) H[c] = nan;
     double cost = nan;
     int n_in = 0, best_h = -1, n_valid = 0;
-    bool model = false;
-
-    if (mm < a.min_matches) {
-        flags |= MM_HOMOG_TOO_FEW;
-    } else {
-        double c_best;
-        int h_best;
-        mm_block_argmin_finite(a.cost_h + (size_t)p * a.n_hyp, a.n_hyp, a.Hh + (size_t)p * a.n_hyp * 9, 9, bc, bh, sm, c_best, h_best,
-                               n_valid);
-        if (h_best == INT32_MAX) {
-            flags |= MM_HOMOG_NO_MODEL;
-        } else {
-            model = true;
-            best_h = h_best;
+    // a refit round: the 24 sums over the inliers of the current H, the same solve
+    const auto refit = [&](const HgModel &M, double cx, double cy, double s, double cx2, double cy2, double s2, double (&Hn)[9]) {
+        double acc[24];
 #pragma unroll
-            for (int c = 0; c < 9; ++c) H[c] = a.Hh[((size_t)p * a.n_hyp + h_best) * 9 + c];
-            hg_cost(a, p, mm, H, sm, cost, n_in);
+        for (int k = 0; k < 24; ++k) acc[k] = 0.0;
+        for (int j = tid; j < mm; j += HG_THREADS) {
+            double x, y, xp, yp;
+            mm_pair_load(a, p, j, x, y, xp, yp);
+            if (mm_pair_inlier(M.distance(x, y, xp, yp), a.tau2))
+                mm_plane_accumulate(acc, s * (x - cx), s * (y - cy), s2 * (xp - cx2), s2 * (yp - cy2));
         }
-    }
-
-    if (model) {
-        for (int it = 0; it < a.refit_iters; ++it) {
-            if (n_in < 4) break;      // (uniform: nothing changes any more)
-            hg_adjugate(H, A);
-            // Hartley normalisation over the inliers of the current H
-            double s5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-            for (int j = tid; j < mm; j += HG_THREADS) {
-                double x, y, xp, yp;
-                hg_load(a, p, j, x, y, xp, yp);
-                if (hg_inlier(hg_transfer(H, A, x, y, xp, yp), a.tau2)) {
-                    s5[0] += 1.0;
-                    s5[1] += x;
-                    s5[2] += y;
-                    s5[3] += xp;
-                    s5[4] += yp;
-                }
-            }
-            mm_block_sum<5>(s5, sm);
-            const double n = s5[0], cx = s5[1] / n, cy = s5[2] / n, cx2 = s5[3] / n, cy2 = s5[4] / n;
-            double dd[2] = {0.0, 0.0};
-            for (int j = tid; j < mm; j += HG_THREADS) {
-                double x, y, xp, yp;
-                hg_load(a, p, j, x, y, xp, yp);
-                if (hg_inlier(hg_transfer(H, A, x, y, xp, yp), a.tau2)) {
-                    dd[0] += sqrt((x - cx) * (x - cx) + (y - cy) * (y - cy));
-                    dd[1] += sqrt((xp - cx2) * (xp - cx2) + (yp - cy2) * (yp - cy2));
-                }
-            }
-            mm_block_sum<2>(dd, sm);
-            const double s = 1.4142135623730951 / (dd[0] / n), s2 = 1.4142135623730951 / (dd[1] / n);
-            double acc[24];
-#pragma unroll
-            for (int k = 0; k < 24; ++k) acc[k] = 0.0;
-            for (int j = tid; j < mm; j += HG_THREADS) {
-                double x, y, xp, yp;
-                hg_load(a, p, j, x, y, xp, yp);
-                if (hg_inlier(hg_transfer(H, A, x, y, xp, yp), a.tau2))
-                    hg_accumulate(acc, s * (x - cx), s * (y - cy), s2 * (xp - cx2), s2 * (yp - cy2));
-            }
-            mm_block_sum<24>(acc, sm);
-            double Hn[9];
-            const bool okH = hg_solve(acc, cx, cy, s, cx2, cy2, s2, Hn);
-            double cn;
-            int nn_in;
-            hg_cost(a, p, mm, Hn, sm, cn, nn_in);
-            if (okH && isfinite(cn) && cn < cost) {
-                cost = cn;
-                n_in = nn_in;
-#pragma unroll
-                for (int c = 0; c < 9; ++c) H[c] = Hn[c];
-            }
-        }
-        if (n_in < a.min_inliers) flags |= MM_HOMOG_WEAK;
-    }
+        mm_block_sum<24>(acc, sm);
+        return hg_solve(acc, cx, cy, s, cx2, cy2, s2, Hn);
+    };
+    const int none = mm_pairs_winner_refit<HgModel>(a, p, mm, 4, sm, bc, bh, refit, H, cost, n_in, best_h, n_valid);
+    if (none == MM_PAIRS_TOO_FEW) flags |= MM_HOMOG_TOO_FEW;
+    if (none == MM_PAIRS_NO_MODEL) flags |= MM_HOMOG_NO_MODEL;
+    if (none == 0 && n_in < a.min_inliers) flags |= MM_HOMOG_WEAK;
 
     const bool failed = (flags & (MM_HOMOG_TOO_FEW | MM_HOMOG_NO_MODEL | MM_HOMOG_WEAK)) != 0;
     int n_f = -1;
@@ -466,20 +198,8 @@ __global__ __launch_bounds__(HG_THREADS) void hg_finish_kernel(HgArgs a, int32_t
     // the inliers of H in their input order; a failed pair keeps none
     int kept = 0;
     if (!failed) {
-        hg_adjugate(H, A);
-        for (int j0 = 0; j0 < mm; j0 += HG_THREADS) {
-            const int j = j0 + tid;
-            bool keep = false;
-            int2 qt = make_int2(0, 0);
-            if (j < mm) {
-                qt = reinterpret_cast<const int2 *>(a.pairs)[(size_t)p * a.cap + j];
-                double x, y, xp, yp;
-                hg_load(a, p, j, x, y, xp, yp);
-                keep = hg_inlier(hg_transfer(H, A, x, y, xp, yp), a.tau2);
-            }
-            const int at = mm_block_compact_slot(keep, kept, wcount);
-            if (keep) reinterpret_cast<int2 *>(pairs_out)[(size_t)p * a.cap + at] = qt;
-        }
+        const HgModel M(H);
+        kept = mm_pairs_compact(a, p, mm, [&](int j) { return mm_pair_inlier_of(M, a, p, j); }, pairs_out, wcount);
     }
     if (tid == 0) {
         m_out[p] = kept;
@@ -508,29 +228,6 @@ struct HpArgs {
     double *R, *t, *sigma, *normal, *depth;
     int32_t *info;
 };
-
-struct Vec3 {
-    double x, y, z;
-};
-__device__ __forceinline__ double dot3(Vec3 a, Vec3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ Vec3 cross3(Vec3 a, Vec3 b) {
-    return Vec3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-__device__ __forceinline__ Vec3 mat3(const double (&M)[9], Vec3 v) {
-    return Vec3{(M[0] * v.x + M[1] * v.y) + M[2] * v.z, (M[3] * v.x + M[4] * v.y) + M[5] * v.z, (M[6] * v.x + M[7] * v.y) + M[8] * v.z};
-}
-
-// rays of match j of pair p (mm_recover_poses); false for a malformed match -- nothing is read through a bad index
-__device__ __forceinline__ bool hp_rays(const HpArgs &a, int p, int j, Vec3 &ra, Vec3 &rb) {
-    double x, y, xp, yp;
-    const bool wf = hg_load(a.kp_xy, a.pairs, a.cap, p, j, x, y, xp, yp);
-    ra = rb = Vec3{0.0, 0.0, 1.0};
-    if (wf) {
-        ra = Vec3{(a.Ki[0] * x + a.Ki[1] * y) + a.Ki[2], a.Ki[3] * y + a.Ki[4], 1.0};
-        rb = Vec3{(a.Ki[0] * xp + a.Ki[1] * yp) + a.Ki[2], a.Ki[3] * yp + a.Ki[4], 1.0};
-    }
-    return wf;
-}
 
 // depths of a match on the plane n . X = 1 seen from camera 1: l1 = 1 / (n . a), l2 = (l1 R a + t)_z; true: both > 0
 __device__ __forceinline__ bool hp_depths(const double (&R)[9], Vec3 t, Vec3 n, Vec3 ra, double &l1, double &l2) {
@@ -568,7 +265,7 @@ __device__ __forceinline__ int hp_block_count(int slot, int (*cnt)[5]) {      //
 __global__ __launch_bounds__(HG_THREADS) void hp_pair_kernel(HpArgs a) {
     __shared__ int cnt[HG_WAVES][5];
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int mm = hg_count(a.m, a.cap, p);
+    const int mm = mm_pair_count(a.m, a.cap, p);
     const double nan = __builtin_nan("");
     int flags = 0;
     double G[9], Rp[9], Rm[9];
@@ -647,7 +344,7 @@ __global__ __launch_bounds__(HG_THREADS) void hp_pair_kernel(HpArgs a) {
     int neg = 0, pos = 0, bad = 0;
     for (int j = tid; j < mm; j += HG_THREADS) {
         Vec3 ra, rb;
-        const bool wf = hp_rays(a, p, j, ra, rb);
+        const bool wf = mm_pair_rays(a, p, j, ra, rb);
         bad += wf ? 0 : 1;
         if (model && wf) {
             const double d = dot3(rb, mat3(G, ra));
@@ -721,7 +418,7 @@ __global__ __launch_bounds__(HG_THREADS) void hp_pair_kernel(HpArgs a) {
         const Vec3 tmn = Vec3{-tmi.x, -tmi.y, -tmi.z}, nmn = Vec3{-nmi.x, -nmi.y, -nmi.z};
         for (int j = tid; j < mm; j += HG_THREADS) {
             Vec3 ra, rb;
-            if (hp_rays(a, p, j, ra, rb)) {
+            if (mm_pair_rays(a, p, j, ra, rb)) {
                 double l1, l2;
                 v0 += hp_depths(Rp, tpl, npl, ra, l1, l2) ? 1 : 0;
                 v1c += hp_depths(Rp, tpn, npn, ra, l1, l2) ? 1 : 0;
@@ -810,7 +507,7 @@ __global__ __launch_bounds__(HG_THREADS) void hp_pair_kernel(HpArgs a) {
         double l1 = nan, l2 = nan;
         if (planar && j < mm) {
             Vec3 ra, rb;
-            if (hp_rays(a, p, j, ra, rb)) {
+            if (mm_pair_rays(a, p, j, ra, rb)) {
                 double d1, d2;
                 if (hp_depths(Rw, tw, nw, ra, d1, d2)) {
                     l1 = d1 / tnorm;
@@ -844,15 +541,10 @@ __global__ __launch_bounds__(HG_THREADS) void hp_pair_kernel(HpArgs a) {
     }
 }
 
-size_t hg_workspace(size_t np, size_t nh) {
-    return mm_align_up(np * 8 * sizeof(double), 256) + mm_align_up(np * nh * 9 * sizeof(double), 256) +
-           mm_align_up(np * nh * sizeof(double), 256);
-}
-
 }  // namespace
 
 extern "C" size_t mm_homography_workspace_bytes(int n_pairs, int n_hyp) {
-    return hg_workspace(n_pairs > 0 ? (size_t)n_pairs : 0, n_hyp > 0 ? (size_t)n_hyp : 0);
+    return mm_pairs_workspace(n_pairs, n_hyp);
 }
 
 extern "C" int mm_verify_homography(mm_ctx *ctx, const float *kp_xy, const int32_t *pairs, const int32_t *m, int n_pairs, int cap,
@@ -891,12 +583,7 @@ extern "C" int mm_verify_homography(mm_ctx *ctx, const float *kp_xy, const int32
     a.tau2 = prm->threshold_px * prm->threshold_px;
     a.collinear_tol = prm->collinear_tol;
     a.degenerate_frac = prm->degenerate_frac;
-    char *w = (char *)ws;
-    a.norm = (double *)w;
-    w += mm_align_up((size_t)n_pairs * 8 * sizeof(double), 256);
-    a.Hh = (double *)w;
-    w += mm_align_up((size_t)n_pairs * a.n_hyp * 9 * sizeof(double), 256);
-    a.cost_h = (double *)w;
+    mm_pairs_carve(a, ws);
     const dim3 per_hyp((unsigned)n_pairs, (unsigned)((a.n_hyp + 63) / 64));
     MM_LAUNCH(ctx, "hg_normalise_kernel", hg_normalise_kernel, dim3((unsigned)n_pairs), dim3(HG_THREADS), 0, a);
     MM_LAUNCH(ctx, "hg_hypothesis_kernel", hg_hypothesis_kernel, per_hyp, dim3(64), 0, a);

@@ -1,12 +1,15 @@
-// The deterministic building blocks that the geometry stages share (verify.hip, pose.hip, resect.hip, homography.hip,
-// triangulate.hip).
+// What the geometry stages share (verify.hip, pose.hip, resect.hip, homography.hip, triangulate.hip); mm_pairs.h holds what
+// only the stages over match pairs share.
 //
-// include/meatmodeler.h states each of them once and lets the later stages refer back ("the integer scheme of
-// mm_verify_matches", "the 3 x 3 cyclic Jacobi of ..."); the stages promise results that repeat bit for bit, so every one of
-// these is a definition, written here once.  Header only, __forceinline__ templates: each is compiled under the flags of
-// the file that includes it (FMA contraction is off for pose.hip, resect.hip and homography.hip, on for verify.hip and triangulate.hip --
-// Makefile), so a stage's bits are those of its own build.  What belongs here: a definition the C header gives once and
-// several stages rely on.  What does not: one stage's model (its score kernel, its solver).
+// include/meatmodeler.h states each of these once and lets the later stages refer back ("the integer scheme of
+// mm_verify_matches", "the reduced DLT of mm_resect_planar"); the stages promise results that repeat bit for bit, so every one
+// of them is written once.  The rule: shared means a definition (a sampling scheme, a reduction order, a solve the C header
+// gives once) or a skeleton (a loop that is the same around any model); a stage's model -- its distance, its solver's own
+// tail, its verdict and flags -- stays in the stage's file and is plugged in.  Header only, __forceinline__ templates: each is
+// compiled under the flags of the file that includes it (FMA contraction is off for pose.hip, resect.hip and homography.hip, on
+// for verify.hip and triangulate.hip -- Makefile), so a stage's bits are those of its own build.  With contraction off the
+// bits follow from the expression trees alone; with it on, where a piece stands can change which products fuse, and a file
+// then keeps a written-out copy, marked as such (mm_jacobi below, tri_tracks_kernel, verify.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -130,6 +133,19 @@ __device__ __forceinline__ void mm_cross3(const double (&a)[3], const double (&b
     c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
+// ---- 3-vectors held by value (pose.hip, homography.hip) -------------------------------------------------------------------
+struct Vec3 {
+    double x, y, z;
+};
+__device__ __forceinline__ double dot3(Vec3 a, Vec3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ __forceinline__ Vec3 cross3(Vec3 a, Vec3 b) {
+    return Vec3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
+// row-major 3 x 3 times vector
+__device__ __forceinline__ Vec3 mat3(const double (&M)[9], Vec3 v) {
+    return Vec3{(M[0] * v.x + M[1] * v.y) + M[2] * v.z, (M[3] * v.x + M[4] * v.y) + M[5] * v.z, (M[6] * v.x + M[7] * v.y) + M[8] * v.z};
+}
+
 // Cholesky S = L L^T of a small symmetric matrix in registers, column by column, each entry reduced by its products left to
 // right.  false: some pivot was not finite or <= 1e-12 times the diagonal entry it started from (the factor is then
 // unusable; every entry is still written).  Only the lower triangle of L is set.
@@ -183,6 +199,123 @@ __device__ __forceinline__ bool mm_polar3(const double (&A)[3][3], double (&R)[3
     for (int r = 0; r < 3; ++r)
 #pragma unroll
         for (int c = 0; c < 3; ++c) R[r][c] = (A[r][0] * W[0][c] + A[r][1] * W[1][c]) + A[r][2] * W[2][c];
+    return ok;
+}
+
+// ---- the reduced DLT of a plane-to-image map (mm_resect_planar, mm_verify_homography) -------------------------------------
+// one correspondence into the 24 sums: S, Bu, Bv, C, each the upper triangle of a 3 x 3, row-major, over m = (ma, mb, 1), the
+// normalised plane point, with (u, v) its image
+__device__ __forceinline__ void mm_plane_accumulate(double (&acc)[24], double ma, double mb, double u, double v) {
+    const double m[3] = {ma, mb, 1.0};
+    const double r2 = u * u + v * v;
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = i; j < 3; ++j) {
+            const double w = m[i] * m[j];
+            acc[k] += w;
+            acc[6 + k] += u * w;
+            acc[12 + k] += v * w;
+            acc[18 + k] += r2 * w;
+            ++k;
+        }
+}
+
+// true: the triangle (i, j, k) is not near-collinear: |cross| > tol x its longest squared side (NaN: false)
+__device__ __forceinline__ bool mm_triple_ok(double ai, double bi, double aj, double bj, double ak, double bk, double tol) {
+    const double pa = aj - ai, pb = bj - bi, qa = ak - ai, qb = bk - bi, ra = ak - aj, rb = bk - bj;
+    const double cr = pa * qb - pb * qa;
+    const double d0 = pa * pa + pb * pb, d1 = qa * qa + qb * qb, d2 = ra * ra + rb * rb;
+    double lng = d0 > d1 ? d0 : d1;
+    lng = lng > d2 ? lng : d2;
+    return fabs(cr) > tol * lng;
+}
+// the rule over the four triples of four sampled points (a[k], b[k])
+__device__ __forceinline__ bool mm_triples_ok(const double (&a)[4], const double (&b)[4], double tol) {
+    bool ok = mm_triple_ok(a[0], b[0], a[1], b[1], a[2], b[2], tol);
+    ok = mm_triple_ok(a[0], b[0], a[1], b[1], a[3], b[3], tol) && ok;
+    ok = mm_triple_ok(a[0], b[0], a[2], b[2], a[3], b[3], tol) && ok;
+    ok = mm_triple_ok(a[1], b[1], a[2], b[2], a[3], b[3], tol) && ok;
+    return ok;
+}
+
+// The rows h1, h2, h3 of the map from the 24 sums: Cholesky of S, C - Bu S^-1 Bu - Bv S^-1 Bv through the two triangular
+// solves, h3 = its eigenvector of the smallest eigenvalue (3 x 3 Jacobi, ties to the lowest column), h1 = S^-1 Bu h3 and
+// h2 = S^-1 Bv h3 by back substitution.  Returns the pivot verdict of the Cholesky; every entry is written either way.
+__device__ __forceinline__ bool mm_plane_dlt(const double (&acc)[24], double (&h1)[3], double (&h2)[3], double (&h3)[3]) {
+    double S[3][3], Bu[3][3], Bv[3][3], M[3][3];
+    {
+        int k = 0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = i; j < 3; ++j) {
+                S[i][j] = S[j][i] = acc[k];
+                Bu[i][j] = Bu[j][i] = acc[6 + k];
+                Bv[i][j] = Bv[j][i] = acc[12 + k];
+                M[i][j] = M[j][i] = acc[18 + k];
+                ++k;
+            }
+    }
+    double L[3][3];
+    bool ok = mm_cholesky_pivot<3>(S, L);
+    double Yu[3][3], Yv[3][3];      // L^-1 Bu, L^-1 Bv
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            double vu = Bu[i][c], vv = Bv[i][c];
+#pragma unroll
+            for (int k = 0; k < i; ++k) {
+                vu -= L[i][k] * Yu[k][c];
+                vv -= L[i][k] * Yv[k][c];
+            }
+            Yu[i][c] = vu / L[i][i];
+            Yv[i][c] = vv / L[i][i];
+        }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = i; j < 3; ++j) {
+            const double tu = (Yu[0][i] * Yu[0][j] + Yu[1][i] * Yu[1][j]) + Yu[2][i] * Yu[2][j];
+            const double tv = (Yv[0][i] * Yv[0][j] + Yv[1][i] * Yv[1][j]) + Yv[2][i] * Yv[2][j];
+            M[i][j] = M[j][i] = (M[i][j] - tu) - tv;
+        }
+    double V3[3][3];
+    mm_identity<3>(V3);
+    mm_jacobi<3>(M, V3);
+    double ev = M[0][0];      // smallest eigenvalue, ties to the lowest column
+    h3[0] = V3[0][0];
+    h3[1] = V3[1][0];
+    h3[2] = V3[2][0];
+#pragma unroll
+    for (int c = 1; c < 3; ++c) {
+        if (M[c][c] < ev) {
+            ev = M[c][c];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) h3[r] = V3[r][c];
+        }
+    }
+    {   // S^-1 Bu h3 = L^-T (Yu h3), S^-1 Bv h3
+        double wu[3], wv[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            wu[i] = (Yu[i][0] * h3[0] + Yu[i][1] * h3[1]) + Yu[i][2] * h3[2];
+            wv[i] = (Yv[i][0] * h3[0] + Yv[i][1] * h3[1]) + Yv[i][2] * h3[2];
+        }
+#pragma unroll
+        for (int i = 2; i >= 0; --i) {
+            double vu = wu[i], vv = wv[i];
+#pragma unroll
+            for (int k = i + 1; k < 3; ++k) {
+                vu -= L[k][i] * h1[k];
+                vv -= L[k][i] * h2[k];
+            }
+            h1[i] = vu / L[i][i];
+            h2[i] = vv / L[i][i];
+        }
+    }
     return ok;
 }
 

@@ -14,8 +14,7 @@
 // Built without FMA contraction (Makefile): the vote pass and the depth pass evaluate the same expression and must agree on
 // every bit, and a product-sum then has one value whatever the compiler makes of its surroundings.  All counts are integers,
 // the only atomics are integer min / add in LDS: a pair's row does not depend on which other pairs share the call.
-#include "mm_common.h"
-#include "mm_geom.h"
+#include "mm_pairs.h"
 
 namespace {
 
@@ -35,18 +34,6 @@ struct PoseArgs {
     int32_t *info;
 };
 
-struct Vec3 {
-    double x, y, z;
-};
-__device__ __forceinline__ double dot3(Vec3 a, Vec3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ Vec3 cross3(Vec3 a, Vec3 b) {
-    return Vec3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-// row-major 3 x 3 times vector
-__device__ __forceinline__ Vec3 mat3(const double (&M)[9], Vec3 v) {
-    return Vec3{(M[0] * v.x + M[1] * v.y) + M[2] * v.z, (M[3] * v.x + M[4] * v.y) + M[5] * v.z, (M[6] * v.x + M[7] * v.y) + M[8] * v.z};
-}
-
 // depths (l1, l2) of the least-squares solution of l2 b = l1 r + t; true: both finite and positive
 __device__ __forceinline__ bool pose_depths(Vec3 r, Vec3 b, Vec3 t, double &l1, double &l2) {
     const double rr = dot3(r, r), bb = dot3(b, b), rb = dot3(r, b), bt = dot3(b, t), rt = dot3(r, t);
@@ -54,20 +41,6 @@ __device__ __forceinline__ bool pose_depths(Vec3 r, Vec3 b, Vec3 t, double &l1, 
     l1 = (rb * bt - rt * bb) / det;
     l2 = (rr * bt - rb * rt) / det;
     return isfinite(l1) && isfinite(l2) && l1 > 0.0 && l2 > 0.0;
-}
-
-// rays of match j of pair p; false for a malformed match -- nothing is read through a bad index
-__device__ __forceinline__ bool pose_rays(const PoseArgs &a, int p, int j, Vec3 &ra, Vec3 &rb) {
-    const int2 qt = reinterpret_cast<const int2 *>(a.pairs)[(size_t)p * a.cap + j];
-    const bool wf = (unsigned)qt.x < (unsigned)a.cap && (unsigned)qt.y < (unsigned)a.cap;
-    ra = rb = Vec3{0.0, 0.0, 1.0};
-    if (wf) {
-        const float2 u = reinterpret_cast<const float2 *>(a.kp_xy)[(size_t)p * a.cap + qt.x];
-        const float2 v = reinterpret_cast<const float2 *>(a.kp_xy)[(size_t)(p + 1) * a.cap + qt.y];
-        ra = Vec3{(a.Ki[0] * (double)u.x + a.Ki[1] * (double)u.y) + a.Ki[2], a.Ki[3] * (double)u.y + a.Ki[4], 1.0};
-        rb = Vec3{(a.Ki[0] * (double)v.x + a.Ki[1] * (double)v.y) + a.Ki[2], a.Ki[3] * (double)v.y + a.Ki[4], 1.0};
-    }
-    return wf;
 }
 
 // R = U W V^T (transposed_w false) or U W^T V^T (true), row-major; U and V given by their columns
@@ -89,8 +62,7 @@ __device__ __forceinline__ void pose_rotation(Vec3 u1, Vec3 u2, Vec3 u3, Vec3 v1
 __global__ __launch_bounds__(POSE_THREADS) void pose_pair_kernel(PoseArgs a) {
     __shared__ int cnt[POSE_WAVES][5];
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int mraw = a.m[p];
-    const int mm = mraw < 0 ? 0 : (mraw > a.cap ? a.cap : mraw);
+    const int mm = mm_pair_count(a.m, a.cap, p);
     const double nan = __builtin_nan("");
     int flags = 0;
     double Ra[9], Rb[9];
@@ -164,7 +136,7 @@ __global__ __launch_bounds__(POSE_THREADS) void pose_pair_kernel(PoseArgs a) {
     int v0 = 0, v1c = 0, v2c = 0, v3c = 0, bad = 0;
     for (int j = tid; j < mm; j += POSE_THREADS) {
         Vec3 ra, rb;
-        const bool wf = pose_rays(a, p, j, ra, rb);
+        const bool wf = mm_pair_rays(a, p, j, ra, rb);
         bad += wf ? 0 : 1;
         if (model && wf) {
             const Vec3 qa = mat3(Ra, ra), qb = mat3(Rb, ra);
@@ -236,7 +208,7 @@ __global__ __launch_bounds__(POSE_THREADS) void pose_pair_kernel(PoseArgs a) {
         double l1 = nan, l2 = nan;
         if (model && j < mm) {
             Vec3 ra, rb;
-            if (pose_rays(a, p, j, ra, rb)) {
+            if (mm_pair_rays(a, p, j, ra, rb)) {
                 double d1, d2;
                 if (pose_depths(mat3(Rw, ra), rb, tw, d1, d2)) {
                     l1 = d1;

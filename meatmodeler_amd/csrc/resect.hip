@@ -267,108 +267,12 @@ __device__ __forceinline__ void rp_row(const RsArgs &a, const double (&fr)[9], d
     v = a.Ki[3] * oy + a.Ki[4];
 }
 
-// one row into the 24 sums: S, Bu, Bv, C, each the upper triangle of a 3 x 3, row-major, over m = (ma, mb, 1)
-__device__ __forceinline__ void rp_accumulate(double (&acc)[24], double ma, double mb, double u, double v) {
-    const double m[3] = {ma, mb, 1.0};
-    const double r2 = u * u + v * v;
-    int k = 0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = i; j < 3; ++j) {
-            const double w = m[i] * m[j];
-            acc[k] += w;
-            acc[6 + k] += u * w;
-            acc[12 + k] += v * w;
-            acc[18 + k] += r2 * w;
-            ++k;
-        }
-}
-
-// true: the triangle (i, j, k) of plane points is not near-collinear: |cross| > tol x its longest squared side (NaN: false)
-__device__ __forceinline__ bool rp_triple_ok(double ai, double bi, double aj, double bj, double ak, double bk, double tol) {
-    const double pa = aj - ai, pb = bj - bi, qa = ak - ai, qb = bk - bi, ra = ak - aj, rb = bk - bj;
-    const double cr = pa * qb - pb * qa;
-    const double d0 = pa * pa + pb * pb, d1 = qa * qa + qb * qb, d2 = ra * ra + rb * rb;
-    double lng = d0 > d1 ? d0 : d1;
-    lng = lng > d2 ? lng : d2;
-    return fabs(cr) > tol * lng;
-}
-
 // [R|t] from the 24 sums: the homography H = [h1; h2; h3] by the reduced DLT, then the pose of the plane's frame fr = e1, e2, n
 // about the centroid.  false: a failed pivot, a non-positive eigenvalue or a non-finite result.
 __device__ __forceinline__ bool rp_solve(const double (&acc)[24], const double (&fr)[9], double cx, double cy, double cz, double s,
                                          double (&E)[12]) {
-    double S[3][3], Bu[3][3], Bv[3][3], M[3][3];
-    {
-        int k = 0;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = i; j < 3; ++j) {
-                S[i][j] = S[j][i] = acc[k];
-                Bu[i][j] = Bu[j][i] = acc[6 + k];
-                Bv[i][j] = Bv[j][i] = acc[12 + k];
-                M[i][j] = M[j][i] = acc[18 + k];
-                ++k;
-            }
-    }
-    double L[3][3];
-    bool ok = mm_cholesky_pivot<3>(S, L);
-    double Yu[3][3], Yv[3][3];      // L^-1 Bu, L^-1 Bv
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            double vu = Bu[i][c], vv = Bv[i][c];
-#pragma unroll
-            for (int k = 0; k < i; ++k) {
-                vu -= L[i][k] * Yu[k][c];
-                vv -= L[i][k] * Yv[k][c];
-            }
-            Yu[i][c] = vu / L[i][i];
-            Yv[i][c] = vv / L[i][i];
-        }
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = i; j < 3; ++j) {
-            const double tu = (Yu[0][i] * Yu[0][j] + Yu[1][i] * Yu[1][j]) + Yu[2][i] * Yu[2][j];
-            const double tv = (Yv[0][i] * Yv[0][j] + Yv[1][i] * Yv[1][j]) + Yv[2][i] * Yv[2][j];
-            M[i][j] = M[j][i] = (M[i][j] - tu) - tv;
-        }
-    double V3[3][3];
-    mm_identity<3>(V3);
-    mm_jacobi<3>(M, V3);
-    double ev = M[0][0], h3[3] = {V3[0][0], V3[1][0], V3[2][0]};      // smallest eigenvalue, ties to the lowest column
-#pragma unroll
-    for (int c = 1; c < 3; ++c) {
-        if (M[c][c] < ev) {
-            ev = M[c][c];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) h3[r] = V3[r][c];
-        }
-    }
-    double h1[3], h2[3];      // S^-1 Bu h3 = L^-T (Yu h3), S^-1 Bv h3
-    {
-        double wu[3], wv[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            wu[i] = (Yu[i][0] * h3[0] + Yu[i][1] * h3[1]) + Yu[i][2] * h3[2];
-            wv[i] = (Yv[i][0] * h3[0] + Yv[i][1] * h3[1]) + Yv[i][2] * h3[2];
-        }
-#pragma unroll
-        for (int i = 2; i >= 0; --i) {
-            double vu = wu[i], vv = wv[i];
-#pragma unroll
-            for (int k = i + 1; k < 3; ++k) {
-                vu -= L[k][i] * h1[k];
-                vv -= L[k][i] * h2[k];
-            }
-            h1[i] = vu / L[i][i];
-            h2[i] = vv / L[i][i];
-        }
-    }
+    double h1[3], h2[3], h3[3];
+    bool ok = mm_plane_dlt(acc, h1, h2, h3);
     const double sg = h3[2] < 0.0 ? -1.0 : 1.0;      // H[2][2] >= 0: the centroid in front
     const double g1[3] = {sg * h1[0], sg * h2[0], sg * h3[0]}, g2[3] = {sg * h1[1], sg * h2[1], sg * h3[1]};
     const double g3[3] = {sg * h1[2], sg * h2[2], sg * h3[2]};
@@ -652,12 +556,9 @@ __global__ __launch_bounds__(64) void rp_hypothesis_kernel(RsArgs a) {
         double X, Y, Z, ox, oy, u, v;
         rs_load(a, lo, pick[k], X, Y, Z, ox, oy);
         rp_row(a, fr, cx, cy, cz, s, X, Y, Z, ox, oy, ma[k], mb[k], u, v);
-        rp_accumulate(acc, ma[k], mb[k], u, v);
+        mm_plane_accumulate(acc, ma[k], mb[k], u, v);
     }
-    ok = rp_triple_ok(ma[0], mb[0], ma[1], mb[1], ma[2], mb[2], a.collinear_tol) && ok;
-    ok = rp_triple_ok(ma[0], mb[0], ma[1], mb[1], ma[3], mb[3], a.collinear_tol) && ok;
-    ok = rp_triple_ok(ma[0], mb[0], ma[2], mb[2], ma[3], mb[3], a.collinear_tol) && ok;
-    ok = rp_triple_ok(ma[1], mb[1], ma[2], mb[2], ma[3], mb[3], a.collinear_tol) && ok;
+    ok = mm_triples_ok(ma, mb, a.collinear_tol) && ok;
     double E[12];
     ok = rp_solve(acc, fr, cx, cy, cz, s, E) && ok;
     double *o = a.Eh + ((size_t)c * a.n_hyp + h) * 12;
@@ -902,7 +803,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_finish_kernel(RsArgs a) {
                     if (rs_distance(Q, X, Y, Z, ox, oy, a.tau2, d2)) {
                         double ma, mb, u, v;
                         rp_row(a, fr, cx, cy, cz, s, X, Y, Z, ox, oy, ma, mb, u, v);
-                        rp_accumulate(acc, ma, mb, u, v);
+                        mm_plane_accumulate(acc, ma, mb, u, v);
                     }
                 }
                 mm_block_sum<24>(acc, sm);

@@ -9,50 +9,23 @@
 //                          reads the same address (broadcast), summing min(d^2, tau^2) over j ascending: no cross-lane step
 //   vfy_refit_kernel       one workgroup per pair: argmin, refit rounds (45 sums of A^T A, 9 x 9 Jacobi in LDS), inlier mask,
 //                          order-preserving compaction, outputs
+// How a match is read, the normalisation and the MSAC skeleton (score body, cost, winner / refit frame, compaction) are
+// mm_pairs.h's; here is the model: vfy_sampson, the eight-point hypothesis, vfy_rank2 / vfy_finish and the refit's 45 sums.
+// This file is built with FMA contraction (Makefile), where the arrangement of the code can change which products fuse: a
+// shared piece is used here only while every output stays byte-equal to the written-out form on the MI355X.
 // Plain f64 VALU work; sums in an order that depends on the pair alone (per-thread strides, xor butterflies, waves in order),
 // no atomics: a pair's row repeats bit for bit whatever else shares the call.
-#include "mm_common.h"
-#include "mm_geom.h"
+#include "mm_pairs.h"
 
 namespace {
 
 constexpr int VFY_THREADS = 256;      // normalise / refit: one workgroup per pair
 constexpr int VFY_WAVES = VFY_THREADS / 64;
-constexpr int VFY_TILE = 256;         // matches per LDS tile of the score kernel
 static_assert(VFY_THREADS == MM_BLOCK_THREADS, "the mm_block_* helpers are written for this workgroup");
 
-struct VfyArgs {
-    const float *kp_xy;
-    const int32_t *pairs, *m;
-    int n_pairs, cap, n_hyp, min_matches, min_inliers, refit_iters, on_fail;
-    uint32_t seed, pair_base;
-    double tau2;
-    double *norm;      // [n_pairs, 8]: cx, cy, s, cx', cy', s', number of malformed matches, -
-    double *Fh;        // [n_pairs, n_hyp, 9] (NaN: invalid hypothesis)
-    double *cost_h;    // [n_pairs, n_hyp] (+inf: invalid hypothesis)
+struct VfyArgs : MmPairArgs {      // (model_h: the hypotheses' F)
+    int on_fail;
 };
-
-__device__ __forceinline__ int vfy_count(const VfyArgs &a, int p) {
-    const int mm = a.m[p];
-    return mm < 0 ? 0 : (mm > a.cap ? a.cap : mm);
-}
-
-// match j of pair p, widened; false (and NaN coordinates) for a malformed match -- nothing is read through a bad index
-__device__ __forceinline__ bool vfy_load(const VfyArgs &a, int p, int j, double &x, double &y, double &xp, double &yp) {
-    const int2 qt = reinterpret_cast<const int2 *>(a.pairs)[(size_t)p * a.cap + j];
-    const bool wf = (unsigned)qt.x < (unsigned)a.cap && (unsigned)qt.y < (unsigned)a.cap;
-    const double nan = __builtin_nan("");
-    x = y = xp = yp = nan;
-    if (wf) {
-        const float2 u = reinterpret_cast<const float2 *>(a.kp_xy)[(size_t)p * a.cap + qt.x];
-        const float2 v = reinterpret_cast<const float2 *>(a.kp_xy)[(size_t)(p + 1) * a.cap + qt.y];
-        x = (double)u.x;
-        y = (double)u.y;
-        xp = (double)v.x;
-        yp = (double)v.y;
-    }
-    return wf;
-}
 
 __device__ __forceinline__ double vfy_sampson(const double (&F)[9], double x, double y, double xp, double yp) {
     const double fx0 = F[0] * x + F[1] * y + F[2], fx1 = F[3] * x + F[4] * y + F[5], fx2 = F[6] * x + F[7] * y + F[8];
@@ -60,7 +33,16 @@ __device__ __forceinline__ double vfy_sampson(const double (&F)[9], double x, do
     const double e = xp * fx0 + yp * fx1 + fx2;
     return e * e / (fx0 * fx0 + fx1 * fx1 + ft0 * ft0 + ft1 * ft1);
 }
-__device__ __forceinline__ bool vfy_inlier(double d2, double tau2) { return isfinite(d2) && d2 <= tau2; }
+
+// the model of the MSAC skeleton (mm_pairs.h): F, nothing prepared
+struct VfyModel {
+    double F[9];
+    __device__ __forceinline__ explicit VfyModel(const double (&f)[9]) {
+#pragma unroll
+        for (int c = 0; c < 9; ++c) F[c] = f[c];
+    }
+    __device__ __forceinline__ double distance(double x, double y, double xp, double yp) const { return vfy_sampson(F, x, y, xp, yp); }
+};
 
 // F^ <- F^ - (F^ v3) v3^T, v3 the eigenvector of the smallest eigenvalue of F^^T F^ (3 x 3 cyclic Jacobi in registers)
 __device__ __forceinline__ void vfy_rank2(double (&F)[9]) {
@@ -122,50 +104,13 @@ __device__ __forceinline__ bool vfy_finish(double (&F)[9], double cx, double cy,
 }
 
 // ---- normalisation over all well-formed matches of the pair -----------------------------------------------------------------
-__global__ __launch_bounds__(VFY_THREADS) void vfy_normalise_kernel(VfyArgs a) {
-    __shared__ double sm[VFY_WAVES * 5];
-    const int p = blockIdx.x, tid = threadIdx.x;
-    const int mm = vfy_count(a, p);
-    double s5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int j = tid; j < mm; j += VFY_THREADS) {
-        double x, y, xp, yp;
-        if (vfy_load(a, p, j, x, y, xp, yp)) {
-            s5[0] += 1.0;
-            s5[1] += x;
-            s5[2] += y;
-            s5[3] += xp;
-            s5[4] += yp;
-        }
-    }
-    mm_block_sum<5>(s5, sm);
-    const double n = s5[0], cx = s5[1] / n, cy = s5[2] / n, cx2 = s5[3] / n, cy2 = s5[4] / n;
-    double d2[2] = {0.0, 0.0};
-    for (int j = tid; j < mm; j += VFY_THREADS) {
-        double x, y, xp, yp;
-        if (vfy_load(a, p, j, x, y, xp, yp)) {
-            d2[0] += sqrt((x - cx) * (x - cx) + (y - cy) * (y - cy));
-            d2[1] += sqrt((xp - cx2) * (xp - cx2) + (yp - cy2) * (yp - cy2));
-        }
-    }
-    mm_block_sum<2>(d2, sm);
-    if (tid == 0) {
-        double *o = a.norm + 8 * (size_t)p;
-        o[0] = cx;
-        o[1] = cy;
-        o[2] = 1.4142135623730951 / (d2[0] / n);
-        o[3] = cx2;
-        o[4] = cy2;
-        o[5] = 1.4142135623730951 / (d2[1] / n);
-        o[6] = (double)mm - n;
-        o[7] = 0.0;
-    }
-}
+__global__ __launch_bounds__(VFY_THREADS) void vfy_normalise_kernel(VfyArgs a) { mm_pairs_normalise(a); }
 
 // ---- one hypothesis per lane --------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void vfy_hypothesis_kernel(VfyArgs a) {
     const int p = blockIdx.x;
     const int h = blockIdx.y * 64 + threadIdx.x;
-    const int mm = vfy_count(a, p);
+    const int mm = mm_pair_count(a.m, a.cap, p);
     if (h >= a.n_hyp || mm < a.min_matches) return;      // (a pair with too few matches is never scored either)
     const double *nr = a.norm + 8 * (size_t)p;
     const double cx = nr[0], cy = nr[1], s = nr[2], cx2 = nr[3], cy2 = nr[4], s2 = nr[5];
@@ -178,7 +123,7 @@ __global__ __launch_bounds__(64) void vfy_hypothesis_kernel(VfyArgs a) {
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         double x, y, xp, yp;
-        ok = vfy_load(a, p, pick[k], x, y, xp, yp) && ok;
+        ok = mm_pair_load(a, p, pick[k], x, y, xp, yp) && ok;
         x = s * (x - cx);
         y = s * (y - cy);
         xp = s2 * (xp - cx2);
@@ -259,7 +204,7 @@ __global__ __launch_bounds__(64) void vfy_hypothesis_kernel(VfyArgs a) {
 #pragma unroll
         for (int c = 0; c < 9; ++c) F[c] *= inv;
         ok = vfy_finish(F, cx, cy, s, cx2, cy2, s2) && ok;
-        double *o = a.Fh + ((size_t)p * a.n_hyp + h) * 9;
+        double *o = a.model_h + ((size_t)p * a.n_hyp + h) * 9;
         const double nan = __builtin_nan("");
 #pragma unroll
         for (int c = 0; c < 9; ++c) o[c] = ok ? F[c] : nan;
@@ -267,55 +212,9 @@ __global__ __launch_bounds__(64) void vfy_hypothesis_kernel(VfyArgs a) {
 }
 
 // ---- MSAC cost of every hypothesis --------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void vfy_score_kernel(VfyArgs a) {
-    __shared__ double tile[VFY_TILE * 4];
-    const int p = blockIdx.x;
-    const int h = blockIdx.y * 64 + threadIdx.x;
-    const int mm = vfy_count(a, p);
-    if (mm < a.min_matches) return;      // (uniform over the workgroup)
-    const bool live = h < a.n_hyp;
-    double F[9];
-    const double *src = a.Fh + ((size_t)p * a.n_hyp + (live ? h : 0)) * 9;
-#pragma unroll
-    for (int c = 0; c < 9; ++c) F[c] = src[c];
-    double cost = 0.0;
-    for (int j0 = 0; j0 < mm; j0 += VFY_TILE) {
-        const int nt = min(VFY_TILE, mm - j0);
-        __syncthreads();
-        for (int j = threadIdx.x; j < nt; j += 64) {
-            double x, y, xp, yp;
-            vfy_load(a, p, j0 + j, x, y, xp, yp);
-            tile[4 * j] = x;
-            tile[4 * j + 1] = y;
-            tile[4 * j + 2] = xp;
-            tile[4 * j + 3] = yp;
-        }
-        __syncthreads();
-        for (int j = 0; j < nt; ++j) {
-            const double d2 = vfy_sampson(F, tile[4 * j], tile[4 * j + 1], tile[4 * j + 2], tile[4 * j + 3]);
-            cost += vfy_inlier(d2, a.tau2) ? d2 : a.tau2;
-        }
-    }
-    if (live) a.cost_h[(size_t)p * a.n_hyp + h] = isfinite(F[0]) ? cost : __builtin_huge_val();
-}
+__global__ __launch_bounds__(64) void vfy_score_kernel(VfyArgs a) { mm_pairs_score<VfyModel>(a); }
 
 // ---- winner, refit, compaction --------------------------------------------------------------------------------------------
-// MSAC cost and inlier count of F over all matches of the pair (every thread returns the same bits)
-__device__ __forceinline__ void vfy_cost(const VfyArgs &a, int p, int mm, const double (&F)[9], double *sm, double &cost, int &n_in) {
-    double v[2] = {0.0, 0.0};
-    for (int j = threadIdx.x; j < mm; j += VFY_THREADS) {
-        double x, y, xp, yp;
-        vfy_load(a, p, j, x, y, xp, yp);
-        const double d2 = vfy_sampson(F, x, y, xp, yp);
-        const bool in = vfy_inlier(d2, a.tau2);
-        v[0] += in ? d2 : a.tau2;
-        v[1] += in ? 1.0 : 0.0;
-    }
-    mm_block_sum<2>(v, sm);
-    cost = v[0];
-    n_in = (int)v[1];
-}
-
 __global__ __launch_bounds__(VFY_THREADS) void vfy_refit_kernel(VfyArgs a, int32_t *__restrict__ pairs_out, int32_t *__restrict__ m_out,
                                                                 double *__restrict__ Fm, double *__restrict__ cost_out,
                                                                 int32_t *__restrict__ info) {
@@ -324,7 +223,7 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_refit_kernel(VfyArgs a, int32
     __shared__ double bc[VFY_WAVES];
     __shared__ int bh[VFY_WAVES], wcount[VFY_WAVES];
     const int p = blockIdx.x, tid = threadIdx.x;
-    const int mm = vfy_count(a, p);
+    const int mm = mm_pair_count(a.m, a.cap, p);
     const double nan = __builtin_nan("");
     int flags = a.norm[8 * (size_t)p + 6] > 0.0 ? MM_VERIFY_MALFORMED : 0;
     double F[9];
@@ -332,173 +231,103 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_refit_kernel(VfyArgs a, int32
     for (int c = 0; c < 9; ++c) F[c] = nan;
     double cost = nan;
     int n_in = 0, best_h = -1, n_valid = 0;
-    bool model = false;
-
-    if (mm < a.min_matches) {
-        flags |= MM_VERIFY_TOO_FEW;
-    } else {
-        // lowest finite cost, ties to the lowest h; and the number of valid hypotheses
-        double c_best;
-        int h_best;
-        mm_block_argmin_finite(a.cost_h + (size_t)p * a.n_hyp, a.n_hyp, a.Fh + (size_t)p * a.n_hyp * 9, 9, bc, bh, sm, c_best, h_best,
-                               n_valid);
-        if (h_best == INT32_MAX) {
-            flags |= MM_VERIFY_NO_MODEL;
-        } else {
-            model = true;
-            best_h = h_best;
+    // a refit round: the null vector of A^T A over the inliers of the current F, rank 2, denormalised
+    const auto refit = [&](const VfyModel &cur, double cx, double cy, double s, double cx2, double cy2, double s2, double (&Fn)[9]) {
+        // M = A^T A over the inliers: 45 sums (upper triangle, row-major)
+        double acc[45];
 #pragma unroll
-            for (int c = 0; c < 9; ++c) F[c] = a.Fh[((size_t)p * a.n_hyp + h_best) * 9 + c];
-            vfy_cost(a, p, mm, F, sm, cost, n_in);
-        }
-    }
-
-    if (model) {
-        for (int it = 0; it < a.refit_iters; ++it) {
-            if (n_in < 8) break;      // (uniform: nothing changes any more)
-            // Hartley normalisation over the inliers of the current F
-            double s5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-            for (int j = tid; j < mm; j += VFY_THREADS) {
-                double x, y, xp, yp;
-                vfy_load(a, p, j, x, y, xp, yp);
-                if (vfy_inlier(vfy_sampson(F, x, y, xp, yp), a.tau2)) {
-                    s5[0] += 1.0;
-                    s5[1] += x;
-                    s5[2] += y;
-                    s5[3] += xp;
-                    s5[4] += yp;
-                }
-            }
-            mm_block_sum<5>(s5, sm);
-            const double n = s5[0], cx = s5[1] / n, cy = s5[2] / n, cx2 = s5[3] / n, cy2 = s5[4] / n;
-            double dd[2] = {0.0, 0.0};
-            for (int j = tid; j < mm; j += VFY_THREADS) {
-                double x, y, xp, yp;
-                vfy_load(a, p, j, x, y, xp, yp);
-                if (vfy_inlier(vfy_sampson(F, x, y, xp, yp), a.tau2)) {
-                    dd[0] += sqrt((x - cx) * (x - cx) + (y - cy) * (y - cy));
-                    dd[1] += sqrt((xp - cx2) * (xp - cx2) + (yp - cy2) * (yp - cy2));
-                }
-            }
-            mm_block_sum<2>(dd, sm);
-            const double s = 1.4142135623730951 / (dd[0] / n), s2 = 1.4142135623730951 / (dd[1] / n);
-            // M = A^T A over the inliers: 45 sums (upper triangle, row-major)
-            double acc[45];
-#pragma unroll
-            for (int k = 0; k < 45; ++k) acc[k] = 0.0;
-            for (int j = tid; j < mm; j += VFY_THREADS) {
-                double x, y, xp, yp;
-                vfy_load(a, p, j, x, y, xp, yp);
-                if (vfy_inlier(vfy_sampson(F, x, y, xp, yp), a.tau2)) {
-                    x = s * (x - cx);
-                    y = s * (y - cy);
-                    xp = s2 * (xp - cx2);
-                    yp = s2 * (yp - cy2);
-                    const double r[9] = {xp * x, xp * y, xp, yp * x, yp * y, yp, x, y, 1.0};
-                    int k = 0;
-#pragma unroll
-                    for (int i = 0; i < 9; ++i)
-#pragma unroll
-                        for (int c = i; c < 9; ++c) acc[k++] += r[i] * r[c];
-                }
-            }
-            mm_block_sum<45>(acc, sm);
-            __syncthreads();
-            if (tid == 0) {
+        for (int k = 0; k < 45; ++k) acc[k] = 0.0;
+        for (int j = tid; j < mm; j += VFY_THREADS) {
+            double x, y, xp, yp;
+            mm_pair_load(a, p, j, x, y, xp, yp);
+            if (mm_pair_inlier(cur.distance(x, y, xp, yp), a.tau2)) {
+                x = s * (x - cx);
+                y = s * (y - cy);
+                xp = s2 * (xp - cx2);
+                yp = s2 * (yp - cy2);
+                const double r[9] = {xp * x, xp * y, xp, yp * x, yp * y, yp, x, y, 1.0};
                 int k = 0;
 #pragma unroll
                 for (int i = 0; i < 9; ++i)
 #pragma unroll
-                    for (int c = i; c < 9; ++c) {
-                        M[i][c] = acc[k];
-                        M[c][i] = acc[k];
-                        ++k;
-                    }
-            }
-            if (tid < 81) V[tid / 9][tid % 9] = (tid / 9 == tid % 9) ? 1.0 : 0.0;
-            __syncthreads();
-            // cyclic Jacobi on M with V in LDS: every thread takes the same decisions from the same LDS words, lane k < 9
-            // rotates row / column k.  A rotation is skipped once |m_pq| <= eps sqrt(m_pp m_qq).
-            for (int sweep = 0; sweep < 30; ++sweep) {
-                bool rotated = false;
-                for (int pp = 0; pp < 8; ++pp) {
-                    for (int q = pp + 1; q < 9; ++q) {
-                        const double apq = M[pp][q], app = M[pp][pp], aqq = M[q][q];
-                        if (fabs(apq) > MM_F64_EPS * sqrt(fabs(app * aqq)) && apq != 0.0) {      // (uniform)
-                            rotated = true;
-                            const double zeta = (aqq - app) / (2.0 * apq);
-                            const double tn = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                            const double cs = 1.0 / sqrt(1.0 + tn * tn);
-                            const double sn = cs * tn;
-                            __syncthreads();
-                            if (tid < 9) {
-                                const double akp = M[tid][pp], akq = M[tid][q];
-                                M[tid][pp] = cs * akp - sn * akq;
-                                M[tid][q] = sn * akp + cs * akq;
-                                const double vkp = V[tid][pp], vkq = V[tid][q];
-                                V[tid][pp] = cs * vkp - sn * vkq;
-                                V[tid][q] = sn * vkp + cs * vkq;
-                            }
-                            __syncthreads();
-                            if (tid < 9) {
-                                const double apk = M[pp][tid], aqk = M[q][tid];
-                                M[pp][tid] = cs * apk - sn * aqk;
-                                M[q][tid] = sn * apk + cs * aqk;
-                            }
-                            __syncthreads();
-                            if (tid == 0) M[pp][q] = M[q][pp] = 0.0;
-                            __syncthreads();
-                        }
-                    }
-                }
-                if (!rotated) break;
-            }
-            int cbest = 0;
-            double ev = M[0][0];
-            for (int c = 1; c < 9; ++c) {
-                if (M[c][c] < ev) {
-                    ev = M[c][c];
-                    cbest = c;
-                }
-            }
-            double Fn[9];
-#pragma unroll
-            for (int c = 0; c < 9; ++c) Fn[c] = V[c][cbest];
-            __syncthreads();      // (M and V are rewritten by the next round)
-            const bool okF = vfy_finish(Fn, cx, cy, s, cx2, cy2, s2);
-            double cn;
-            int nn_in;
-            vfy_cost(a, p, mm, Fn, sm, cn, nn_in);
-            if (okF && isfinite(cn) && cn < cost) {
-                cost = cn;
-                n_in = nn_in;
-#pragma unroll
-                for (int c = 0; c < 9; ++c) F[c] = Fn[c];
+                    for (int c = i; c < 9; ++c) acc[k++] += r[i] * r[c];
             }
         }
-        if (n_in < a.min_inliers) flags |= MM_VERIFY_WEAK;
-    }
+        mm_block_sum<45>(acc, sm);
+        __syncthreads();
+        if (tid == 0) {
+            int k = 0;
+#pragma unroll
+            for (int i = 0; i < 9; ++i)
+#pragma unroll
+                for (int c = i; c < 9; ++c) {
+                    M[i][c] = acc[k];
+                    M[c][i] = acc[k];
+                    ++k;
+                }
+        }
+        if (tid < 81) V[tid / 9][tid % 9] = (tid / 9 == tid % 9) ? 1.0 : 0.0;
+        __syncthreads();
+        // cyclic Jacobi on M with V in LDS: every thread takes the same decisions from the same LDS words, lane k < 9
+        // rotates row / column k.  A rotation is skipped once |m_pq| <= eps sqrt(m_pp m_qq).
+        for (int sweep = 0; sweep < 30; ++sweep) {
+            bool rotated = false;
+            for (int pp = 0; pp < 8; ++pp) {
+                for (int q = pp + 1; q < 9; ++q) {
+                    const double apq = M[pp][q], app = M[pp][pp], aqq = M[q][q];
+                    if (fabs(apq) > MM_F64_EPS * sqrt(fabs(app * aqq)) && apq != 0.0) {      // (uniform)
+                        rotated = true;
+                        const double zeta = (aqq - app) / (2.0 * apq);
+                        const double tn = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                        const double cs = 1.0 / sqrt(1.0 + tn * tn);
+                        const double sn = cs * tn;
+                        __syncthreads();
+                        if (tid < 9) {
+                            const double akp = M[tid][pp], akq = M[tid][q];
+                            M[tid][pp] = cs * akp - sn * akq;
+                            M[tid][q] = sn * akp + cs * akq;
+                            const double vkp = V[tid][pp], vkq = V[tid][q];
+                            V[tid][pp] = cs * vkp - sn * vkq;
+                            V[tid][q] = sn * vkp + cs * vkq;
+                        }
+                        __syncthreads();
+                        if (tid < 9) {
+                            const double apk = M[pp][tid], aqk = M[q][tid];
+                            M[pp][tid] = cs * apk - sn * aqk;
+                            M[q][tid] = sn * apk + cs * aqk;
+                        }
+                        __syncthreads();
+                        if (tid == 0) M[pp][q] = M[q][pp] = 0.0;
+                        __syncthreads();
+                    }
+                }
+            }
+            if (!rotated) break;
+        }
+        int cbest = 0;
+        double ev = M[0][0];
+        for (int c = 1; c < 9; ++c) {
+            if (M[c][c] < ev) {
+                ev = M[c][c];
+                cbest = c;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 9; ++c) Fn[c] = V[c][cbest];
+        __syncthreads();      // (M and V are rewritten by the next round)
+        return vfy_finish(Fn, cx, cy, s, cx2, cy2, s2);
+    };
+    const int none = mm_pairs_winner_refit<VfyModel>(a, p, mm, 8, sm, bc, bh, refit, F, cost, n_in, best_h, n_valid);
+    if (none == MM_PAIRS_TOO_FEW) flags |= MM_VERIFY_TOO_FEW;
+    if (none == MM_PAIRS_NO_MODEL) flags |= MM_VERIFY_NO_MODEL;
+    if (none == 0 && n_in < a.min_inliers) flags |= MM_VERIFY_WEAK;
 
     const bool failed = (flags & (MM_VERIFY_TOO_FEW | MM_VERIFY_NO_MODEL | MM_VERIFY_WEAK)) != 0;
     // the kept matches in their input order: the inliers of F, or -- a failed pair -- all of them (on_fail 0) / none (1)
     int kept = 0;
     if (!(failed && a.on_fail != 0)) {
-        for (int j0 = 0; j0 < mm; j0 += VFY_THREADS) {
-            const int j = j0 + tid;
-            bool keep = false;
-            int2 qt = make_int2(0, 0);
-            if (j < mm) {
-                qt = reinterpret_cast<const int2 *>(a.pairs)[(size_t)p * a.cap + j];
-                keep = true;
-                if (!failed) {
-                    double x, y, xp, yp;
-                    vfy_load(a, p, j, x, y, xp, yp);
-                    keep = vfy_inlier(vfy_sampson(F, x, y, xp, yp), a.tau2);
-                }
-            }
-            const int at = mm_block_compact_slot(keep, kept, wcount);
-            if (keep) reinterpret_cast<int2 *>(pairs_out)[(size_t)p * a.cap + at] = qt;
-        }
+        const VfyModel M_(F);
+        kept = mm_pairs_compact(a, p, mm, [&](int j) { return failed || mm_pair_inlier_of(M_, a, p, j); }, pairs_out, wcount);
     }
     if (tid == 0) {
         m_out[p] = kept;
@@ -515,9 +344,7 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_refit_kernel(VfyArgs a, int32
 }  // namespace
 
 extern "C" size_t mm_verify_workspace_bytes(int n_pairs, int n_hyp) {
-    const size_t np = n_pairs > 0 ? (size_t)n_pairs : 0, nh = n_hyp > 0 ? (size_t)n_hyp : 0;
-    return mm_align_up(np * 8 * sizeof(double), 256) + mm_align_up(np * nh * 9 * sizeof(double), 256) +
-           mm_align_up(np * nh * sizeof(double), 256);
+    return mm_pairs_workspace(n_pairs, n_hyp);
 }
 
 extern "C" int mm_verify_matches(mm_ctx *ctx, const float *kp_xy, const int32_t *pairs, const int32_t *m, int n_pairs, int cap,
@@ -552,12 +379,7 @@ extern "C" int mm_verify_matches(mm_ctx *ctx, const float *kp_xy, const int32_t 
     a.seed = prm->seed;
     a.pair_base = prm->pair_base;
     a.tau2 = prm->threshold_px * prm->threshold_px;
-    char *w = (char *)ws;
-    a.norm = (double *)w;
-    w += mm_align_up((size_t)n_pairs * 8 * sizeof(double), 256);
-    a.Fh = (double *)w;
-    w += mm_align_up((size_t)n_pairs * a.n_hyp * 9 * sizeof(double), 256);
-    a.cost_h = (double *)w;
+    mm_pairs_carve(a, ws);
     const dim3 per_hyp((unsigned)n_pairs, (unsigned)((a.n_hyp + 63) / 64));
     MM_LAUNCH(ctx, "vfy_normalise_kernel", vfy_normalise_kernel, dim3((unsigned)n_pairs), dim3(VFY_THREADS), 0, a);
     MM_LAUNCH(ctx, "vfy_hypothesis_kernel", vfy_hypothesis_kernel, per_hyp, dim3(64), 0, a);

@@ -30,9 +30,9 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from test_verify_matches_cpu import CAP, K_SCENE, scene_cameras, verify_numpy  # noqa: E402
 from test_recover_poses_cpu import (POSE_AMBIGUOUS, POSE_MALFORMED, POSE_NO_MODEL, POSE_TOO_FEW, CHAIN_FEW_COMMON,  # noqa: E402
-                                    chain_numpy, cross3, dot3, fundamental, jacobi3, k_inverse, mat3, recover_pair)
-from test_resect_cameras_cpu import block_sum, jacobi, pcg  # noqa: E402
-from test_resect_planar_cpu import TRIPLES, factor_from, plane_terms, triple_measure  # noqa: E402
+                                    chain_numpy, cross3, dot3, fundamental, mat3, recover_pair)
+from oracle.geom_oracle import (TRIPLES, block_sum, factor_from, jacobi, jacobi3, k_inverse, pcg, plane_dlt,  # noqa: E402
+                                plane_terms, polar3, triple_measure)
 from meatmodeler_amd import synth  # noqa: E402
 
 TOO_FEW, NO_MODEL, WEAK, MALFORMED, DEGENERATE = 1, 2, 4, 8, 16      # MM_HOMOG_*
@@ -114,61 +114,8 @@ def solve_h(acc, c, s, c2, s2):
     """The reduced DLT on a batch of sums acc [B, 24] under one normalisation -> (H [B, 9], ok [B])."""
     acc = np.asarray(acc, float)
     B = acc.shape[0]
-    S, Bu, Bv, M = ([[None] * 3 for _ in range(3)] for _ in range(4))
-    k = 0
-    for i in range(3):
-        for j in range(i, 3):
-            S[i][j] = S[j][i] = acc[:, k]
-            Bu[i][j] = Bu[j][i] = acc[:, 6 + k]
-            Bv[i][j] = Bv[j][i] = acc[:, 12 + k]
-            M[i][j] = M[j][i] = acc[:, 18 + k]
-            k += 1
-    ok = np.ones(B, bool)
+    h1, h2, h3, ok = plane_dlt(acc)
     with np.errstate(all="ignore"):
-        L = [[None] * 3 for _ in range(3)]
-        for j in range(3):
-            d = S[j][j]
-            for k in range(j):
-                d = d - L[j][k] * L[j][k]
-            ok &= np.isfinite(d) & (d > 1e-12 * S[j][j])
-            ljj = np.sqrt(d)
-            L[j][j] = ljj
-            for i in range(j + 1, 3):
-                v = S[i][j]
-                for k in range(j):
-                    v = v - L[i][k] * L[j][k]
-                L[i][j] = v / ljj
-        Yu, Yv = [[None] * 3 for _ in range(3)], [[None] * 3 for _ in range(3)]
-        for i in range(3):
-            for cc in range(3):
-                vu, vv = Bu[i][cc], Bv[i][cc]
-                for k in range(i):
-                    vu = vu - L[i][k] * Yu[k][cc]
-                    vv = vv - L[i][k] * Yv[k][cc]
-                Yu[i][cc] = vu / L[i][i]
-                Yv[i][cc] = vv / L[i][i]
-        for i in range(3):
-            for j in range(i, 3):
-                tu = (Yu[0][i] * Yu[0][j] + Yu[1][i] * Yu[1][j]) + Yu[2][i] * Yu[2][j]
-                tv = (Yv[0][i] * Yv[0][j] + Yv[1][i] * Yv[1][j]) + Yv[2][i] * Yv[2][j]
-                M[i][j] = M[j][i] = (M[i][j] - tu) - tv
-        V3 = jacobi(M, 3)
-        ev = M[0][0]
-        h3 = [V3[r][0] for r in range(3)]
-        for cc in range(1, 3):
-            lower = M[cc][cc] < ev
-            ev = np.where(lower, M[cc][cc], ev)
-            h3 = [np.where(lower, V3[r][cc], h3[r]) for r in range(3)]
-        wu = [(Yu[i][0] * h3[0] + Yu[i][1] * h3[1]) + Yu[i][2] * h3[2] for i in range(3)]
-        wv = [(Yv[i][0] * h3[0] + Yv[i][1] * h3[1]) + Yv[i][2] * h3[2] for i in range(3)]
-        h1, h2 = [None] * 3, [None] * 3
-        for i in (2, 1, 0):
-            vu, vv = wu[i], wv[i]
-            for k in range(i + 1, 3):
-                vu = vu - L[k][i] * h1[k]
-                vv = vv - L[k][i] * h2[k]
-            h1[i] = vu / L[i][i]
-            h2[i] = vv / L[i][i]
         Hn = [h1[0], h1[1], h1[2], h2[0], h2[1], h2[2], h3[0], h3[1], h3[2]]
         G = [[(Hn[r] * Hn[cc] + Hn[3 + r] * Hn[3 + cc]) + Hn[6 + r] * Hn[6 + cc] for cc in range(3)] for r in range(3)]
         jacobi(G, 3)
@@ -320,19 +267,6 @@ def sign_gap(Ha, Hb):
 
 
 # ------------------------------------------------------------------------------------------------ restatement: the motion
-
-def polar3(A):
-    """mm_polar3 on a 3 x 3 list / array -> (R [3][3], ok)."""
-    G = [[(A[0][r] * A[0][c] + A[1][r] * A[1][c]) + A[2][r] * A[2][c] for c in range(3)] for r in range(3)]
-    lam, V = jacobi3(G)
-    ok = all(np.isfinite(v) and v > 0 for v in lam)
-    with np.errstate(all="ignore"):
-        dk = [1.0 / np.sqrt(np.float64(v)) for v in lam]
-        W = [[((V[i][0] * dk[0]) * V[j][0] + (V[i][1] * dk[1]) * V[j][1]) + (V[i][2] * dk[2]) * V[j][2] for j in range(3)]
-             for i in range(3)]
-        R = [[(A[r][0] * W[0][c] + A[r][1] * W[1][c]) + A[r][2] * W[2][c] for c in range(3)] for r in range(3)]
-    return np.array(R, float), ok
-
 
 def h_rays(K, x):
     ki = k_inverse(K)

@@ -27,46 +27,14 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from test_verify_matches_cpu import K_SCENE, pack, scene_cameras, true_F, two_view_scene  # noqa: E402,F401
 from meatmodeler_amd import synth  # noqa: E402
+from oracle.geom_oracle import jacobi3, k_inverse  # noqa: E402,F401
 
 POSE_TOO_FEW, POSE_NO_MODEL, POSE_AMBIGUOUS, POSE_MALFORMED = 1, 2, 4, 8      # MM_POSE_*
 CHAIN_FEW_COMMON, CHAIN_BROKEN = 1, 2                                         # MM_CHAIN_*
 CAP = 320
-EPS = 2.220446049250313e-16
 
 
 # ------------------------------------------------------------------------------------------------ the restatement: one pair
-
-def jacobi3(G):
-    """Cyclic Jacobi of the header: (eigenvalues [3] = the diagonal, V with the eigenvectors in its columns)."""
-    G = [[float(G[r][c]) for c in range(3)] for r in range(3)]
-    V = [[1.0 if r == c else 0.0 for c in range(3)] for r in range(3)]
-    for _ in range(30):
-        rotated = False
-        for p in range(2):
-            for q in range(p + 1, 3):
-                apq = G[p][q]
-                if abs(apq) > EPS * math.sqrt(abs(G[p][p] * G[q][q])) and apq != 0.0:
-                    rotated = True
-                    zeta = (G[q][q] - G[p][p]) / (2.0 * apq)
-                    tn = math.copysign(1.0, zeta) / (abs(zeta) + math.sqrt(1.0 + zeta * zeta))
-                    cs = 1.0 / math.sqrt(1.0 + tn * tn)
-                    sn = cs * tn
-                    for k in range(3):
-                        akp, akq = G[k][p], G[k][q]
-                        G[k][p] = cs * akp - sn * akq
-                        G[k][q] = sn * akp + cs * akq
-                        vkp, vkq = V[k][p], V[k][q]
-                        V[k][p] = cs * vkp - sn * vkq
-                        V[k][q] = sn * vkp + cs * vkq
-                    for k in range(3):
-                        apk, aqk = G[p][k], G[q][k]
-                        G[p][k] = cs * apk - sn * aqk
-                        G[q][k] = sn * apk + cs * aqk
-                    G[p][q] = G[q][p] = 0.0
-        if not rotated:
-            break
-    return [G[0][0], G[1][1], G[2][2]], np.array(V)
-
 
 def dot3(a, b):
     return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
@@ -85,13 +53,6 @@ def essential(F, K):
     F, K = np.asarray(F, float).reshape(9), np.asarray(K, float).reshape(9)
     FK = [(F[3 * r] * K[c] + F[3 * r + 1] * K[3 + c]) + F[3 * r + 2] * K[6 + c] for r in range(3) for c in range(3)]
     return np.array([(K[r] * FK[c] + K[3 + r] * FK[3 + c]) + K[6 + r] * FK[6 + c] for r in range(3) for c in range(3)])
-
-
-def k_inverse(K):
-    """The five entries of the closed form of the header."""
-    K = np.asarray(K, float).reshape(9)
-    fx, sk, cx, fy, cy = K[0], K[1], K[2], K[4], K[5]
-    return [1.0 / fx, -sk / (fx * fy), (sk * cy - cx * fy) / (fx * fy), 1.0 / fy, -cy / fy]
 
 
 def rotation(u1, u2, u3, v1, v2, v3, transposed_w):

@@ -27,81 +27,15 @@ import os
 import numpy as np
 import pytest
 
+from oracle.geom_oracle import block_sum, jacobi, k_inverse, pcg  # noqa: F401
+
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 K_SCENE = np.array([[1500.0, 0.0, 960.0], [0.0, 1500.0, 540.0], [0.0, 0.0, 1.0]])
 TOO_FEW, NO_MODEL, WEAK, MALFORMED = 1, 2, 4, 8
-EPS = 2.220446049250313e-16
 UNTOUCHED = 7      # what the inlier bytes hold before a call in these tests
-M32 = np.uint64(0xFFFFFFFF)
 
 
 # ------------------------------------------------------------------------------------------------ the restatement
-
-def pcg(v):
-    v = np.asarray(v, np.uint64) & M32
-    s = (v * np.uint64(747796405) + np.uint64(2891336453)) & M32
-    w = (((s >> ((s >> np.uint64(28)) + np.uint64(4))) ^ s) * np.uint64(277803737)) & M32
-    return ((w >> np.uint64(22)) ^ w) & M32
-
-
-def k_inverse(K):
-    K = np.asarray(K, float).reshape(3, 3)
-    fx, sk, cx, fy, cy = K[0, 0], K[0, 1], K[0, 2], K[1, 1], K[1, 2]
-    return np.array([1.0 / fx, -sk / (fx * fy), (sk * cy - cx * fy) / (fx * fy), 1.0 / fy, -cy / fy])
-
-
-def block_sum(vals):
-    """Sum of the rows of vals [n, N] in the workgroup's order: thread t takes rows t, t + 256, ...; xor butterfly over the 64
-    lanes of a wave; the four waves in order."""
-    vals = np.asarray(vals, float)
-    n, N = vals.shape
-    chunks = max(1, -(-n // 256))
-    pad = np.zeros((chunks * 256, N))
-    pad[:n] = vals
-    acc = np.zeros((256, N))
-    for ch in range(chunks):
-        acc = acc + pad[ch * 256:(ch + 1) * 256]
-    a = acc.reshape(4, 64, N)
-    lane = np.arange(64)
-    for off in (32, 16, 8, 4, 2, 1):
-        a = a + a[:, lane ^ off]
-    return ((a[0, 0] + a[1, 0]) + a[2, 0]) + a[3, 0]
-
-
-def jacobi(G, N):
-    """Cyclic Jacobi on the batch of symmetric matrices G[i][j] (arrays [B]): -> V[i][j]; eigenvalues on G's diagonal."""
-    B = G[0][0].shape
-    V = [[np.ones(B) if r == c else np.zeros(B) for c in range(N)] for r in range(N)]
-    for _ in range(30):
-        rotated = False
-        for p in range(N - 1):
-            for q in range(p + 1, N):
-                apq = G[p][q]
-                do = (np.abs(apq) > EPS * np.sqrt(np.abs(G[p][p] * G[q][q]))) & (apq != 0.0)
-                if not do.any():
-                    continue
-                rotated = True
-                zeta = (G[q][q] - G[p][p]) / (2.0 * apq)
-                tn = np.copysign(1.0, zeta) / (np.abs(zeta) + np.sqrt(1.0 + zeta * zeta))
-                cs = 1.0 / np.sqrt(1.0 + tn * tn)
-                sn = cs * tn
-                for k in range(N):
-                    akp, akq = G[k][p], G[k][q]
-                    G[k][p] = np.where(do, cs * akp - sn * akq, akp)
-                    G[k][q] = np.where(do, sn * akp + cs * akq, akq)
-                    vkp, vkq = V[k][p], V[k][q]
-                    V[k][p] = np.where(do, cs * vkp - sn * vkq, vkp)
-                    V[k][q] = np.where(do, sn * vkp + cs * vkq, vkq)
-                for k in range(N):
-                    apk, aqk = G[p][k], G[q][k]
-                    G[p][k] = np.where(do, cs * apk - sn * aqk, apk)
-                    G[q][k] = np.where(do, sn * apk + cs * aqk, aqk)
-                G[p][q] = np.where(do, 0.0, G[p][q])
-                G[q][p] = np.where(do, 0.0, G[q][p])
-        if not rotated:
-            break
-    return V
-
 
 def row_terms(Ki, c, s, X, obs):
     """The 40 numbers one row adds to (S, Bu, Bv, C): X [n, 3], obs [n, 2] -> [n, 40]."""

@@ -28,13 +28,13 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_resect_cameras_cpu import (K_SCENE, MALFORMED, NO_MODEL, TOO_FEW, UNTOUCHED, WEAK, block_sum, camera,  # noqa: E402
-                                     cayley_update, distance, g6_fixture, jacobi, k_inverse, lm_step, packed, pcg, polish_pass,
-                                     rel_gap, rodrigues, rot_err_deg, scene)
+from test_resect_cameras_cpu import (K_SCENE, MALFORMED, NO_MODEL, TOO_FEW, UNTOUCHED, WEAK, camera, cayley_update,  # noqa: E402
+                                     distance, g6_fixture, lm_step, packed, polish_pass, rel_gap, rodrigues, rot_err_deg, scene)
+from oracle.geom_oracle import (TRIPLES, block_sum, factor_from, jacobi, k_inverse, pcg, plane_dlt, plane_terms,  # noqa: E402,F401
+                                triple_measure)
 
 PLANAR = 16
 PLANAR_TOL, COLLINEAR_TOL = 1e-2, 1e-3
-TRIPLES = ((0, 1, 2), (0, 1, 3), (0, 2, 3), (1, 2, 3))
 
 
 # ------------------------------------------------------------------------------------------------ the restatement
@@ -73,90 +73,13 @@ def plane_rows(Ki, pf, X, obs):
     return ma, mb, u, v
 
 
-def plane_terms(ma, mb, u, v):
-    """The 24 numbers one row adds to (S, Bu, Bv, C) -> [n, 24]."""
-    m = [ma, mb, np.ones(len(ma))]
-    r2 = u * u + v * v
-    out = np.zeros((len(ma), 24))
-    k = 0
-    for i in range(3):
-        for j in range(i, 3):
-            w = m[i] * m[j]
-            out[:, k], out[:, 6 + k], out[:, 12 + k], out[:, 18 + k] = w, u * w, v * w, r2 * w
-            k += 1
-    return out
-
-
-def triple_measure(ai, bi, aj, bj, ak, bk):
-    """(|cross|, longest squared side) of the triangle (i, j, k)."""
-    pa, pb, qa, qb, ra, rb = aj - ai, bj - bi, ak - ai, bk - bi, ak - aj, bk - bj
-    cr = pa * qb - pb * qa
-    d0, d1, d2 = pa * pa + pb * pb, qa * qa + qb * qb, ra * ra + rb * rb
-    lng = np.where(d0 > d1, d0, d1)
-    lng = np.where(lng > d2, lng, d2)
-    return np.abs(cr), lng
-
-
 def solve_planar(acc, pf):
     """The reduced DLT one dimension down on a batch of sums acc [B, 24] -> (E [B, 12], ok [B])."""
     acc = np.asarray(acc, float)
     B = acc.shape[0]
     cen, s = pf["cen"], pf["s"]
     fr = [pf["e1"], pf["e2"], pf["n"]]
-    S, Bu, Bv, M = ([[None] * 3 for _ in range(3)] for _ in range(4))
-    k = 0
-    for i in range(3):
-        for j in range(i, 3):
-            S[i][j] = S[j][i] = acc[:, k]
-            Bu[i][j] = Bu[j][i] = acc[:, 6 + k]
-            Bv[i][j] = Bv[j][i] = acc[:, 12 + k]
-            M[i][j] = M[j][i] = acc[:, 18 + k]
-            k += 1
-    ok = np.ones(B, bool)
-    L = [[None] * 3 for _ in range(3)]
-    for j in range(3):
-        d = S[j][j]
-        for k in range(j):
-            d = d - L[j][k] * L[j][k]
-        ok &= np.isfinite(d) & (d > 1e-12 * S[j][j])
-        ljj = np.sqrt(d)
-        L[j][j] = ljj
-        for i in range(j + 1, 3):
-            v = S[i][j]
-            for k in range(j):
-                v = v - L[i][k] * L[j][k]
-            L[i][j] = v / ljj
-    Yu, Yv = [[None] * 3 for _ in range(3)], [[None] * 3 for _ in range(3)]
-    for i in range(3):
-        for cc in range(3):
-            vu, vv = Bu[i][cc], Bv[i][cc]
-            for k in range(i):
-                vu = vu - L[i][k] * Yu[k][cc]
-                vv = vv - L[i][k] * Yv[k][cc]
-            Yu[i][cc] = vu / L[i][i]
-            Yv[i][cc] = vv / L[i][i]
-    for i in range(3):
-        for j in range(i, 3):
-            tu = (Yu[0][i] * Yu[0][j] + Yu[1][i] * Yu[1][j]) + Yu[2][i] * Yu[2][j]
-            tv = (Yv[0][i] * Yv[0][j] + Yv[1][i] * Yv[1][j]) + Yv[2][i] * Yv[2][j]
-            M[i][j] = M[j][i] = (M[i][j] - tu) - tv
-    V3 = jacobi(M, 3)
-    ev = M[0][0]
-    h3 = [V3[r][0] for r in range(3)]
-    for cc in range(1, 3):
-        lower = M[cc][cc] < ev
-        ev = np.where(lower, M[cc][cc], ev)
-        h3 = [np.where(lower, V3[r][cc], h3[r]) for r in range(3)]
-    wu = [(Yu[i][0] * h3[0] + Yu[i][1] * h3[1]) + Yu[i][2] * h3[2] for i in range(3)]
-    wv = [(Yv[i][0] * h3[0] + Yv[i][1] * h3[1]) + Yv[i][2] * h3[2] for i in range(3)]
-    h1, h2 = [None] * 3, [None] * 3
-    for i in (2, 1, 0):
-        vu, vv = wu[i], wv[i]
-        for k in range(i + 1, 3):
-            vu = vu - L[k][i] * h1[k]
-            vv = vv - L[k][i] * h2[k]
-        h1[i] = vu / L[i][i]
-        h2[i] = vv / L[i][i]
+    h1, h2, h3, ok = plane_dlt(acc)
     sg = np.where(h3[2] < 0.0, -1.0, 1.0)
     g = [[sg * h1[cc], sg * h2[cc], sg * h3[cc]] for cc in range(3)]      # g[cc] = column cc of H
     g1, g2, g3 = g
@@ -184,15 +107,6 @@ def solve_planar(acc, pf):
         E[:, 4 * r + 3] = g3[r] / (sigma * s) - ((E[:, 4 * r] * cen[0] + E[:, 4 * r + 1] * cen[1]) + E[:, 4 * r + 2] * cen[2])
     ok &= np.isfinite(E).all(axis=1)
     return E, ok
-
-
-def factor_from(x, tol):
-    """How many times x is away from tol, in either direction (inf for x = 0 against a positive tol)."""
-    if x == tol:
-        return 1.0
-    if x == 0.0 or tol == 0.0:
-        return math.inf
-    return max(x / tol, tol / x)
 
 
 def resect_planar_numpy(K, X, obs, pi, cam_ptr, cam_obs, pt_ok=None, prior=None, n_hyp=256, threshold_px=2.0, min_rows=8,

@@ -18,20 +18,14 @@ import math
 import numpy as np
 import pytest
 
+from oracle.geom_oracle import pcg
+
 TOO_FEW, NO_MODEL, WEAK, MALFORMED = 1, 2, 4, 8      # MM_VERIFY_*
 CAP = 320
 M32 = 0xFFFFFFFF
 
 
 # ------------------------------------------------------------------------------------------------ sampling
-
-def pcg(v):
-    """The 32-bit PCG output function on uint64 arrays holding 32-bit values."""
-    v = np.asarray(v, np.uint64)
-    s = (v * np.uint64(747796405) + np.uint64(2891336453)) & np.uint64(M32)
-    w = (((s >> ((s >> np.uint64(28)) + np.uint64(4))) ^ s) * np.uint64(277803737)) & np.uint64(M32)
-    return ((w >> np.uint64(22)) ^ w) & np.uint64(M32)
-
 
 def sample(seed, pair_index, n_hyp, m):
     """picks [n_hyp, 8] and ok [n_hyp] of the pair with global index pair_index."""
