@@ -572,6 +572,67 @@ int mm_recover_poses_homography(mm_ctx *ctx, const double *K /*host [9]*/, const
                                 double *sigma /*[n_pairs,3]*/, double *normal /*[n_pairs,3]*/, double *depth /*[n_pairs,cap,2]*/,
                                 int32_t *info /*[n_pairs,8]*/);
 
+/* ---- a-2d: guided matching -- matches recovered along each pair's epipolar geometry (no reference counterpart) -------------
+ * mm_verify_matches and mm_verify_homography only remove matches.  The Lowe ratio test of the match stage is global: a key point
+ * with a look-alike anywhere in the next image fails it.  Once a pair has a model the look-alike is almost never near the
+ * epipolar line (or the transferred point): mm_guided_match searches the key points no match uses again, among the
+ * candidates the model admits only.
+ *   Inputs, all DEVICE pointers except prm.  Pair p joins frame p (query) and frame p + 1 (train) of a block of n_pairs + 1
+ *   frames: kp_xy [n_pairs+1, cap, 2] f32, desc [n_pairs+1, cap, 32] u8 (256-bit binary descriptors), n [n_pairs+1] i32 key points
+ *   per frame (clamped to 0 .. cap): n_q = n[p], n_t = n[p+1].  pairs [n_pairs, cap, 2] i32 = (queryIdx, trainIdx) and m
+ *   [n_pairs] i32 (clamped to 0 .. cap): the seed matches, as mm_verify_matches / mm_verify_homography write them.  model
+ *   [n_pairs, 9] f64 row-major, kind [n_pairs] i32 or NULL (all 0).  kind 0: model is F with x'^T F x = 0; kind 1: model is H
+ *   with x' ~ H x; anything else: the pair has no model.
+ *   Gate.  g(i, j) holds when d^2(x_i, x'_j) is finite and <= tau^2, tau = threshold_px, x_i = kp_xy[p, i], x'_j =
+ *   kp_xy[p+1, j] widened to f64.  kind 0: the Sampson distance of mm_verify_matches, evaluated as written here:
+ *   fx_r = F_r0 x + F_r1 y + F_r2 (r = 0, 1, 2), ft0 = F_00 x' + F_10 y' + F_20, ft1 = F_01 x' + F_11 y' + F_21,
+ *   e = x' fx0 + y' fx1 + fx2, d^2 = e e / (fx0 fx0 + fx1 fx1 + ft0 ft0 + ft1 ft1), every sum left to right, no fused
+ *   multiply-add.  kind 1: the symmetric transfer distance of mm_verify_homography as written there, the adjugate computed once
+ *   per pair.  These are the inlier rules of the two verify stages, so a guided match is an inlier of the model it came from.
+ *   Both distances are symmetric in the two images: the gate is the same set in either search direction.
+ *   Seeds.  The input rows j < m must be in strictly increasing query order, q_j < q_(j+1) on the raw values (what the ratio
+ *   filter and the compactions of the verify stages emit); otherwise the pair is MM_GUIDED_UNORDERED and passes through.  A row
+ *   with an index outside [0, cap) is MALFORMED: it is dropped, nothing is read through it, the flag is set.  Every other input
+ *   row is kept as it is and marks its query and its train as used.
+ *   Search.  For every unused query i < n_q: C_i = { j < n_t : train j unused, g(i, j) }; j0 and j1 the nearest and the second
+ *   nearest of C_i by the Hamming distance of the descriptors, ties to the lower j, d0 and d1 their distances.  (i, j0) is
+ *   PROPOSED when d0 <= max_dist and either C_i has a single member or (double)d0 < ratio * (double)d1 (the comparison of
+ *   mm_ratio_filter_batched).
+ *   One-to-one.  cross_check = 1: the proposal is kept iff i is the nearest of { i' < n_q unused : g(i', j0) } to train j0, ties
+ *   to the lower i' (the search in the reverse direction over the same gate).  cross_check = 0: among the proposals with the
+ *   same train the lowest (d0, i) is kept.  Either way no train gains two new matches.
+ *   Outputs.  pairs_out [n_pairs, cap, 2] (must not alias pairs): the kept input rows and the new rows merged in query order,
+ *   -1 from row m_out[p] on -- every element is written; m_out [n_pairs]; is_new [n_pairs, cap] u8 parallel to pairs_out (1: a
+ *   new row; 0 elsewhere, the tail included); info [n_pairs, 4] i32 = (flags, input rows kept, rows added, proposals before the
+ *   one-to-one step).  A pair that passes through (SKIPPED, UNORDERED) has its m input rows copied as they are -- malformed
+ *   ones included, the flag says so -- and info = (flags, m, 0, 0).
+ *   Flags.  MM_GUIDED_SKIPPED: kind names no model, or model has a non-finite entry | MM_GUIDED_UNORDERED |
+ *   MM_GUIDED_MALFORMED.
+ * Three launches: prepare (one workgroup per pair: the order test, the used marks, the unused queries and trains listed in
+ * ascending order), search (workgroup = pair x 256 unused queries, lane = query; a train passes a cheap necessary test on
+ * terms prepared once before the distance itself is evaluated; best and second on a packed (distance, index) key; the reverse
+ * direction is an integer atomicMin of (distance, query) per train in the same pass, whose result does not depend on order)
+ * and finish (one workgroup per pair: the proposal rule, one-to-one, the merge by ballot / popcount prefix).  Nothing else
+ * depends on order and nothing is sampled: a call repeats bit for bit, a pair's row does not depend on which other pairs share
+ * the call, rows [a, b) of a call equal a call on that sub-block.  n_pairs = 0 returns MM_OK without a launch.  kp_xy, pairs
+ * and pairs_out 8-byte aligned, desc and ws 16-byte aligned; ws holds mm_guided_workspace_bytes(n_pairs, cap) bytes.  Argument
+ * errors -- null pointers other than kind, cap < 1 or above 2^22, a negative or NaN threshold_px (+inf admits every finite
+ * distance), a negative or NaN ratio, max_dist outside 0 .. 256, cross_check outside {0, 1}, pairs_out == pairs: MM_ERR_ARG; a
+ * workspace that is too small: MM_ERR_WORKSPACE -- are returned before the device is touched. */
+#define MM_GUIDED_SKIPPED 1
+#define MM_GUIDED_UNORDERED 2
+#define MM_GUIDED_MALFORMED 8
+typedef struct mm_guided_params {
+    double threshold_px, ratio;          /* defaults 2, 0.8 */
+    int32_t max_dist, cross_check;       /* defaults 64, 1 */
+} mm_guided_params;
+size_t mm_guided_workspace_bytes(int n_pairs, int cap);
+int mm_guided_match(mm_ctx *ctx, const float *kp_xy /*[n_pairs+1,cap,2]*/, const uint8_t *desc /*[n_pairs+1,cap,32]*/,
+                    const int32_t *n /*[n_pairs+1]*/, const int32_t *pairs /*[n_pairs,cap,2]*/, const int32_t *m /*[n_pairs]*/,
+                    const double *model /*[n_pairs,9]*/, const int32_t *kind /*[n_pairs] or NULL*/, int n_pairs, int cap,
+                    const mm_guided_params *prm, int32_t *pairs_out /*[n_pairs,cap,2]*/, int32_t *m_out /*[n_pairs]*/,
+                    uint8_t *is_new /*[n_pairs,cap]*/, int32_t *info /*[n_pairs,4]*/, void *ws, size_t ws_bytes);
+
 /* ---- a-4: two-view DLT triangulation ------------------------------------------------------------
  * Replaces the per-track cv2.triangulatePoints + dehomogenise loop, processor.py:254-261.
  * proj [F,3,4] f64; track i uses views f0[i], f1[i] with pixels x0[i], x1[i]; X [n,3]. */

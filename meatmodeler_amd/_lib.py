@@ -93,6 +93,11 @@ class HPoseParams(C.Structure):
                 ("ambiguous_frac", C.c_double), ("rotation_tol", C.c_double)]
 
 
+class GuidedParams(C.Structure):
+    """mm_guided_params: gate threshold, ratio, distance ceiling and the one-to-one rule of mm_guided_match."""
+    _fields_ = [("threshold_px", C.c_double), ("ratio", C.c_double), ("max_dist", C.c_int32), ("cross_check", C.c_int32)]
+
+
 class ResectParams(C.Structure):
     """mm_resect_params: hypotheses, row and inlier floors, refit and polish counts, sampling key and threshold of
     mm_resect_cameras."""
@@ -167,6 +172,9 @@ SIGNATURES = {
                                        C.c_size_t]),
     "mm_recover_poses_homography": (C.c_int, [vp, c_f64p, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(HPoseParams), vp, vp, vp,
                                               vp, vp, vp]),
+    "mm_guided_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "mm_guided_match": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(GuidedParams), vp, vp, vp, vp, vp,
+                                  C.c_size_t]),
     "mm_resect_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int64]),
     "mm_resect_cameras": (C.c_int, [vp, c_f64p, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int, vp, vp,
                                     C.POINTER(ResectParams), vp, vp, vp, vp, vp, C.c_size_t]),

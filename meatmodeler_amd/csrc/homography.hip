@@ -33,28 +33,7 @@ struct HgArgs : MmPairArgs {      // (model_h: the hypotheses' H)
     double collinear_tol, degenerate_frac;
 };
 
-// adj(H), written out: every entry one difference of two products, no division by the determinant
-__device__ __forceinline__ void hg_adjugate(const double (&H)[9], double (&A)[9]) {
-    A[0] = H[4] * H[8] - H[5] * H[7];
-    A[1] = H[2] * H[7] - H[1] * H[8];
-    A[2] = H[1] * H[5] - H[2] * H[4];
-    A[3] = H[5] * H[6] - H[3] * H[8];
-    A[4] = H[0] * H[8] - H[2] * H[6];
-    A[5] = H[2] * H[3] - H[0] * H[5];
-    A[6] = H[3] * H[7] - H[4] * H[6];
-    A[7] = H[1] * H[6] - H[0] * H[7];
-    A[8] = H[0] * H[4] - H[1] * H[3];
-}
-
-// symmetric transfer distance d^2 = (|x' - pi(H x)|^2 + |x - pi(adj(H) x')|^2) / 2
-__device__ __forceinline__ double hg_transfer(const double (&H)[9], const double (&A)[9], double x, double y, double xp, double yp) {
-    const double y0 = (H[0] * x + H[1] * y) + H[2], y1 = (H[3] * x + H[4] * y) + H[5], y2 = (H[6] * x + H[7] * y) + H[8];
-    const double z0 = (A[0] * xp + A[1] * yp) + A[2], z1 = (A[3] * xp + A[4] * yp) + A[5], z2 = (A[6] * xp + A[7] * yp) + A[8];
-    const double ex = xp - y0 / y2, ey = yp - y1 / y2, fx = x - z0 / z2, fy = y - z1 / z2;
-    return ((ex * ex + ey * ey) + (fx * fx + fy * fy)) * 0.5;
-}
-
-// the model of the MSAC skeleton (mm_pairs.h): H with its adjugate prepared once
+// the model of the MSAC skeleton (mm_pairs.h): H with its adjugate prepared once; hg_adjugate and hg_transfer are mm_pairs.h's
 struct HgModel {
     double H[9], A[9];
     __device__ __forceinline__ explicit HgModel(const double (&h)[9]) {

@@ -1,10 +1,11 @@
-// What the stages over the matches of consecutive frame pairs share (verify.hip, pose.hip, homography.hip): how a match is
-// read, the Hartley normalisation, and the MSAC skeleton around a model.
+// What the stages over the matches of consecutive frame pairs share (verify.hip, pose.hip, homography.hip, guided.hip): how a
+// match is read, the two distances, the Hartley normalisation, and the MSAC skeleton around a model.
 //
 // The rule of mm_geom.h holds here: shared means a definition or a skeleton.  A stage plugs in its model and keeps it in its
 // own file: a type built from nine doubles (with whatever it prepares once, such as an adjugate) that has
 //     double distance(double x, double y, double xp, double yp) const
-// and the stage's solver, verdict and flags.  Everything here is __forceinline__ and compiled under the including file's
+// and the stage's solver, verdict and flags.  The distances themselves (vfy_sampson, hg_adjugate / hg_transfer) are here
+// since guided.hip gates by them: one definition each.  Everything here is __forceinline__ and compiled under the including file's
 // flags; sums run in an order that depends on the pair alone (per-thread strides, mm_block_sum), so a pair's row repeats bit
 // for bit whatever else shares the call.
 #pragma once
@@ -67,6 +68,36 @@ __device__ __forceinline__ bool mm_pair_rays(const Args &a, int p, int j, Vec3 &
 }
 
 __device__ __forceinline__ bool mm_pair_inlier(double d2, double tau2) { return isfinite(d2) && d2 <= tau2; }
+
+// ---- the two distances (verify.hip, homography.hip and guided.hip read these and nothing else) -------------------------------
+// Sampson distance of x'^T F x = 0
+__device__ __forceinline__ double vfy_sampson(const double (&F)[9], double x, double y, double xp, double yp) {
+    const double fx0 = F[0] * x + F[1] * y + F[2], fx1 = F[3] * x + F[4] * y + F[5], fx2 = F[6] * x + F[7] * y + F[8];
+    const double ft0 = F[0] * xp + F[3] * yp + F[6], ft1 = F[1] * xp + F[4] * yp + F[7];
+    const double e = xp * fx0 + yp * fx1 + fx2;
+    return e * e / (fx0 * fx0 + fx1 * fx1 + ft0 * ft0 + ft1 * ft1);
+}
+
+// adj(H), written out: every entry one difference of two products, no division by the determinant
+__device__ __forceinline__ void hg_adjugate(const double (&H)[9], double (&A)[9]) {
+    A[0] = H[4] * H[8] - H[5] * H[7];
+    A[1] = H[2] * H[7] - H[1] * H[8];
+    A[2] = H[1] * H[5] - H[2] * H[4];
+    A[3] = H[5] * H[6] - H[3] * H[8];
+    A[4] = H[0] * H[8] - H[2] * H[6];
+    A[5] = H[2] * H[3] - H[0] * H[5];
+    A[6] = H[3] * H[7] - H[4] * H[6];
+    A[7] = H[1] * H[6] - H[0] * H[7];
+    A[8] = H[0] * H[4] - H[1] * H[3];
+}
+
+// symmetric transfer distance d^2 = (|x' - pi(H x)|^2 + |x - pi(adj(H) x')|^2) / 2
+__device__ __forceinline__ double hg_transfer(const double (&H)[9], const double (&A)[9], double x, double y, double xp, double yp) {
+    const double y0 = (H[0] * x + H[1] * y) + H[2], y1 = (H[3] * x + H[4] * y) + H[5], y2 = (H[6] * x + H[7] * y) + H[8];
+    const double z0 = (A[0] * xp + A[1] * yp) + A[2], z1 = (A[3] * xp + A[4] * yp) + A[5], z2 = (A[6] * xp + A[7] * yp) + A[8];
+    const double ex = xp - y0 / y2, ey = yp - y1 / y2, fx = x - z0 / z2, fy = y - z1 / z2;
+    return ((ex * ex + ey * ey) + (fx * fx + fy * fy)) * 0.5;
+}
 
 // is match j an inlier of the model (a malformed match has NaN coordinates, a NaN distance, and is none)
 template <class Model, class Args>

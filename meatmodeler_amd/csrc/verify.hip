@@ -27,14 +27,7 @@ struct VfyArgs : MmPairArgs {      // (model_h: the hypotheses' F)
     int on_fail;
 };
 
-__device__ __forceinline__ double vfy_sampson(const double (&F)[9], double x, double y, double xp, double yp) {
-    const double fx0 = F[0] * x + F[1] * y + F[2], fx1 = F[3] * x + F[4] * y + F[5], fx2 = F[6] * x + F[7] * y + F[8];
-    const double ft0 = F[0] * xp + F[3] * yp + F[6], ft1 = F[1] * xp + F[4] * yp + F[7];
-    const double e = xp * fx0 + yp * fx1 + fx2;
-    return e * e / (fx0 * fx0 + fx1 * fx1 + ft0 * ft0 + ft1 * ft1);
-}
-
-// the model of the MSAC skeleton (mm_pairs.h): F, nothing prepared
+// the model of the MSAC skeleton (mm_pairs.h): F, nothing prepared; the distance is mm_pairs.h's vfy_sampson
 struct VfyModel {
     double F[9];
     __device__ __forceinline__ explicit VfyModel(const double (&f)[9]) {

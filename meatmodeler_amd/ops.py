@@ -266,6 +266,51 @@ def verify_homography(kp_xy, pairs, m, verify_info=None, n_hyp=256, threshold_px
     return pairs_out, m_out, H, cost, info
 
 
+GUIDED_SKIPPED, GUIDED_UNORDERED, GUIDED_MALFORMED = 1, 2, 8      # MM_GUIDED_*
+
+
+def guided_match(kp_xy, desc, n, pairs, m, model, kind=None, threshold_px=2.0, ratio=0.8, max_dist=64, cross_check=True, ctx=None):
+    """Guided matching of consecutive frame pairs (mm_guided_match): the key points no seed match uses are matched again among
+    the candidates each pair's model admits.  kp_xy [n_pairs+1, cap, 2] f32, desc [n_pairs+1, cap, 32] u8, n [n_pairs+1] i32 key
+    points per frame; pairs [n_pairs, cap, 2] i32 and m [n_pairs] i32 the seeds, in strictly increasing query order (what
+    verify_matches / verify_homography return); model [n_pairs, 9] f64 and kind [n_pairs] i32 (0: model is F with
+    x'^T F x = 0, 1: H with x' ~ H x, anything else: no model; None: all 0) -- device tensors
+    -> (pairs_out [n_pairs, cap, 2] i32 -- seeds and new rows merged in query order, -1 beyond m_out --, m_out [n_pairs] i32,
+    is_new [n_pairs, cap] u8 parallel to pairs_out, info [n_pairs, 4] i32 = (GUIDED_* flags, input rows kept, rows added,
+    proposals before the one-to-one step)).  A new row is within threshold_px of the model (the inlier rule of the verify
+    stages), at most max_dist bits from its query, the only candidate or under `ratio` times the second, and one-to-one:
+    cross_check=True keeps it when the query is also the train's nearest candidate, False the lowest distance per train."""
+    if not float(threshold_px) >= 0:
+        raise ValueError("guided_match: threshold_px must not be negative")
+    if not float(ratio) >= 0:
+        raise ValueError("guided_match: ratio must not be negative")
+    if not 0 <= int(max_dist) <= 256:
+        raise ValueError("guided_match: max_dist must be in 0 .. 256")
+    _pair_shapes("guided_match", kp_xy, pairs, m)
+    n_pairs, cap = pairs.shape[0], pairs.shape[1]
+    if tuple(desc.shape) != (n_pairs + 1, cap, 32) or tuple(n.shape) != (n_pairs + 1,) or tuple(model.shape) != (n_pairs, 9) \
+            or (kind is not None and tuple(kind.shape) != (n_pairs,)):
+        raise ValueError("guided_match: desc [n_pairs+1, cap, 32], n [n_pairs+1], model [n_pairs, 9] and kind [n_pairs] expected")
+    ctx = ctx or default_context()
+    d = pairs.device
+    pairs_out = torch.empty((n_pairs, cap, 2), dtype=torch.int32, device=d)      # (every element is written by the kernels)
+    m_out = torch.zeros(n_pairs, dtype=torch.int32, device=d)
+    is_new = torch.zeros((n_pairs, cap), dtype=torch.uint8, device=d)
+    info = torch.zeros((n_pairs, 4), dtype=torch.int32, device=d)
+    if n_pairs == 0 or cap == 0:
+        return pairs_out, m_out, is_new, info
+    assert kp_xy.dtype == torch.float32 and desc.dtype == torch.uint8 and model.dtype == torch.float64
+    prm = _lib.GuidedParams(float(threshold_px), float(ratio), int(max_dist), 1 if cross_check else 0)
+    wsb = lib.mm_guided_workspace_bytes(n_pairs, cap)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=d)
+    kd = None if kind is None else _i32(kind.contiguous())
+    ctx.check(lib.mm_guided_match(ctx.h, ptr(kp_xy.contiguous()), ptr(desc.contiguous()), ptr(_i32(n.contiguous())),
+                                  ptr(_i32(pairs.contiguous())), ptr(_i32(m.contiguous())), ptr(model.contiguous()), ptr(kd),
+                                  n_pairs, cap, C.byref(prm), ptr(pairs_out), ptr(m_out), ptr(is_new), ptr(info), ptr(ws), wsb),
+              "mm_guided_match")
+    return pairs_out, m_out, is_new, info
+
+
 def recover_poses_homography(kp_xy, pairs, m, H, K, normal_hint=None, min_matches=8, min_front_frac=0.5, ambiguous_frac=0.9,
                              rotation_tol=1e-2, ctx=None):
     """The motion each pair's homography implies (mm_recover_poses_homography): kp_xy, pairs, m and H [n_pairs, 9] f64 as

@@ -29,6 +29,7 @@ DEGENERACY_HOMOGRAPHY_KEYS = ("n_hyp", "threshold_px", "min_matches", "min_inlie
                               "degenerate_frac")
 DEGENERACY_POSE_KEYS = ("min_front_frac", "ambiguous_frac", "rotation_tol")
 DEGENERACY_KEYS = DEGENERACY_HOMOGRAPHY_KEYS + DEGENERACY_POSE_KEYS
+GUIDED_KEYS = ("threshold_px", "ratio", "max_dist", "cross_check")
 RESECT_KEYS = ("n_hyp", "threshold_px", "min_rows", "min_inliers", "refit_iters", "polish_iters", "seed", "planar", "planar_tol",
                "collinear_tol")
 
@@ -63,6 +64,12 @@ def degeneracy_options(degeneracy):
     ops.recover_poses_homography (min_front_frac, ambiguous_frac, rotation_tol) -- verify_info, pair_base, the hint and ctx are
     the pipeline's own.  Returns it as a dict; an unknown key raises ValueError."""
     return _stage_options("degeneracy", degeneracy, DEGENERACY_KEYS)
+
+
+def guided_options(guided):
+    """`run(..., guided=)`: None (no guided matching) or a dict of the parameters of ops.guided_match -- the seeds, the model,
+    its kind and ctx are the pipeline's own.  Returns it as a dict; an unknown key raises ValueError."""
+    return _stage_options("guided", guided, GUIDED_KEYS)
 
 
 def resect_options(resect):
@@ -134,6 +141,15 @@ class ClipPipeline:
         rotation-only verdict needs; pair_lo as in `verify`.  -> (pairs_out, m_out, H [n,9], cost [n], info [n,6])."""
         n = pairs.shape[0]
         return ops.verify_homography(det["xy"][:n + 1], pairs, m, verify_info=verify_info, pair_base=pair_lo, ctx=self.ctx, **params)
+
+    # ------------------------------------------------------------------------------------------- guided
+    def guided(self, det, pairs, m, model, kind=None, **params):
+        """Guided matching on what `verify` (or `homography`) returned for the frames in `det` (ops.guided_match): pairs, m the
+        seeds, model [n,9] each pair's F (kind 0) or H (kind 1; anything else: no model, the pair passes through).
+        -> (pairs_out, m_out, is_new [n,cap] u8, info [n,4]), device tensors."""
+        n = pairs.shape[0]
+        return ops.guided_match(det["xy"][:n + 1], det["desc"][:n + 1], det["n"][:n + 1], pairs, m, model, kind=kind, ctx=self.ctx,
+                                **params)
 
     # ------------------------------------------------------------------------------------------- poses
     def recover_poses(self, det, pairs, m, F, K, E0=None, min_common=8, **params):
@@ -515,7 +531,8 @@ class ClipPipeline:
 
     # ------------------------------------------------------------------------------------------- whole clip
     def run(self, frames, K, extrinsics=None, ba=True, ftol=1e-4, verbose=0, dist=None, timers=None, max_nfev=None,
-            force_collectives=False, triangulation="two_view", cull=None, verify=None, poses=None, resect=None, degeneracy=None):
+            force_collectives=False, triangulation="two_view", cull=None, verify=None, poses=None, resect=None, degeneracy=None,
+            guided=None):
         """frames [F,H,W] u8 (device).  With `dist` = torch.distributed (initialised), frames are the FULL clip on
         every rank (synthetic input is generated locally) and the work is sharded as described in parallel.py.
         `max_nfev`: evaluation budget of the adjustment (None = SciPy's default, as adjustPoints).
@@ -544,6 +561,13 @@ class ClipPipeline:
         `poses` its relative pose comes from the homography -- a pure rotation is chained with t = 0 and the scale carried --
         before the one chain call.  The selection is a torch.where on the device, no host read.  The result gains `degeneracy`
         = dict(H [n,9], cost [n], info [n,6], and with `poses` pose_info [n,8], sigma [n,3], normal [n,3]); timer "degeneracy".
+        `guided`: None (default: nothing below runs) or a dict of the parameters of ops.guided_match ({} for the defaults; needs
+        `verify`): after `verify` and `degeneracy` and before the gather / `link`, every rank matches the key points its pairs'
+        matches leave unused once more, among the candidates within threshold_px of the pair's model: F of
+        `verify`, no model where it flagged TOO_FEW, NO_MODEL or WEAK, and with `degeneracy` the homography where the pair is
+        HOMOG_DEGENERATE -- a torch.where on the device, no host read.  The enlarged set replaces the matches: the linker reads
+        it, `poses` and the chain read the linked matches as before.  The result gains `guided` = dict(info [n,4],
+        is_new [n,cap]); timer "guided".
         `resect`: None (default) or a dict of the parameters of ops.resect_cameras ({} for the defaults; one rank only): after
         the triangulation every frame is resected against `points0` (under "multi_view" only against the tracks no test
         flagged), with the extrinsics in use -- given or recovered -- as the prior, so no frame ends with a higher MSAC cost
@@ -554,6 +578,10 @@ class ClipPipeline:
         poses = pose_options(poses)
         resect = resect_options(resect)
         degeneracy = degeneracy_options(degeneracy)
+        guided = guided_options(guided)
+        if guided is not None and verify is None:
+            raise ValueError("guided needs verify (it supplies each pair's fundamental matrix, the model the search is gated by): "
+                             "pass verify={} for the defaults")
         if degeneracy is not None and verify is None:
             raise ValueError("degeneracy needs verify (the verdict compares the homography with each pair's fundamental matrix): "
                              "pass verify={} for the defaults")
@@ -631,6 +659,22 @@ class ClipPipeline:
                 info_d = torch.zeros((0, 6), dtype=torch.int32, device=self.device)
             degenerate = dict(H=H_d, cost=cost_d, info=info_d)
             toc("degeneracy")
+        guided_out = None
+        if guided is not None:
+            tic("guided")
+            if det is not None:
+                failed = (info_v[:, 0] & (ops.VERIFY_TOO_FEW | ops.VERIFY_NO_MODEL | ops.VERIFY_WEAK)) != 0
+                kind_g = torch.where(failed, -1, 0).to(torch.int32)
+                model_g = F_v
+                if degenerate is not None:
+                    kind_g = torch.where(is_deg, 1, kind_g).to(torch.int32)
+                    model_g = torch.where(is_deg[:, None], H_d, F_v)
+                pairs, m, new_g, info_g = self.guided(det, pairs, m, model_g, kind=kind_g, **guided)
+            else:
+                new_g = torch.zeros((0, self.cap), dtype=torch.uint8, device=self.device)
+                info_g = torch.zeros((0, 4), dtype=torch.int32, device=self.device)
+            guided_out = dict(info=info_g, is_new=new_g)
+            toc("guided")
         tic("link")
         if sharded:
             # every rank needs every frame's key points and every pair's matches to link identical tracks.  The block
@@ -724,6 +768,8 @@ class ClipPipeline:
             out["poses"] = recovered
         if degenerate is not None:
             out["degeneracy"] = degenerate
+        if guided_out is not None:
+            out["guided"] = guided_out
         if resected is not None:
             out["resect"] = resected
         kept = None

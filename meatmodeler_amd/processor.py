@@ -337,6 +337,38 @@ def verifyMatches(prev_matches, curr_matches, **params):
     return mask, F[0].cpu().numpy().reshape(3, 3)
 
 
+def guidedMatching(prev_xy, prev_desc, curr_xy, curr_desc, matches, model, homography=False, **params):
+    """Guided matching of one keyframe pair: prev_xy [n1,2] / curr_xy [n2,2] pixel coordinates and prev_desc [n1,32] /
+    curr_desc [n2,32] u8 descriptors of ALL key points of the previous and the new keyframe, matches [k,2] int
+    (index into prev, index into curr) in strictly increasing order of the first column -- the matches `verifyMatches` kept --
+    and model [3,3]: the F it returned (curr^T F prev = 0), or with homography=True an H with curr ~ H prev
+    -> (matches_out [k',2] int32: the given matches and the new ones merged in order of the first column, is_new [k'] bool).
+    `params` as ops.guided_match takes them (threshold_px, ratio, max_dist, cross_check).  A model that is not finite, or
+    matches that are not in order, return the matches as they came."""
+    prev = np.asarray(prev_xy, np.float32).reshape(-1, 2)
+    curr = np.asarray(curr_xy, np.float32).reshape(-1, 2)
+    dp = np.asarray(prev_desc, np.uint8).reshape(-1, 32)
+    dc = np.asarray(curr_desc, np.uint8).reshape(-1, 32)
+    if dp.shape[0] != prev.shape[0] or dc.shape[0] != curr.shape[0]:
+        raise ValueError("guidedMatching: one descriptor per key point expected")
+    seeds = np.asarray(matches, np.int32).reshape(-1, 2)
+    cap = max(prev.shape[0], curr.shape[0], seeds.shape[0], 1)
+    kp = np.zeros((2, cap, 2), np.float32)
+    ds = np.zeros((2, cap, 32), np.uint8)
+    kp[0, :prev.shape[0]], kp[1, :curr.shape[0]] = prev, curr
+    ds[0, :dp.shape[0]], ds[1, :dc.shape[0]] = dp, dc
+    pr = np.full((1, cap, 2), -1, np.int32)
+    pr[0, :seeds.shape[0]] = seeds
+    dev = default_context().device
+    to = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(dev)
+    out, m_out, new, _ = ops.guided_match(to(kp), to(ds), to(np.array([prev.shape[0], curr.shape[0]], np.int32)), to(pr),
+                                          to(np.array([seeds.shape[0]], np.int32)),
+                                          to(np.asarray(model, np.float64).reshape(1, 9)),
+                                          kind=to(np.array([1 if homography else 0], np.int32)), **params)
+    k = int(m_out[0].item())
+    return out[0, :k].cpu().numpy(), new[0, :k].cpu().numpy().astype(bool)
+
+
 def recoverPose(prev_matches, curr_matches, K, F, **params):
     """The relative pose of two keyframes from their matches, the calibration and the fundamental matrix `verifyMatches`
     returned (curr^T F prev = 0): -> (n_front, R [3,3], t [3], mask [n] bool) with X_curr = R X_prev + t, |t| = 1; mask marks
