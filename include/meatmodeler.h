@@ -92,11 +92,12 @@ int mm_profile_report(mm_ctx *ctx, char *buf, size_t buf_len);
  *   dist [n_pairs, nq_cap, 2] int32 : their Hamming distances (-1 if absent)
  * Rows >= nq[p] are left untouched.
  * The distances are computed on the matrix cores (descriptors expanded to +1 / -1 FP4 values: dot product = 256 - 2 dist,
- * exact).  The default kernel (MM_BF_VARIANT=314, or 310) expands the train descriptors tile by tile on their way into LDS
- * and needs a token workspace only; variants 300 (FP4 MFMA, packed streams) and 200 (int8 MFMA) expand the train sets in
- * a pass of their own and the workspace holds them, 128 / 256 bytes per train descriptor (mm_bf_workspace_bytes, never 0;
- * 16-byte aligned).  Train sets of fewer than 64 or of 65536 and more descriptors take the xor / popcount kernel
- * (MM_BF_VARIANT=114) instead -- all return identical results.
+ * exact).  The default kernel expands the train descriptors tile by tile on their way into LDS and needs a token
+ * workspace only (mm_bf_workspace_bytes: 256 bytes, never 0; 16-byte aligned).  Train sets of fewer than 64 or of 65536
+ * and more descriptors take the xor / popcount kernel instead, whose workspace holds the partial results when a small
+ * launch splits its train range -- both return identical results.  MM_BF_VARIANT=114 in the environment puts the
+ * xor / popcount kernel on every shape (tests, tools/bench_bf.py); 314, 0 or unset is the rule above; any other value
+ * names a kernel that was removed: the compute calls return MM_ERR_ARG, the size functions answer as for the default.
  */
 size_t mm_bf_workspace_bytes(int n_pairs, int nq_cap, int nt_cap);
 int mm_bf_knn2_batched(mm_ctx *ctx, const uint8_t *q /*dev*/, const int32_t *nq /*dev|NULL*/, int nq_cap,
@@ -112,8 +113,8 @@ int mm_ratio_filter_batched(mm_ctx *ctx, const int32_t *idx /*dev*/, const int32
                             const int32_t *nq /*dev|NULL*/, int nq_cap, int n_pairs, double threshold,
                             int32_t *pairs /*dev [n_pairs,nq_cap,2]*/, int32_t *m_out /*dev [n_pairs]*/);
 /* The whole match stage in one call: exactly what mm_bf_knn2_batched followed by mm_ratio_filter_batched produce, without
- * idx / dist ever being stored where the kernel has the ratio test in its epilogue (variants 314 / 310: one int32 per query
- * goes to the workspace instead; the other variants keep idx / dist there).  Every element of pairs [n_pairs, nq_cap, 2]
+ * idx / dist ever being stored where the kernel has the ratio test in its epilogue (the default, matrix-core kernel: one
+ * int32 per query goes to the workspace instead; the xor / popcount kernel keeps idx / dist there).  Every element of pairs [n_pairs, nq_cap, 2]
  * and of m_out [n_pairs] is written: pairs[p, j] = (queryIdx, trainIdx) of the j-th kept match in query order for
  * j < m_out[p], -1 from there on -- the outputs need no initialisation.  Workspace: mm_bf_match_ratio_workspace_bytes,
  * 16-byte aligned. */

@@ -12,7 +12,7 @@ def sizes(n_pairs, nq_cap, nt_cap):
             _lib.lib.mm_bf_workspace_bytes(n_pairs, nq_cap, nt_cap))
 
 
-@pytest.mark.parametrize("variant", ["314", "310"])
+@pytest.mark.parametrize("variant", ["314"])
 def test_fused_variants_hold_one_code_per_query_and_no_expanded_train_set(variant, monkeypatch):
     monkeypatch.setenv("MM_BF_VARIANT", variant)
     total, knn = sizes(499, 4000, 4000)
@@ -24,14 +24,36 @@ def test_fused_variants_hold_one_code_per_query_and_no_expanded_train_set(varian
         assert knn % 256 == 0 and total == knn + 2 * up(9 * 300 * 2 * 4)
 
 
-@pytest.mark.parametrize("variant,per_train", [("300", 128), ("200", 256), ("114", 0)])
+@pytest.mark.parametrize("variant,per_train", [("114", 0)])
 def test_other_variants_keep_idx_and_dist_behind_the_search_workspace(variant, per_train, monkeypatch):
     monkeypatch.setenv("MM_BF_VARIANT", variant)
     total, knn = sizes(9, 300, 300)
-    if per_train:
-        assert knn == up(9 * 320 * per_train)                  # expanded train sets, 300 rows padded to 10 tiles of 32
     assert knn > 0 and knn % 256 == 0
     assert total == knn + 2 * up(9 * 300 * 2 * 4)
+
+
+@pytest.mark.parametrize("shape", [(499, 4000, 4000), (9, 300, 300), (9, 300, 63), (9, 300, 65536), (1, 70, 64)])
+def test_a_removed_variant_sizes_as_the_default(shape, monkeypatch):
+    """MM_BF_VARIANT=300 names a kernel that is gone: the compute calls refuse it (test_match_stage_gpu.py), the two size
+    functions cannot fail and plan as if it were unset."""
+    monkeypatch.delenv("MM_BF_VARIANT", raising=False)
+    default = sizes(*shape)
+    monkeypatch.setenv("MM_BF_VARIANT", "300")
+    assert sizes(*shape) == default
+    monkeypatch.setenv("MM_BF_VARIANT", "314")
+    assert sizes(*shape) == default
+
+
+@pytest.mark.parametrize("nt_cap,fused", [(63, False), (64, True), (65535, True), (65536, False)])
+def test_layout_at_the_dispatch_boundaries(nt_cap, fused, monkeypatch):
+    """One pair of 70 queries (the shape of test_dispatch_boundaries in test_match_stage_gpu.py), no environment: one code
+    per query behind the search's workspace where the matrix-core kernel runs, idx + dist on either side of its range."""
+    monkeypatch.delenv("MM_BF_VARIANT", raising=False)
+    total, knn = sizes(1, 70, nt_cap)
+    assert knn > 0 and knn % 256 == 0
+    assert total == (knn + up(70 * 4) if fused else knn + 2 * up(70 * 8))
+    if fused:
+        assert knn == 256
 
 
 def test_degenerate_shapes():

@@ -86,7 +86,7 @@ def batch():
     return dict(q=dev(q), t=dev(t), nq=dev(nq), nt=dev(nt), oracle=oracle)
 
 
-@pytest.mark.parametrize("variant", ["314", "310", "114"])
+@pytest.mark.parametrize("variant", ["314", "114"])
 def test_match_ratio_against_oracle(variant, batch, monkeypatch):
     monkeypatch.setenv("MM_BF_VARIANT", variant)
     pairs, m = ops.bf_match_ratio_batched(batch["q"], batch["t"], batch["nq"], batch["nt"], THRESHOLD)
@@ -99,7 +99,7 @@ def test_match_ratio_against_oracle(variant, batch, monkeypatch):
     assert m[0] > 0 and m[8] > 0 and m[1] == 0 and m[2] == 0
 
 
-@pytest.mark.parametrize("variant", ["314", "310", "300", "200", "114"])
+@pytest.mark.parametrize("variant", ["314", "114"])
 def test_match_ratio_equals_the_two_calls(variant, batch, monkeypatch):
     monkeypatch.setenv("MM_BF_VARIANT", variant)
     idx, dist = ops.bf_knn2_batched(batch["q"], batch["t"], batch["nq"], batch["nt"])
@@ -125,7 +125,7 @@ def test_match_ratio_without_counts_and_single_pair():
         np.testing.assert_array_equal(pairs[0, :60].cpu().numpy(), np.stack([np.arange(60), np.arange(60) + 60], 1))
 
 
-@pytest.mark.parametrize("variant", ["314", "310"])
+@pytest.mark.parametrize("variant", ["314"])
 def test_rows_past_the_train_count_never_win(variant, monkeypatch):
     """The kernel stages its train tiles from the packed descriptors: rows in [nt, nt_cap) hold garbage (0xFF here) and
     rows in [nt_cap, next multiple of 32) do not exist (they read as 0 bits).  An all-ones and an all-zeros query would
@@ -152,3 +152,119 @@ def test_rows_past_the_train_count_never_win(variant, monkeypatch):
         np.testing.assert_array_equal(pairs[p, :m[p]], po)
         assert (pairs[p, m[p]:] == -1).all()
         assert list(pairs[p, 0]) == [0, 7] and list(pairs[p, 1]) == [1, 8]
+
+
+# ---- what the plan (bf_plan in csrc/bf_match.hip) decides: kernel, splits, workspace ------------------------------------------
+
+def planted(nq, nt, seed):
+    """One pair of random rows with three planted queries; rows `hi` = nt - 1 and `hi` - k lie in the last 32-row tile.
+      query 3: best row hi (d = 10), second row 1 (d = 40)          -> a match, the two in the last and the first split
+      query 5: best row hi - 3 (d = 12), second row hi - 1 (d = 40) -> a match, both in the last tile
+      query 7: row 2 and its copy at hi - 2, both d = 4             -> ties go to the lower index; never a match
+      query 9: row hi - 6 and its copy at hi - 5, both d = 6        -> the same with both copies in the last tile
+    Only the plants the train count has room for are made (nt >= 12); the oracle is the reference either way."""
+    rng = np.random.default_rng(seed)
+    q = rng.integers(0, 256, (1, nq, 32), dtype=np.uint8)
+    t = rng.integers(0, 256, (1, nt, 32), dtype=np.uint8)
+    want = {}
+    if nt >= 12 and nq > 9:
+        hi, bits = nt - 1, rng.permutation(256)
+        q[0, 3] = flipped(t[0, hi], bits[:10])
+        t[0, 1] = flipped(t[0, hi], bits[10:40])
+        q[0, 5] = flipped(t[0, hi - 3], bits[:12])
+        t[0, hi - 1] = flipped(t[0, hi - 3], bits[12:40])
+        t[0, hi - 2] = t[0, 2]
+        q[0, 7] = flipped(t[0, 2], bits[:4])
+        t[0, hi - 5] = t[0, hi - 6]
+        q[0, 9] = flipped(t[0, hi - 6], bits[:6])
+        want = {3: ([hi, 1], [10, 40]), 5: ([hi - 3, hi - 1], [12, 40]), 7: ([2, hi - 2], [4, 4]),
+                9: ([hi - 6, hi - 5], [6, 6])}
+    return q, t, want
+
+
+def check_pair_against_oracle(q, t, want):
+    """bf_knn2_batched exactly against the C oracle, bf_match_ratio_batched against the oracle's ratio filter and byte for
+    byte against the two calls."""
+    io, do = oo.bf_knn2(q[0], t[0])
+    for qi, (ii, dd) in want.items():                # the plants are what they were meant to be
+        assert list(io[qi]) == ii and list(do[qi]) == dd, (qi, io[qi], do[qi])
+    qd, td = dev(q), dev(t)
+    idx, dist = ops.bf_knn2_batched(qd, td)
+    np.testing.assert_array_equal(idx[0].cpu().numpy(), io)
+    np.testing.assert_array_equal(dist[0].cpu().numpy(), do)
+    pairs_o, m_o = ops.ratio_filter_batched(idx, dist, THRESHOLD)
+    pairs, m = ops.bf_match_ratio_batched(qd, td, None, None, THRESHOLD)
+    assert torch.equal(m, m_o) and torch.equal(pairs, pairs_o)
+    po = oo.ratio_filter(io, do, THRESHOLD)
+    assert int(m[0]) == len(po)
+    np.testing.assert_array_equal(pairs[0, :len(po)].cpu().numpy(), po)
+    if want:
+        assert [3, want[3][0][0]] in po.tolist() and [5, want[5][0][0]] in po.tolist()
+        assert 7 not in po[:, 0] and 9 not in po[:, 0]
+
+
+@pytest.mark.parametrize("nt_cap", [63, 64, 65535, 65536])
+def test_dispatch_boundaries_without_the_environment(nt_cap, monkeypatch):
+    """The matrix-core kernel takes 64 <= nt_cap < 65536, the popcount kernel the rest (the layouts on either side:
+    test_match_stage_abi.py).  70 queries; the plants sit in the last 32-row tile, which is partial at 63 and 65535; at
+    65536 the best of query 3 is row 65535, the last index the matrix-core kernel's 16-bit train indices could hold."""
+    monkeypatch.delenv("MM_BF_VARIANT", raising=False)
+    q, t, want = planted(70, nt_cap, seed=nt_cap)
+    assert want[3][0][0] == nt_cap - 1
+    check_pair_against_oracle(q, t, want)
+
+
+@pytest.mark.parametrize("variant", ["114", None])
+@pytest.mark.parametrize("nt", [1, 2, 63])
+def test_single_query_single_split(nt, variant, monkeypatch):
+    """nq = 1 at nt_cap = 63 (one split, whatever the environment says): one, two and 63 valid trains."""
+    if variant is None:
+        monkeypatch.delenv("MM_BF_VARIANT", raising=False)
+    else:
+        monkeypatch.setenv("MM_BF_VARIANT", variant)
+    from meatmodeler_amd import _lib
+    assert _lib.lib.mm_bf_workspace_bytes(1, 1, 63) == 256          # one split: no partial keys
+    rng = np.random.default_rng(nt)
+    q = rng.integers(0, 256, (1, 1, 32), dtype=np.uint8)
+    t = rng.integers(0, 256, (1, 63, 32), dtype=np.uint8)
+    t[0, nt:] = q[0, 0]                                             # rows past the count would win at distance 0
+    t[0, nt - 1] = flipped(q[0, 0], [9, 99])                        # the true best: the last valid row, d = 2
+    io, do = oo.bf_knn2(q[0], t[0, :nt])
+    assert io[0, 0] == nt - 1 and do[0, 0] == 2 and (io[0, 1] == -1) == (nt == 1)
+    ntd = dev(np.array([nt], np.int32))
+    idx, dist = ops.bf_knn2_batched(dev(q), dev(t), None, ntd)
+    np.testing.assert_array_equal(idx[0].cpu().numpy(), io)
+    np.testing.assert_array_equal(dist[0].cpu().numpy(), do)
+    pairs, m = ops.bf_match_ratio_batched(dev(q), dev(t), None, ntd, THRESHOLD)
+    po = oo.ratio_filter(io, do, THRESHOLD)
+    assert int(m[0]) == len(po) == (0 if nt == 1 else 1)
+    np.testing.assert_array_equal(pairs[0, :len(po)].cpu().numpy(), po)
+    assert (pairs[0, len(po):] == -1).all()
+
+
+@pytest.mark.parametrize("nt,splits", [(127, 1), (128, 1), (129, 2), (257, 3)])
+def test_split_and_merge_at_the_split_rule(nt, splits, monkeypatch):
+    """The popcount kernel on one small pair splits its train range, at least 128 trains per split: 1, 1, 2, 3 splits.
+    Query 3 has its best in the last split and its second best in the first, query 7 a tie across them."""
+    monkeypatch.setenv("MM_BF_VARIANT", "114")
+    from meatmodeler_amd import _lib
+    knn = _lib.lib.mm_bf_workspace_bytes(1, 70, nt)
+    assert knn == (256 if splits == 1 else (splits * 70 * 2 * 4 + 255) // 256 * 256)      # partial keys of every split
+    q, t, want = planted(70, nt, seed=nt)
+    check_pair_against_oracle(q, t, want)
+
+
+def test_removed_variants_are_refused(monkeypatch):
+    from meatmodeler_amd._lib import MMError
+    q, t, _ = planted(10, 70, seed=1)
+    monkeypatch.setenv("MM_BF_VARIANT", "300")
+    with pytest.raises(MMError, match=r"\(-1\)") as err:            # MM_ERR_ARG
+        ops.bf_knn2_batched(dev(q), dev(t))
+    assert "314" in str(err.value) and "114" in str(err.value) and "removed" in str(err.value)
+    with pytest.raises(MMError, match=r"\(-1\)"):
+        ops.bf_match_ratio_batched(dev(q), dev(t))
+    monkeypatch.delenv("MM_BF_VARIANT")
+    idx, dist = ops.bf_knn2_batched(dev(q), dev(t))
+    io, do = oo.bf_knn2(q[0], t[0])
+    np.testing.assert_array_equal(idx[0].cpu().numpy(), io)
+    np.testing.assert_array_equal(dist[0].cpu().numpy(), do)

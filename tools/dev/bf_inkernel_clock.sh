@@ -1,10 +1,10 @@
 #!/bin/bash
 # shader clock INSIDE the matching kernel (s_memtime vs s_memrealtime per workgroup): rebuild bf_match.o with
-# -DMM_BF_CLOCK, run the C3-shaped benchmark on one variant, restore the product build.  usage: bf_inkernel_clock.sh [variant]
+# -DMM_BF_CLOCK, run the C3-shaped benchmark, restore the product build.  The stamps are on the default kernel (variant 314) only.
 v=${1:-314}
 mkdir -p gpurun_out
 cd meatmodeler_amd/csrc || exit 1
-hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -munsafe-fp-atomics -mllvm -amdgpu-mfma-vgpr-form=1 -DMM_BF_CLOCK -c bf_match.hip -o bf_match.o || exit 1
+hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -munsafe-fp-atomics -Wall -Wno-unused-result -mllvm -amdgpu-mfma-vgpr-form=1 -DMM_BF_CLOCK -c bf_match.hip -o bf_match.o || exit 1
 make > ../../gpurun_out/make_clk.log 2>&1 || { tail ../../gpurun_out/make_clk.log; exit 1; }
 cd ../..
 BF_ONLY=$v timeout -k 10 200 python - <<'PY' > gpurun_out/bf_inkernel_clock_$v.log 2>&1

@@ -1,9 +1,9 @@
 #!/bin/bash
-# per-kernel time of the matching stage alone (tools/bench_bf.py, MFMA variant) under rocprofv3 --stats
+# per-kernel time of the matching stage alone (tools/bench_bf.py, BF_ONLY=314 matrix cores or 114 xor / popcount) under rocprofv3 --stats
 ROOT=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/bfstats
-BF_ONLY=${BF_ONLY:-200} timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/bfstats -- python3 $ROOT/tools/bench_bf.py > /tmp/bfstats.log 2>&1
+BF_ONLY=${BF_ONLY:-314} timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/bfstats -- python3 $ROOT/tools/bench_bf.py > /tmp/bfstats.log 2>&1
 tail -2 /tmp/bfstats.log
 python3 -c "
 import csv,glob
