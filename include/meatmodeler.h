@@ -734,7 +734,8 @@ int mm_ba_jvp_dots(mm_ctx *ctx, const mm_ba_problem *pb, const double *cams, con
 int mm_ba_schur(mm_ctx *ctx, const mm_ba_problem *pb, const double *cams, const double *pts, const double *Bd,
                 const double *Cd, const double *gc, const double *gp, double *S, double *v, double *Cinv, void *ws,
                 size_t ws_bytes);
-size_t mm_ba_schur_workspace_bytes(const mm_ba_problem *pb); /* 42 doubles per chunk (0 without a pair list) */
+/* partial sums and a descriptor per chunk, a counter per segment, a table row per camera, the slab flags (0 without chunks) */
+size_t mm_ba_schur_workspace_bytes(const mm_ba_problem *pb);
 /* Device-side construction of the pair list (needs fi, pi and the CSR by point in *pb):
  *   count: cnt[o] = number of observations o2 of o's point with camera(o2) <= camera(o); span_out[0] = widest camera
  *          distance inside a point (= cam_span);
@@ -805,8 +806,11 @@ int mm_ba_backsub(mm_ctx *ctx, const mm_ba_problem *pb, const double *cams, cons
 /* mm_ba_schur followed by mm_chol_solve(S, 6F, v, 1, half_bandwidth), overlapped: S is built in n_slabs ascending camera
  * slabs (slab s = cameras [s, s+1) * cams_per_slab; slab_seg_ptr / slab_chunk_ptr: HOST arrays [n_slabs+1] with the first
  * segment / chunk of each slab) on the context's stream while the single-launch banded factorisation runs on a second
- * stream and consumes block rows as their slabs complete.  On return (stream-ordered) v holds the solution and info the
- * factorisation status.  Without a pair list / slabs, or for wide bands, the two steps simply run one after the other. */
+ * stream and consumes block rows as their slabs complete.  The build is what mm_ba_schur launches -- zero fill of S, one
+ * prepare launch, the pair kernel -- with the pair kernel cut in two: its first half runs alone, its second half beside
+ * the factorisation.  On return (stream-ordered) v holds the solution and info the factorisation status.  Without a pair
+ * list / slabs (2 .. 64 of at least 16 cameras), without points, or for bands the single-launch factorisation does not
+ * take, the two steps simply run one after the other. */
 int mm_ba_schur_solve(mm_ctx *ctx, const mm_ba_problem *pb, const double *cams, const double *pts, const double *Bd,
                       const double *Cd, const double *gc, const double *gp, double *S, double *v, double *Cinv,
                       int half_bandwidth, int32_t *info, void *ws_schur, size_t ws_schur_bytes, void *ws_chol,

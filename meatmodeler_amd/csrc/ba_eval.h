@@ -41,36 +41,19 @@ __device__ __forceinline__ CamCoef cam_coef_of(const double *__restrict__ cam) {
     return k;
 }
 
-// Camera parameters + rotation coefficients held as VALUES (11 doubles).  A wave that works on one camera makes them
-// wave-uniform with cam_vals_uniform(): they then live in scalar registers and reach the f64 FMAs as SGPR operands
-// instead of occupying 22 vector registers per camera.
+// Camera parameters + rotation coefficients held as VALUES (11 doubles).
 struct CamVals {
     double rx, ry, rz, tx, ty, tz;
     CamCoef k;
 };
 
+// a value the whole wave shares, moved into scalar registers: it then reaches the f64 FMAs as an SGPR operand instead of
+// occupying two vector registers
 __device__ __forceinline__ double uniform_f64(double x) {
     const unsigned long long u = __double_as_longlong(x);
     const unsigned lo = __builtin_amdgcn_readfirstlane((int)(u & 0xffffffffu));
     const unsigned hi = __builtin_amdgcn_readfirstlane((int)(u >> 32));
     return __longlong_as_double(((unsigned long long)hi << 32) | lo);
-}
-
-__device__ __forceinline__ CamVals cam_vals_uniform(const double *__restrict__ cam) {
-    const CamCoef k = cam_coef_of(cam);
-    CamVals v;
-    v.rx = uniform_f64(cam[0]);
-    v.ry = uniform_f64(cam[1]);
-    v.rz = uniform_f64(cam[2]);
-    v.tx = uniform_f64(cam[3]);
-    v.ty = uniform_f64(cam[4]);
-    v.tz = uniform_f64(cam[5]);
-    v.k.c = uniform_f64(k.c);
-    v.k.a = uniform_f64(k.a);
-    v.k.b = uniform_f64(k.b);
-    v.k.a1 = uniform_f64(k.a1);
-    v.k.b1 = uniform_f64(k.b1);
-    return v;
 }
 
 template <bool WANT_JC, bool WANT_JP>

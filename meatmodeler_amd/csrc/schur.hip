@@ -2,6 +2,36 @@
 //
 //   S = blockdiag(Bd) - sum_p E_p Cd_p^-1 E_p^T ,   v = gc - sum_p E_p Cd_p^-1 gp_p ,   E_o = Jc_o^T Jp_o (6x3)
 //
+// Which path a problem takes:
+//   - with a co-observation pair list (ops.BADevice builds one when no point spans more than max_band_span cameras): the
+//     PAIR kernel, one wave per chunk of a block segment, deterministic, only the block band of S is touched.  A prepare
+//     launch in front of it inverts the point blocks and writes the per-camera tables and per-chunk descriptors;
+//   - without one (wide spans): point_inverse_kernel + the GENERAL kernel, one workgroup per block row, LDS atomics, all
+//     of S filled.
+// Entry points (bottom of the file): mm_ba_schur (plain build), mm_ba_schur_solve (build + banded Cholesky, overlapped
+// slab by slab on request), mm_ba_schur_solve_damped (mm_ba_trf: damping, zero fill and the factorisation's fills folded
+// into the prepare launch), mm_batch_schur_setup / mm_batch_schur (mm_ba_trf_batched: blockIdx.y picks the problem).
+// The file in order: general kernel, pair kernel, prepare, construction of the pair list, plan and entry points.
+#include <type_traits>
+#include "ba_eval.h"
+#include "chol_init.h"
+
+namespace {
+
+// Cinv = Cd^-1, 3 x 3 symmetric, upper triangle storage xx,xy,xz,yy,yz,zz = (a, b, d, e, f, g)
+__device__ __forceinline__ void sym3_inverse(double a, double b, double d, double e, double f, double g, double *__restrict__ o) {
+    const double m00 = e * g - f * f, m01 = d * f - b * g, m02 = b * f - d * e;
+    const double det = a * m00 + b * m01 + d * m02;
+    const double id = 1.0 / det;
+    o[0] = m00 * id;
+    o[1] = m01 * id;
+    o[2] = m02 * id;
+    o[3] = (a * g - d * d) * id;
+    o[4] = (b * d - a * f) * id;
+    o[5] = (a * e - b * b) * id;
+}
+
+// ---- the general kernel (problems without a pair list) ------------------------------------------------------------------
 // One workgroup owns one block ROW of S (camera i) x one window of SR_WIN column blocks.  It walks the observations of
 // camera i (CSR by camera); for each (point p) it forms Y = E_o Cd_p^-1 and then visits the other observations of p
 // (CSR by point, contiguous) whose camera lies in the window, re-evaluates their E and accumulates -Y E_2^T into a
@@ -9,30 +39,14 @@
 // coalesced stores: S needs no zero fill, no global atomics and both triangles come out filled.  Every (o, o2) pair is
 // evaluated from both of its rows — 2x the flops of a symmetric scheme, but the flops are free here: the kernel is bound
 // by the LDS atomic rate, and the global-atomic version it replaces ran 16x slower (profiles/r01_*).
-#include "ba_eval.h"
-#include "chol_init.h"
-
-namespace {
-
 constexpr int SR_WIN = 256;  // cameras per column window: 6 x 1536 doubles = 73,728 B of LDS -> 2 workgroups per CU
 
-// Cinv = Cd^-1 (3x3 symmetric, upper triangle storage xx,xy,xz,yy,yz,zz)
 __global__ __launch_bounds__(256) void point_inverse_kernel(int P, const double *__restrict__ Cd,
                                                             double *__restrict__ Cinv) {
     int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= P) return;
     const double *c = Cd + (size_t)p * 6;
-    const double a = c[0], b = c[1], d = c[2], e = c[3], f = c[4], g = c[5];
-    const double m00 = e * g - f * f, m01 = d * f - b * g, m02 = b * f - d * e;
-    const double det = a * m00 + b * m01 + d * m02;
-    const double id = 1.0 / det;
-    double *o = Cinv + (size_t)p * 6;
-    o[0] = m00 * id;
-    o[1] = m01 * id;
-    o[2] = m02 * id;
-    o[3] = (a * g - d * d) * id;
-    o[4] = (b * d - a * f) * id;
-    o[5] = (a * e - b * b) * id;
+    sym3_inverse(c[0], c[1], c[2], c[3], c[4], c[5], Cinv + (size_t)p * 6);
 }
 
 __global__ __launch_bounds__(256) void schur_rows_kernel(mm_ba_problem pb, const double *__restrict__ cams,
@@ -111,12 +125,14 @@ __global__ __launch_bounds__(256) void schur_rows_kernel(mm_ba_problem pb, const
     }
 }
 
-// Banded, deterministic variant driven by the co-observation pair list (mm_ba_build_pairs).  One WAVE per non-empty
-// block segment (i, f2 = i - d): lanes stride over the segment's (o, o2) pairs, accumulate Y_o E_o2^T in 36 private
-// registers (+6 for the right-hand side on the self pairs) and a fixed shuffle tree adds the lanes, so every entry of
-// S is summed in the same order on every run — the trust-region iteration, which is chaotic on outlier-laden matches,
-// then repeats bit for bit.  No atomics; every block is written together with its mirror image, so both triangles of the
-// band are filled (S is zero-filled first).
+// ---- the pair kernel (problems with a pair list) ------------------------------------------------------------------------
+// Banded, deterministic variant driven by the co-observation pair list (pair-list construction below).  One WAVE per
+// chunk of a non-empty block segment (i, f2 = i - d): lanes stride over the chunk's (o, o2) pairs, accumulate
+// Y_o E_o2^T in 36 private registers (+6 for the right-hand side on the self pairs) and a fixed-order reduction adds the
+// lanes, so every entry of S is summed in the same order on every run — the trust-region iteration, which is chaotic on
+// outlier-laden matches, then repeats bit for bit.  No atomics on S; every block is written together with its mirror
+// image, so both triangles of the band are filled (S is zero-filled first).
+//
 // waves (= chunks) per workgroup of the pair kernel.  ONE since the second half of round 4: the workgroup barrier behind the
 // descriptor / camera-table loads made every wave wait for the slowest of its workgroup -- 259.7 / 230.7 / 205.6 / 198.4 us
 // with 8 / 4 / 2 / 1 waves at the bench shape (512 pairs per chunk)
@@ -132,64 +148,6 @@ struct SlabSync {
     int32_t seg_count[MAX_SLABS];
     int cams_per_slab;
 };
-// Per-camera table for the pair kernel: parameters + rotation coefficients (11 doubles per camera), computed once
-// per build instead of a sincos / sqrt / four divisions in every chunk's prologue.
-constexpr int CAMTAB = 11;
-// per-chunk descriptors of the lean pair kernel (struct ChunkDesc below): 8 int32 per chunk
-__device__ __forceinline__ void write_chunk_desc(const mm_ba_problem &pb, int32_t *__restrict__ desc, int64_t first, int64_t stride) {
-    for (int64_t k = first; k < pb.n_chunks; k += stride) {
-        const int sidx = pb.chunk_seg[k], seg = pb.seg_ids[sidx];
-        const int ci = seg / (pb.cam_span + 1), cdd = seg % (pb.cam_span + 1);
-        const int c_first = pb.seg_chunk_ptr[sidx];
-        int32_t *o = desc + 8 * k;
-        o[0] = ci;
-        o[1] = ci - cdd;
-        o[2] = pb.chunk_begin[k];
-        o[3] = pb.chunk_end[k];
-        o[4] = sidx;
-        o[5] = c_first;
-        o[6] = pb.seg_chunk_ptr[sidx + 1] - c_first;
-        o[7] = 0;
-    }
-}
-__global__ __launch_bounds__(64) void cam_table_kernel(int F, const double *__restrict__ cams, double *__restrict__ tab,
-                                                       int32_t *__restrict__ seg_done, int64_t n_seg, const double *__restrict__ K_lean,
-                                                       mm_ba_problem pb, int32_t *__restrict__ desc) {
-    const int f = blockIdx.x * 64 + threadIdx.x;
-    // (also clears the finished-chunk counters of the build that follows: one fill launch less)
-    for (int64_t k = f; k < n_seg; k += (int64_t)gridDim.x * 64) seg_done[k] = 0;
-    if (desc) write_chunk_desc(pb, desc, f, (int64_t)gridDim.x * 64);
-    if (f >= F) return;
-    const double *c = cams + (size_t)f * 6;
-    if (K_lean) {      // the lean pair kernel's table (P, q, J_r: 24 doubles per camera)
-        cam_table2_row(c, K_lean, tab + (size_t)f * CAMTAB2);
-        return;
-    }
-    const CamCoef k = cam_coef_of(c);
-    double *t = tab + (size_t)f * CAMTAB;
-    for (int q = 0; q < 6; ++q) t[q] = c[q];
-    t[6] = k.c;
-    t[7] = k.a;
-    t[8] = k.b;
-    t[9] = k.a1;
-    t[10] = k.b1;
-}
-
-__device__ __forceinline__ CamVals cam_vals_from_table(const double *__restrict__ t) {
-    CamVals v;
-    v.rx = uniform_f64(t[0]);
-    v.ry = uniform_f64(t[1]);
-    v.rz = uniform_f64(t[2]);
-    v.tx = uniform_f64(t[3]);
-    v.ty = uniform_f64(t[4]);
-    v.tz = uniform_f64(t[5]);
-    v.k.c = uniform_f64(t[6]);
-    v.k.a = uniform_f64(t[7]);
-    v.k.b = uniform_f64(t[8]);
-    v.k.a1 = uniform_f64(t[9]);
-    v.k.b1 = uniform_f64(t[10]);
-    return v;
-}
 
 // Sum over the 64 lanes of a wave of 42 per-lane values, in two rounds of 21 through a [21][65] LDS slab of the wave
 // (row stride 65: the 21 readers hit 21 different banks): every lane writes its values (conflict-free rows), lane q < 21
@@ -230,170 +188,7 @@ __device__ __forceinline__ void wave_reduce_42(const double (&acc)[42], double *
     }
 }
 
-// The round-3 formulation (MM_SCHUR_PAIRS=ref): both observations of a pair go through the sweeps' full evaluator
-// (projection, residual, both Jacobians from the Rodrigues coefficients: ~200 f64 instructions each).  Kept as the
-// cross-check of the lean kernel below.
-// launch bound 2 waves per SIMD (no scratch: the cameras' values live in scalar registers)
-__global__ __launch_bounds__(64 * SP_WAVES, 2) void schur_pairs_ref_kernel(mm_ba_problem pb, const double *__restrict__ camtab,
-                                                                    const double *__restrict__ pts,
-                                                                    const double *__restrict__ Cinv,
-                                                                    const double *__restrict__ gp,
-                                                                    double *partial, const double *__restrict__ Bd,
-                                                                    const double *__restrict__ gc, double *S, double *v,
-                                                                    int32_t *seg_done, SlabSync slabs, unsigned wg_begin,
-                                                                    unsigned wg_total) {
-    __shared__ double Ks[9];
-    __shared__ double red[SP_WAVES][21 * RED_LD];
-    if (threadIdx.x < 9) Ks[threadIdx.x] = pb.K[threadIdx.x];
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    // chunks are ordered by camera; the workgroups take them alternately from the front and from the back, because the
-    // two-ended factorisation that may be consuming S concurrently starts at both ends and needs the middle last
-    // (a build may be cut into several launches: this one covers the positions wg_begin .. of that order)
-    const unsigned gpos = blockIdx.x + wg_begin;
-    const unsigned wg = (gpos & 1) ? wg_total - 1 - (gpos >> 1) : (gpos >> 1);
-    const int64_t c = (int64_t)wg * SP_WAVES + (threadIdx.x >> 6);
-    if (c >= pb.n_chunks) return;  // wave-uniform; no workgroup barriers below
-    const int sidx = __builtin_amdgcn_readfirstlane(pb.chunk_seg[c]);
-    const int seg = __builtin_amdgcn_readfirstlane(pb.seg_ids[sidx]);
-    const int i = seg / (pb.cam_span + 1), d = seg % (pb.cam_span + 1);
-    const int f2 = i - d;
-    // two cameras per chunk, not per pair: parameters and rotation coefficients as wave-uniform scalars
-    const CamVals cv_i = cam_vals_from_table(camtab + (size_t)i * CAMTAB), cv_2 = cam_vals_from_table(camtab + (size_t)f2 * CAMTAB);
-    double acc[42];
-#pragma unroll
-    for (int q = 0; q < 42; ++q) acc[q] = 0.0;
-    const int e_end = __builtin_amdgcn_readfirstlane(pb.chunk_end[c]);
-    const int e_begin = __builtin_amdgcn_readfirstlane(pb.chunk_begin[c]);
-    // A chunk holds at most 256 pairs = four per lane: all their indices are requested up front (one memory round trip
-    // instead of one -- two without pair_p -- per trip of the loop), so that a trip only waits for its own data gathers
-    constexpr int MAXT = 4;
-    int oi[MAXT], o2i[MAXT], pidx[MAXT];
-#pragma unroll
-    for (int k = 0; k < MAXT; ++k) {
-        const int e = e_begin + lane + 64 * k;
-        const bool in = e < e_end;
-        oi[k] = in ? pb.pair_o[e] : -1;
-        o2i[k] = in ? pb.pair_o2[e] : -1;
-        pidx[k] = in ? (pb.pair_p ? pb.pair_p[e] : -2) : -1;
-    }
-    auto pair_body = [&](int o, int o2, int p) {
-        const double *Xp = pts + (size_t)p * 3;
-        Proj pr;
-        ba_eval_vals<true, true>(cv_i, Xp, Ks, pb.obs[2 * (size_t)o], pb.obs[2 * (size_t)o + 1], pr);
-        const double *ci = Cinv + (size_t)p * 6;
-        const double q00 = ci[0], q01 = ci[1], q02 = ci[2], q11 = ci[3], q12 = ci[4], q22 = ci[5];
-        // E_o C^-1 E_o2^T = Jc_o^T (Jp_o C^-1 Jp_o2^T) Jc_o2: the middle factor is 2 x 2, so the 6 x 6 block costs
-        // 18 + 12 + 24 + 72 multiply-adds through Z = Jp_o C^-1 (2 x 3), M = Z Jp_o2^T (2 x 2), T = M Jc_o2 (2 x 6)
-        // instead of 90 + 36 + 108 through the two 6 x 3 products E_o C^-1 and E_o2
-        double Z[2][3];
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            Z[m][0] = pr.Jp[m][0] * q00 + pr.Jp[m][1] * q01 + pr.Jp[m][2] * q02;
-            Z[m][1] = pr.Jp[m][0] * q01 + pr.Jp[m][1] * q11 + pr.Jp[m][2] * q12;
-            Z[m][2] = pr.Jp[m][0] * q02 + pr.Jp[m][1] * q12 + pr.Jp[m][2] * q22;
-        }
-        if (o2 == o) {  // self pair: once per observation -> right-hand side
-            const double g0 = gp[(size_t)p * 3], g1 = gp[(size_t)p * 3 + 1], g2 = gp[(size_t)p * 3 + 2];
-            const double z0 = Z[0][0] * g0 + Z[0][1] * g1 + Z[0][2] * g2, z1 = Z[1][0] * g0 + Z[1][1] * g1 + Z[1][2] * g2;
-#pragma unroll
-            for (int a = 0; a < 6; ++a) acc[36 + a] += pr.Jc[0][a] * z0 + pr.Jc[1][a] * z1;
-        }
-        Proj p2;
-        ba_eval_vals<true, true>(cv_2, Xp, Ks, pb.obs[2 * (size_t)o2], pb.obs[2 * (size_t)o2 + 1], p2);
-        double M[2][2];
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int n_ = 0; n_ < 2; ++n_) M[m][n_] = Z[m][0] * p2.Jp[n_][0] + Z[m][1] * p2.Jp[n_][1] + Z[m][2] * p2.Jp[n_][2];
-#pragma unroll
-        for (int b = 0; b < 6; ++b) {
-            const double t0 = M[0][0] * p2.Jc[0][b] + M[0][1] * p2.Jc[1][b], t1 = M[1][0] * p2.Jc[0][b] + M[1][1] * p2.Jc[1][b];
-#pragma unroll
-            for (int a = 0; a < 6; ++a) acc[a * 6 + b] += pr.Jc[0][a] * t0 + pr.Jc[1][a] * t1;
-        }
-    };
-    const int trips = (e_end - e_begin + 63) / 64;   // wave-uniform
-    for (int k = 0; k < MAXT; ++k) {                 // (rolled: the body is ~450 f64 instructions)
-        if (k >= trips) break;
-        int o = oi[0], o2 = o2i[0], p = pidx[0];
-#pragma unroll
-        for (int q = 1; q < MAXT; ++q)               // select slot k without dynamic register indexing
-            if (q == k) {
-                o = oi[q];
-                o2 = o2i[q];
-                p = pidx[q];
-            }
-        if (o >= 0) {
-            if (p == -2) p = pb.pi[o];
-            pair_body(o, o2, p);
-        }
-    }
-    for (int e = e_begin + lane + 64 * MAXT; e < e_end; e += 64) {   // chunks longer than 256 pairs (other callers)
-        const int o = pb.pair_o[e], o2 = pb.pair_o2[e];
-        pair_body(o, o2, pb.pair_p ? pb.pair_p[e] : pb.pi[o]);
-    }
-    // totals: lane q < 21 holds value q (tot0) and value 21 + q (tot1); values 0..35 = the 6 x 6 block (row-major),
-    // 36..41 = the right-hand side rows of the self segment
-    double tot0, tot1;
-    wave_reduce_42(acc, red[threadIdx.x >> 6], lane, tot0, tot1);
-    // ---- finish the segment: the wave that completes its last chunk writes the block of S (and the rhs rows) ----
-    // One chunk (the common case: ~160 pairs per segment): straight from the registers.  Several chunks: every wave
-    // leaves its partial sums and counts up; the last one adds the partials IN CHUNK ORDER, so the result does not
-    // depend on which wave that was.  Everything another workgroup (or the concurrently running factorisation) reads
-    // goes through write-through stores / cache-bypassing loads, and a producer drains its stores before it counts.
-    const int c_first = pb.seg_chunk_ptr[sidx], n_ch = pb.seg_chunk_ptr[sidx + 1] - c_first;
-    const size_t n = (size_t)pb.F * 6;
-    bool writer = true;
-    if (n_ch > 1) {
-        if (lane < 21) {
-            __hip_atomic_store(partial + (size_t)c * 42 + lane, tot0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(partial + (size_t)c * 42 + 21 + lane, tot1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-        int last = 0;
-        if (lane == 0) last = atomicAdd(seg_done + sidx, 1) == n_ch - 1;
-        writer = __shfl(last, 0, 64) != 0;
-        if (writer && lane < 21) {
-            tot0 = 0.0;
-            tot1 = 0.0;
-            for (int cc = 0; cc < n_ch; ++cc) {
-                tot0 += __hip_atomic_load(partial + (size_t)(c_first + cc) * 42 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                tot1 += __hip_atomic_load(partial + (size_t)(c_first + cc) * 42 + 21 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    }
-    if (!writer) return;
-    if (lane < 21) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int q = 21 * h + lane;
-            const double sum = h == 0 ? tot0 : tot1;
-            if (q < 36) {
-                double val = -sum;
-                if (d == 0) val += Bd[(size_t)i * 36 + q];
-                __hip_atomic_store(S + ((size_t)i * 6 + q / 6) * n + (size_t)f2 * 6 + q % 6, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (d != 0)   // the mirror image: the two-ended factorisation eliminates the last cameras in the upper triangle
-                    __hip_atomic_store(S + ((size_t)f2 * 6 + q % 6) * n + (size_t)i * 6 + q / 6, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else if (d == 0) {
-                __hip_atomic_store(v + (size_t)i * 6 + (q - 36), gc[(size_t)i * 6 + (q - 36)] - sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    }
-    if (slabs.ready) {  // a concurrent consumer waits for whole camera slabs: count finished segments per slab
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-        if (lane == 0) {
-            const int sl = i / slabs.cams_per_slab;
-            if (atomicAdd(slabs.done + sl, 1) == slabs.seg_count[sl] - 1)
-                __hip_atomic_store(slabs.ready + sl, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-
-
-// ---- the lean pair kernel (round 4) ---------------------------------------------------------------------------------------
+// The evaluator ("lean", round 4; the round-3 kernel ran both observations of a pair through the sweeps' full evaluator).
 // S needs the two Jacobians of an observation, not its residual, and both follow from per-CAMERA matrices:
 //   u = P X + q           P = K R (3 x 3), q = K t                       (9 FMA)
 //   Jp[m] = (P[m] - p_m P[2]) / u_2      d proj / d X                    (12)
@@ -481,6 +276,9 @@ __device__ __forceinline__ void schur_pairs_body(const mm_ba_problem pb, const d
     if (threadIdx.x < 9) Ks[threadIdx.x] = pb.K[threadIdx.x];
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    // chunks are ordered by camera; the workgroups take them alternately from the front and from the back, because the
+    // two-ended factorisation that may be consuming S concurrently starts at both ends and needs the middle last
+    // (a build may be cut into several launches: this one covers the positions wg_begin .. of that order)
     const unsigned gpos = bx + wg_begin;
     const unsigned wg = (gpos & 1) ? wg_total - 1 - (gpos >> 1) : (gpos >> 1);
     const int64_t c = (int64_t)wg * SP_WAVES + wv;
@@ -617,9 +415,15 @@ __device__ __forceinline__ void schur_pairs_body(const mm_ba_problem pb, const d
         p_next = p_nn;
         self_next = self_nn;
     }
+    // totals: lane q < 21 holds value q (tot0) and value 21 + q (tot1); values 0..35 = the 6 x 6 block (row-major),
+    // 36..41 = the right-hand side rows of the self segment
     double tot0, tot1;
     wave_reduce_42(acc, red[wv], lane, tot0, tot1);
-    // ---- finish the segment (as in the reference formulation above) ----
+    // ---- finish the segment: the wave that completes its last chunk writes the block of S (and the rhs rows) ----
+    // One chunk (the common case: ~160 pairs per segment): straight from the registers.  Several chunks: every wave
+    // leaves its partial sums and counts up; the last one adds the partials IN CHUNK ORDER, so the result does not
+    // depend on which wave that was.  Everything another workgroup (or the concurrently running factorisation) reads
+    // goes through write-through stores / cache-bypassing loads, and a producer drains its stores before it counts.
     const int c_first = cd.c_first, n_ch = cd.n_ch;
     const size_t n = (size_t)pb.F * 6;
     bool writer = true;
@@ -660,6 +464,7 @@ __device__ __forceinline__ void schur_pairs_body(const mm_ba_problem pb, const d
                 double *mir = S + ((size_t)f2 * 6 + q % 6) * n + (size_t)i * 6 + q / 6;
                 if (through) {
                     __hip_atomic_store(dst, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    // (the mirror image: the two-ended factorisation eliminates the last cameras in the upper triangle)
                     if (d != 0) __hip_atomic_store(mir, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 } else {
                     *dst = val;
@@ -673,7 +478,7 @@ __device__ __forceinline__ void schur_pairs_body(const mm_ba_problem pb, const d
             }
         }
     }
-    if (slabs.ready) {
+    if (slabs.ready) {  // a concurrent consumer waits for whole camera slabs: count finished segments per slab
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
         if (lane == 0) {
@@ -683,8 +488,8 @@ __device__ __forceinline__ void schur_pairs_body(const mm_ba_problem pb, const d
         }
     }
 }
-template <int OCC>      // waves per SIMD the register allocation aims at (2; 3 spills into scratch and is 1.8x slower: measured)
-__global__ __launch_bounds__(64 * SP_WAVES, OCC) void schur_pairs_kernel(mm_ba_problem pb, const double *__restrict__ camtab,
+// launch bound: 2 waves per SIMD for the register allocation to aim at (3 spills into scratch and is 1.8x slower: measured)
+__global__ __launch_bounds__(64 * SP_WAVES, 2) void schur_pairs_kernel(mm_ba_problem pb, const double *__restrict__ camtab,
                                                                     const ChunkDesc *__restrict__ desc,
                                                                     const double *__restrict__ pts,
                                                                     const double *__restrict__ Cinv,
@@ -696,13 +501,6 @@ __global__ __launch_bounds__(64 * SP_WAVES, OCC) void schur_pairs_kernel(mm_ba_p
     schur_pairs_body<false>(pb, camtab, desc, pts, Cinv, gp, partial, Bd, gc, S, v, seg_done, slabs, wg_begin, wg_total, blockIdx.x);
 }
 // batched (mm_ba_trf_batched): blockIdx.y picks the problem
-__global__ __launch_bounds__(256) void zero_batch_kernel(const mm_batch_prob *__restrict__ tab, const int32_t *__restrict__ list) {
-    const mm_batch_prob &bp = tab[list[blockIdx.y]];
-    if (blockIdx.x >= bp.g_zero) return;
-    double2 *S2 = reinterpret_cast<double2 *>(bp.S);      // (nc is even: nc * nc doubles = nc * nc / 2 pairs)
-    const int64_t n2 = bp.nc * bp.nc / 2;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n2; i += (int64_t)bp.g_zero * 256) S2[i] = make_double2(0.0, 0.0);
-}
 __global__ __launch_bounds__(64 * SP_WAVES, 2) void schur_pairs_batch_kernel(const mm_batch_prob *__restrict__ tab, const int32_t *__restrict__ list) {
     const mm_batch_prob &bp = tab[list[blockIdx.y]];
     if (blockIdx.x >= bp.g_pairs) return;
@@ -710,8 +508,6 @@ __global__ __launch_bounds__(64 * SP_WAVES, 2) void schur_pairs_batch_kernel(con
     schur_pairs_body<true>(bp.pb, bp.schur_camtab, (const ChunkDesc *)bp.schur_desc, bp.x + bp.nc, bp.Cinv, bp.g + bp.nc, bp.schur_partial, bp.Bd,
                      bp.g, bp.S, bp.v, bp.schur_seg_done, none, 0u, bp.g_pairs, blockIdx.x);
 }
-
-
 
 // (Round 4, tried and dropped: a PERSISTENT variant of this kernel in which a wave walks a sequence of chunks and requests the
 // next chunks' descriptors, camera tables, point indices and first point / C^-1 while it works on the current one.  It
@@ -722,24 +518,28 @@ __global__ __launch_bounds__(64 * SP_WAVES, 2) void schur_pairs_batch_kernel(con
 // vector memory returns in order, so the first load a trip consumes -- the next index, gp of a self pair -- waits for every
 // prefetch issued before it; the second wave is what hides latency here, not issue order.)
 
-// marks a camera slab without any segment as complete (its rows only hold what schur_diag_fill wrote)
-__global__ void slab_flag_kernel(int32_t *flags, int s) {
-    __hip_atomic_store(flags + s, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+// ---- prepare: everything a build by the pair kernel needs first, in ONE launch -------------------------------------------
+// (the point inverses, the cameras' diagonal fill and the camera table were three launches of a few microseconds each in
+// front of every build).  Workgroup b: the points 256 b .., camera b's diagonal block and right-hand side if it has no
+// observation (such a camera never appears in a segment: they are just (Bd, gc); S has been zero-filled before), the table
+// rows of cameras 256 b .., and its share of the chunk descriptors and of the finished-chunk counters.  The grid is
+// max(ceil(P / 256), F) workgroups: either the points or the cameras run out first.
+__device__ __forceinline__ void write_chunk_desc(const mm_ba_problem &pb, int32_t *__restrict__ desc, int64_t first, int64_t stride) {
+    for (int64_t k = first; k < pb.n_chunks; k += stride) {      // (struct ChunkDesc: 8 int32 per chunk)
+        const int sidx = pb.chunk_seg[k], seg = pb.seg_ids[sidx];
+        const int ci = seg / (pb.cam_span + 1), cdd = seg % (pb.cam_span + 1);
+        const int c_first = pb.seg_chunk_ptr[sidx];
+        int32_t *o = desc + 8 * k;
+        o[0] = ci;
+        o[1] = ci - cdd;
+        o[2] = pb.chunk_begin[k];
+        o[3] = pb.chunk_end[k];
+        o[4] = sidx;
+        o[5] = c_first;
+        o[6] = pb.seg_chunk_ptr[sidx + 1] - c_first;
+        o[7] = 0;
+    }
 }
-
-// cameras without any observation never appear in a segment: their diagonal block / rhs is just (Bd, gc)
-__global__ void schur_diag_fill_kernel(mm_ba_problem pb, const double *__restrict__ Bd, const double *__restrict__ gc,
-                                       double *__restrict__ S, double *__restrict__ v) {
-    const int i = blockIdx.x;
-    if (pb.cam_ptr[i + 1] != pb.cam_ptr[i]) return;
-    const size_t n = (size_t)pb.F * 6;
-    if (threadIdx.x < 36) S[((size_t)i * 6 + threadIdx.x / 6) * n + (size_t)i * 6 + threadIdx.x % 6] = Bd[(size_t)i * 36 + threadIdx.x];
-    if (threadIdx.x < 6) v[(size_t)i * 6 + threadIdx.x] = gc[(size_t)i * 6 + threadIdx.x];
-}
-
-// point_inverse + schur_diag_fill + cam_table in ONE launch (the banded build's three small preparation steps: each was a
-// launch of a few microseconds in front of every build).  Workgroup b: the points 256 b .., camera b's diagonal block if it
-// has no observation, the table rows of cameras 256 b .. (and its share of the finished-chunk counters).
 // What the prepare kernel does on behalf of its neighbours when mm_ba_trf hands the whole reduced solve to
 // mm_ba_schur_solve_damped: the damping (mm_ba_damp's arithmetic, fma(si^2, reg, .) on the diagonals), the zero fill of
 // the band tiles of S, and the fills of the single-launch factorisation.
@@ -753,8 +553,8 @@ __device__ __forceinline__ void schur_prepare_body(mm_ba_problem pb, const doubl
                                                             double *__restrict__ Bd, const double *__restrict__ Cd,
                                                             const double *__restrict__ gc, double *__restrict__ Cinv,
                                                             double *__restrict__ S, double *__restrict__ v,
-                                                            double *__restrict__ tab, int32_t *__restrict__ seg_done, bool lean,
-                                                            int32_t *__restrict__ desc /* [n_chunks][8] or NULL */, const unsigned bx, const unsigned gx,
+                                                            double *__restrict__ tab, int32_t *__restrict__ seg_done,
+                                                            int32_t *__restrict__ desc /* [n_chunks][8]; null: none written */, const unsigned bx, const unsigned gx,
                                                             const PrepExtra *ex = nullptr) {
     const int b = (int)bx, tid = threadIdx.x;
     for (int64_t k = (int64_t)b * 256 + tid; k < pb.n_seg; k += (int64_t)gx * 256) seg_done[k] = 0;
@@ -789,21 +589,7 @@ __device__ __forceinline__ void schur_prepare_body(mm_ba_problem pb, const doubl
         }
     }
     const int f = b * 256 + tid;
-    if (f < pb.F) {
-        const double *c = cams + (size_t)f * 6;
-        if (lean) {
-            cam_table2_row(c, pb.K, tab + (size_t)f * CAMTAB2);
-        } else {
-            const CamCoef k = cam_coef_of(c);
-            double *t = tab + (size_t)f * CAMTAB;
-            for (int q = 0; q < 6; ++q) t[q] = c[q];
-            t[6] = k.c;
-            t[7] = k.a;
-            t[8] = k.b;
-            t[9] = k.a1;
-            t[10] = k.b1;
-        }
-    }
+    if (f < pb.F) cam_table2_row(cams + (size_t)f * 6, pb.K, tab + (size_t)f * CAMTAB2);      // (P, q, J_r: 24 doubles per camera)
     if (b < pb.F) {
         const bool empty = pb.cam_ptr[b + 1] == pb.cam_ptr[b];      // camera b never appears in a segment: (Bd, gc) as they are
         if (tid < 36) {
@@ -841,25 +627,16 @@ __device__ __forceinline__ void schur_prepare_body(mm_ba_problem pb, const doubl
             const double *c = Cd + (size_t)p * 6;
             a = c[0], bq = c[1], d = c[2], e = c[3], ff = c[4], g = c[5];
         }
-        const double m00 = e * g - ff * ff, m01 = d * ff - bq * g, m02 = bq * ff - d * e;
-        const double det = a * m00 + bq * m01 + d * m02;
-        const double id = 1.0 / det;
-        double *o = Cinv + (size_t)p * 6;
-        o[0] = m00 * id;
-        o[1] = m01 * id;
-        o[2] = m02 * id;
-        o[3] = (a * g - d * d) * id;
-        o[4] = (bq * d - a * ff) * id;
-        o[5] = (a * e - bq * bq) * id;
+        sym3_inverse(a, bq, d, e, ff, g, Cinv + (size_t)p * 6);
     }
 }
 __global__ __launch_bounds__(256) void schur_prepare_kernel(mm_ba_problem pb, const double *__restrict__ cams,
                                                             double *__restrict__ Bd, const double *__restrict__ Cd,
                                                             const double *__restrict__ gc, double *__restrict__ Cinv,
                                                             double *__restrict__ S, double *__restrict__ v,
-                                                            double *__restrict__ tab, int32_t *__restrict__ seg_done, bool lean,
+                                                            double *__restrict__ tab, int32_t *__restrict__ seg_done,
                                                             int32_t *__restrict__ desc) {
-    schur_prepare_body(pb, cams, Bd, Cd, gc, Cinv, S, v, tab, seg_done, lean, desc, blockIdx.x, gridDim.x);
+    schur_prepare_body(pb, cams, Bd, Cd, gc, Cinv, S, v, tab, seg_done, desc, blockIdx.x, gridDim.x);
 }
 __global__ __launch_bounds__(256) void schur_prepare_damped_kernel(mm_ba_problem pb, const double *__restrict__ cams,
                                                                    double *__restrict__ Bd, const double *__restrict__ gc,
@@ -867,15 +644,27 @@ __global__ __launch_bounds__(256) void schur_prepare_damped_kernel(mm_ba_problem
                                                                    double *__restrict__ v, double *__restrict__ tab,
                                                                    int32_t *__restrict__ seg_done, int32_t *__restrict__ desc,
                                                                    PrepExtra ex) {
-    schur_prepare_body(pb, cams, Bd, nullptr, gc, Cinv, S, v, tab, seg_done, true, desc, blockIdx.x, gridDim.x, &ex);
+    schur_prepare_body(pb, cams, Bd, nullptr, gc, Cinv, S, v, tab, seg_done, desc, blockIdx.x, gridDim.x, &ex);
+}
+// batched (mm_ba_trf_batched): blockIdx.y picks the problem; S is zero-filled by a launch of its own
+__global__ __launch_bounds__(256) void zero_batch_kernel(const mm_batch_prob *__restrict__ tab, const int32_t *__restrict__ list) {
+    const mm_batch_prob &bp = tab[list[blockIdx.y]];
+    if (blockIdx.x >= bp.g_zero) return;
+    double2 *S2 = reinterpret_cast<double2 *>(bp.S);      // (nc is even: nc * nc doubles = nc * nc / 2 pairs)
+    const int64_t n2 = bp.nc * bp.nc / 2;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n2; i += (int64_t)bp.g_zero * 256) S2[i] = make_double2(0.0, 0.0);
 }
 __global__ __launch_bounds__(256) void schur_prepare_batch_kernel(const mm_batch_prob *__restrict__ tab, const int32_t *__restrict__ list) {
     const mm_batch_prob &bp = tab[list[blockIdx.y]];
     if (blockIdx.x >= bp.g_prep) return;
-    schur_prepare_body(bp.pb, bp.x, bp.Bd, bp.Cd, bp.g, bp.Cinv, bp.S, bp.v, bp.schur_camtab, bp.schur_seg_done, true, bp.schur_desc,
+    schur_prepare_body(bp.pb, bp.x, bp.Bd, bp.Cd, bp.g, bp.Cinv, bp.S, bp.v, bp.schur_camtab, bp.schur_seg_done, bp.schur_desc,
                        blockIdx.x, bp.g_prep);
 }
 
+// marks a camera slab without any segment as complete (its rows only hold what the prepare launch wrote)
+__global__ void slab_flag_kernel(int32_t *flags, int s) {
+    __hip_atomic_store(flags + s, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+}
 
 // ---- device-side construction of the co-observation pair list ------------------------------------------------------
 // cnt[o] = number of observations o2 of the same point with camera(o2) <= camera(o); span = max camera distance.
@@ -942,53 +731,69 @@ extern "C" int mm_ba_pairs_emit(mm_ctx *ctx, const mm_ba_problem *pb, const int6
     return MM_OK;
 }
 
-extern "C" size_t mm_ba_schur_workspace_bytes(const mm_ba_problem *pb) {
-    if (!pb || pb->n_chunks <= 0) return 0;
-    return mm_align_up((size_t)pb->n_chunks * 42 * sizeof(double), 256) /* partial sums of multi-chunk segments */ +
-           mm_align_up((size_t)pb->n_seg * sizeof(int32_t), 256) /* finished-chunk counters */ +
-           mm_align_up(2 * MAX_SLABS * sizeof(int32_t), 256) /* slab flags, slab counters */ +
-           mm_align_up((size_t)pb->F * CAMTAB2 * sizeof(double), 256) /* per-camera table */ +
-           mm_align_up((size_t)pb->n_chunks * 32, 256) /* per-chunk descriptors */;
-}
-
+// ---- plan and entry points ----------------------------------------------------------------------------------------------
 namespace {
-// MM_SCHUR_PAIRS=ref: the round-3 pair kernel (full evaluator per observation, index chain); default: the lean one
-bool schur_pairs_lean() {
-    static const bool lean = [] {
-        const char *e = getenv("MM_SCHUR_PAIRS");
-        return !(e && e[0] == 'r');
-    }();
-    return lean;
-}
-#define MM_LAUNCH_PAIRS(ctx, grid, pbv, camtab_, desc_, ...)                                                             \
-    do {                                                                                                                 \
-        if (schur_pairs_lean())                                                                                          \
-            MM_LAUNCH(ctx, "schur_pairs_kernel", schur_pairs_kernel<2>, grid, dim3(64 * SP_WAVES), 0, pbv, camtab_,      \
-                      (const ChunkDesc *)(desc_), __VA_ARGS__);                                                          \
-        else                                                                                                             \
-            MM_LAUNCH(ctx, "schur_pairs_ref_kernel", schur_pairs_ref_kernel, grid, dim3(64 * SP_WAVES), 0, pbv, camtab_, \
-                      __VA_ARGS__);                                                                                      \
-    } while (0)
 struct SchurWs {
-    double *partial, *camtab;
-    int32_t *seg_done, *slab_ready, *slab_done, *desc;
+    double *partial;        // [n_chunks][42] partial sums of multi-chunk segments
+    int32_t *seg_done;      // [n_seg] finished-chunk counters
+    int32_t *slab_ready;    // [MAX_SLABS] slab flags, and behind them
+    int32_t *slab_done;     // [MAX_SLABS] slab counters
+    double *camtab;         // [F][CAMTAB2] per-camera table
+    int32_t *desc;          // [n_chunks][8] per-chunk descriptors
 };
-SchurWs carve_schur_ws(const mm_ba_problem *pb, void *ws) {
-    SchurWs w;
-    char *p = (char *)ws;
-    w.partial = (double *)p;
-    p += mm_align_up((size_t)pb->n_chunks * 42 * sizeof(double), 256);
-    w.seg_done = (int32_t *)p;
-    p += mm_align_up((size_t)pb->n_seg * sizeof(int32_t), 256);
-    w.slab_ready = (int32_t *)p;
+// THE layout of the workspace: points w into base (null: sizes only) and returns the bytes it takes
+size_t carve_schur_ws(SchurWs &w, char *base, const mm_ba_problem *pb) {
+    size_t off = 0;
+    auto take = [&](auto *&p, size_t n) {
+        using T = std::remove_reference_t<decltype(*p)>;
+        p = reinterpret_cast<T *>(base + off);
+        off += mm_align_up(n * sizeof(T), 256);
+    };
+    take(w.partial, (size_t)pb->n_chunks * 42);
+    take(w.seg_done, (size_t)pb->n_seg);
+    take(w.slab_ready, 2 * MAX_SLABS);
     w.slab_done = w.slab_ready + MAX_SLABS;
-    p += mm_align_up(2 * MAX_SLABS * sizeof(int32_t), 256);
-    w.camtab = (double *)p;
-    p += mm_align_up((size_t)pb->F * CAMTAB2 * sizeof(double), 256);
-    w.desc = (int32_t *)p;
-    return w;
+    take(w.camtab, (size_t)pb->F * CAMTAB2);
+    take(w.desc, (size_t)pb->n_chunks * 8);
+    return off;
+}
+// What every entry point asks about a problem, computed once per call.
+struct SchurPlan {
+    bool pairs;             // a complete co-observation pair list is present: prepare + pair kernel (else the general kernel)
+    unsigned g_prep;        // workgroups of the prepare launch: max(ceil(P / 256), F)
+    unsigned g_pairs;       // workgroups of the pair kernel: ceil(n_chunks / SP_WAVES)
+    size_t ws_bytes;        // workspace the pair path needs
+    SchurWs ws;             // ... carved out of the caller's
+};
+SchurPlan schur_plan(const mm_ba_problem *pb, void *ws) {
+    SchurPlan pl;
+    pl.pairs = pb->n_seg > 0 && pb->n_chunks > 0 && pb->seg_ids && pb->seg_chunk_ptr && pb->chunk_seg && pb->chunk_begin &&
+               pb->chunk_end && pb->pair_o && pb->pair_o2;
+    pl.g_prep = (unsigned)((pb->P + 255) / 256 > pb->F ? (pb->P + 255) / 256 : pb->F);
+    pl.g_pairs = (unsigned)((pb->n_chunks + SP_WAVES - 1) / SP_WAVES);
+    pl.ws_bytes = carve_schur_ws(pl.ws, (char *)ws, pb);
+    return pl;
+}
+int launch_prepare(mm_ctx *ctx, const mm_ba_problem *pb, const SchurPlan &pl, const double *cams, const double *Bd, const double *Cd,
+                   const double *gc, double *Cinv, double *S, double *v) {
+    // (Bd is only written by the damped form of the kernel)
+    MM_LAUNCH(ctx, "schur_prepare_kernel", schur_prepare_kernel, dim3(pl.g_prep), dim3(256), 0, *pb, cams, const_cast<double *>(Bd), Cd, gc,
+              Cinv, S, v, pl.ws.camtab, pl.ws.seg_done, pl.ws.desc);
+    return MM_OK;
+}
+// wg_count workgroups of the build's front / back order from position wg_begin on (the whole build: 0, pl.g_pairs)
+int launch_pairs(mm_ctx *ctx, const mm_ba_problem *pb, const SchurPlan &pl, const double *pts, const double *Cinv, const double *gp,
+                 const double *Bd, const double *gc, double *S, double *v, const SlabSync &slabs, unsigned wg_begin, unsigned wg_count) {
+    MM_LAUNCH(ctx, "schur_pairs_kernel", schur_pairs_kernel, dim3(wg_count), dim3(64 * SP_WAVES), 0, *pb, (const double *)pl.ws.camtab,
+              (const ChunkDesc *)pl.ws.desc, pts, Cinv, gp, pl.ws.partial, Bd, gc, S, v, pl.ws.seg_done, slabs, wg_begin, pl.g_pairs);
+    return MM_OK;
 }
 }  // namespace
+
+extern "C" size_t mm_ba_schur_workspace_bytes(const mm_ba_problem *pb) {
+    if (!pb || pb->n_chunks <= 0) return 0;
+    return schur_plan(pb, nullptr).ws_bytes;
+}
 
 extern "C" int mm_ba_schur(mm_ctx *ctx, const mm_ba_problem *pb, const double *cams, const double *pts,
                            const double *Bd, const double *Cd, const double *gc, const double *gp, double *S, double *v,
@@ -999,20 +804,13 @@ extern "C" int mm_ba_schur(mm_ctx *ctx, const mm_ba_problem *pb, const double *c
         (pb->O > 0 && (!pb->pt_obs || !pb->cam_obs || !pb->fi || !pb->pi || !pb->obs)))
         return mm_fail(ctx, MM_ERR_ARG, "mm_ba_schur: null pointer");
     if (pb->F == 0) return MM_OK;
-    if (pb->n_seg > 0 && pb->n_chunks > 0 && pb->seg_ids && pb->seg_chunk_ptr && pb->chunk_seg && pb->chunk_begin &&
-        pb->chunk_end && pb->pair_o && pb->pair_o2) {
-        if (!ws || ws_bytes < mm_ba_schur_workspace_bytes(pb)) return mm_fail(ctx, MM_ERR_WORKSPACE, "mm_ba_schur: workspace too small");
-        // banded + deterministic: zero S (the Cholesky touches whole 64-blocks of the band), then the lower blocks
+    const SchurPlan pl = schur_plan(pb, ws);
+    if (pl.pairs) {
+        if (!ws || ws_bytes < pl.ws_bytes) return mm_fail(ctx, MM_ERR_WORKSPACE, "mm_ba_schur: workspace too small");
+        // banded + deterministic: zero S (the Cholesky touches whole 64-blocks of the band), then the blocks of the band
         MM_HIP(ctx, hipMemsetAsync(S, 0, (size_t)pb->F * 6 * pb->F * 6 * sizeof(double), ctx->stream));
-        const int64_t wgs = (pb->n_chunks + SP_WAVES - 1) / SP_WAVES;
-        const SchurWs w = carve_schur_ws(pb, ws);
-        SlabSync none = {};
-        const int prep = (pb->P + 255) / 256 > pb->F ? (pb->P + 255) / 256 : pb->F;
-        MM_LAUNCH(ctx, "schur_prepare_kernel", schur_prepare_kernel, dim3(prep), dim3(256), 0, *pb, cams, const_cast<double *>(Bd), Cd, gc,
-                  Cinv, S, v, w.camtab, w.seg_done, schur_pairs_lean(), schur_pairs_lean() ? w.desc : (int32_t *)nullptr);
-        MM_LAUNCH_PAIRS(ctx, dim3((unsigned)wgs), *pb, (const double *)w.camtab, w.desc, pts, (const double *)Cinv, gp, w.partial, Bd, gc, S, v,
-                        w.seg_done, none, 0u, (unsigned)wgs);
-        return MM_OK;
+        if (int rc = launch_prepare(ctx, pb, pl, cams, Bd, Cd, gc, Cinv, S, v)) return rc;
+        return launch_pairs(ctx, pb, pl, pts, Cinv, gp, Bd, gc, S, v, SlabSync{}, 0u, pl.g_pairs);
     }
     if (pb->P > 0)
         MM_LAUNCH(ctx, "point_inverse_kernel", point_inverse_kernel, dim3((pb->P + 255) / 256), dim3(256), 0, pb->P, Cd,
@@ -1036,9 +834,10 @@ extern "C" int mm_ba_schur_solve(mm_ctx *ctx, const mm_ba_problem *pb, const dou
     if (!ctx) return MM_ERR_ARG;
     if (!pb || !info) return mm_fail(ctx, MM_ERR_ARG, "mm_ba_schur_solve: bad argument");
     const int n = pb->F * 6;
-    const bool pairs_ok = pb->n_seg > 0 && pb->n_chunks > 0 && pb->seg_ids && pb->seg_chunk_ptr && pb->chunk_seg &&
-                          pb->chunk_begin && pb->chunk_end && pb->pair_o && pb->pair_o2;
-    const bool overlap = pairs_ok && n_slabs >= 2 && n_slabs <= MAX_SLABS && cams_per_slab >= 16 && slab_seg_ptr &&
+    const SchurPlan pl = schur_plan(pb, ws_schur);
+    // overlapped: slabs are ranges of the pair list's segments (2 .. MAX_SLABS of them, 16 cameras or more each: what the
+    // gated factorisation waits on), the band must be one the single-launch factorisation takes, and there are points
+    const bool overlap = pl.pairs && n_slabs >= 2 && n_slabs <= MAX_SLABS && cams_per_slab >= 16 && slab_seg_ptr &&
                          slab_chunk_ptr && mm_chol_fused_eligible(n, half_bandwidth) && pb->P > 0;
     if (!overlap) {
         int rc = mm_ba_schur(ctx, pb, cams, pts, Bd, Cd, gc, gp, S, v, Cinv, ws_schur, ws_schur_bytes);
@@ -1047,7 +846,7 @@ extern "C" int mm_ba_schur_solve(mm_ctx *ctx, const mm_ba_problem *pb, const dou
         return mm_chol_solve_sym(ctx, S, n, v, half_bandwidth, 1, info, ws_chol, ws_chol_bytes);
     }
     if (!cams || !pts || !Bd || !Cd || !gc || !gp || !S || !v || !Cinv) return mm_fail(ctx, MM_ERR_ARG, "mm_ba_schur_solve: null pointer");
-    if (!ws_schur || ws_schur_bytes < mm_ba_schur_workspace_bytes(pb)) return mm_fail(ctx, MM_ERR_WORKSPACE, "mm_ba_schur_solve: workspace too small");
+    if (!ws_schur || ws_schur_bytes < pl.ws_bytes) return mm_fail(ctx, MM_ERR_WORKSPACE, "mm_ba_schur_solve: workspace too small");
     if (slab_seg_ptr[0] != 0 || slab_seg_ptr[n_slabs] != pb->n_seg || slab_chunk_ptr[0] != 0 || slab_chunk_ptr[n_slabs] != pb->n_chunks ||
         (int64_t)n_slabs * cams_per_slab < pb->F)
         return mm_fail(ctx, MM_ERR_ARG, "mm_ba_schur_solve: slab tables do not cover the problem");
@@ -1058,36 +857,30 @@ extern "C" int mm_ba_schur_solve(mm_ctx *ctx, const mm_ba_problem *pb, const dou
         MM_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
         MM_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
     }
-    const SchurWs w = carve_schur_ws(pb, ws_schur);
-    MM_LAUNCH(ctx, "point_inverse_kernel", point_inverse_kernel, dim3((pb->P + 255) / 256), dim3(256), 0, pb->P, Cd, Cinv);
     SlabSync slabs = {};
-    slabs.ready = w.slab_ready;
-    slabs.done = w.slab_done;
+    slabs.ready = pl.ws.slab_ready;
+    slabs.done = pl.ws.slab_done;
     slabs.cams_per_slab = cams_per_slab;
     for (int sl = 0; sl < n_slabs; ++sl) slabs.seg_count[sl] = (int32_t)(slab_seg_ptr[sl + 1] - slab_seg_ptr[sl]);
-    MM_LAUNCH(ctx, "cam_table_kernel", cam_table_kernel, dim3((pb->F + 63) / 64), dim3(64), 0, pb->F, cams, w.camtab, w.seg_done,
-              (int64_t)pb->n_seg, schur_pairs_lean() ? pb->K : (const double *)nullptr, *pb,
-              schur_pairs_lean() ? w.desc : (int32_t *)nullptr);
+    // the zero fill of S in front of the prepare launch, which writes the diagonal blocks of cameras without observations
     MM_HIP(ctx, hipMemsetAsync(S, 0, (size_t)n * n * sizeof(double), ctx->stream));
-    MM_HIP(ctx, hipMemsetAsync(w.slab_ready, 0, 2 * MAX_SLABS * sizeof(int32_t), ctx->stream));
-    MM_LAUNCH(ctx, "schur_diag_fill_kernel", schur_diag_fill_kernel, dim3(pb->F), dim3(64), 0, *pb, Bd, gc, S, v);
+    MM_HIP(ctx, hipMemsetAsync(pl.ws.slab_ready, 0, 2 * MAX_SLABS * sizeof(int32_t), ctx->stream));
+    if (int rc = launch_prepare(ctx, pb, pl, cams, Bd, Cd, gc, Cinv, S, v)) return rc;
     for (int sl = 0; sl < n_slabs; ++sl)   // a slab without any segment is complete as it is
-        if (slabs.seg_count[sl] == 0) MM_LAUNCH(ctx, "slab_flag_kernel", slab_flag_kernel, dim3(1), dim3(1), 0, w.slab_ready, sl);
+        if (slabs.seg_count[sl] == 0) MM_LAUNCH(ctx, "slab_flag_kernel", slab_flag_kernel, dim3(1), dim3(1), 0, pl.ws.slab_ready, sl);
     // The build is ONE ordered list of chunks taken alternately from the front and the back (the two-ended factorisation
     // needs the outer cameras first, the middle last), cut into two launches: the first half runs alone at full speed;
     // the factorisation -- whose workgroups use the whole register file of their CUs, so no wave of the build fits
     // beside them -- starts behind it on a second stream and shares the chip with the second half only, consuming
     // block rows as their slabs are flagged complete.
-    const unsigned wg_total = (unsigned)((pb->n_chunks + SP_WAVES - 1) / SP_WAVES);
-    const unsigned wg_first = wg_total / 2;
+    const unsigned wg_first = pl.g_pairs / 2;
     if (wg_first > 0)
-        MM_LAUNCH_PAIRS(ctx, dim3(wg_first), *pb, (const double *)w.camtab, w.desc, pts, (const double *)Cinv, gp, w.partial, Bd, gc, S, v,
-                        w.seg_done, slabs, 0u, wg_total);
+        if (int rc = launch_pairs(ctx, pb, pl, pts, Cinv, gp, Bd, gc, S, v, slabs, 0u, wg_first)) return rc;
     MM_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
     MM_HIP(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
     {
         mm_stream_swap sw(ctx, ctx->aux);
-        int rc = mm_chol_solve_gated(ctx, S, n, v, 1, half_bandwidth, info, ws_chol, ws_chol_bytes, w.slab_ready, cams_per_slab, pb->F, 2);
+        int rc = mm_chol_solve_gated(ctx, S, n, v, 1, half_bandwidth, info, ws_chol, ws_chol_bytes, pl.ws.slab_ready, cams_per_slab, pb->F, 2);
         if (rc) {  // whatever did get enqueued on the second stream is joined before the error travels up
             (void)hipEventRecord(ctx->ev_join, ctx->aux);
             (void)hipStreamWaitEvent(sw.saved, ctx->ev_join, 0);
@@ -1095,8 +888,7 @@ extern "C" int mm_ba_schur_solve(mm_ctx *ctx, const mm_ba_problem *pb, const dou
         }
         MM_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->aux));
     }
-    MM_LAUNCH_PAIRS(ctx, dim3(wg_total - wg_first), *pb, (const double *)w.camtab, w.desc, pts, (const double *)Cinv, gp, w.partial, Bd, gc, S, v,
-                    w.seg_done, slabs, wg_first, wg_total);
+    if (int rc = launch_pairs(ctx, pb, pl, pts, Cinv, gp, Bd, gc, S, v, slabs, wg_first, pl.g_pairs - wg_first)) return rc;
     MM_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
     return MM_OK;
 }
@@ -1114,9 +906,11 @@ int mm_ba_schur_solve_damped(mm_ctx *ctx, const mm_ba_problem *pb, const double 
     static const bool off = [] { const char *e = getenv("MM_SCHUR_FOLD"); return e && atoi(e) == 0; }();
     mm_chol_init_args ia = {};
     int sides = 0, bwb = 0;
-    const bool pairs_ok = pb->n_seg > 0 && pb->n_chunks > 0 && pb->seg_ids && pb->seg_chunk_ptr && pb->chunk_seg && pb->chunk_begin &&
-                          pb->chunk_end && pb->pair_o && pb->pair_o2 && pb->P > 0 && schur_pairs_lean();
-    const bool fold = !off && pairs_ok && ws_schur && ws_schur_bytes >= mm_ba_schur_workspace_bytes(pb) &&
+    const SchurPlan pl = schur_plan(pb, ws_schur);
+    // folded: not switched off (MM_SCHUR_FOLD=0), a pair list and points (the prepare launch is what carries the extras), a
+    // workspace for it (too small a one is left to the separate calls to report), and a factorisation whose fills can be
+    // planned ahead (mm_chol_init_plan: the single-launch one)
+    const bool fold = !off && pl.pairs && pb->P > 0 && ws_schur && ws_schur_bytes >= pl.ws_bytes &&
                       mm_chol_init_plan(ctx, n, half_bandwidth, info, ws_chol, ws_chol_bytes, &ia, &sides, &bwb);
     if (!fold) {
         if (!Cd) return mm_fail(ctx, MM_ERR_ARG, "mm_ba_schur_solve_damped: the separate calls need Cd");
@@ -1127,39 +921,35 @@ int mm_ba_schur_solve_damped(mm_ctx *ctx, const mm_ba_problem *pb, const double 
         return mm_ba_schur_solve(ctx, pb, cams, pts, Bd, Cd, gc, gp, S, v, Cinv, half_bandwidth, info, ws_schur, ws_schur_bytes, ws_chol,
                                  ws_chol_bytes, 0, 0, nullptr, nullptr);
     }
-    const SchurWs w = carve_schur_ws(pb, ws_schur);
     PrepExtra ex = {};
     ex.dmp = *dmp;
     ex.zero_bwb = bwb;
     ex.chol_init = 1;
     ex.init = ia;
-    const int prep = (pb->P + 255) / 256 > pb->F ? (pb->P + 255) / 256 : pb->F;
-    MM_LAUNCH(ctx, "schur_prepare_kernel", schur_prepare_damped_kernel, dim3(prep), dim3(256), 0, *pb, cams, Bd, gc, Cinv, S, v, w.camtab,
-              w.seg_done, w.desc, ex);
-    const int64_t wgs = (pb->n_chunks + SP_WAVES - 1) / SP_WAVES;
-    SlabSync none = {};
-    MM_LAUNCH_PAIRS(ctx, dim3((unsigned)wgs), *pb, (const double *)w.camtab, w.desc, pts, (const double *)Cinv, gp, w.partial,
-                    (const double *)Bd, gc, S, v, w.seg_done, none, 0u, (unsigned)wgs);
+    MM_LAUNCH(ctx, "schur_prepare_kernel", schur_prepare_damped_kernel, dim3(pl.g_prep), dim3(256), 0, *pb, cams, Bd, gc, Cinv, S, v,
+              pl.ws.camtab, pl.ws.seg_done, pl.ws.desc, ex);
+    if (int rc = launch_pairs(ctx, pb, pl, pts, Cinv, gp, Bd, gc, S, v, SlabSync{}, 0u, pl.g_pairs)) return rc;
     mm_chol_init_done(ctx, ws_chol, sides);
     const int rc = mm_chol_solve_sym(ctx, S, n, v, half_bandwidth, 1, info, ws_chol, ws_chol_bytes);
     mm_chol_init_done(ctx, nullptr, 0);
     return rc;
 }
 
-// ---- batched build of the reduced camera systems (mm_ba_trf_batched, trf.hip) ------------------------------------------------
+// batched build of the reduced camera systems (mm_ba_trf_batched, trf.hip)
 int mm_batch_schur_setup(mm_ctx *ctx, mm_batch_prob *bp, void *ws_schur, size_t ws_schur_bytes) {
     const mm_ba_problem *pb = &bp->pb;
-    if (!(pb->n_seg > 0 && pb->n_chunks > 0 && pb->seg_ids && pb->seg_chunk_ptr && pb->chunk_seg && pb->chunk_begin && pb->chunk_end &&
-          pb->pair_o && pb->pair_o2 && pb->pair_p) || pb->P <= 0)
+    const SchurPlan pl = schur_plan(pb, ws_schur);
+    // the batch has the pair kernel only (no general path to fall back on), and asks for the pairs' point indices (pair_p)
+    // and for points, as both index builders of ops.BADevice provide them
+    if (!(pl.pairs && pb->pair_p) || pb->P <= 0)
         return mm_fail(ctx, MM_ERR_ARG, "mm_ba_trf_batched: a problem without a co-observation pair list");
-    if (!ws_schur || ws_schur_bytes < mm_ba_schur_workspace_bytes(pb)) return mm_fail(ctx, MM_ERR_WORKSPACE, "mm_ba_trf_batched: Schur workspace");
-    const SchurWs w = carve_schur_ws(pb, ws_schur);
-    bp->schur_partial = w.partial;
-    bp->schur_camtab = w.camtab;
-    bp->schur_seg_done = w.seg_done;
-    bp->schur_desc = w.desc;
-    bp->g_prep = (uint32_t)((pb->P + 255) / 256 > pb->F ? (pb->P + 255) / 256 : pb->F);
-    bp->g_pairs = (uint32_t)((pb->n_chunks + SP_WAVES - 1) / SP_WAVES);
+    if (!ws_schur || ws_schur_bytes < pl.ws_bytes) return mm_fail(ctx, MM_ERR_WORKSPACE, "mm_ba_trf_batched: Schur workspace");
+    bp->schur_partial = pl.ws.partial;
+    bp->schur_camtab = pl.ws.camtab;
+    bp->schur_seg_done = pl.ws.seg_done;
+    bp->schur_desc = pl.ws.desc;
+    bp->g_prep = pl.g_prep;
+    bp->g_pairs = pl.g_pairs;
     const int64_t n2 = bp->nc * bp->nc / 2;
     const int64_t gz = (n2 + 2047) / 2048;
     bp->g_zero = (uint32_t)(gz < 1 ? 1 : (gz > 1024 ? 1024 : gz));
@@ -1173,3 +963,4 @@ int mm_batch_schur(mm_ctx *ctx, const mm_batch_prob *tab, const int32_t *list, i
     MM_LAUNCH(ctx, "schur_pairs_kernel", schur_pairs_batch_kernel, dim3(max_g_pairs, (unsigned)n_list), dim3(64 * SP_WAVES), 0, tab, list);
     return MM_OK;
 }
+

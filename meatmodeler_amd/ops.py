@@ -758,6 +758,19 @@ class BADevice:
             self._slabs = (n_slabs, cps, np.ascontiguousarray(sseg.cpu().numpy(), np.int64),
                            np.ascontiguousarray(schunk.cpu().numpy(), np.int64))
 
+    def _set_pair_list(self, pair_o, pair_o2, pair_p, seg_ids, seg_chunk_ptr, chunk_seg, chunk_begin, chunk_end):
+        """Keeps the co-observation pair list (int32 device tensors, whichever builder made them) and points the problem
+        descriptor at it."""
+        self.pair_o, self.pair_o2, self.pair_p = pair_o, pair_o2, pair_p
+        self.seg_ids, self.seg_chunk_ptr = seg_ids, seg_chunk_ptr
+        self.chunk_seg, self.chunk_begin, self.chunk_end = chunk_seg, chunk_begin, chunk_end
+        self.n_pairs = int(pair_o.numel())
+        self.pb.n_seg = int(seg_ids.numel())
+        self.pb.n_chunks = int(chunk_seg.numel())
+        self.pb.seg_ids, self.pb.seg_chunk_ptr = ptr(seg_ids), ptr(seg_chunk_ptr)
+        self.pb.chunk_seg, self.pb.chunk_begin, self.pb.chunk_end = ptr(chunk_seg), ptr(chunk_begin), ptr(chunk_end)
+        self.pb.pair_o, self.pb.pair_o2, self.pb.pair_p = ptr(pair_o), ptr(pair_o2), ptr(pair_p)
+
     def _build_index_native(self, pairs):
         """mm_ba_index_build.  -> False (nothing set) when the observations are not point-major."""
         F, P, O, dev = self.F, self.P, self.O, self.device
@@ -802,15 +815,8 @@ class BADevice:
             ws1 = torch.empty(ws1b, dtype=torch.uint8, device=dev)
             self.ctx.check(lib.mm_ba_index_build(self.ctx.h, C.byref(ix), 1, ptr(ws0), ws0b, ptr(ws1), ws1b), "mm_ba_index_build")
             n_seg, n_chunks = head[4:6].tolist()      # read-back 2 of 2 (the workspaces are free to go after it)
-            self.pair_o, self.pair_o2, self.pair_p = pair_o, pair_o2, pair_p
-            self.seg_ids, self.seg_chunk_ptr = seg_ids[:n_seg], seg_chunk_ptr[:n_seg + 1]
-            self.chunk_seg, self.chunk_begin, self.chunk_end = chunk_seg[:n_chunks], chunk_begin[:n_chunks], chunk_end[:n_chunks]
-            self.n_pairs = n
-            self.pb.n_seg = n_seg
-            self.pb.n_chunks = n_chunks
-            self.pb.seg_ids, self.pb.seg_chunk_ptr = ptr(self.seg_ids), ptr(self.seg_chunk_ptr)
-            self.pb.chunk_seg, self.pb.chunk_begin, self.pb.chunk_end = ptr(self.chunk_seg), ptr(self.chunk_begin), ptr(self.chunk_end)
-            self.pb.pair_o, self.pb.pair_o2, self.pb.pair_p = ptr(self.pair_o), ptr(self.pair_o2), ptr(self.pair_p)
+            self._set_pair_list(pair_o, pair_o2, pair_p, seg_ids[:n_seg], seg_chunk_ptr[:n_seg + 1], chunk_seg[:n_chunks],
+                                chunk_begin[:n_chunks], chunk_end[:n_chunks])
             self._slab_src = (self.seg_ids, self.seg_chunk_ptr)
         return True
 
@@ -884,10 +890,10 @@ class BADevice:
                 self.ctx.check(lib.mm_ba_pairs_emit(self.ctx.h, C.byref(pair_pb), ptr(offs_ex), self.cam_span, ptr(key),
                                                     ptr(po), ptr(po2)), "mm_ba_pairs_emit")
                 key_s, perm = torch.sort(key, stable=True)          # fixed order inside every segment
-                self.pair_o, self.pair_o2 = po[perm].contiguous(), po2[perm].contiguous()
+                pair_o, pair_o2 = po[perm].contiguous(), po2[perm].contiguous()
                 if free_idx is not None:
-                    self.pair_o = free_idx[self.pair_o.long()].to(torch.int32).contiguous()
-                    self.pair_o2 = free_idx[self.pair_o2.long()].to(torch.int32).contiguous()
+                    pair_o = free_idx[pair_o.long()].to(torch.int32).contiguous()
+                    pair_o2 = free_idx[pair_o2.long()].to(torch.int32).contiguous()
                 seg_ids, counts = torch.unique_consecutive(key_s, return_counts=True)
                 seg_hi = torch.cumsum(counts, 0)
                 seg_lo = seg_hi - counts
@@ -900,17 +906,9 @@ class BADevice:
                 chunk_begin = seg_lo[chunk_seg] + CH * (torch.arange(nchunks, **i64) - first[chunk_seg])
                 chunk_end = torch.minimum(chunk_begin + CH, seg_hi[chunk_seg])
                 i32 = lambda t: t.to(torch.int32).contiguous()
-                self.seg_ids = i32(seg_ids)
-                self.seg_chunk_ptr = i32(torch.cat([first, first_hi[-1:]]))
-                self.chunk_seg, self.chunk_begin, self.chunk_end = i32(chunk_seg), i32(chunk_begin), i32(chunk_end)
-                self.n_pairs = int(n)
-                self.pb.n_seg = len(seg_ids)
-                self.pb.n_chunks = nchunks
-                self.pb.seg_ids, self.pb.seg_chunk_ptr = ptr(self.seg_ids), ptr(self.seg_chunk_ptr)
-                self.pb.chunk_seg, self.pb.chunk_begin, self.pb.chunk_end = ptr(self.chunk_seg), ptr(self.chunk_begin), ptr(self.chunk_end)
-                self.pb.pair_o, self.pb.pair_o2 = ptr(self.pair_o), ptr(self.pair_o2)
-                self.pair_p = self.pi[self.pair_o.long()].contiguous()   # saves the pair kernel a dependent gather
-                self.pb.pair_p = ptr(self.pair_p)
+                pair_p = self.pi[pair_o.long()].contiguous()   # saves the pair kernel a dependent gather
+                self._set_pair_list(pair_o, pair_o2, pair_p, i32(seg_ids), i32(torch.cat([first, first_hi[-1:]])), i32(chunk_seg),
+                                    i32(chunk_begin), i32(chunk_end))
                 self._set_slabs(seg_ids.to(torch.int64), torch.cat([first, first_hi[-1:]]))
 
     def residual(self, cams, pts, want_res=False, cost_out=None):
@@ -985,14 +983,9 @@ class BADevice:
         (deterministically) and the rest of S is zero; otherwise all of S is filled."""
         self._no_fixed("schur")
         n = 6 * self.F
-        if self._S is None:
-            self._alloc_S(n)
-        S = self._S
+        S = self._schur_buffers(n)
         v = torch.empty(n, dtype=torch.float64, device=self.device)
         Cinv = torch.empty((self.P, 6), dtype=torch.float64, device=self.device)
-        if self._schur_ws is None:
-            nb = lib.mm_ba_schur_workspace_bytes(C.byref(self.pb))
-            self._schur_ws = torch.empty(max(nb, 256), dtype=torch.uint8, device=self.device)
         self.ctx.check(lib.mm_ba_schur(self.ctx.h, C.byref(self.pb), ptr(cams), ptr(pts), ptr(Bd), ptr(Cd), ptr(gc),
                                        ptr(gp), ptr(S), ptr(v), ptr(Cinv), ptr(self._schur_ws),
                                        self._schur_ws.numel()), "mm_ba_schur")
@@ -1002,6 +995,15 @@ class BADevice:
         # n extra (zeroed) rows behind the matrix: band_view's diagonal-major strides run past row n - 1
         self._S_storage = torch.zeros(2 * n * n, dtype=torch.float64, device=self.device)
         self._S = self._S_storage[:n * n].view(n, n)
+
+    def _schur_buffers(self, n):
+        """S and the workspace of the Schur build, allocated on first use.  -> S"""
+        if self._S is None:
+            self._alloc_S(n)
+        if self._schur_ws is None:
+            nb = lib.mm_ba_schur_workspace_bytes(C.byref(self.pb))
+            self._schur_ws = torch.empty(max(nb, 256), dtype=torch.uint8, device=self.device)
+        return self._S
 
     def band_view(self, half_bandwidth):
         """The lower band of the reduced camera system as a strided [n, hb + 1] view of its storage: entry [j, k] is
@@ -1015,14 +1017,10 @@ class BADevice:
         dc is the solution of S dc = v (the camera part of the damped Gauss-Newton step)."""
         self._no_fixed("schur_solve")
         n = 6 * self.F
-        if self._S is None:
-            self._alloc_S(n)
+        self._schur_buffers(n)
         v = torch.empty(n, dtype=torch.float64, device=self.device)
         Cinv = torch.empty((self.P, 6), dtype=torch.float64, device=self.device)
         info = torch.zeros(1, dtype=torch.int32, device=self.device)
-        if self._schur_ws is None:
-            nb = lib.mm_ba_schur_workspace_bytes(C.byref(self.pb))
-            self._schur_ws = torch.empty(max(nb, 256), dtype=torch.uint8, device=self.device)
         if self._chol_ws is None:
             self._chol_ws = torch.empty(lib.mm_chol_workspace_bytes(n), dtype=torch.uint8, device=self.device)
         hb = int(min(half_bandwidth, n))

@@ -572,10 +572,12 @@ def test_chol_solve_sym_reports_non_spd():
         assert int(info) > 0, (bad_col, int(info))
 
 
-@pytest.mark.parametrize("F,P,L", [(200, 6000, 12), (130, 2000, 40)])
+@pytest.mark.parametrize("F,P,L", [(200, 6000, 12), (130, 2000, 40), (128, 33000, 12)])
 def test_schur_solve_overlapped_equals_sequential(F, P, L):
     """mm_ba_schur_solve (S built in camera slabs on one stream while the single-launch Cholesky consumes finished
-    block rows on another) returns bit for bit what mm_ba_schur followed by mm_chol_solve returns."""
+    block rows on another) returns bit for bit what mm_ba_schur followed by mm_chol_solve returns.
+    (128, 33000, 12): the prepare launch's grid is set by the points (129 workgroups of 256 against 128 cameras, the
+    last one without a camera); 8 slabs of exactly 16 cameras, the smallest slab the entry accepts."""
     pr = synth.make_ba_problem(F, P, L, seed=F)
     cams = dev(bo.frame_parameters(pr["ext"]).reshape(F, 6))
     pts = dev(pr["pts0"])
