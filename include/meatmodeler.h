@@ -634,6 +634,80 @@ int mm_guided_match(mm_ctx *ctx, const float *kp_xy /*[n_pairs+1,cap,2]*/, const
                     const mm_guided_params *prm, int32_t *pairs_out /*[n_pairs,cap,2]*/, int32_t *m_out /*[n_pairs]*/,
                     uint8_t *is_new /*[n_pairs,cap]*/, int32_t *info /*[n_pairs,4]*/, void *ws, size_t ws_bytes);
 
+/* ---- a-2h: similarity registration, a robust 7-DoF alignment to known geometry ---------------------------------------------------
+ * No reference counterpart: the reference is metric through its chessboard.  A chain recovered by mm_chain_poses, a triangulated
+ * cloud or an adjusted result lives in a frame nobody chose (first camera at the origin, first baseline the unit of length); this
+ * call estimates, for each of n_prob independent problems, the similarity (s, R, d) with dst_j ~ s R src_j + d from correspondences
+ * that may hold gross outliers.
+ *   Inputs.  src, dst [N, 3] f64.  ptr [n_prob+1] i64 HOST (the grids are sized without a device read): problem q owns rows
+ *   ptr[q] .. ptr[q+1] - 1, n = ptr[q+1] - ptr[q] of them (at most 2^31 - 1).
+ *   Fit -- one routine for the three-point hypothesis and the refit over n rows.  Centroids cs, cd: each coordinate sum / n.
+ *   a = src - cs, b = dst - cd; M = sum b a^T (nine sums, M_rc += b_r a_c) and var = sum ((a0 a0 + a1 a1) + a2 a2), rows ascending
+ *   for a hypothesis, in the chunked order below for a refit.  G = M^T M, G_rc = (M_0r M_0c + M_1r M_1c) + M_2r M_2c; 3 x 3 cyclic
+ *   Jacobi (the one of mm_resect_cameras) gives lambda and V.  v1 = the column of the largest lambda (lambda1), v2 = the column of
+ *   the larger of the other two (lambda2), ties to the lowest column both times; v3 = v1 x v2.  Invalid: lambda1 not finite and
+ *   positive, lambda2 not finite or <= collinear_tol^2 lambda1 (points collinear on either side: a three-point M has rank 2 at
+ *   best, which is why the polar factor of mm_resect_cameras cannot serve here), var not finite and positive, or a non-finite
+ *   entry of the result.  u1 = M v1 / |M v1|; w2 = M v2 - (u1 . M v2) u1, u2 = w2 / |w2|; u3 = u1 x u2 (norms as
+ *   sqrt((x x + y y) + z z), products M v as (M_r0 v_0 + M_r1 v_1) + M_r2 v_2).  R_rc = (u1_r v1_c + u2_r v2_c) + u3_r v3_c:
+ *   det R = +1 by construction, the Kabsch / Umeyama solution with its reflection case.  s = (sum_k R_k M_k, k = 0 .. 8 row-major,
+ *   left to right) / var, or 1 when with_scale = 0.  d_r = cd_r - s ((R_r0 cs_0 + R_r1 cs_1) + R_r2 cs_2).
+ *   Sampling, the integer scheme of mm_verify_matches with three picks: base = pcg(pcg(seed + pcg(prob_base + q)) + h); pick
+ *   k = 0 .. 2 tries t = 0 .. 7: i = (uint64(pcg(base + 8 k + t)) * n) >> 32, the first i that is not an earlier pick; eight
+ *   collisions, or a picked row with a non-finite coordinate, make the hypothesis invalid.  The three rows enter the fit in
+ *   ascending row order: two hypotheses over the same rows are the same bits and tie exactly (with few rows that happens, and
+ *   the tie then goes to the lowest h on any machine).  prob_base is the global index of problem 0 of the call.
+ *   Score.  With A = s R (nine products) e_r = dst_r - (((A_r0 x + A_r1 y) + A_r2 z) + d_r), e^2 = (e0 e0 + e1 e1) + e2 e2.  A row
+ *   is an inlier iff e^2 is finite and <= tau^2.  MSAC: cost = sum of (inlier ? e^2 : tau^2); an invalid hypothesis costs +inf.
+ *   Order of every sum over rows.  Rows go in chunks of MM_ALIGN_CHUNK = 4096 rows of the problem, a constant of this definition;
+ *   across chunks the partial sums are added chunk index ascending, starting from 0.  Inside a chunk the ranking cost of a
+ *   hypothesis is taken rows ascending; every other sum (a model's cost and inlier count, the refit's moments) is the workgroup's
+ *   fixed order of mm_resect_cameras (256 threads striding the chunk's rows, xor butterfly, waves in order).  The bits depend on
+ *   the problem alone, not on the grid.
+ *   Winner.  The lowest finite ranking cost, ties to the lowest h.  Its cost and inliers are then taken in the workgroup order,
+ *   like every cost from here on.
+ *   Refit.  refit_iters rounds (a fixed count) over the inliers of the current model, two passes: the sums of src and dst and the
+ *   count give the centroids, then M and var about them.  Fewer than 3 inliers: the round changes nothing.  The candidate is
+ *   accepted only when it is valid and its cost over ALL rows is finite and strictly lower.
+ *   Outputs.  sim [n_prob, 13] f64 = (s, R row-major, d), NaN without a model; cost [n_prob] f64 (NaN without a model); inlier
+ *   [N] u8, every row of every problem written (0 without a model); info [n_prob, 4] i32 = (flags, n_inliers, best_h or -1, valid
+ *   hypotheses).
+ *   Flags.  MM_ALIGN_TOO_FEW n < max(min_points, 3): no RANSAC is run | MM_ALIGN_NO_MODEL no finite-cost hypothesis (collinear
+ *   data, a straight dolly, ends here) | MM_ALIGN_WEAK n_inliers < min_inliers | MM_ALIGN_NONFINITE some row of the problem has a
+ *   non-finite coordinate (such a row is never an inlier and costs tau^2).
+ * No float atomics: a call repeats bit for bit, a problem's row does not depend on which other problems share the call, and
+ * rows [a, b) of a call equal a call on that block with prob_base + a.  n_prob = 0 returns MM_OK without a launch.  src, dst and
+ * the outputs are DEVICE pointers, ptr and prm host; ws holds mm_align_workspace_bytes(n_prob, n_hyp, N) bytes, N = ptr[n_prob],
+ * 8-byte aligned.  Argument errors -- n_hyp outside 1 .. 4096, tau not finite and positive, a collinear_tol that is negative or not
+ * finite, refit_iters outside 0 .. 1000, a negative min_inliers, with_scale outside {0, 1}, a negative or decreasing ptr, null
+ * pointers: MM_ERR_ARG; a workspace that is too small: MM_ERR_WORKSPACE -- are returned before the device is touched. */
+#define MM_ALIGN_TOO_FEW 1
+#define MM_ALIGN_NO_MODEL 2
+#define MM_ALIGN_WEAK 4
+#define MM_ALIGN_NONFINITE 8
+#define MM_ALIGN_CHUNK 4096
+typedef struct mm_align_params {
+    int32_t n_hyp, min_points, min_inliers, refit_iters, with_scale, reserved;      /* defaults 256, 3, 3, 2, 1 */
+    uint32_t seed, prob_base;
+    double tau;                                                                     /* in dst units; required, > 0 */
+    double collinear_tol;                                                           /* default 1e-6 */
+} mm_align_params;
+size_t mm_align_workspace_bytes(int n_prob, int n_hyp, int64_t N);
+int mm_align_similarity(mm_ctx *ctx, const double *src /*[N,3]*/, const double *dst /*[N,3]*/, const int64_t *ptr /*host [n_prob+1]*/,
+                        int n_prob, const mm_align_params *prm, double *sim /*[n_prob,13]*/, double *cost /*[n_prob]*/,
+                        uint8_t *inlier /*[N]*/, int32_t *info /*[n_prob,4]*/, void *ws, size_t ws_bytes);
+
+/* A similarity applied to a reconstruction, in place; sim [13] f64 = (s, R, d) as mm_align_similarity writes it (DEVICE).
+ *   Points pts [P, 3] or NULL: X' = s R X + d, evaluated as the score above evaluates it (A = s R first).
+ *   Extrinsics ext [F, 3, 4] or NULL: Rc' = Rc R^T, Rc'_ij = (Rc_i0 R_j0 + Rc_i1 R_j1) + Rc_i2 R_j2, and
+ *   tc'_i = s tc_i - ((Rc'_i0 d_0 + Rc'_i1 d_1) + Rc'_i2 d_2): the camera frame is scaled by s, Rc' X' + tc' = s (Rc X + tc), so
+ *   every projection is unchanged.
+ * A sim with a non-finite entry leaves both untouched and returns MM_OK.  One thread per point / camera, plain stores. */
+int mm_apply_similarity(mm_ctx *ctx, const double *sim /*dev [13]*/, double *pts /*[P,3] in/out or NULL*/, int64_t P,
+                        double *ext /*[F,3,4] in/out or NULL*/, int64_t F);
+/* Camera centres C [F, 3] of ext [F, 3, 4]: C_j = -((Rc_0j tc_0 + Rc_1j tc_1) + Rc_2j tc_2). */
+int mm_camera_centres(mm_ctx *ctx, const double *ext /*[F,3,4]*/, int64_t F, double *C /*[F,3]*/);
+
 /* ---- a-4: two-view DLT triangulation ------------------------------------------------------------
  * Replaces the per-track cv2.triangulatePoints + dehomogenise loop, processor.py:254-261.
  * proj [F,3,4] f64; track i uses views f0[i], f1[i] with pixels x0[i], x1[i]; X [n,3]. */

@@ -112,6 +112,14 @@ class ResectPlanarParams(C.Structure):
     _fields_ = ResectParams._fields_ + [("planar_tol", C.c_double), ("collinear_tol", C.c_double)]
 
 
+class AlignParams(C.Structure):
+    """mm_align_params: hypotheses, row and inlier floors, refit count, rigid / similarity switch, sampling key, threshold and
+    the collinearity tolerance of mm_align_similarity."""
+    _fields_ = [("n_hyp", C.c_int32), ("min_points", C.c_int32), ("min_inliers", C.c_int32), ("refit_iters", C.c_int32),
+                ("with_scale", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint32), ("prob_base", C.c_uint32),
+                ("tau", C.c_double), ("collinear_tol", C.c_double)]
+
+
 ALLREDUCE_FN =C.CFUNCTYPE(C.c_int, vp, vp, C.c_int64)
 
 
@@ -181,6 +189,10 @@ SIGNATURES = {
     "mm_resect_planar_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int64]),
     "mm_resect_planar": (C.c_int, [vp, c_f64p, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int, vp, vp,
                                    C.POINTER(ResectPlanarParams), vp, vp, vp, vp, vp, vp, C.c_size_t]),
+    "mm_align_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int64]),
+    "mm_align_similarity": (C.c_int, [vp, vp, vp, c_i64p, C.c_int, C.POINTER(AlignParams), vp, vp, vp, vp, vp, C.c_size_t]),
+    "mm_apply_similarity": (C.c_int, [vp, vp, vp, C.c_int64, vp, C.c_int64]),
+    "mm_camera_centres": (C.c_int, [vp, vp, C.c_int64, vp]),
     "mm_triangulate_dlt": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int64, vp]),
     "mm_triangulate_tracks_workspace_bytes": (C.c_size_t, [C.c_int]),
     "mm_triangulate_tracks": (C.c_int, [vp, vp, C.c_int, vp, C.c_int64, vp, vp, C.POINTER(TriParams), vp, vp, vp, vp, C.c_size_t]),

@@ -13,6 +13,8 @@ import torch
 from . import _lib
 from ._lib import lib, ptr, vp, OrbParams, BAProblem, default_context
 
+ptr_ = ptr      # (align_similarity has an argument of that name)
+
 
 def _i32(t):
     assert t.dtype == torch.int32 and t.is_contiguous()
@@ -469,6 +471,91 @@ def resect_planar(K, X, obs, pi, cam_ptr, cam_obs, pt_ok=None, prior=None, n_hyp
                                    n_rows, n_cams, ptr(pt_ok), ptr(prior), C.byref(prm), ptr(ext), ptr(cost), ptr(inlier),
                                    ptr(info), ptr(plane), ptr(ws), wsb), "mm_resect_planar")
     return ext, cost, inlier, info, plane
+
+
+ALIGN_TOO_FEW, ALIGN_NO_MODEL, ALIGN_WEAK, ALIGN_NONFINITE = 1, 2, 4, 8      # MM_ALIGN_* of include/meatmodeler.h
+
+
+def align_similarity(src, dst, ptr=None, tau=None, tau_rel=None, n_hyp=256, min_points=3, min_inliers=3, refit_iters=2,
+                     with_scale=True, seed=0, prob_base=0, collinear_tol=1e-6, ctx=None):
+    """A robust similarity per problem, dst ~ s R src + d (mm_align_similarity): src, dst [N, 3] f64 device tensors; ptr
+    [n_prob+1] integers on the HOST (a sequence or array; None: one problem over all rows)
+    -> (sim [n_prob, 13] f64 = (s, R row-major, d), NaN without a model; cost [n_prob] f64; inlier [N] u8; info [n_prob, 4] i32 =
+    (ALIGN_* flags, n_inliers, best_h or -1, valid hypotheses)).
+    Exactly one of `tau` (the inlier distance in dst units) and `tau_rel` must be given; tau_rel multiplies the root-mean-square
+    distance of the finite rows of dst from their centroid (one problem only: tau is one number per call).  with_scale False:
+    rigid, s = 1."""
+    if (tau is None) == (tau_rel is None):
+        raise ValueError("align_similarity: exactly one of tau and tau_rel must be given")
+    if src.dim() != 2 or src.shape[1] != 3 or tuple(dst.shape) != tuple(src.shape):
+        raise ValueError("align_similarity: src [N, 3] and dst [N, 3] expected")
+    if src.dtype != torch.float64 or dst.dtype != torch.float64:
+        raise ValueError("align_similarity: src and dst must be f64")
+    N = src.shape[0]
+    ph = np.array([0, N], np.int64) if ptr is None else np.ascontiguousarray(np.asarray(ptr, dtype=np.int64).ravel())
+    if ph.size < 1 or ph[0] < 0 or (np.diff(ph) < 0).any() or ph[-1] > N:
+        raise ValueError("align_similarity: ptr must start at or above 0, not decrease and end at or below N")
+    n_prob = ph.size - 1
+    if not 1 <= int(n_hyp) <= 4096:
+        raise ValueError("align_similarity: n_hyp must be in 1 .. 4096")
+    if not 0 <= int(refit_iters) <= 1000 or int(min_inliers) < 0:
+        raise ValueError("align_similarity: refit_iters must be in 0 .. 1000 and min_inliers not negative")
+    if not (float(collinear_tol) >= 0 and math.isfinite(float(collinear_tol))):
+        raise ValueError("align_similarity: collinear_tol must be finite and not negative")
+    src, dst = src.contiguous(), dst.contiguous()
+    if tau_rel is not None:
+        if n_prob > 1:
+            raise ValueError("align_similarity: tau_rel needs a single problem (tau is one number per call)")
+        if not (float(tau_rel) > 0 and math.isfinite(float(tau_rel))):
+            raise ValueError("align_similarity: tau_rel must be finite and positive")
+        rows = dst[int(ph[0]):int(ph[-1])]
+        rows = rows[torch.isfinite(rows).all(dim=1)]
+        spread = float(torch.sqrt(((rows - rows.mean(dim=0)) ** 2).sum(dim=1).mean())) if rows.shape[0] else math.nan
+        tau = float(tau_rel) * spread if spread > 0 and math.isfinite(spread) else float(tau_rel)      # (no spread: nothing to scale by)
+    if not (float(tau) > 0 and math.isfinite(float(tau))):
+        raise ValueError("align_similarity: tau must be finite and positive")
+    d = src.device
+    sim = torch.full((n_prob, 13), math.nan, dtype=torch.float64, device=d)
+    cost = torch.full((n_prob,), math.nan, dtype=torch.float64, device=d)
+    inlier = torch.zeros(N, dtype=torch.uint8, device=d)
+    info = torch.zeros((n_prob, 4), dtype=torch.int32, device=d)
+    ctx = ctx or default_context()
+    if n_prob == 0:
+        return sim, cost, inlier, info
+    prm = _lib.AlignParams(int(n_hyp), int(min_points), int(min_inliers), int(refit_iters), 1 if with_scale else 0, 0,
+                           int(seed) & 0xFFFFFFFF, int(prob_base) & 0xFFFFFFFF, float(tau), float(collinear_tol))
+    wsb = lib.mm_align_workspace_bytes(n_prob, int(n_hyp), int(ph[-1]))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=d)
+    ctx.check(lib.mm_align_similarity(ctx.h, ptr_(src), ptr_(dst), ph.ctypes.data_as(_lib.c_i64p), n_prob, C.byref(prm), ptr_(sim),
+                                      ptr_(cost), ptr_(inlier), ptr_(info), ptr_(ws), wsb), "mm_align_similarity")
+    return sim, cost, inlier, info
+
+
+def apply_similarity(sim, points=None, extrinsics=None, ctx=None):
+    """A similarity applied in place (mm_apply_similarity): sim [13] f64 device tensor as align_similarity returns a row; points
+    [P, 3] -> s R X + d; extrinsics [F, 3, 4] -> [Rc R^T | s tc - Rc R^T d], so that every projection is unchanged.  Both are
+    contiguous f64 device tensors or None and are returned.  A non-finite sim changes nothing."""
+    if sim.numel() != 13 or sim.dtype != torch.float64 or not sim.is_contiguous():
+        raise ValueError("apply_similarity: sim must be a contiguous f64 tensor of 13 numbers")
+    for name, t, tail in (("points", points, (3,)), ("extrinsics", extrinsics, (3, 4))):
+        if t is not None and (t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape[1:]) != tail):
+            raise ValueError(f"apply_similarity: {name} must be a contiguous f64 tensor [n, {', '.join(map(str, tail))}]")
+    ctx = ctx or default_context()
+    P = 0 if points is None else points.shape[0]
+    F = 0 if extrinsics is None else extrinsics.shape[0]
+    ctx.check(lib.mm_apply_similarity(ctx.h, ptr_(sim), ptr_(points), P, ptr_(extrinsics), F), "mm_apply_similarity")
+    return points, extrinsics
+
+
+def camera_centres(extrinsics, ctx=None):
+    """extrinsics [F, 3, 4] f64 device tensor -> the camera centres -Rc^T tc, [F, 3] f64 (mm_camera_centres)."""
+    if extrinsics.dim() != 3 or tuple(extrinsics.shape[1:]) != (3, 4) or extrinsics.dtype != torch.float64:
+        raise ValueError("camera_centres: extrinsics [F, 3, 4] f64 expected")
+    ctx = ctx or default_context()
+    ext = extrinsics.contiguous()
+    Cn = torch.empty((ext.shape[0], 3), dtype=torch.float64, device=ext.device)
+    ctx.check(lib.mm_camera_centres(ctx.h, ptr_(ext), ext.shape[0], ptr_(Cn)), "mm_camera_centres")
+    return Cn
 
 
 # ------------------------------------------------------------------------------------------------ ORB

@@ -7,7 +7,8 @@ Keyframe gating, calibration and PnP are outside the scope: the 
 per frame (the reference gets them from calibrate / poseEstimation / adjustPose, processor.py:422-448) -- or, with
 `run(verify={...}, poses={...})`, K alone: the extrinsics are then recovered from the verified matches; with
 `run(resect={...})` every frame is registered once more against the triangulated points (a RANSAC resection, DESIGN.md 6f;
-`planar="auto"` adds the homography branch for coplanar points, 6g).
+`planar="auto"` adds the homography branch for coplanar points, 6g); with `run(align={...})` the cameras are registered to
+positions the caller knows and everything downstream runs in that frame and scale (a robust similarity).
 """
 import ctypes as C
 import queue
@@ -19,7 +20,7 @@ import torch
 
 from . import _lib, ops, parallel
 from ._lib import lib, default_context, c_i32p, c_i64p, c_f32p, MMError
-from .bundleAdjuster import SchurTRF, frameParameters
+from .bundleAdjuster import SchurTRF, frameParameters, _rodrigues_matrix
 from .orb_pattern import brief_pattern
 
 
@@ -32,6 +33,7 @@ DEGENERACY_KEYS = DEGENERACY_HOMOGRAPHY_KEYS + DEGENERACY_POSE_KEYS
 GUIDED_KEYS = ("threshold_px", "ratio", "max_dist", "cross_check")
 RESECT_KEYS = ("n_hyp", "threshold_px", "min_rows", "min_inliers", "refit_iters", "polish_iters", "seed", "planar", "planar_tol",
                "collinear_tol")
+ALIGN_KEYS = ("frames", "extrinsics", "centres", "tau", "tau_rel", "n_hyp", "seed", "refit_iters", "with_scale", "min_inliers")
 
 
 def _stage_options(stage, value, keys):
@@ -76,6 +78,37 @@ def resect_options(resect):
     """`run(..., resect=)`: None (no resection) or a dict of the parameters of ops.resect_cameras -- the points, the prior,
     cam_base and ctx are the pipeline's own.  Returns it as a dict; an unknown key raises ValueError."""
     return _stage_options("resect", resect, RESECT_KEYS)
+
+
+def align_options(align, n_frames=None):
+    """`run(..., align=)`: None (no registration) or a dict: `frames`, at least 3 distinct indices in [0, F); the targets of
+    those frames as one of `extrinsics` [n, 3|4, 4] or `centres` [n, 3], in the frame the result is wanted in; and optionally
+    tau or tau_rel (default tau_rel = 0.05: five percent of the targets' spread admits the drift DESIGN.md 6e measured on a
+    recovered chain, 2.16 % at its worst, and not a broken link), n_hyp, seed, refit_iters, with_scale, min_inliers.  Returns
+    dict(frames [n] i64, centres [n, 3] f64, params for ops.align_similarity); anything else raises ValueError."""
+    align = _stage_options("align", align, ALIGN_KEYS)
+    if align is None:
+        return None
+    if "frames" not in align or ("extrinsics" in align) == ("centres" in align):
+        raise ValueError("align needs frames and exactly one of extrinsics and centres")
+    frames = np.asarray(align.pop("frames"))
+    if frames.ndim != 1 or frames.size < 3 or not np.issubdtype(frames.dtype, np.integer) or np.unique(frames).size != frames.size \
+            or frames.min() < 0 or (n_frames is not None and frames.max() >= n_frames):
+        raise ValueError("align: frames must be at least 3 distinct indices in [0, F)")
+    if "centres" in align:
+        centres = np.asarray(align.pop("centres"), np.float64)
+    else:
+        E = np.asarray(align.pop("extrinsics"), np.float64)
+        if E.ndim != 3 or E.shape[1] not in (3, 4) or E.shape[2] != 4:
+            raise ValueError("align: extrinsics [n, 3|4, 4] expected")
+        centres = -np.einsum("nji,nj->ni", E[:, :3, :3], E[:, :3, 3])
+    if centres.shape != (frames.size, 3):
+        raise ValueError("align: one target per entry of frames expected (extrinsics [n, 3|4, 4] or centres [n, 3])")
+    if "tau" in align and "tau_rel" in align:
+        raise ValueError("align takes tau or tau_rel, not both")
+    if "tau" not in align and "tau_rel" not in align:
+        align["tau_rel"] = 0.05
+    return dict(frames=frames.astype(np.int64), centres=np.ascontiguousarray(centres), params=align)
 
 
 class ClipPipeline:
@@ -529,10 +562,21 @@ class ClipPipeline:
         out["obs_kp"] = out["obs_kp_dev"].cpu().numpy()
         return out
 
+    # ------------------------------------------------------------------------------------------- align
+    def align(self, ext_d, align):
+        """The cameras ext_d [F, 3, 4] (device) registered to the targets of `align` (align_options): the centres of
+        ext_d[frames] against the target centres (ops.camera_centres, ops.align_similarity) -> dict(sim [13], cost, info [4],
+        inlier [n]), device tensors.  Nothing is transformed here."""
+        idx = torch.as_tensor(align["frames"]).to(self.device)
+        src = ops.camera_centres(ext_d.index_select(0, idx).contiguous(), ctx=self.ctx)
+        dst = torch.as_tensor(align["centres"]).to(self.device)
+        sim, cost, inlier, info = ops.align_similarity(src, dst, ctx=self.ctx, **align["params"])
+        return dict(sim=sim[0].contiguous(), cost=cost[0], info=info[0], inlier=inlier)
+
     # ------------------------------------------------------------------------------------------- whole clip
     def run(self, frames, K, extrinsics=None, ba=True, ftol=1e-4, verbose=0, dist=None, timers=None, max_nfev=None,
             force_collectives=False, triangulation="two_view", cull=None, verify=None, poses=None, resect=None, degeneracy=None,
-            guided=None):
+            guided=None, align=None):
         """frames [F,H,W] u8 (device).  With `dist` = torch.distributed (initialised), frames are the FULL clip on
         every rank (synthetic input is generated locally) and the work is sharded as described in parallel.py.
         `max_nfev`: evaluation budget of the adjustment (None = SciPy's default, as adjustPoints).
@@ -573,12 +617,21 @@ class ClipPipeline:
         flagged), with the extrinsics in use -- given or recovered -- as the prior, so no frame ends with a higher MSAC cost
         than it came in with; the tracks are then triangulated again with the new poses and the adjustment starts from those.
         Its key `planar` ("auto" / "only", with planar_tol and collinear_tol) sends frames whose points are coplanar through
-        the homography branch; without it exactly the one call of 6f is launched.  The result gains `resect` = dict(extrinsics [F,3,4], cost [F], info [F,6], inliers_per_frame [F]); timer "resect"."""
+        the homography branch; without it exactly the one call of 6f is launched.  The result gains `resect` = dict(extrinsics [F,3,4], cost [F], info [F,6], inliers_per_frame [F]); timer "resect".
+        `align`: None (default: nothing below runs) or the dict of `align_options` (frames, their target extrinsics or centres,
+        optional tau / tau_rel, n_hyp, seed, refit_iters, with_scale, min_inliers; one rank only): once the extrinsics are
+        settled -- given or recovered -- and before the first triangulation, the centres of the cameras `frames` are registered
+        to the targets by a robust similarity and the extrinsics are replaced by their image, so triangulation,
+        `resect` and the adjustment run in the target frame and scale; with `poses`, `poses["extrinsics"]` holds the image.
+        The result gains `align` = dict(sim [13], cost, info [4], inlier [n]); timer "align".  If the adjustment runs, its
+        cameras are registered to the same targets once more: `ba_aligned` = dict(extrinsics [F,3,4], points, sim, info);
+        `ba` itself is left as it is.  ALIGN_TOO_FEW or ALIGN_NO_MODEL: nothing is transformed, the flags say so."""
         verify = verify_options(verify)
         poses = pose_options(poses)
         resect = resect_options(resect)
         degeneracy = degeneracy_options(degeneracy)
         guided = guided_options(guided)
+        align = align_options(align)
         if guided is not None and verify is None:
             raise ValueError("guided needs verify (it supplies each pair's fundamental matrix, the model the search is gated by): "
                              "pass verify={} for the defaults")
@@ -592,6 +645,8 @@ class ClipPipeline:
         if triangulation not in ("two_view", "multi_view"):
             raise ValueError("triangulation must be 'two_view' or 'multi_view'")
         F = frames.shape[0]
+        if align is not None and align["frames"].max() >= F:
+            raise ValueError("align: frames must be at least 3 distinct indices in [0, F)")
         world = dist.get_world_size() if dist is not None else 1
         rank = dist.get_rank() if dist is not None else 0
         if cull is not None and triangulation != "multi_view":
@@ -603,6 +658,8 @@ class ClipPipeline:
                              "across every rank boundary")
         if resect is not None and world > 1:
             raise ValueError("resect is not supported with more than one rank: every frame needs the whole point table")
+        if align is not None and world > 1:
+            raise ValueError("align is not supported with more than one rank: the cameras of `frames` live on different ranks")
         if cull is not None:
             tests = {"max_reproj_px", "min_angle_deg", "min_depth"}
             unknown = set(cull) - tests - {"refine_iters"}
@@ -736,6 +793,16 @@ class ClipPipeline:
             toc("poses")
         else:
             ext = np.asarray(extrinsics, float)[:, :3, :]
+        aligned = None
+        if align is not None:
+            tic("align")
+            ext_d = torch.as_tensor(np.ascontiguousarray(ext, dtype=np.float64)).to(self.device)
+            aligned = self.align(ext_d, align)
+            ops.apply_similarity(aligned["sim"], None, ext_d, ctx=self.ctx)      # (a NaN sim -- no model -- changes nothing)
+            if recovered is not None:
+                recovered["extrinsics"] = ext_d
+            ext = ext_d.cpu().numpy()
+            toc("align")
 
         def triangulated(ext):
             """(points, quality, flags) of the linked tracks under the extrinsics `ext`; two-view has no quality or flags."""
@@ -772,6 +839,8 @@ class ClipPipeline:
             out["guided"] = guided_out
         if resected is not None:
             out["resect"] = resected
+        if aligned is not None:
+            out["align"] = aligned
         kept = None
         if triangulation == "multi_view":
             out.update(track_quality=quality, track_flags=flags)
@@ -807,5 +876,15 @@ class ClipPipeline:
         toc("ba_solve")
         toc("ba")
         out.update(ba=res, n_obs_local=pb.O, cam_span=pb.cam_span, n_pairs=pb.n_pairs)
+        if align is not None:
+            tic("align")
+            cams_h = res.cams.reshape(F, 6).cpu().numpy()
+            ext_b = np.stack([np.concatenate([_rodrigues_matrix(c[:3]), c[3:, None]], axis=1) for c in cams_h])
+            ext_b = torch.as_tensor(np.ascontiguousarray(ext_b)).to(self.device)
+            again = self.align(ext_b, align)
+            pts_b = res.pts.reshape(-1, 3).clone().contiguous()
+            ops.apply_similarity(again["sim"], pts_b, ext_b, ctx=self.ctx)
+            out["ba_aligned"] = dict(extrinsics=ext_b, points=pts_b, sim=again["sim"], info=again["info"])
+            toc("align")
         T.pop("_open", None)
         return out

@@ -472,6 +472,37 @@ def resectCameras(points_3D, points_2D, K, prior=None, **params):
     return ext.cpu().numpy(), [mask[cam_ptr[f]:cam_ptr[f + 1]] for f in range(n)], info.cpu().numpy()
 
 
+def alignSimilarity(points_src, points_dst, **params):
+    """A robust similarity between two sets of corresponding 3-D points, points_dst ~ s R points_src + d (the reference has no
+    counterpart: it is metric through its chessboard): [n, 3] host arrays, row i of one belongs to row i of the other
+    -> (sim [13] f64 = (s, R row-major, d), NaN where no model was found; mask [n] bool, the inliers; info [4] i32 as
+    ops.align_similarity returns it).  `params` as ops.align_similarity takes them (tau or tau_rel, n_hyp, min_points,
+    min_inliers, refit_iters, with_scale, seed, collinear_tol)."""
+    src = np.ascontiguousarray(np.asarray(points_src, np.float64).reshape(-1, 3))
+    dst = np.ascontiguousarray(np.asarray(points_dst, np.float64).reshape(-1, 3))
+    if src.shape != dst.shape:
+        raise ValueError("alignSimilarity: points_src and points_dst must have the same length")
+    dev = default_context().device
+    sim, _, inlier, info = ops.align_similarity(torch.as_tensor(src).to(dev), torch.as_tensor(dst).to(dev), **params)
+    return sim[0].cpu().numpy(), inlier.cpu().numpy().astype(bool), info[0].cpu().numpy()
+
+
+def applySimilarity(sim, points=None, extrinsics=None):
+    """The similarity `sim` [13] (alignSimilarity) applied to host arrays: points [P, 3] -> s R X + d, extrinsics [F, 3|4, 4] ->
+    [Rc R^T | s tc - Rc R^T d] as [F, 3, 4] (every projection is unchanged).  -> (points, extrinsics), new arrays or None; a
+    non-finite sim returns them as they were."""
+    dev = default_context().device
+    sd = torch.as_tensor(np.ascontiguousarray(np.asarray(sim, np.float64).reshape(13))).to(dev)
+    pd = ed = None
+    if points is not None:
+        pd = torch.as_tensor(np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))).to(dev)
+    if extrinsics is not None:
+        e = np.asarray(extrinsics, np.float64)
+        ed = torch.as_tensor(np.ascontiguousarray(e.reshape(-1, e.shape[-2], 4)[:, :3, :])).to(dev)
+    ops.apply_similarity(sd, pd, ed)
+    return (None if pd is None else pd.cpu().numpy()), (None if ed is None else ed.cpu().numpy())
+
+
 def rotation_vector(R):
     """The rotation vector (axis times angle, what cv2.Rodrigues returns for a matrix) of a 3 x 3 rotation, on the host."""
     R = np.asarray(R, np.float64).reshape(3, 3)
