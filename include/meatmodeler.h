@@ -751,6 +751,65 @@ int mm_triangulate_tracks(mm_ctx *ctx, const double *proj /*[F,3,4]*/, int F, co
                           const int32_t *obs_frame /*[O]*/, const double *obs_xy /*[O,2]*/, const mm_tri_params *prm,
                           double *X /*[T,3]*/, double *quality /*[T,4]*/, int32_t *flags /*[T]*/, void *ws, size_t ws_bytes);
 
+/* ---- a-9b: observation filter at the adjusted solution ---------------------------------------------------------------------------
+ * No reference counterpart: the reference adjusts whatever its matcher linked.  Every test in front of the solver judges a track
+ * at its initial triangulation under the initial poses; this call judges every observation, and every point by what it has left,
+ * at the cameras and points an adjustment returned, and compacts the problem for the next solve.
+ *   Inputs, what the adjustment takes and returns.  cams [F, 6] f64 (Rodrigues vector, then t), one row for every value fi takes
+ *   (a caller with fixed cameras concatenates them); pts [P, 3] f64; fi, pi [O] i32 and obs [O, 2] f64 point-major, as
+ *   mm_flatten_tracks emits them; pt_ptr [P+1] i32: point p owns observations pt_ptr[p] .. pt_ptr[p+1] - 1 (what
+ *   mm_ba_index_build writes).  The caller checks 0 <= fi < F, 0 <= pi < P and that pt_ptr is that CSR.  These and the outputs
+ *   are DEVICE pointers; K [9] row-major and prm are HOST (K is judged before the device is touched and travels by value).
+ *   Camera table, a small pre-kernel, 15 doubles per camera.  th2 = (rx rx + ry ry) + rz rz.  th2 < 1e-4 (the series of the
+ *   adjustment's own sweeps): c = cos(sqrt(th2)), a = 1 + th2 (-1/6 + th2 (1/120 - th2 / 5040)), b = 1/2 + th2 (-1/24 + th2
+ *   (1/720 - th2 / 40320)); otherwise th = sqrt(th2), c = cos th, a = sin th / th, b = (2 sin^2(th / 2)) / th2.
+ *   R = c I + a [r]x + b r r^T, every entry as written here, products left to right: R00 = c + b rx rx, R01 = -a rz + b rx ry,
+ *   R02 = a ry + b rx rz, R10 = a rz + b ry rx, R11 = c + b ry ry, R12 = -a rx + b ry rz, R20 = -a ry + b rz rx,
+ *   R21 = a rx + b rz ry, R22 = c + b rz rz.  Centre C_j = -((R_0j t_0 + R_1j t_1) + R_2j t_2).
+ *   Step 1, per observation o (camera f, point p).  Y_i = ((R_i0 X_0 + R_i1 X_1) + R_i2 X_2) + t_i; depth = Y_2;
+ *   u_i = (K_i0 Y_0 + K_i1 Y_1) + K_i2 Y_2; dx = u_0 / u_2 - obs_x, dy = u_1 / u_2 - obs_y; e = sqrt(dx dx + dy dy).
+ *   obs_flags[o] = MM_OBS_NONFINITE e or depth is not finite | MM_OBS_BEHIND depth <= min_depth | MM_OBS_REPROJ
+ *   e > max_reproj_px.  A comparison with NaN is false, as in mm_triangulate_tracks; thresholds +inf, -inf and 2.0 switch a test
+ *   off, as in mm_tri_params.  err [O] = e and depth [O] are outputs.
+ *   Step 2, per point p, over its observations with obs_flags == 0 (the survivors), in order.  n_ok = their count.  With
+ *   a = C_first - X of the first survivor and b = C_i - X of each later one, dots as (x x + y y) + z z,
+ *   cos_parallax[p] = min over them of (a . b) / sqrt((a . a) (b . b)) -- a NaN stays, as NumPy's min keeps it -- and NaN when
+ *   n_ok < 2: the cosine of mm_triangulate_tracks restricted to survivors.  pt_flags[p] = MM_PT_NONFINITE a component of X is
+ *   not finite | MM_PT_SHORT n_ok < min_views | MM_PT_PARALLAX cos_parallax > max_cos_parallax.
+ *   Step 3.  An observation is kept iff its flags are 0 and its point's flags are 0; an unflagged observation of a flagged point
+ *   gains MM_OBS_ORPHAN.
+ *   Step 4, compaction, order preserved.  Kept observations stay in input order and kept points are renumbered in input order, so
+ *   the output is point-major again: fi_out, pi_out (renumbered), obs_out (the input's bits), obs_map [O'] (input row of each
+ *   kept observation), point_map [P'] (input index of each kept point), each sized by the caller for O and P rows; counts [4]
+ *   i64 = (O', P', observations flagged by a test of their own, points flagged).  The positions are two exclusive scans of 0 / 1
+ *   flags in chunks of MM_FILTER_CHUNK = 1024 rows, a constant of this definition: sums per chunk, one scan of the sums, then
+ *   each chunk places its rows -- separate launches, no workgroup waits for another.
+ * Every number is computed by one thread from its own inputs, the counts are integers and there are no atomics: a call repeats
+ * bit for bit and a point's verdict does not depend on which other points share the call.  O = 0 or P = 0 returns MM_OK with
+ * counts = 0 and writes nothing else.  ws holds mm_filter_workspace_bytes(F, P, O) bytes, 8-byte aligned; obs and obs_out
+ * 16-byte aligned.  Argument errors -- min_views < 2, a NaN threshold, a K that mm_resect_cameras would refuse, null pointers,
+ * negative sizes, O or P beyond 2^31 - 1: MM_ERR_ARG; a workspace that is too small: MM_ERR_WORKSPACE -- are returned before the
+ * device is touched. */
+#define MM_OBS_REPROJ 1
+#define MM_OBS_BEHIND 2
+#define MM_OBS_NONFINITE 4
+#define MM_OBS_ORPHAN 8
+#define MM_PT_SHORT 1
+#define MM_PT_PARALLAX 2
+#define MM_PT_NONFINITE 4
+#define MM_FILTER_CHUNK 1024
+typedef struct mm_filter_params {
+    int32_t min_views, reserved;
+    double max_reproj_px, min_depth, max_cos_parallax;
+} mm_filter_params;
+size_t mm_filter_workspace_bytes(int F, int64_t P, int64_t O);
+int mm_filter_observations(mm_ctx *ctx, const double *cams /*[F,6]*/, int F, const double *pts /*[P,3]*/, int64_t P,
+                           const double *K /*host [9]*/, const int32_t *fi /*[O]*/, const int32_t *pi /*[O]*/,
+                           const double *obs /*[O,2]*/, int64_t O, const int32_t *pt_ptr /*[P+1]*/, const mm_filter_params *prm,
+                           int32_t *obs_flags /*[O]*/, double *err /*[O]*/, double *depth /*[O]*/, int32_t *pt_flags /*[P]*/,
+                           double *cos_parallax /*[P]*/, int32_t *fi_out /*[O]*/, int32_t *pi_out /*[O]*/, double *obs_out /*[O,2]*/,
+                           int32_t *obs_map /*[O]*/, int32_t *point_map /*[P]*/, int64_t *counts /*[4]*/, void *ws, size_t ws_bytes);
+
 /* ---- a-7..a-9: bundle adjustment sweeps -----------------------------------------------------------
  * Cost model of bundleAdjuster.py:7-52,81-102 (Rodrigues rotate, translate, full 3x3 K, divide, minus obs),
  * f64 throughout.  The LM/trust-region driver (the reference's scipy least_squares TRF loop,

@@ -120,6 +120,12 @@ class AlignParams(C.Structure):
                 ("tau", C.c_double), ("collinear_tol", C.c_double)]
 
 
+class FilterParams(C.Structure):
+    """mm_filter_params: the view floor and the three thresholds of mm_filter_observations."""
+    _fields_ = [("min_views", C.c_int32), ("reserved", C.c_int32), ("max_reproj_px", C.c_double), ("min_depth", C.c_double),
+                ("max_cos_parallax", C.c_double)]
+
+
 ALLREDUCE_FN =C.CFUNCTYPE(C.c_int, vp, vp, C.c_int64)
 
 
@@ -196,6 +202,9 @@ SIGNATURES = {
     "mm_triangulate_dlt": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int64, vp]),
     "mm_triangulate_tracks_workspace_bytes": (C.c_size_t, [C.c_int]),
     "mm_triangulate_tracks": (C.c_int, [vp, vp, C.c_int, vp, C.c_int64, vp, vp, C.POINTER(TriParams), vp, vp, vp, vp, C.c_size_t]),
+    "mm_filter_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int64]),
+    "mm_filter_observations": (C.c_int, [vp, vp, C.c_int, vp, C.c_int64, c_f64p, vp, vp, vp, C.c_int64, vp, C.POINTER(FilterParams),
+                                         vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]),
     "mm_ba_residual": (C.c_int, [vp, C.POINTER(BAProblem), vp, vp, vp, vp, vp, C.c_size_t]),
     "mm_ba_jacobian": (C.c_int, [vp, C.POINTER(BAProblem), vp, vp, vp, vp]),
     "mm_ba_normal_eq": (C.c_int, [vp, C.POINTER(BAProblem), vp, vp, vp, vp, vp, vp]),

@@ -697,6 +697,149 @@ def adjustPoints(frame_extrinsic_matrices, camera_intrinsic_matrix, points_3D, p
     return reformatPointResult(res, F, len(np.asarray(points_3D).reshape(-1, 3)))
 
 
+# ----------------------------------------------------------------------------------------------- filter and re-adjust
+
+REFINE_KEYS = ("max_reproj_px", "min_angle_deg", "min_depth", "min_views", "rounds", "ftol", "max_nfev")
+
+
+def refine_schedule(**options):
+    """The filter-and-re-adjust rounds from their options: max_reproj_px, a number or a sequence with one
+    threshold per round, the last one repeated (default (8, 4): a least-squares solve smears each gross outlier over its
+    camera's other observations, so the first round is wide and the next one tight); min_angle_deg, min_depth, min_views (the
+    tests of ops.filter_observations); rounds (default 2); ftol (default 1e-4) and max_nfev (default None) of the re-solves.
+    -> dict(max_reproj_px [rounds], min_angle_deg, min_depth, min_views, rounds, ftol, max_nfev); anything else raises
+    ValueError."""
+    unknown = set(options) - set(REFINE_KEYS)
+    if unknown:
+        raise ValueError(f"refine takes {', '.join(REFINE_KEYS)}; not {sorted(unknown)}")
+    rounds = options.get("rounds", 2)
+    if isinstance(rounds, bool) or not isinstance(rounds, (int, np.integer)) or rounds < 1:
+        raise ValueError("refine: rounds must be an integer of at least 1")
+    taus = options.get("max_reproj_px", (8.0, 4.0))
+    try:
+        taus = [float(t) for t in (taus if np.ndim(taus) else [taus])]
+    except (TypeError, ValueError):
+        raise ValueError("refine: max_reproj_px must be a number or a sequence of numbers") from None
+    if not taus:
+        raise ValueError("refine: max_reproj_px must not be empty")
+    taus = [taus[min(r, len(taus) - 1)] for r in range(int(rounds))]
+    tests = {k: options[k] for k in ("min_angle_deg", "min_depth", "min_views") if k in options}
+    for tau in taus:      # (every round must have an active test; a NaN or a negative angle ends here too)
+        ops.filter_thresholds(max_reproj_px=tau, what="refine", **tests)
+    ftol, max_nfev = options.get("ftol", 1e-4), options.get("max_nfev")
+    if not (isinstance(ftol, (int, float)) and ftol > 0):
+        raise ValueError("refine: ftol must be positive")
+    if max_nfev is not None and (isinstance(max_nfev, bool) or not isinstance(max_nfev, (int, np.integer)) or max_nfev < 1):
+        raise ValueError("refine: max_nfev must be None or a positive integer")
+    return dict(max_reproj_px=taus, rounds=int(rounds), ftol=float(ftol), max_nfev=None if max_nfev is None else int(max_nfev), **tests)
+
+
+def refine_rounds(pb, res, K, schedule, verbose=0):
+    """The rounds after an adjustment `res` of the problem `pb` (an ops.BADevice): filter at the returned cameras and points
+    (ops.filter_observations); nothing flagged: stop; otherwise build a BADevice from the compacted arrays and solve again from
+    the same cameras and pts[point_map]; up to schedule["rounds"] times (`refine_schedule`).  A round that would keep no
+    observation ends the loop without a solve.
+    -> dict(ba = the last result, point_map / obs_map into the rows of `pb`, composed across rounds, rounds = [dict(max_reproj_px,
+    n_obs, n_points, removed_obs, removed_points, cost_in, cost_out, nfev, status)], obs_flags / pt_flags of the first round, and
+    filters = each round's ops.filter_observations result, results = the result of each re-solve)."""
+    dev = pb.device
+    tests = {k: schedule[k] for k in ("min_angle_deg", "min_depth", "min_views") if k in schedule}
+    point_map = torch.arange(pb.P, dtype=torch.int32, device=dev)
+    obs_map = torch.arange(pb.O, dtype=torch.int32, device=dev)
+    out = dict(ba=res, rounds=[], filters=[], results=[], obs_flags=None, pt_flags=None)
+    for tau in schedule["max_reproj_px"]:
+        cams, pts = res.cams.reshape(pb.F, 6), res.pts.reshape(pb.P, 3)
+        cams_all = cams if pb.fixed_cams is None else torch.cat([cams, pb.fixed_cams])
+        flt = ops.filter_observations(cams_all, pts, K, pb, max_reproj_px=tau, ctx=pb.ctx, **tests)
+        out["filters"].append(flt)
+        if out["obs_flags"] is None:
+            out["obs_flags"], out["pt_flags"] = flt["obs_flags"], flt["pt_flags"]
+        row = dict(max_reproj_px=tau, n_obs=flt["n_obs"], n_points=flt["n_points"], removed_obs=pb.O - flt["n_obs"],
+                   removed_points=pb.P - flt["n_points"], cost_in=None, cost_out=None, nfev=0, status=None)
+        out["rounds"].append(row)
+        if row["removed_obs"] == 0 and row["removed_points"] == 0:
+            break
+        point_map, obs_map = point_map[flt["point_map"].long()], obs_map[flt["obs_map"].long()]
+        if flt["n_obs"] == 0:
+            break
+        pb = ops.BADevice(K, flt["fi"], flt["pi"], flt["obs"], pb.F, flt["n_points"], dev, pb.ctx, fixed_cams=pb.fixed_cams)
+        pts0 = pts[flt["point_map"].long()].contiguous()
+        solver = SchurTRF(pb)
+        row["cost_in"] = solver._cost(cams, pts0)
+        res = solver.solve(cams, pts0, ftol=schedule["ftol"], max_nfev=schedule["max_nfev"], verbose=verbose)
+        row.update(cost_out=res.cost, nfev=res.nfev, status=res.status)
+        out["ba"] = res
+        out["results"].append(res)
+    out.update(point_map=point_map, obs_map=obs_map)
+    return out
+
+
+def filterPoints(points, extrinsics, K, points_2D, frame_indices, point_indices, **thresholds):
+    """What adjustPoints returns (points [P,3], F extrinsics) and was given (K, points_2D [O,2], frame_indices, point_indices,
+    point-major) judged by ops.filter_observations under `thresholds` (max_reproj_px, min_angle_deg, min_depth, min_views)
+    -> (points [P',3], points_2D [O',2], frame_indices [O'], point_indices [O'] renumbered, point_map [P'] = the input index of
+    each kept point), NumPy arrays ready for the next adjustPoints."""
+    unknown = set(thresholds) - {"max_reproj_px", "min_angle_deg", "min_depth", "min_views"}
+    if unknown:
+        raise ValueError(f"filterPoints takes max_reproj_px, min_angle_deg, min_depth and min_views; not {sorted(unknown)}")
+    ops.filter_thresholds(what="filterPoints", **thresholds)
+    ext = np.asarray(extrinsics, float)
+    pts = np.ascontiguousarray(np.asarray(points, float).reshape(-1, 3))
+    fi = np.asarray(frame_indices).reshape(-1)
+    pi = np.asarray(point_indices).reshape(-1)
+    obs = np.asarray(points_2D, float).reshape(-1, 2)
+    if fi.size != pi.size or obs.shape[0] != fi.size:
+        raise ValueError("filterPoints: points_2D, frame_indices and point_indices must have one row per observation")
+    if pi.size and (np.diff(pi) < 0).any():
+        raise ValueError("filterPoints: the observations are not point-major")
+    ctx = default_context()
+    dev = ctx.device
+    with np.errstate(all="ignore"):
+        cams = frameParameters(ext).reshape(len(ext), 6)
+    i32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.int32)).to(dev)
+    flt = ops.filter_observations(_dev(cams, dev), _dev(pts, dev), K, i32(fi), i32(pi), _dev(obs, dev), ctx=ctx, **thresholds)
+    pm = flt["point_map"].cpu().numpy()
+    return pts[pm], flt["obs"].cpu().numpy(), flt["fi"].cpu().numpy(), flt["pi"].cpu().numpy(), pm
+
+
+def refinePoints(frame_extrinsic_matrices, camera_intrinsic_matrix, points_3D, points_2D, frame_indices, point_indices,
+                 *, fixed_frames=None, verbose=2, **refine):
+    """adjustPoints, then the filter-and-re-adjust rounds of `refine_rounds` under the options of `refine_schedule`
+    -> (points [P',3], list of F 4x4 extrinsics, report): adjustPoints' return shape for the points that survived, plus the
+    report of refine_rounds with point_map, obs_map, obs_flags and pt_flags as NumPy arrays (the result objects and the
+    per-round filter outputs dropped).  fixed_frames: as in adjustPoints; their extrinsics come back as given."""
+    schedule = refine_schedule(**refine)
+    ctx = default_context()
+    dev = ctx.device
+    ext = np.asarray(frame_extrinsic_matrices, float)
+    F = len(ext)
+    pts0 = np.asarray(points_3D, float).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        cams0 = frameParameters(ext).reshape(F, 6)
+    fi = np.asarray(frame_indices, np.int64).reshape(-1)
+    order, F_free, fixed_d = np.arange(F), F, None
+    if fixed_frames is not None:
+        order, new_index, F_free = fixed_frame_order(fixed_frames, F)
+        if F_free == 0:
+            raise ValueError("fixed_frames: every frame is fixed (points-only refinement is not supported)")
+        fi = new_index[fi]
+        fixed_d = _dev(np.ascontiguousarray(cams0[order][F_free:]), dev)
+    pb = ops.BADevice(camera_intrinsic_matrix, fi.astype(np.int32), point_indices, points_2D, F_free, len(pts0), dev, ctx,
+                      fixed_cams=fixed_d)
+    res = SchurTRF(pb).solve(_dev(np.ascontiguousarray(cams0[order][:F_free]), dev), _dev(pts0, dev), ftol=1e-4, verbose=verbose)
+    rep = refine_rounds(pb, res, camera_intrinsic_matrix, schedule, verbose=verbose)
+    last = rep.pop("ba")
+    rep.pop("filters")
+    rep.pop("results")
+    cams = cams0.copy()
+    cams[order[:F_free]] = last.cams.cpu().numpy().reshape(F_free, 6)
+    pts = last.pts.cpu().numpy().reshape(-1, 3)
+    for k in ("point_map", "obs_map", "obs_flags", "pt_flags"):
+        rep[k] = rep[k].cpu().numpy()
+    x = np.concatenate([cams.reshape(-1), pts.reshape(-1)])
+    return reformatPointResult(BAResult(x=x), F, len(pts)) + (rep,)
+
+
 # ----------------------------------------------------------------------------------------------- pose-only refinement
 
 def _solve_lsq_trust_region_eig(lam, vg, V, Delta, m, initial_alpha, rtol=0.01, max_iter=10):

@@ -1297,6 +1297,109 @@ def trf_solve_batched(problems, cams_list, pts_list, ftol, xtol, gtol, max_nfev=
     return list(reps), [bool(a) for a in alone]
 
 
+OBS_REPROJ, OBS_BEHIND, OBS_NONFINITE, OBS_ORPHAN = 1, 2, 4, 8      # MM_OBS_* of include/meatmodeler.h
+PT_SHORT, PT_PARALLAX, PT_NONFINITE = 1, 2, 4                        # MM_PT_*
+FILTER_CHUNK = 1024                                                  # MM_FILTER_CHUNK: rows per chunk of the compaction's scans
+
+
+def filter_thresholds(max_reproj_px=math.inf, min_angle_deg=0, min_depth=-math.inf, min_views=2, what="filter_observations"):
+    """The thresholds of filter_observations as mm_filter_params; a NaN, a negative angle, min_views < 2 or no active test at
+    all (every threshold at its off value and min_views = 2) raises ValueError."""
+    try:
+        tau, ang, dep, mv = float(max_reproj_px), float(min_angle_deg), float(min_depth), int(min_views)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: max_reproj_px, min_angle_deg and min_depth must be numbers and min_views an integer") from None
+    if math.isnan(tau) or math.isnan(dep) or not ang >= 0 or not ang <= 180:
+        raise ValueError(f"{what}: thresholds must be numbers and min_angle_deg in 0 .. 180")
+    if mv < 2 or mv != min_views:
+        raise ValueError(f"{what}: min_views must be an integer of at least 2")
+    if tau == math.inf and ang == 0 and dep == -math.inf and mv == 2:
+        raise ValueError(f"{what}: no active test (give max_reproj_px, min_angle_deg, min_depth or min_views > 2)")
+    return _lib.FilterParams(mv, 0, tau, dep, math.cos(math.radians(ang)) if ang > 0 else 2.0)
+
+
+def filter_observations(cams, pts, K, fi, pi=None, obs=None, pt_ptr=None, max_reproj_px=math.inf, min_angle_deg=0,
+                        min_depth=-math.inf, min_views=2, ctx=None):
+    """Observations and points judged at an adjusted solution and the problem compacted (mm_filter_observations): cams [F, 6]
+    f64 (one row for every value fi takes: fixed cameras behind the free ones), pts [P, 3] f64, K 3 x 3 on the host, fi / pi [O]
+    i32 and obs [O, 2] f64 point-major (what flatten_tracks emits), optional pt_ptr [P+1] i32 -- device tensors; or a BADevice
+    in place of fi, which supplies the four of them.
+    An observation is flagged when its reprojection error exceeds max_reproj_px, its depth is <= min_depth or either is not
+    finite; a point when fewer than min_views observations survive, its parallax over the survivors is below min_angle_deg
+    (0: test off) or it is not finite; an unflagged observation of a flagged point is an orphan.
+    -> dict(fi [O'], pi [O'] (renumbered), obs [O', 2], obs_map [O'], point_map [P'] -- views of worst-case buffers, sized after
+    one host read of the counts --, n_obs, n_points, removed_obs (flagged by a test of their own), removed_points, obs_flags [O]
+    of OBS_* bits, pt_flags [P] of PT_* bits, err [O], depth [O], cos_parallax [P]).
+    Bad shapes or dtypes, indices out of range, observations that are not point-major and a call without an active test raise
+    ValueError before the library is called."""
+    name = "filter_observations"
+    prm = filter_thresholds(max_reproj_px, min_angle_deg, min_depth, min_views, name)
+    Kh = _host_f64(K, 9, f"{name}: K")
+    if not np.isfinite(Kh).all() or Kh[3] != 0 or Kh[6] != 0 or Kh[7] != 0 or Kh[8] != 1 or Kh[0] == 0 or Kh[4] == 0:
+        raise ValueError(f"{name}: K must be finite, upper triangular with K[2, 2] = 1 and non-zero focal lengths")
+    checked = False
+    if isinstance(fi, BADevice):
+        pb = fi
+        if pi is not None or obs is not None or pt_ptr is not None:
+            raise ValueError(f"{name}: a BADevice supplies fi, pi, obs and pt_ptr")
+        fi, pi, obs, pt_ptr = pb.fi, pb.pi, pb.obs, pb.pt_ptr
+        checked = pb.index_build == "native"      # (ranges and point-major order were judged by mm_ba_index_build)
+        ctx = ctx or pb.ctx
+    for what, t, dtype, tail in (("cams [F, 6] f64", cams, torch.float64, (6,)), ("pts [P, 3] f64", pts, torch.float64, (3,)),
+                                 ("fi [O] i32", fi, torch.int32, ()), ("pi [O] i32", pi, torch.int32, ()),
+                                 ("obs [O, 2] f64", obs, torch.float64, (2,))):
+        if not torch.is_tensor(t) or t.dtype != dtype or t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail:
+            raise ValueError(f"{name}: {what} expected")
+    F, P, O = cams.shape[0], pts.shape[0], fi.shape[0]
+    if checked and (F != pb.F + pb.F_fixed or P != pb.P):
+        raise ValueError(f"{name}: cams must have a row per camera of the BADevice (fixed ones included) and pts a row per point")
+    if pi.shape[0] != O or obs.shape[0] != O:
+        raise ValueError(f"{name}: fi, pi and obs must have one row per observation")
+    if O > 2 ** 31 - 1 or P >= 2 ** 31 - 1:
+        raise ValueError(f"{name}: more than 2^31 - 1 rows")
+    d = pts.device
+    if any(t.device != d for t in (cams, fi, pi, obs)) or (pt_ptr is not None and (not torch.is_tensor(pt_ptr) or pt_ptr.device != d)):
+        raise ValueError(f"{name}: every tensor must live on one device")
+    if pt_ptr is not None and (pt_ptr.dtype != torch.int32 or tuple(pt_ptr.shape) != (P + 1,)):
+        raise ValueError(f"{name}: pt_ptr [P+1] i32 expected")
+    if O and P and not checked:
+        lim = [fi.min(), fi.max(), pi.min(), pi.max(), (pi[1:] >= pi[:-1]).all()]
+        if pt_ptr is not None:
+            lim += [pt_ptr[0], pt_ptr[-1], (pt_ptr[1:] >= pt_ptr[:-1]).all()]
+        lim = torch.stack([v.long() for v in lim]).tolist()      # (one read-back)
+        if lim[0] < 0 or lim[1] >= F or lim[2] < 0 or lim[3] >= P:
+            raise ValueError(f"{name}: frame / point index out of range")
+        if not lim[4]:
+            raise ValueError(f"{name}: the observations are not point-major")
+        if pt_ptr is not None and (lim[5] != 0 or lim[6] != O or not lim[7]):
+            raise ValueError(f"{name}: pt_ptr is not a CSR over the observations")
+    elif O and not P:
+        raise ValueError(f"{name}: observations without points")
+    if pt_ptr is None:
+        pt_ptr = torch.searchsorted(pi, torch.arange(P + 1, dtype=torch.int32, device=d)).to(torch.int32)
+    ctx = ctx or default_context()
+    cams, pts, fi, pi, obs, pt_ptr = (t.contiguous() for t in (cams, pts, fi, pi, obs, pt_ptr))
+    i32, f64 = dict(dtype=torch.int32, device=d), dict(dtype=torch.float64, device=d)
+    obs_flags, err, depth = torch.zeros(O, **i32), torch.full((O,), math.nan, **f64), torch.full((O,), math.nan, **f64)
+    # (a call without observations launches nothing per row: every point is then short, as step 2 would find it)
+    pt_flags = torch.zeros(P, **i32) if O else torch.full((P,), PT_SHORT, **i32)
+    cosp = torch.full((P,), math.nan, **f64)
+    fi_out, pi_out, obs_map = torch.empty(O, **i32), torch.empty(O, **i32), torch.empty(O, **i32)
+    obs_out, point_map = torch.empty((O, 2), **f64), torch.empty(P, **i32)
+    counts = torch.zeros(4, dtype=torch.int64, device=d)
+    wsb = lib.mm_filter_workspace_bytes(F, P, O)
+    ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=d)
+    ctx.check(lib.mm_filter_observations(ctx.h, ptr(cams), F, ptr(pts), P, Kh.ctypes.data_as(_lib.c_f64p), ptr(fi), ptr(pi), ptr(obs),
+                                         O, ptr(pt_ptr), C.byref(prm), ptr(obs_flags), ptr(err), ptr(depth), ptr(pt_flags), ptr(cosp),
+                                         ptr(fi_out), ptr(pi_out), ptr(obs_out), ptr(obs_map), ptr(point_map), ptr(counts), ptr(ws),
+                                         ws.numel()), "mm_filter_observations")
+    n_obs, n_points, own, flagged = counts.tolist()      # (the one host read: it sizes the views)
+    flagged = flagged if O else P
+    return dict(fi=fi_out[:n_obs], pi=pi_out[:n_obs], obs=obs_out[:n_obs], obs_map=obs_map[:n_obs], point_map=point_map[:n_points],
+                n_obs=n_obs, n_points=n_points, removed_obs=own, removed_points=flagged, obs_flags=obs_flags, pt_flags=pt_flags,
+                err=err, depth=depth, cos_parallax=cosp)
+
+
 class MultiDot:
     """[<a, b> for (a, b) in pairs] in one launch (mm_multi_dot): returns a device tensor [k, 3] =
     (sum over i < split, sum over i >= split, total).  Holds the zero-initialised workspace."""

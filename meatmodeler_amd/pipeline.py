@@ -8,7 +8,9 @@ per frame (the reference gets them from calibrate / poseEstimation / adjustPose,
 `run(verify={...}, poses={...})`, K alone: the extrinsics are then recovered from the verified matches; with
 `run(resect={...})` every frame is registered once more against the triangulated points (a RANSAC resection, DESIGN.md 6f;
 `planar="auto"` adds the homography branch for coplanar points, 6g); with `run(align={...})` the cameras are registered to
-positions the caller knows and everything downstream runs in that frame and scale (a robust similarity).
+positions the caller knows and everything downstream runs in that frame and scale (a robust similarity); with
+`run(refine={...})` the adjustment's own result is judged -- every observation by its reprojection error and depth, every point
+by what it has left -- and what survives is adjusted again.
 """
 import ctypes as C
 import queue
@@ -20,7 +22,7 @@ import torch
 
 from . import _lib, ops, parallel
 from ._lib import lib, default_context, c_i32p, c_i64p, c_f32p, MMError
-from .bundleAdjuster import SchurTRF, frameParameters, _rodrigues_matrix
+from .bundleAdjuster import SchurTRF, frameParameters, _rodrigues_matrix, refine_schedule, refine_rounds, REFINE_KEYS
 from .orb_pattern import brief_pattern
 
 
@@ -109,6 +111,15 @@ def align_options(align, n_frames=None):
     if "tau" not in align and "tau_rel" not in align:
         align["tau_rel"] = 0.05
     return dict(frames=frames.astype(np.int64), centres=np.ascontiguousarray(centres), params=align)
+
+
+def refine_options(refine):
+    """`run(..., refine=)`: None (no filtering after the adjustment) or a dict of the options of bundleAdjuster.refine_schedule
+    ({} for the defaults): max_reproj_px, a number or one threshold per round with the last one repeated; min_angle_deg,
+    min_depth, min_views; rounds (default 2); ftol / max_nfev of the re-solves.  Returns the schedule as a dict; anything else
+    raises ValueError."""
+    refine = _stage_options("refine", refine, REFINE_KEYS)
+    return None if refine is None else refine_schedule(**refine)
 
 
 class ClipPipeline:
@@ -576,7 +587,7 @@ class ClipPipeline:
     # ------------------------------------------------------------------------------------------- whole clip
     def run(self, frames, K, extrinsics=None, ba=True, ftol=1e-4, verbose=0, dist=None, timers=None, max_nfev=None,
             force_collectives=False, triangulation="two_view", cull=None, verify=None, poses=None, resect=None, degeneracy=None,
-            guided=None, align=None):
+            guided=None, align=None, refine=None):
         """frames [F,H,W] u8 (device).  With `dist` = torch.distributed (initialised), frames are the FULL clip on
         every rank (synthetic input is generated locally) and the work is sharded as described in parallel.py.
         `max_nfev`: evaluation budget of the adjustment (None = SciPy's default, as adjustPoints).
@@ -625,13 +636,22 @@ class ClipPipeline:
         `resect` and the adjustment run in the target frame and scale; with `poses`, `poses["extrinsics"]` holds the image.
         The result gains `align` = dict(sim [13], cost, info [4], inlier [n]); timer "align".  If the adjustment runs, its
         cameras are registered to the same targets once more: `ba_aligned` = dict(extrinsics [F,3,4], points, sim, info);
-        `ba` itself is left as it is.  ALIGN_TOO_FEW or ALIGN_NO_MODEL: nothing is transformed, the flags say so."""
+        `ba` itself is left as it is.  ALIGN_TOO_FEW or ALIGN_NO_MODEL: nothing is transformed, the flags say so.
+        `refine`: None (default: nothing below runs) or the dict of `refine_options` ({} for the defaults; one rank only): after
+        the adjustment every observation is judged at the adjusted cameras and points and every point by the observations it
+        has left (ops.filter_observations); if anything is flagged, what survives is adjusted again from the same
+        cameras and the surviving points, up to `rounds` times.  The result gains `refine` = dict(ba = the last result,
+        point_map / obs_map into the rows of the first adjustment, rounds = [dict(max_reproj_px, n_obs, n_points, removed_obs,
+        removed_points, cost_in, cost_out, nfev, status)], obs_flags / pt_flags of the first round, filters = each round's
+        filter output, results = the result of each re-solve); timer "refine".  `ba` itself is left as it is; with `align`, `ba_aligned` is computed from the refined
+        result, so its points are those of `refine["point_map"]`."""
         verify = verify_options(verify)
         poses = pose_options(poses)
         resect = resect_options(resect)
         degeneracy = degeneracy_options(degeneracy)
         guided = guided_options(guided)
         align = align_options(align)
+        refine = refine_options(refine)
         if guided is not None and verify is None:
             raise ValueError("guided needs verify (it supplies each pair's fundamental matrix, the model the search is gated by): "
                              "pass verify={} for the defaults")
@@ -660,6 +680,8 @@ class ClipPipeline:
             raise ValueError("resect is not supported with more than one rank: every frame needs the whole point table")
         if align is not None and world > 1:
             raise ValueError("align is not supported with more than one rank: the cameras of `frames` live on different ranks")
+        if refine is not None and world > 1:
+            raise ValueError("refine is not supported with more than one rank: the compaction renumbers the points of one shard")
         if cull is not None:
             tests = {"max_reproj_px", "min_angle_deg", "min_depth"}
             unknown = set(cull) - tests - {"refine_iters"}
@@ -876,6 +898,11 @@ class ClipPipeline:
         toc("ba_solve")
         toc("ba")
         out.update(ba=res, n_obs_local=pb.O, cam_span=pb.cam_span, n_pairs=pb.n_pairs)
+        if refine is not None:
+            tic("refine")
+            out["refine"] = refine_rounds(pb, res, K, refine, verbose=verbose)
+            res = out["refine"]["ba"]
+            toc("refine")
         if align is not None:
             tic("align")
             cams_h = res.cams.reshape(F, 6).cpu().numpy()
