@@ -869,30 +869,30 @@ int mm_ba_schur(mm_ctx *ctx, const mm_ba_problem *pb, const double *cams, const 
                 size_t ws_bytes);
 /* partial sums and a descriptor per chunk, a counter per segment, a table row per camera, the slab flags (0 without chunks) */
 size_t mm_ba_schur_workspace_bytes(const mm_ba_problem *pb);
-/* Device-side construction of the pair list (needs fi, pi and the CSR by point in *pb):
- *   count: cnt[o] = number of observations o2 of o's point with camera(o2) <= camera(o); span_out[0] = widest camera
- *          distance inside a point (= cam_span);
- *   emit : after an exclusive scan of cnt (offsets), writes key = camera(o)*(span+1) + camera(o) - camera(o2) and the
- *          pair (o, o2) at offsets[o]...; a STABLE sort by key then yields the segments in a fixed order. */
-int mm_ba_pairs_count(mm_ctx *ctx, const mm_ba_problem *pb, int32_t *cnt /*dev [O]*/, int32_t *span_out /*dev [1]*/);
-int mm_ba_pairs_emit(mm_ctx *ctx, const mm_ba_problem *pb, const int64_t *offsets /*dev [O]*/, int span,
-                     int32_t *key /*dev [n]*/, int32_t *pair_o /*dev [n]*/, int32_t *pair_o2 /*dev [n]*/);
-/* All of the above in two native calls, for POINT-MAJOR observations (pi non-decreasing, as mm_flatten_tracks emits
- * them; pt_obs is then the identity).  Every array is what the count / scan / emit / stable sort construction yields,
- * byte for byte.
- *   stage 0: pt_ptr [P+1], pt_obs [O], cam_ptr [F+1], cam_obs [O] (stable by camera) and head [8] (dev):
- *            head[0] = cam_span, head[1] = number of pairs, head[2] != 0: an index out of range, head[3] != 0: not
- *            point-major.  With head[2] or head[3] set nothing else is valid.
+/* The index structures of a problem, built on the device in two calls: the CSR by point over all observations, the CSR
+ * by camera (stable) over the F free cameras, cam_span = the widest camera distance inside a point, and the pair list:
+ * every (o, o2) of one point with camera(o2) <= camera(o) < F, sorted STABLY by key = camera(o) * (cam_span + 1) +
+ * camera(o) - camera(o2) from the order o ascending, then o2 in pt_obs order; a segment per key, cut into chunks.
+ * Cameras F .. F + F_fixed - 1 are fixed (mm_ba_fixed): their observations count for the CSR by point only.
+ *   stage 0: pt_ptr [P+1], pt_obs [O], cam_ptr [F+1], cam_obs [O] and head [8] (dev): head[0] = cam_span, head[1] =
+ *            number of pairs (0: no free camera observes anything), head[2] != 0: an index outside 0 <= fi < F + F_fixed,
+ *            0 <= pi < P, head[3] != 0: not point-major, head[6] = n_free, the number of observations of free cameras:
+ *            cam_obs[:n_free] is the CSR's.  With head[2] or head[3] set nothing else is valid.
+ *            sort_by_point == 0 assumes POINT-MAJOR observations (pi non-decreasing, as mm_flatten_tracks emits them;
+ *            pt_obs is then the identity) and reports others in head[3]; the caller then runs stage 0 again with
+ *            sort_by_point != 0, which sorts (pi, identity) stably first and never sets head[3].
  *   stage 1: (the caller read head, set cam_span and n_pairs and allocated the pair arrays [n_pairs], seg_ids [seg_cap],
  *            seg_chunk_ptr [seg_cap + 1] and the chunk arrays [chunk_cap]: mm_ba_index_bounds)  the pair list in
  *            segment order, its segment and chunk tables, head[4] = n_seg, head[5] = n_chunks.  chunk = pairs per
- *            chunk, a multiple of 64.  Needs cam_span < F and F * (cam_span + 1) < 2^31.  ws0 is stage 0's workspace,
- *            untouched since.
+ *            chunk, a multiple of 64.  Needs n_pairs > 0, cam_span < F and F * (cam_span + 1) < 2^31.  ws0 is stage 0's
+ *            workspace, untouched since, and sort_by_point what stage 0 last ran with.
  * Workspaces (16-byte aligned): mm_ba_index_workspace_bytes(ctx, ix, stage); it asks the sort / scan library, which
  * needs the context's device, and returns 0 when it cannot. */
 typedef struct mm_ba_index {
     int32_t F, P;
     int64_t O;
+    int32_t F_fixed;                                /* cameras F .. F + F_fixed - 1 are observed but not optimised */
+    int32_t sort_by_point;                          /* != 0: the observations come in any order */
     const int32_t *fi, *pi;                         /* dev [O] */
     int32_t *pt_ptr, *pt_obs, *cam_ptr, *cam_obs;   /* dev, stage 0 */
     int64_t *head;                                  /* dev [8] */
@@ -1045,8 +1045,8 @@ int mm_ba_trf_batched(mm_ctx *ctx, int n_prob, const mm_ba_problem *const *pbs, 
  * (bundleAdjuster.py:180-192) over the FREE parameters [free cams | points] only: n = 6F + 3P, and every norm, scale and
  * termination test (|x| of the xtol test included) is over those n entries.  Fixed-camera observations enter the residual,
  * the cost, the point blocks C / g_p and the point half of J v -- not B, g_c, the pair list, S or cam_span.  So the CSR by
- * camera (cam_ptr / cam_obs) covers the F free cameras and the pair list (mm_ba_pairs_count / _emit on the free
- * observations) holds free-free pairs only.  The caller guarantees fi < F + F_fixed.
+ * camera (cam_ptr / cam_obs) covers the F free cameras and the pair list holds free-free pairs only (mm_ba_index_build
+ * with F_fixed makes both).  The caller guarantees fi < F + F_fixed.
  * fx == NULL or F_fixed == 0: exactly the call without _fixed. */
 typedef struct mm_ba_fixed {
     int32_t F_fixed;        /* observations with fi in [pb->F, pb->F + F_fixed) use these cameras */

@@ -38,8 +38,8 @@ class BAProblem(C.Structure):
 
 class BAIndex(C.Structure):
     """mm_ba_index: inputs and output arrays of mm_ba_index_build."""
-    _fields_ = [("F", C.c_int32), ("P", C.c_int32), ("O", C.c_int64), ("fi", vp), ("pi", vp),
-                ("pt_ptr", vp), ("pt_obs", vp), ("cam_ptr", vp), ("cam_obs", vp), ("head", vp),
+    _fields_ = [("F", C.c_int32), ("P", C.c_int32), ("O", C.c_int64), ("F_fixed", C.c_int32), ("sort_by_point", C.c_int32),
+                ("fi", vp), ("pi", vp), ("pt_ptr", vp), ("pt_obs", vp), ("cam_ptr", vp), ("cam_obs", vp), ("head", vp),
                 ("cam_span", C.c_int32), ("chunk", C.c_int32), ("n_pairs", C.c_int64),
                 ("pair_o", vp), ("pair_o2", vp), ("pair_p", vp), ("seg_ids", vp), ("seg_chunk_ptr", vp),
                 ("chunk_seg", vp), ("chunk_begin", vp), ("chunk_end", vp)]
@@ -211,8 +211,6 @@ SIGNATURES = {
     "mm_ba_jvp": (C.c_int, [vp, C.POINTER(BAProblem), vp, vp, vp, vp, vp]),
     "mm_ba_schur": (C.c_int, [vp, C.POINTER(BAProblem), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]),
     "mm_ba_schur_workspace_bytes": (C.c_size_t, [C.POINTER(BAProblem)]),
-    "mm_ba_pairs_count": (C.c_int, [vp, C.POINTER(BAProblem), vp, vp]),
-    "mm_ba_pairs_emit": (C.c_int, [vp, C.POINTER(BAProblem), vp, C.c_int, vp, vp, vp]),
     "mm_ba_index_bounds": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int, c_i64p, c_i64p]),
     "mm_ba_index_workspace_bytes": (C.c_size_t, [vp, C.POINTER(BAIndex), C.c_int]),
     "mm_ba_index_build": (C.c_int, [vp, C.POINTER(BAIndex), C.c_int, vp, C.c_size_t, vp, C.c_size_t]),

@@ -1,14 +1,15 @@
 // Index structures of a bundle-adjustment problem in two native calls (mm_ba_index_build, stage 0 and stage 1).
 //
-// What ops.BADevice used to assemble from ~25 torch operations and six host read-backs: the CSR by point, the CSR by camera
-// (stable order), the camera span, and -- for banded problems -- the co-observation pair list in segment order with its
-// segment and chunk tables.  Every array comes out byte for byte as the torch construction gives it:
+// The CSR by point, the CSR by camera (stable order), the camera span, and -- for banded problems -- the co-observation
+// pair list in segment order with its segment and chunk tables:
 //   * pairs in ascending key camera(o) * (span + 1) + camera(o) - camera(o2); inside a key in emission order (o ascending,
 //     then the point's observations in pt_obs order) -- what a stable sort of the emitted keys gives;
 //   * cam_obs = the stable order of the observations by camera.
-// The observations must be point-major (pi non-decreasing), as flatten_tracks emits them: pt_obs is then the identity and
-// pt_ptr follows from the places where pi changes.  Stage 0 reports whether they are (and whether every index is in
-// range) in its head; a caller with other input takes another path.
+// Cameras F .. F + F_fixed - 1 are fixed: their observations are in the CSR by point, but not in the CSR by camera (they
+// sort behind the free ones; head[6] says where) and in no pair.
+// Point-major observations (pi non-decreasing, as flatten_tracks emits them) make pt_obs the identity and pt_ptr the
+// places where pi changes.  Stage 0 assumes them and reports in its head whether they are (and whether every index is in
+// range); for other input the caller runs it again with sort_by_point set, which sorts (pi, identity) stably first.
 //
 // The two sorts are rocPRIM's radix sort (stable) over the bits that can be set only: the camera index (9 bits at 500
 // cameras instead of 32) and the pair key (16 bits at the bench shape: 500 cameras x span 87).  The pair sort carries
@@ -23,26 +24,30 @@
 
 namespace {
 
-constexpr int HEAD_SPAN = 0, HEAD_PAIRS = 1, HEAD_BAD_RANGE = 2, HEAD_NOT_POINT_MAJOR = 3, HEAD_SEG = 4, HEAD_CHUNKS = 5;
+constexpr int HEAD_SPAN = 0, HEAD_PAIRS = 1, HEAD_BAD_RANGE = 2, HEAD_NOT_POINT_MAJOR = 3, HEAD_SEG = 4, HEAD_CHUNKS = 5, HEAD_FREE = 6;
 
 __device__ __forceinline__ bool idx_ok(const int64_t *head) { return head[HEAD_BAD_RANGE] == 0 && head[HEAD_NOT_POINT_MAJOR] == 0; }
 
-// validity of the input; nothing else runs on input that fails here (every later kernel looks at the head first)
+// validity of the input; nothing else runs on input that fails here (every later kernel looks at the head first).
+// F_all counts the fixed cameras in.  identity (sort by point): receives 0 .. O - 1, and the order is not judged.
 __global__ __launch_bounds__(256) void idx_validate_kernel(const int32_t *__restrict__ fi, const int32_t *__restrict__ pi,
-                                                           int64_t O, int F, int P, int64_t *__restrict__ head) {
+                                                           int64_t O, int F_all, int P, int32_t *__restrict__ identity,
+                                                           int64_t *__restrict__ head) {
     const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
     bool bad = false, unsorted = false;
     if (o < O) {
         const int f = fi[o], p = pi[o];
-        bad = f < 0 || f >= F || p < 0 || p >= P;
-        unsorted = o > 0 && pi[o - 1] > p;
+        bad = f < 0 || f >= F_all || p < 0 || p >= P;
+        unsorted = !identity && o > 0 && pi[o - 1] > p;
+        if (identity) identity[o] = (int32_t)o;
     }
     if (__ballot(bad) != 0 && (threadIdx.x & 63) == 0) head[HEAD_BAD_RANGE] = 1;      // (any writer writes the same value)
     if (__ballot(unsorted) != 0 && (threadIdx.x & 63) == 0) head[HEAD_NOT_POINT_MAJOR] = 1;
 }
 
 // ptr [nbins + 1] of a CSR whose keys [n] are sorted: entry i opens the bins (keys[i - 1], keys[i]], the last one closes
-// the rest.  identity (optional) receives 0 .. n - 1.
+// the rest.  Keys >= nbins (fixed cameras) open no bin past ptr[nbins], which is then the number of keys < nbins.
+// identity (optional) receives 0 .. n - 1.
 __global__ __launch_bounds__(256) void idx_ptr_kernel(const int32_t *__restrict__ keys, int64_t n, int nbins,
                                                       int32_t *__restrict__ ptr, int32_t *__restrict__ identity,
                                                       const int64_t *__restrict__ head) {
@@ -51,29 +56,32 @@ __global__ __launch_bounds__(256) void idx_ptr_kernel(const int32_t *__restrict_
     if (i >= n) return;
     const int k = keys[i];
     const int lo = i == 0 ? 0 : keys[i - 1] + 1;
-    for (int b = lo; b <= k; ++b) ptr[b] = (int32_t)i;
+    for (int b = lo; b <= min(k, nbins); ++b) ptr[b] = (int32_t)i;
     if (i == n - 1)
         for (int b = k + 1; b <= nbins; ++b) ptr[b] = (int32_t)n;
     if (identity) identity[i] = (int32_t)i;
 }
 
-// cnt[o] = number of observations o2 of the same point with camera(o2) <= camera(o); span = max camera distance
-// (pt_obs is the identity: the observations of point p are pt_ptr[p] .. pt_ptr[p + 1])
+// cnt[o] = number of observations o2 of the same point with camera(o2) <= camera(o); span = max camera distance.
+// The observations of point p are pt_obs[pt_ptr[p] .. pt_ptr[p + 1]]; IDENT: pt_obs is the identity and is not read.
+// An observation of a fixed camera (f >= F) has no pairs and no span; as o2 it drops out by d < 0.
+template <bool IDENT>
 __global__ __launch_bounds__(256) void idx_count_kernel(const int32_t *__restrict__ fi, const int32_t *__restrict__ pi,
-                                                        const int32_t *__restrict__ pt_ptr, int64_t O,
-                                                        int32_t *__restrict__ cnt, int32_t *__restrict__ span_out,
-                                                        const int64_t *__restrict__ head) {
+                                                        const int32_t *__restrict__ pt_ptr, const int32_t *__restrict__ pt_obs,
+                                                        int64_t O, int F, int32_t *__restrict__ cnt,
+                                                        int32_t *__restrict__ span_out, const int64_t *__restrict__ head) {
     if (!idx_ok(head)) return;
     const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
     int dmax = 0;
     if (o < O) {
         const int f = fi[o], p = pi[o];
         int c = 0;
-        for (int e = pt_ptr[p]; e < pt_ptr[p + 1]; ++e) {
-            const int d = f - fi[e];
-            c += d >= 0;
-            dmax = max(dmax, d);
-        }
+        if (f < F)
+            for (int e = pt_ptr[p]; e < pt_ptr[p + 1]; ++e) {
+                const int d = f - fi[IDENT ? e : pt_obs[e]];
+                c += d >= 0;
+                dmax = max(dmax, d);
+            }
         cnt[o] = c;
     }
     for (int off = 32; off > 0; off >>= 1) dmax = max(dmax, __shfl_down(dmax, off, 64));
@@ -81,29 +89,35 @@ __global__ __launch_bounds__(256) void idx_count_kernel(const int32_t *__restric
 }
 
 __global__ void idx_head0_kernel(const int32_t *__restrict__ cnt, const int64_t *__restrict__ offs, int64_t O,
-                                 const int32_t *__restrict__ span, int64_t *__restrict__ head) {
+                                 const int32_t *__restrict__ span, const int32_t *__restrict__ cam_ptr, int F,
+                                 int64_t *__restrict__ head) {
     if (!idx_ok(head)) return;
     head[HEAD_SPAN] = *span;
     head[HEAD_PAIRS] = offs[O - 1] + cnt[O - 1];
+    head[HEAD_FREE] = cam_ptr[F];
 }
 
 // the pairs of observation o at offs[o] ..: key = camera(o) * (span + 1) + camera(o) - camera(o2), value = o2 << 32 | o
+// (IDENT and fixed cameras as in idx_count_kernel)
+template <bool IDENT>
 __global__ __launch_bounds__(256) void idx_emit_kernel(const int32_t *__restrict__ fi, const int32_t *__restrict__ pi,
-                                                       const int32_t *__restrict__ pt_ptr, int64_t O,
-                                                       const int64_t *__restrict__ offs, int span, int64_t n_pairs,
-                                                       int32_t *__restrict__ key, uint64_t *__restrict__ val,
+                                                       const int32_t *__restrict__ pt_ptr, const int32_t *__restrict__ pt_obs,
+                                                       int64_t O, int F, const int64_t *__restrict__ offs, int span,
+                                                       int64_t n_pairs, int32_t *__restrict__ key, uint64_t *__restrict__ val,
                                                        const int64_t *__restrict__ head) {
     if (!idx_ok(head)) return;
     const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (o >= O) return;
     const int f = fi[o], p = pi[o];
+    if (f >= F) return;
     int64_t w = offs[o];
     for (int e = pt_ptr[p]; e < pt_ptr[p + 1]; ++e) {
-        const int d = f - fi[e];
+        const int o2 = IDENT ? e : pt_obs[e];
+        const int d = f - fi[o2];
         if (d < 0) continue;
         if (w >= n_pairs) return;      // (cannot happen with the n_pairs stage 0 reported; keeps a wrong one inside the arrays)
         key[w] = f * (span + 1) + min(d, span);      // (min: a span smaller than the truth cannot make a key past F (span + 1))
-        val[w] = ((uint64_t)(uint32_t)e << 32) | (uint32_t)o;
+        val[w] = ((uint64_t)(uint32_t)o2 << 32) | (uint32_t)o;
         ++w;
     }
 }
@@ -177,11 +191,20 @@ struct Ws1 {
     size_t key, val, key_s, val_s, counts, n_seg, pairs_of, chunks_of, seg_lo, tmp, tmp_bytes, total;
 };
 
-hipError_t ws0_layout(int F, int64_t O, hipStream_t st, Ws0 &w) {
-    size_t t_sort = 0, t_scan = 0;
+// keys holds the sorted point indices (sort by point) until pt_ptr is made of them, then the sorted camera indices; cnt
+// holds the identity the two sorts carry (sort by point) until the count kernel writes it
+hipError_t ws0_layout(const mm_ba_index *ix, hipStream_t st, Ws0 &w) {
+    const int64_t O = ix->O;
+    size_t t_sort = 0, t_sort_p = 0, t_scan = 0;
     hipError_t e = rocprim::radix_sort_pairs(nullptr, t_sort, (const int32_t *)nullptr, (int32_t *)nullptr, (const int32_t *)nullptr,
-                                             (int32_t *)nullptr, (size_t)O, 0u, (unsigned)bits_for(F), st);
+                                             (int32_t *)nullptr, (size_t)O, 0u, (unsigned)bits_for((int64_t)ix->F + ix->F_fixed), st);
     if (e != hipSuccess) return e;
+    if (ix->sort_by_point) {
+        e = rocprim::radix_sort_pairs(nullptr, t_sort_p, (const int32_t *)nullptr, (int32_t *)nullptr, (const int32_t *)nullptr,
+                                      (int32_t *)nullptr, (size_t)O, 0u, (unsigned)bits_for(ix->P), st);
+        if (e != hipSuccess) return e;
+        if (t_sort_p > t_sort) t_sort = t_sort_p;
+    }
     e = rocprim::exclusive_scan(nullptr, t_scan, (const int32_t *)nullptr, (int64_t *)nullptr, (int64_t)0, (size_t)O,
                                 rocprim::plus<int64_t>(), st);
     if (e != hipSuccess) return e;
@@ -225,7 +248,8 @@ hipError_t ws1_layout(int64_t n_pairs, int64_t seg_cap, int key_bits, hipStream_
 }
 
 bool index_args_ok(const mm_ba_index *ix) {
-    return ix && ix->F > 0 && ix->P > 0 && ix->O > 0 && ix->O < 0x7fffffffLL && ix->fi && ix->pi && ix->head;
+    return ix && ix->F >= 0 && ix->F_fixed >= 0 && (int64_t)ix->F + ix->F_fixed > 0 && (int64_t)ix->F + ix->F_fixed < 0x7fffffffLL &&
+           ix->P > 0 && ix->O > 0 && ix->O < 0x7fffffffLL && ix->fi && ix->pi && ix->head;
 }
 bool band_ok(const mm_ba_index *ix) {      // the condition under which ops.BADevice builds a pair list
     return ix->cam_span >= 0 && ix->cam_span < ix->F && (int64_t)ix->F * (ix->cam_span + 1) < 0x80000000LL && ix->n_pairs > 0 &&
@@ -248,7 +272,7 @@ size_t mm_ba_index_workspace_bytes(mm_ctx *ctx, const mm_ba_index *ix, int stage
     if (!ctx || !index_args_ok(ix)) return 0;
     if (stage == 0) {
         Ws0 w;
-        return ws0_layout(ix->F, ix->O, ctx->stream, w) == hipSuccess ? w.total : 0;
+        return ws0_layout(ix, ctx->stream, w) == hipSuccess ? w.total : 0;
     }
     if (stage != 1 || !band_ok(ix)) return 0;
     int64_t seg_cap, chunk_cap;
@@ -263,9 +287,11 @@ int mm_ba_index_build(mm_ctx *ctx, const mm_ba_index *ix, int stage, void *ws0, 
         return mm_fail(ctx, MM_ERR_ARG, "mm_ba_index_build: bad argument");
     const int64_t O = ix->O;
     const unsigned gO = (unsigned)((O + 255) / 256);
+    const int F_all = ix->F + ix->F_fixed;
+    const bool ident = !ix->sort_by_point;
     hipStream_t st = ctx->stream;
     Ws0 w0;
-    MM_HIP(ctx, ws0_layout(ix->F, O, st, w0));
+    MM_HIP(ctx, ws0_layout(ix, st, w0));
     if (ws0_bytes < w0.total) return mm_fail(ctx, MM_ERR_WORKSPACE, "mm_ba_index_build: stage 0 workspace too small");
     uint8_t *b0 = (uint8_t *)ws0;
     int32_t *keys = (int32_t *)(b0 + w0.keys), *cnt = (int32_t *)(b0 + w0.cnt), *span = (int32_t *)(b0 + w0.span);
@@ -273,22 +299,31 @@ int mm_ba_index_build(mm_ctx *ctx, const mm_ba_index *ix, int stage, void *ws0, 
     if (stage == 0) {
         MM_HIP(ctx, hipMemsetAsync(ix->head, 0, 8 * sizeof(int64_t), st));
         MM_HIP(ctx, hipMemsetAsync(span, 0, sizeof(int32_t), st));
-        MM_LAUNCH(ctx, "idx_validate_kernel", idx_validate_kernel, dim3(gO), dim3(256), 0, ix->fi, ix->pi, O, ix->F, ix->P, ix->head);
-        MM_LAUNCH(ctx, "idx_ptr_kernel", idx_ptr_kernel, dim3(gO), dim3(256), 0, ix->pi, O, ix->P, ix->pt_ptr, ix->pt_obs,
-                  (const int64_t *)ix->head);
-        // cam_obs: the identity carried through a stable sort of the camera indices (garbage, but in bounds, on bad input)
+        MM_LAUNCH(ctx, "idx_validate_kernel", idx_validate_kernel, dim3(gO), dim3(256), 0, ix->fi, ix->pi, O, F_all, ix->P,
+                  ident ? (int32_t *)nullptr : cnt, ix->head);
         size_t tb = w0.tmp_bytes;
-        MM_HIP(ctx, rocprim::radix_sort_pairs((void *)(b0 + w0.tmp), tb, ix->fi, keys, (const int32_t *)ix->pt_obs, ix->cam_obs,
-                                              (size_t)O, 0u, (unsigned)bits_for(ix->F), st));
+        if (ident) {
+            MM_LAUNCH(ctx, "idx_ptr_kernel", idx_ptr_kernel, dim3(gO), dim3(256), 0, ix->pi, O, ix->P, ix->pt_ptr, ix->pt_obs,
+                      (const int64_t *)ix->head);
+        } else {      // pt_obs: the identity carried through a stable sort of the point indices
+            MM_HIP(ctx, rocprim::radix_sort_pairs((void *)(b0 + w0.tmp), tb, ix->pi, keys, (const int32_t *)cnt, ix->pt_obs, (size_t)O, 0u,
+                                                  (unsigned)bits_for(ix->P), st));
+            MM_LAUNCH(ctx, "idx_ptr_kernel", idx_ptr_kernel, dim3(gO), dim3(256), 0, (const int32_t *)keys, O, ix->P, ix->pt_ptr,
+                      (int32_t *)nullptr, (const int64_t *)ix->head);
+            tb = w0.tmp_bytes;
+        }
+        // cam_obs: the same through a stable sort of the camera indices (garbage, but in bounds, on bad input)
+        MM_HIP(ctx, rocprim::radix_sort_pairs((void *)(b0 + w0.tmp), tb, ix->fi, keys, (const int32_t *)(ident ? ix->pt_obs : cnt),
+                                              ix->cam_obs, (size_t)O, 0u, (unsigned)bits_for(F_all), st));
         MM_LAUNCH(ctx, "idx_ptr_kernel", idx_ptr_kernel, dim3(gO), dim3(256), 0, (const int32_t *)keys, O, ix->F, ix->cam_ptr,
                   (int32_t *)nullptr, (const int64_t *)ix->head);
-        MM_LAUNCH(ctx, "idx_count_kernel", idx_count_kernel, dim3(gO), dim3(256), 0, ix->fi, ix->pi, (const int32_t *)ix->pt_ptr, O,
-                  cnt, span, (const int64_t *)ix->head);
+        MM_LAUNCH(ctx, "idx_count_kernel", (ident ? idx_count_kernel<true> : idx_count_kernel<false>), dim3(gO), dim3(256), 0, ix->fi,
+                  ix->pi, (const int32_t *)ix->pt_ptr, (const int32_t *)ix->pt_obs, O, ix->F, cnt, span, (const int64_t *)ix->head);
         tb = w0.tmp_bytes;
         MM_HIP(ctx, rocprim::exclusive_scan((void *)(b0 + w0.tmp), tb, (const int32_t *)cnt, offs, (int64_t)0, (size_t)O,
                                             rocprim::plus<int64_t>(), st));
         MM_LAUNCH(ctx, "idx_head0_kernel", idx_head0_kernel, dim3(1), dim3(1), 0, (const int32_t *)cnt, (const int64_t *)offs, O,
-                  (const int32_t *)span, ix->head);
+                  (const int32_t *)span, (const int32_t *)ix->cam_ptr, ix->F, ix->head);
         return MM_OK;
     }
     if (stage != 1) return mm_fail(ctx, MM_ERR_ARG, "mm_ba_index_build: stage must be 0 or 1");
@@ -311,8 +346,9 @@ int mm_ba_index_build(mm_ctx *ctx, const mm_ba_index *ix, int stage, void *ws0, 
     // (a pair the emit kernel did not reach -- n_pairs larger than the truth -- must still be an index inside the arrays)
     MM_HIP(ctx, hipMemsetAsync(key, 0, (size_t)n * 4, st));
     MM_HIP(ctx, hipMemsetAsync(val, 0, (size_t)n * 8, st));
-    MM_LAUNCH(ctx, "idx_emit_kernel", idx_emit_kernel, dim3(gO), dim3(256), 0, ix->fi, ix->pi, (const int32_t *)ix->pt_ptr, O,
-              (const int64_t *)offs, ix->cam_span, n, key, val, (const int64_t *)ix->head);
+    MM_LAUNCH(ctx, "idx_emit_kernel", (ident ? idx_emit_kernel<true> : idx_emit_kernel<false>), dim3(gO), dim3(256), 0, ix->fi, ix->pi,
+              (const int32_t *)ix->pt_ptr, (const int32_t *)ix->pt_obs, O, ix->F, (const int64_t *)offs, ix->cam_span, n, key, val,
+              (const int64_t *)ix->head);
     size_t tb = w1.tmp_bytes;
     MM_HIP(ctx, rocprim::radix_sort_pairs((void *)(b1 + w1.tmp), tb, (const int32_t *)key, key_s, (const uint64_t *)val, val_s, (size_t)n,
                                           0u, (unsigned)key_bits, st));

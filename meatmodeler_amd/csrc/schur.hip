@@ -666,70 +666,7 @@ __global__ void slab_flag_kernel(int32_t *flags, int s) {
     __hip_atomic_store(flags + s, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// ---- device-side construction of the co-observation pair list ------------------------------------------------------
-// cnt[o] = number of observations o2 of the same point with camera(o2) <= camera(o); span = max camera distance.
-__global__ __launch_bounds__(256) void pairs_count_kernel(mm_ba_problem pb, int32_t *__restrict__ cnt,
-                                                          int32_t *__restrict__ span_out) {
-    const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    int dmax = 0;
-    if (o < pb.O) {
-        const int f = pb.fi[o], p = pb.pi[o];
-        int c = 0;
-        for (int e = pb.pt_ptr[p]; e < pb.pt_ptr[p + 1]; ++e) {
-            const int d = f - pb.fi[pb.pt_obs[e]];
-            c += d >= 0;
-            dmax = max(dmax, d);
-        }
-        cnt[o] = c;
-    }
-    for (int off = 32; off > 0; off >>= 1) dmax = max(dmax, __shfl_down(dmax, off, 64));
-    // (a returning atomic on ONE word per wave is ~11 ns each behind one another -- 22 k waves: 0.25 ms; nearly every wave finds the
-    // maximum already there)
-    if ((threadIdx.x & 63) == 0 && dmax > __hip_atomic_load(span_out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(span_out, dmax);
-}
-
-// writes the pairs of observation o at offsets[o]..: key = camera(o) * (span + 1) + camera(o) - camera(o2)
-__global__ __launch_bounds__(256) void pairs_emit_kernel(mm_ba_problem pb, const int64_t *__restrict__ offsets, int span,
-                                                         int32_t *__restrict__ key, int32_t *__restrict__ po,
-                                                         int32_t *__restrict__ po2) {
-    const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (o >= pb.O) return;
-    const int f = pb.fi[o], p = pb.pi[o];
-    int64_t w = offsets[o];
-    for (int e = pb.pt_ptr[p]; e < pb.pt_ptr[p + 1]; ++e) {
-        const int o2 = pb.pt_obs[e];
-        const int d = f - pb.fi[o2];
-        if (d < 0) continue;
-        key[w] = f * (span + 1) + d;
-        po[w] = (int32_t)o;
-        po2[w] = o2;
-        ++w;
-    }
-}
-
 }  // namespace
-
-extern "C" int mm_ba_pairs_count(mm_ctx *ctx, const mm_ba_problem *pb, int32_t *cnt, int32_t *span_out) {
-    if (!ctx) return MM_ERR_ARG;
-    if (!pb || !cnt || !span_out || (pb->O > 0 && (!pb->fi || !pb->pi || !pb->pt_ptr || !pb->pt_obs)))
-        return mm_fail(ctx, MM_ERR_ARG, "mm_ba_pairs_count: bad argument");
-    MM_HIP(ctx, hipMemsetAsync(span_out, 0, sizeof(int32_t), ctx->stream));
-    if (pb->O == 0) return MM_OK;
-    MM_LAUNCH(ctx, "pairs_count_kernel", pairs_count_kernel, dim3((unsigned)((pb->O + 255) / 256)), dim3(256), 0, *pb, cnt,
-              span_out);
-    return MM_OK;
-}
-
-extern "C" int mm_ba_pairs_emit(mm_ctx *ctx, const mm_ba_problem *pb, const int64_t *offsets, int span, int32_t *key,
-                                int32_t *pair_o, int32_t *pair_o2) {
-    if (!ctx) return MM_ERR_ARG;
-    if (!pb || !offsets || !key || !pair_o || !pair_o2 || span < 0) return mm_fail(ctx, MM_ERR_ARG, "mm_ba_pairs_emit: bad argument");
-    if (pb->O == 0) return MM_OK;
-    if ((int64_t)pb->F * (span + 1) > 0x7fffffffLL) return mm_fail(ctx, MM_ERR_ARG, "mm_ba_pairs_emit: F * (span + 1) overflows the key");
-    MM_LAUNCH(ctx, "pairs_emit_kernel", pairs_emit_kernel, dim3((unsigned)((pb->O + 255) / 256)), dim3(256), 0, *pb, offsets,
-              span, key, pair_o, pair_o2);
-    return MM_OK;
-}
 
 // ---- plan and entry points ----------------------------------------------------------------------------------------------
 namespace {

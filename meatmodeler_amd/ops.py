@@ -757,14 +757,11 @@ def ba_build_index(F, P, fi, pi):
 class BADevice:
     """Device-resident BA problem: observation arrays, CSR indices and the mm_ba_problem descriptor."""
 
-    def __init__(self, K, fi, pi, obs, F, P, device, ctx=None, pairs=True, max_band_span=192, fixed_cams=None,
-                 native_index=True):
+    def __init__(self, K, fi, pi, obs, F, P, device, ctx=None, pairs=True, max_band_span=192, fixed_cams=None):
         """fi, pi: int [O] (numpy or device tensors), obs [O,2] f64 (numpy or device tensor).  All index structures
-        (CSR by point, CSR by camera, co-observation pair list and its chunk table) are built on the device, by
-        mm_ba_index_build (two native calls, two host read-backs) for the plain case: point-major observations and no
-        fixed cameras.  Problems with fixed_cams, observations that are not point-major and native_index=False take the
-        earlier construction, in which torch provides the sorts / scans and two HIP kernels enumerate the pairs; both
-        give the same arrays byte for byte (tests/test_ba_index_gpu.py).
+        (CSR by point, CSR by camera, co-observation pair list and its chunk table) are built on the device by
+        mm_ba_index_build: two native calls with a host read-back each, and one more of each for observations that are
+        not point-major (self.point_major says whether they are).
 
         fixed_cams: [F_fixed, 6] f64 device tensor of cameras that are observed but not optimised (mm_ba_fixed):
         fi in [F, F + F_fixed) is fixed camera fi - F.  The CSR by camera and the pair list then cover the F free
@@ -794,10 +791,9 @@ class BADevice:
             if self.F_fixed:
                 self.fixed_cams = fixed_cams.contiguous()
                 self.fx = _lib.BAFixed(self.F_fixed, 0, ptr(self.fixed_cams))
-        F_all = F + self.F_fixed
         self.cam_span = 0
         self.max_band_span = int(max_band_span)
-        self._slabs, self._slab_src = None, None
+        self._slabs = None
         self.n_pairs = 0
         # build + solve overlapped on two streams (mm_ba_schur_solve).  Needs concurrent kernel execution: tools that
         # serialise kernels (rocprofv3 --pmc, launch-blocking debug modes) make the consumer wait for a producer that
@@ -806,11 +802,16 @@ class BADevice:
         # their CUs (one wave per SIMD), the build slows down by 1.6x beside them and build-then-solve (0.32 + 0.59 ms at
         # 500 cameras) beats the overlapped pair (0.93 ms).  MM_SCHUR_OVERLAP=1 selects the overlapped path.
         self.overlap = os.environ.get("MM_SCHUR_OVERLAP", "0") != "0"
-        self.index_build = "torch"
-        if native_index and O and F > 0 and P > 0 and not self.F_fixed and self._build_index_native(pairs):
-            self.index_build = "native"
-        else:
-            self._build_index_torch(pairs, F_all)
+        if O and F + self.F_fixed > 0 and P > 0:
+            self._build_index(pairs)
+        elif O:
+            raise ValueError("frame / point index out of range")
+        else:      # no observations: empty CSRs, no pair list
+            i32 = dict(dtype=torch.int32, device=dev)
+            self.point_major = True
+            self.pt_ptr, self.pt_obs = torch.zeros(P + 1, **i32), torch.zeros(0, **i32)
+            self.cam_ptr, self.cam_obs = torch.zeros(F + 1, **i32), torch.zeros(0, **i32)
+            self._set_problem()
         self._ws = torch.empty(2048 * 8, dtype=torch.uint8, device=dev)
         self._cost2 = torch.zeros(1, dtype=torch.float64, device=dev)
         self._S = None  # reduced camera system, allocated once (6F x 6F doubles)
@@ -826,28 +827,27 @@ class BADevice:
     @property
     def slabs(self):
         """Camera slabs for the overlapped build + solve (mm_ba_schur_solve): first segment / chunk of each slab, or
-        None.  The native index build leaves them to the first reader (two more host read-backs; the path that wants
-        them, MM_SCHUR_OVERLAP=1, is off by default)."""
-        if self._slabs is None and self._slab_src is not None:
-            seg_ids, seg_chunk_ptr = self._slab_src
-            self._slab_src = None
-            self._set_slabs(seg_ids.to(torch.int64), seg_chunk_ptr.to(torch.int64))
-        return self._slabs
-
-    def _set_slabs(self, seg_ids, seg_chunk_ptr):
+        None.  Left to the first reader (two more host read-backs; the path that wants them, MM_SCHUR_OVERLAP=1, is off
+        by default)."""
         n_slabs = 8
         cps = -(-self.F // n_slabs)
-        if cps >= 16:
-            seg_cam = seg_ids // (self.cam_span + 1)
+        if self._slabs is None and self.n_pairs and cps >= 16:
+            seg_cam = self.seg_ids.to(torch.int64) // (self.cam_span + 1)
             bounds = torch.arange(n_slabs + 1, dtype=torch.int64, device=self.device) * cps
             sseg = torch.searchsorted(seg_cam, bounds)
-            schunk = seg_chunk_ptr[sseg]
+            schunk = self.seg_chunk_ptr.to(torch.int64)[sseg]
             self._slabs = (n_slabs, cps, np.ascontiguousarray(sseg.cpu().numpy(), np.int64),
                            np.ascontiguousarray(schunk.cpu().numpy(), np.int64))
+        return self._slabs
+
+    def _set_problem(self):
+        """The problem descriptor over the observation arrays and the two CSRs, without a pair list."""
+        self.pb = BAProblem(self.F, self.P, self.O, ptr(self.K), ptr(self.fi), ptr(self.pi), ptr(self.obs),
+                            ptr(self.pt_ptr), ptr(self.pt_obs), ptr(self.cam_ptr), ptr(self.cam_obs),
+                            self.cam_span, 0, 0, None, None, 0, None, None, None, None, None, None)
 
     def _set_pair_list(self, pair_o, pair_o2, pair_p, seg_ids, seg_chunk_ptr, chunk_seg, chunk_begin, chunk_end):
-        """Keeps the co-observation pair list (int32 device tensors, whichever builder made them) and points the problem
-        descriptor at it."""
+        """Keeps the co-observation pair list (int32 device tensors) and points the problem descriptor at it."""
         self.pair_o, self.pair_o2, self.pair_p = pair_o, pair_o2, pair_p
         self.seg_ids, self.seg_chunk_ptr = seg_ids, seg_chunk_ptr
         self.chunk_seg, self.chunk_begin, self.chunk_end = chunk_seg, chunk_begin, chunk_end
@@ -858,34 +858,38 @@ class BADevice:
         self.pb.chunk_seg, self.pb.chunk_begin, self.pb.chunk_end = ptr(chunk_seg), ptr(chunk_begin), ptr(chunk_end)
         self.pb.pair_o, self.pb.pair_o2, self.pb.pair_p = ptr(pair_o), ptr(pair_o2), ptr(pair_p)
 
-    def _build_index_native(self, pairs):
-        """mm_ba_index_build.  -> False (nothing set) when the observations are not point-major."""
+    def _build_index(self, pairs):
+        """mm_ba_index_build: stage 0 (again with the sort by point when the observations are not point-major), and for a
+        banded problem stage 1."""
         F, P, O, dev = self.F, self.P, self.O, self.device
         i32 = dict(dtype=torch.int32, device=dev)
         pt_ptr, pt_obs = torch.empty(P + 1, **i32), torch.empty(O, **i32)
         cam_ptr, cam_obs = torch.empty(F + 1, **i32), torch.empty(O, **i32)
         head = torch.empty(8, dtype=torch.int64, device=dev)
-        ix = _lib.BAIndex(F, P, O, ptr(self.fi), ptr(self.pi), ptr(pt_ptr), ptr(pt_obs), ptr(cam_ptr), ptr(cam_obs), ptr(head),
-                          0, self._chunk_pairs(), 0, None, None, None, None, None, None, None, None)
-        ws0b = lib.mm_ba_index_workspace_bytes(self.ctx.h, C.byref(ix), 0)
-        if not ws0b:
-            raise _lib.MMError("mm_ba_index_workspace_bytes: no workspace size for stage 0")
-        ws0 = torch.empty(ws0b, dtype=torch.uint8, device=dev)
-        self.ctx.check(lib.mm_ba_index_build(self.ctx.h, C.byref(ix), 0, ptr(ws0), ws0b, None, 0), "mm_ba_index_build")
-        span, n, bad_range, not_point_major = head[:4].tolist()      # read-back 1 of 2
+        ix = _lib.BAIndex(F, P, O, self.F_fixed, 0, ptr(self.fi), ptr(self.pi), ptr(pt_ptr), ptr(pt_obs), ptr(cam_ptr), ptr(cam_obs),
+                          ptr(head), 0, self._chunk_pairs(), 0, None, None, None, None, None, None, None, None)
+
+        def stage0():
+            ws0b = lib.mm_ba_index_workspace_bytes(self.ctx.h, C.byref(ix), 0)
+            if not ws0b:
+                raise _lib.MMError("mm_ba_index_workspace_bytes: no workspace size for stage 0")
+            ws0 = torch.empty(ws0b, dtype=torch.uint8, device=dev)
+            self.ctx.check(lib.mm_ba_index_build(self.ctx.h, C.byref(ix), 0, ptr(ws0), ws0b, None, 0), "mm_ba_index_build")
+            return ws0, ws0b, head[:7].tolist()      # read-back 1 of 2
+
+        ws0, ws0b, (span, n, bad_range, not_point_major, _, _, n_free) = stage0()
         if bad_range:
             raise ValueError("frame / point index out of range")
-        if not_point_major:
-            return False
-        self.pt_ptr, self.pt_obs, self.cam_ptr, self.cam_obs = pt_ptr, pt_obs, cam_ptr, cam_obs
+        self.point_major = not not_point_major
+        if not_point_major:      # (one more read-back, for input that flatten_tracks did not make)
+            ix.sort_by_point = 1
+            ws0, ws0b, (span, n, _, _, _, _, n_free) = stage0()
+        self.pt_ptr, self.pt_obs, self.cam_ptr, self.cam_obs = pt_ptr, pt_obs, cam_ptr, cam_obs[:n_free]
         self.cam_span = int(span)
-        self.pb = BAProblem(F, P, O, ptr(self.K), ptr(self.fi), ptr(self.pi), ptr(self.obs),
-                            ptr(self.pt_ptr), ptr(self.pt_obs), ptr(self.cam_ptr), ptr(self.cam_obs),
-                            self.cam_span, 0, 0, None, None, 0, None, None, None, None, None, None)
+        self._set_problem()
         # banded problems: co-observation pair list for the atomic-free, bitwise reproducible Schur kernel;
         # wide spans keep the general kernel
-        if pairs and self.cam_span <= self.max_band_span and self.cam_span < F and F * (self.cam_span + 1) < 2 ** 31:
-            n = int(n)
+        if pairs and n and self.cam_span <= self.max_band_span and self.cam_span < F and F * (self.cam_span + 1) < 2 ** 31:
             seg_cap, chunk_cap = C.c_int64(0), C.c_int64(0)
             lib.mm_ba_index_bounds(F, self.cam_span, n, ix.chunk, C.byref(seg_cap), C.byref(chunk_cap))
             seg_cap, chunk_cap = seg_cap.value, chunk_cap.value
@@ -904,99 +908,6 @@ class BADevice:
             n_seg, n_chunks = head[4:6].tolist()      # read-back 2 of 2 (the workspaces are free to go after it)
             self._set_pair_list(pair_o, pair_o2, pair_p, seg_ids[:n_seg], seg_chunk_ptr[:n_seg + 1], chunk_seg[:n_chunks],
                                 chunk_begin[:n_chunks], chunk_end[:n_chunks])
-            self._slab_src = (self.seg_ids, self.seg_chunk_ptr)
-        return True
-
-    def _build_index_torch(self, pairs, F_all):
-        """The construction from torch sorts / scans and the two pair kernels (fixed cameras, any observation order)."""
-        F, P, O, dev = self.F, self.P, self.O, self.device
-        max_band_span = self.max_band_span
-        i64 = dict(dtype=torch.int64, device=dev)
-        if O:
-            lim = torch.stack([self.fi.min(), self.fi.max(), self.pi.min(), self.pi.max(),
-                               (self.pi[1:] >= self.pi[:-1]).all().to(torch.int32)]).tolist()
-            if lim[0] < 0 or lim[1] >= F_all or lim[2] < 0 or lim[3] >= P:
-                raise ValueError("frame / point index out of range")
-            point_major = bool(lim[4])
-        else:
-            point_major = True
-        # CSR by point (identity permutation when the observations are already point-major, as managePoints emits them)
-        if point_major:
-            self.pt_obs = torch.arange(O, dtype=torch.int32, device=dev)
-        else:
-            self.pt_obs = torch.sort(self.pi, stable=True)[1].to(torch.int32)
-        self.pt_ptr = torch.zeros(P + 1, dtype=torch.int32, device=dev)
-        self.cam_ptr = torch.zeros(F + 1, dtype=torch.int32, device=dev)
-        if O and self.F_fixed:      # (the observations of fixed cameras sort behind those of the free ones)
-            self.pt_ptr[1:] = torch.cumsum(torch.bincount(self.pi, minlength=P), 0).to(torch.int32)
-            self.cam_ptr[1:] = torch.cumsum(torch.bincount(self.fi, minlength=F_all)[:F], 0).to(torch.int32)
-            n_free = int(self.cam_ptr[-1].item())
-            self.cam_obs = torch.sort(self.fi, stable=True)[1][:n_free].to(torch.int32).contiguous()
-        elif O:
-            self.pt_ptr[1:] = torch.cumsum(torch.bincount(self.pi, minlength=P), 0).to(torch.int32)
-            self.cam_ptr[1:] = torch.cumsum(torch.bincount(self.fi, minlength=F), 0).to(torch.int32)
-            self.cam_obs = torch.sort(self.fi, stable=True)[1].to(torch.int32)      # stable: observation order kept
-        else:
-            self.cam_obs = torch.zeros(0, dtype=torch.int32, device=dev)
-        self.pb = BAProblem(F, P, O, ptr(self.K), ptr(self.fi), ptr(self.pi), ptr(self.obs),
-                            ptr(self.pt_ptr), ptr(self.pt_obs), ptr(self.cam_ptr), ptr(self.cam_obs),
-                            0, 0, 0, None, None, 0, None, None, None, None, None, None)
-        # the pair list and cam_span are over the free cameras: with fixed ones the two pair kernels see the free
-        # observations only (a problem of its own, same order), and the pairs are mapped back to observation indices
-        pair_pb, free_idx, O_pairs = self.pb, None, O
-        if O and self.F_fixed:
-            free_idx = torch.nonzero(self.fi < F).reshape(-1)
-            O_pairs = int(free_idx.numel())
-            fi_f, pi_f = self.fi[free_idx].contiguous(), self.pi[free_idx].contiguous()
-            pt_ptr_f = torch.zeros(P + 1, dtype=torch.int32, device=dev)
-            pt_ptr_f[1:] = torch.cumsum(torch.bincount(pi_f, minlength=P), 0).to(torch.int32)
-            pt_obs_f = (torch.arange(O_pairs, dtype=torch.int32, device=dev) if point_major
-                        else torch.sort(pi_f, stable=True)[1].to(torch.int32))
-            self._pair_src = (fi_f, pi_f, pt_ptr_f, pt_obs_f)      # (kept alive while the descriptor points at them)
-            pair_pb = BAProblem(F, P, O_pairs, ptr(self.K), ptr(fi_f), ptr(pi_f), ptr(self.obs), ptr(pt_ptr_f),
-                                ptr(pt_obs_f), ptr(self.cam_ptr), ptr(self.cam_obs),
-                                0, 0, 0, None, None, 0, None, None, None, None, None, None)
-        if O_pairs:
-            # widest camera span of any point: cameras further apart never share a point, so the reduced camera system
-            # is block banded with this half-width (tracks from consecutive-keyframe matching span a few frames only)
-            cnt = torch.empty(O_pairs, dtype=torch.int32, device=dev)
-            span_t = torch.zeros(1, dtype=torch.int32, device=dev)
-            self.ctx.check(lib.mm_ba_pairs_count(self.ctx.h, C.byref(pair_pb), ptr(cnt), ptr(span_t)),
-                           "mm_ba_pairs_count")
-            offs = torch.cumsum(cnt, 0, dtype=torch.int64)
-            span, n = torch.stack([span_t[0].to(torch.int64), offs[-1]]).tolist()
-            self.cam_span = int(span)
-            self.pb.cam_span = self.cam_span
-            # banded problems: co-observation pair list for the atomic-free, bitwise reproducible Schur kernel;
-            # wide spans keep the general kernel
-            if pairs and self.cam_span <= max_band_span and self.cam_span < F and F * (self.cam_span + 1) < 2 ** 31:
-                key = torch.empty(n, dtype=torch.int32, device=dev)
-                po = torch.empty(n, dtype=torch.int32, device=dev)
-                po2 = torch.empty(n, dtype=torch.int32, device=dev)
-                offs_ex = (offs - cnt).contiguous()
-                self.ctx.check(lib.mm_ba_pairs_emit(self.ctx.h, C.byref(pair_pb), ptr(offs_ex), self.cam_span, ptr(key),
-                                                    ptr(po), ptr(po2)), "mm_ba_pairs_emit")
-                key_s, perm = torch.sort(key, stable=True)          # fixed order inside every segment
-                pair_o, pair_o2 = po[perm].contiguous(), po2[perm].contiguous()
-                if free_idx is not None:
-                    pair_o = free_idx[pair_o.long()].to(torch.int32).contiguous()
-                    pair_o2 = free_idx[pair_o2.long()].to(torch.int32).contiguous()
-                seg_ids, counts = torch.unique_consecutive(key_s, return_counts=True)
-                seg_hi = torch.cumsum(counts, 0)
-                seg_lo = seg_hi - counts
-                CH = self._chunk_pairs()
-                cntc = (counts + (CH - 1)) // CH
-                first_hi = torch.cumsum(cntc, 0)
-                first = first_hi - cntc
-                nchunks = int(first_hi[-1].item())
-                chunk_seg = torch.repeat_interleave(torch.arange(len(seg_ids), **i64), cntc, output_size=nchunks)
-                chunk_begin = seg_lo[chunk_seg] + CH * (torch.arange(nchunks, **i64) - first[chunk_seg])
-                chunk_end = torch.minimum(chunk_begin + CH, seg_hi[chunk_seg])
-                i32 = lambda t: t.to(torch.int32).contiguous()
-                pair_p = self.pi[pair_o.long()].contiguous()   # saves the pair kernel a dependent gather
-                self._set_pair_list(pair_o, pair_o2, pair_p, i32(seg_ids), i32(torch.cat([first, first_hi[-1:]])), i32(chunk_seg),
-                                    i32(chunk_begin), i32(chunk_end))
-                self._set_slabs(seg_ids.to(torch.int64), torch.cat([first, first_hi[-1:]]))
 
     def residual(self, cams, pts, want_res=False, cost_out=None):
         """-> (sum of squared residuals as a 1-element device tensor, res [O,2] or None).  cost_out: where to put the
@@ -1337,13 +1248,14 @@ def filter_observations(cams, pts, K, fi, pi=None, obs=None, pt_ptr=None, max_re
     Kh = _host_f64(K, 9, f"{name}: K")
     if not np.isfinite(Kh).all() or Kh[3] != 0 or Kh[6] != 0 or Kh[7] != 0 or Kh[8] != 1 or Kh[0] == 0 or Kh[4] == 0:
         raise ValueError(f"{name}: K must be finite, upper triangular with K[2, 2] = 1 and non-zero focal lengths")
-    checked = False
-    if isinstance(fi, BADevice):
+    checked = isinstance(fi, BADevice)      # (its ranges and point-major order were judged by mm_ba_index_build)
+    if checked:
         pb = fi
         if pi is not None or obs is not None or pt_ptr is not None:
             raise ValueError(f"{name}: a BADevice supplies fi, pi, obs and pt_ptr")
         fi, pi, obs, pt_ptr = pb.fi, pb.pi, pb.obs, pb.pt_ptr
-        checked = pb.index_build == "native"      # (ranges and point-major order were judged by mm_ba_index_build)
+        if not pb.point_major:
+            raise ValueError(f"{name}: the observations are not point-major")
         ctx = ctx or pb.ctx
     for what, t, dtype, tail in (("cams [F, 6] f64", cams, torch.float64, (6,)), ("pts [P, 3] f64", pts, torch.float64, (3,)),
                                  ("fi [O] i32", fi, torch.int32, ()), ("pi [O] i32", pi, torch.int32, ()),

@@ -470,6 +470,50 @@ def _pairs_of_points(fi, pi, lower=True):
     return o, o2
 
 
+def index_reference(fi, pi, F, P, F_fixed=0, chunk=512, max_band_span=192, pairs=True):
+    """The index structures of a BA problem as ops.BADevice holds them (int32 arrays): the CSR by point over all
+    observations, the CSR by camera over the F free cameras (fi >= F is a fixed camera), cam_span, and -- if `pairs` and the
+    span allows -- the co-observation pairs of the free observations sorted stably by camera(o) * (span + 1) + camera(o) -
+    camera(o2), cut into segments and chunks of at most `chunk` pairs, with the camera slabs.  Small inputs only."""
+    fi, pi = np.asarray(fi, np.int64).reshape(-1), np.asarray(pi, np.int64).reshape(-1)
+    if fi.size and (fi.min() < 0 or fi.max() >= F + F_fixed or pi.min() < 0 or pi.max() >= P):
+        raise ValueError("frame / point index out of range")
+    i32 = lambda a: np.ascontiguousarray(a, np.int32)
+    ptr_of = lambda counts: np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    pt_ptr, pt_obs = ptr_of(np.bincount(pi, minlength=P)), np.argsort(pi, kind="stable")
+    cam_ptr = ptr_of(np.bincount(fi, minlength=F + F_fixed)[:F])
+    cam_obs = np.argsort(fi, kind="stable")[:cam_ptr[F]]
+    # pairs in emission order: o ascending, then the observations of o's point in pt_obs order
+    o, o2 = [], []
+    for i in np.flatnonzero(fi < F):
+        others = pt_obs[pt_ptr[pi[i]]:pt_ptr[pi[i] + 1]]
+        others = others[fi[others] <= fi[i]]
+        o += [i] * others.size
+        o2 += list(others)
+    o, o2 = np.array(o, np.int64), np.array(o2, np.int64)
+    d = fi[o] - fi[o2]
+    span = int(d.max()) if d.size else 0
+    out = dict(pt_ptr=i32(pt_ptr), pt_obs=i32(pt_obs), cam_ptr=i32(cam_ptr), cam_obs=i32(cam_obs), cam_span=span, n_pairs=0,
+               slabs=None)
+    if not (pairs and d.size and span <= max_band_span and span < F and F * (span + 1) < 2 ** 31):
+        return out
+    key = fi[o] * (span + 1) + d
+    order = np.argsort(key, kind="stable")
+    seg_ids, counts = np.unique(key, return_counts=True)
+    seg_lo, n_chunks = ptr_of(counts), -(-counts // chunk)
+    seg_chunk_ptr = ptr_of(n_chunks)
+    chunk_seg = np.repeat(np.arange(seg_ids.size), n_chunks)
+    chunk_begin = seg_lo[chunk_seg] + chunk * (np.arange(chunk_seg.size) - seg_chunk_ptr[chunk_seg])
+    out.update(n_pairs=int(d.size), pair_o=i32(o[order]), pair_o2=i32(o2[order]), pair_p=i32(pi[o[order]]), seg_ids=i32(seg_ids),
+               seg_chunk_ptr=i32(seg_chunk_ptr), chunk_seg=i32(chunk_seg), chunk_begin=i32(chunk_begin),
+               chunk_end=i32(np.minimum(chunk_begin + chunk, seg_lo[chunk_seg + 1])))
+    per_slab = -(-F // 8)      # 8 slabs of cameras: the first segment and the first chunk of each, and the ends
+    if per_slab >= 16:
+        first = np.searchsorted(seg_ids // (span + 1), np.arange(9) * per_slab)
+        out["slabs"] = (8, per_slab, first.astype(np.int64), seg_chunk_ptr[first])
+    return out
+
+
 def reduced_system(Jc, Jp, fi, pi, n_frames, n_points, Bd, Cd, gc, gp, Cinv=None, chunk=1 << 19):
     """Reduced camera system S = blockdiag(Bd) - sum_p E_p Cd_p^-1 E_p^T (dense 6F x 6F) and v = gc - sum_p E_p Cd_p^-1 gp_p,
     E_o = Jc_o^T Jp_o, summed in long double over the co-observation pairs.  Cd packed [P,6] or [P,3,3]; Cinv (same

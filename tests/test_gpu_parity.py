@@ -439,8 +439,8 @@ def test_ba_full_size_adjoint_and_reduced_system_properties():
 
 
 def test_device_built_indices_equal_host_builders():
-    """CSR by point / camera and the co-observation pair list built on the device (torch sorts + two HIP kernels)
-    are identical to the host C++ builders (mm_ba_build_index / mm_ba_build_pairs)."""
+    """CSR by point / camera and the co-observation pair list built on the device (mm_ba_index_build, point-major and
+    permuted observations) are identical to the host C++ builders (mm_ba_build_index / mm_ba_build_pairs)."""
     import ctypes as C
     from meatmodeler_amd._lib import lib, c_i32p, c_i64p
     rng = np.random.default_rng(9)

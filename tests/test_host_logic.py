@@ -173,6 +173,81 @@ def test_ba_build_index_stable_csr():
         ops.ba_build_index(F, P, np.array([F], np.int32), np.array([0], np.int32))
 
 
+def _index_inputs():
+    """(name, fi, pi, F, P, F_fixed): the kinds of input tests/test_ba_index_gpu.py builds on the device."""
+    rng = np.random.default_rng(11)
+    pr = synth.make_ba_problem(12, 300, 4, seed=5)
+    fi, pi = pr["fi"].astype(np.int32), pr["pi"].astype(np.int32)
+    perm = rng.permutation(fi.size)
+    yield "point-major", fi, pi, 12, 300, 0
+    yield "permuted", fi[perm], pi[perm], 12, 300, 0
+    yield "fixed", fi, pi, 10, 300, 2
+    yield "fixed, permuted", fi[perm], pi[perm], 10, 300, 2
+    yield "ends unobserved", fi[perm], pi[perm] + 1, 12, 302, 0
+    yield "random", rng.integers(0, 9, 160).astype(np.int32), rng.integers(0, 30, 160).astype(np.int32), 7, 30, 2
+    yield "all fixed", np.array([2, 3, 2], np.int32), np.array([0, 0, 1], np.int32), 2, 2, 2
+    yield "last free camera idle", np.array([0, 6, 2, 4, 1, 6], np.int32), np.array([0, 0, 1, 1, 2, 2], np.int32), 4, 3, 3
+
+
+@pytest.mark.parametrize("chunk", [64, 512])
+def test_index_reference_equals_host_builders(chunk):
+    """oracle.ba_oracle.index_reference (NumPy) against mm_ba_build_index / mm_ba_build_pairs.  Fixed cameras: the host CSR is
+    built over F + F_fixed cameras and cut back to the free ones; as o2 a fixed observation drops out by d < 0."""
+    for name, fi, pi, F, P, F_fixed in _index_inputs():
+        ref = bo.index_reference(fi, pi, F, P, F_fixed, chunk)
+        pt_ptr, pt_obs, cam_ptr, cam_obs = ops.ba_build_index(F + F_fixed, P, fi, pi)
+        cam_ptr = np.ascontiguousarray(cam_ptr[:F + 1])
+        cam_obs = np.ascontiguousarray(cam_obs[:cam_ptr[F]])
+        for key, want in (("pt_ptr", pt_ptr), ("pt_obs", pt_obs), ("cam_ptr", cam_ptr), ("cam_obs", cam_obs)):
+            assert ref[key].dtype == np.int32
+            np.testing.assert_array_equal(ref[key], want, err_msg=f"{name}: {key}")
+        span = ref["cam_span"]
+        seg_ptr = np.zeros(F * (span + 1) + 1, np.int64)
+        args = lambda s: (F, P, len(fi), fi.ctypes.data_as(c_i32p), pi.ctypes.data_as(c_i32p), pt_ptr.ctypes.data_as(c_i32p),
+                          np.ascontiguousarray(pt_obs).ctypes.data_as(c_i32p), cam_ptr.ctypes.data_as(c_i32p),
+                          cam_obs.ctypes.data_as(c_i32p), s, seg_ptr.ctypes.data_as(c_i64p))
+        if span:
+            assert lib.mm_ba_build_pairs(*args(span - 1), None, None, 0) == -1, name      # (no smaller span will do)
+        n = lib.mm_ba_build_pairs(*args(span), None, None, 0)
+        assert n == ref["n_pairs"], name
+        if not n:
+            assert "pair_o" not in ref and cam_obs.size == 0 and span == 0, name
+            continue
+        po, po2 = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        assert lib.mm_ba_build_pairs(*args(span), po.ctypes.data_as(c_i32p), po2.ctypes.data_as(c_i32p), n) == n
+        np.testing.assert_array_equal(ref["pair_o"], po, err_msg=name)
+        np.testing.assert_array_equal(ref["pair_o2"], po2, err_msg=name)
+        np.testing.assert_array_equal(ref["pair_p"], pi[po], err_msg=name)
+        ne = np.flatnonzero(np.diff(seg_ptr) > 0)
+        np.testing.assert_array_equal(ref["seg_ids"], ne, err_msg=name)
+        # the chunks of a segment tile its pairs in order, each but the last one full
+        cb, ce, cs, scp = ref["chunk_begin"], ref["chunk_end"], ref["chunk_seg"], ref["seg_chunk_ptr"]
+        assert scp[0] == 0 and scp[-1] == cs.size and scp.size == ne.size + 1, name
+        for s_, seg in enumerate(ne):
+            lo, hi = seg_ptr[seg], seg_ptr[seg + 1]
+            cuts = list(range(lo, hi, chunk)) + [hi]
+            c = slice(scp[s_], scp[s_ + 1])
+            assert list(cb[c]) == cuts[:-1] and list(ce[c]) == cuts[1:] and (cs[c] == s_).all(), name
+    with pytest.raises(ValueError):
+        bo.index_reference([0, 12], [0, 1], 10, 300, 2)
+    with pytest.raises(ValueError):
+        bo.index_reference([0, 1], [0, -1], 10, 300, 2)
+
+
+def test_index_reference_slabs():
+    """130 cameras: 8 slabs of 17; each starts at the first segment (and its first chunk) of its first camera or a later one."""
+    pr = synth.make_ba_problem(130, 400, 5, seed=2)
+    ref = bo.index_reference(pr["fi"], pr["pi"], 130, 400, 0, 64)
+    n_slabs, per_slab, first_seg, first_chunk = ref["slabs"]
+    assert (n_slabs, per_slab) == (8, 17) and first_seg.dtype == first_chunk.dtype == np.int64
+    seg_cam = ref["seg_ids"] // (ref["cam_span"] + 1)
+    for s_ in range(9):
+        assert (seg_cam[:first_seg[s_]] < 17 * s_).all() and (seg_cam[first_seg[s_]:] >= 17 * s_).all()
+    np.testing.assert_array_equal(first_chunk, ref["seg_chunk_ptr"][first_seg])
+    few = pr["fi"] < 120
+    assert bo.index_reference(pr["fi"][few], pr["pi"][few], 120, 400)["slabs"] is None      # (15 cameras per slab: none)
+
+
 def test_ba_build_pairs_matches_brute_force():
     import ctypes as C
     rng = np.random.default_rng(3)
