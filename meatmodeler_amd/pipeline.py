@@ -5,17 +5,16 @@ and key points stay in HBM and each stage is a few large launches instead of one
 
 Keyframe gating, calibration and PnP are outside the scope: the caller provides K and one extrinsic
 per frame (the reference gets them from calibrate / poseEstimation / adjustPose, processor.py:422-448) -- or, with
-`run(verify={...}, poses={...})`, K alone: the extrinsics are then recovered from the verified matches; with
-`run(resect={...})` every frame is registered once more against the triangulated points (a RANSAC resection, DESIGN.md 6f;
-`planar="auto"` adds the homography branch for coplanar points, 6g); with `run(align={...})` the cameras are registered to
-positions the caller knows and everything downstream runs in that frame and scale (a robust similarity); with
-`run(refine={...})` the adjustment's own result is judged -- every observation by its reprojection error and depth, every point
-by what it has left -- and what survives is adjusted again.
+`run(verify={...}, poses={...})`, K alone.  Every stage the reference does not have is an option of `run` that is off by
+default and is described by its `*_options` function below; `run_plan` judges all of them together before anything touches
+the device, and `run` is then one call per phase: `_front`, `_link`, `_poses`, `_structure`, `_adjust`.
 """
 import ctypes as C
 import queue
 import time
 from concurrent.futures import ThreadPoolExecutor
+from collections import namedtuple
+from contextlib import contextmanager
 
 import numpy as np
 import torch
@@ -36,11 +35,12 @@ GUIDED_KEYS = ("threshold_px", "ratio", "max_dist", "cross_check")
 RESECT_KEYS = ("n_hyp", "threshold_px", "min_rows", "min_inliers", "refit_iters", "polish_iters", "seed", "planar", "planar_tol",
                "collinear_tol")
 ALIGN_KEYS = ("frames", "extrinsics", "centres", "tau", "tau_rel", "n_hyp", "seed", "refit_iters", "with_scale", "min_inliers")
+ALIGN_FRAMES = "align: frames must be at least 3 distinct indices in [0, F)"
 
 
 def _stage_options(stage, value, keys):
-    """An option of `run` that is None (the stage is off) or a dict with keys out of `keys`.  Returns it as a dict; anything
-    else, or an unknown key, raises ValueError."""
+    """An option of `run` that is None (the stage is off) or a dict with keys out of `keys` ({} for the defaults).  Returns it
+    as a dict of its own; anything else, or an unknown key, raises ValueError."""
     if value is None:
         return None
     if not isinstance(value, dict):
@@ -52,33 +52,48 @@ def _stage_options(stage, value, keys):
 
 
 def verify_options(verify):
-    """`run(..., verify=)`: None (no verification) or a dict of the parameters of ops.verify_matches -- pair_base and ctx are
-    the pipeline's own.  Returns it as a dict; an unknown key raises ValueError."""
+    """`run(..., verify=)`: None (every Lowe-ratio survivor goes to the linker, as in the reference) or a dict of the parameters
+    of ops.verify_matches (pair_base and ctx are the pipeline's own): each rank verifies its own pairs against a RANSAC
+    fundamental matrix between `match` and the gather / `link`, and only the inliers are linked.  -> as `_stage_options`."""
     return _stage_options("verify", verify, VERIFY_KEYS)
 
 
 def pose_options(poses):
-    """`run(..., poses=)`: None (the caller provides the extrinsics) or a dict of the parameters of ops.recover_poses and
-    ops.chain_poses.  Returns it as a dict; an unknown key raises ValueError."""
+    """`run(..., poses=)`: None (`extrinsics` holds one [3,4] per frame) or a dict of the parameters of ops.recover_poses and
+    ops.chain_poses (needs `verify`, which supplies each pair's F): the extrinsics are recovered from the verified matches and
+    K, and `extrinsics` may be None.  The first baseline is the unit of length.  -> as `_stage_options`."""
     return _stage_options("poses", poses, POSE_KEYS)
 
 
 def degeneracy_options(degeneracy):
     """`run(..., degeneracy=)`: None (no homography stage) or a dict of the parameters of ops.verify_homography and of
     ops.recover_poses_homography (min_front_frac, ambiguous_frac, rotation_tol) -- verify_info, pair_base, the hint and ctx are
-    the pipeline's own.  Returns it as a dict; an unknown key raises ValueError."""
+    the pipeline's own (needs `verify`): every rank fits a homography per pair on the matches `verify` read, and a pair it
+    explains as well as the fundamental matrix (HOMOG_DEGENERATE: a planar scene or a camera that only turns) is
+    linked by the homography's inliers; with `poses` its relative pose comes from the homography -- a pure rotation is chained
+    with t = 0 and the scale carried -- before the one chain call.  The selection is a torch.where on the device, no host
+    read.  -> as `_stage_options`."""
     return _stage_options("degeneracy", degeneracy, DEGENERACY_KEYS)
 
 
 def guided_options(guided):
     """`run(..., guided=)`: None (no guided matching) or a dict of the parameters of ops.guided_match -- the seeds, the model,
-    its kind and ctx are the pipeline's own.  Returns it as a dict; an unknown key raises ValueError."""
+    its kind and ctx are the pipeline's own (needs `verify`): after `verify` and `degeneracy` and before the gather / `link`,
+    every rank matches the key points its pairs' matches leave unused once more, among the candidates within threshold_px of
+    the pair's model: F of `verify`, no model where it flagged TOO_FEW, NO_MODEL or WEAK, and with `degeneracy`
+    the homography where the pair is HOMOG_DEGENERATE (a torch.where on the device, no host read).  The enlarged set replaces
+    the matches: the linker reads it, `poses` and the chain read the linked matches as before.  -> as `_stage_options`."""
     return _stage_options("guided", guided, GUIDED_KEYS)
 
 
 def resect_options(resect):
     """`run(..., resect=)`: None (no resection) or a dict of the parameters of ops.resect_cameras -- the points, the prior,
-    cam_base and ctx are the pipeline's own.  Returns it as a dict; an unknown key raises ValueError."""
+    cam_base and ctx are the pipeline's own: after the triangulation every frame is resected against `points0` (under
+    "multi_view" only against the tracks no test flagged), with the extrinsics in use -- given or recovered -- as the prior, so
+    no frame ends with a higher MSAC cost than it came in with; the tracks are then triangulated again with the new poses and
+    the adjustment starts from those.  `planar` ("auto" / "only", with planar_tol and collinear_tol) sends frames whose points
+    are coplanar through the homography branch; without it exactly the one call of 6f is launched.
+    -> as `_stage_options`."""
     return _stage_options("resect", resect, RESECT_KEYS)
 
 
@@ -86,8 +101,13 @@ def align_options(align, n_frames=None):
     """`run(..., align=)`: None (no registration) or a dict: `frames`, at least 3 distinct indices in [0, F); the targets of
     those frames as one of `extrinsics` [n, 3|4, 4] or `centres` [n, 3], in the frame the result is wanted in; and optionally
     tau or tau_rel (default tau_rel = 0.05: five percent of the targets' spread admits the drift DESIGN.md 6e measured on a
-    recovered chain, 2.16 % at its worst, and not a broken link), n_hyp, seed, refit_iters, with_scale, min_inliers.  Returns
-    dict(frames [n] i64, centres [n, 3] f64, params for ops.align_similarity); anything else raises ValueError."""
+    recovered chain, 2.16 % at its worst, and not a broken link), n_hyp, seed, refit_iters, with_scale, min_inliers.  Once the
+    extrinsics are settled -- given or recovered -- and before the first triangulation, the centres of the cameras `frames` are
+    registered to the targets by a robust similarity and the extrinsics are replaced by their image, so
+    triangulation, `resect` and the adjustment run in the target frame and scale; with `poses`, `poses["extrinsics"]` holds the
+    image.  If the adjustment runs, its cameras are registered to the same targets once more (`ba_aligned`; `ba` itself is left
+    as it is).  ALIGN_TOO_FEW or ALIGN_NO_MODEL: nothing is transformed, the flags say so.  Returns dict(frames [n] i64,
+    centres [n, 3] f64, params for ops.align_similarity); anything else raises ValueError."""
     align = _stage_options("align", align, ALIGN_KEYS)
     if align is None:
         return None
@@ -96,7 +116,7 @@ def align_options(align, n_frames=None):
     frames = np.asarray(align.pop("frames"))
     if frames.ndim != 1 or frames.size < 3 or not np.issubdtype(frames.dtype, np.integer) or np.unique(frames).size != frames.size \
             or frames.min() < 0 or (n_frames is not None and frames.max() >= n_frames):
-        raise ValueError("align: frames must be at least 3 distinct indices in [0, F)")
+        raise ValueError(ALIGN_FRAMES)
     if "centres" in align:
         centres = np.asarray(align.pop("centres"), np.float64)
     else:
@@ -116,10 +136,101 @@ def align_options(align, n_frames=None):
 def refine_options(refine):
     """`run(..., refine=)`: None (no filtering after the adjustment) or a dict of the options of bundleAdjuster.refine_schedule
     ({} for the defaults): max_reproj_px, a number or one threshold per round with the last one repeated; min_angle_deg,
-    min_depth, min_views; rounds (default 2); ftol / max_nfev of the re-solves.  Returns the schedule as a dict; anything else
-    raises ValueError."""
+    min_depth, min_views; rounds (default 2); ftol / max_nfev of the re-solves.  After the adjustment every observation is
+    judged at the adjusted cameras and points and every point by the observations it has left (ops.filter_observations,
+    DESIGN.md 6k); if anything is flagged, what survives is adjusted again from the same cameras and the surviving points, up to
+    `rounds` times.  `ba` itself is left as it is; with `align`, `ba_aligned` is computed from the refined result, so its points
+    are those of `refine["point_map"]`.  Returns the schedule as a dict; anything else raises ValueError."""
     refine = _stage_options("refine", refine, REFINE_KEYS)
     return None if refine is None else refine_schedule(**refine)
+
+
+class RunPlan(namedtuple("RunPlan", "n_frames world sharded force_collectives triangulation cull verify poses resect degeneracy "
+                                    "guided align refine")):
+    """What `run_plan` makes of the options of `ClipPipeline.run`: every stage as its `*_options` function returns it (None: the
+    stage is off), the clip's frame count, the ranks it is spread over, and whether the gather / all-reduce path is taken."""
+    __slots__ = ()
+
+
+def run_plan(n_frames, world=None, has_extrinsics=True, force_collectives=False, triangulation="two_view", cull=None,
+             verify=None, poses=None, resect=None, degeneracy=None, guided=None, align=None, refine=None):
+    """Every check of `ClipPipeline.run` on its options, without a device -> RunPlan; a broken rule raises ValueError.  world:
+    the ranks of the process group, None without one (one rank, and force_collectives has nothing to force).  n_frames and
+    world may each be a function without arguments that gives the value: it is called only after the rules that need neither
+    have passed -- the order the rules are reported in."""
+    verify, poses, resect, degeneracy = verify_options(verify), pose_options(poses), resect_options(resect), degeneracy_options(degeneracy)
+    guided, align, refine = guided_options(guided), align_options(align), refine_options(refine)
+    for stage, on, why in (("guided", guided, "it supplies each pair's fundamental matrix, the model the search is gated by"),
+                           ("degeneracy", degeneracy, "the verdict compares the homography with each pair's fundamental matrix"),
+                           ("poses", poses, "it supplies each pair's fundamental matrix")):
+        if on is not None and verify is None:
+            raise ValueError(f"{stage} needs verify ({why}): pass verify={{}} for the defaults")
+    if poses is None and not has_extrinsics:
+        raise ValueError("extrinsics is required unless poses is set")
+    if triangulation not in ("two_view", "multi_view"):
+        raise ValueError("triangulation must be 'two_view' or 'multi_view'")
+    n_frames = n_frames() if callable(n_frames) else n_frames
+    if align is not None and align["frames"].max() >= n_frames:
+        raise ValueError(ALIGN_FRAMES)
+    world = world() if callable(world) else world
+    ranks = 1 if world is None else world
+    if cull is not None and triangulation != "multi_view":
+        raise ValueError("cull needs triangulation='multi_view' (the two-view path has no per-track verdict)")
+    for stage, on, why in (("cull", cull, "the track partition takes contiguous ranges"),
+                           ("poses", poses, "the chain needs the neighbouring pair's depths across every rank boundary"),
+                           ("resect", resect, "every frame needs the whole point table"),
+                           ("align", align, "the cameras of `frames` live on different ranks"),
+                           ("refine", refine, "the compaction renumbers the points of one shard")):
+        if on is not None and ranks > 1:
+            raise ValueError(f"{stage} is not supported with more than one rank: {why}")
+    if cull is not None:
+        tests = {"max_reproj_px", "min_angle_deg", "min_depth"}
+        unknown = set(cull) - tests - {"refine_iters"}
+        if unknown or not tests & set(cull):
+            raise ValueError("cull takes max_reproj_px, min_angle_deg, min_depth (at least one) and refine_iters"
+                             + (f"; not {sorted(unknown)}" if unknown else ""))
+    return RunPlan(n_frames, ranks, ranks > 1 or (world is not None and bool(force_collectives)), force_collectives, triangulation,
+                   cull, verify, poses, resect, degeneracy, guided, align, refine)
+
+
+class StageClock:
+    """The stage timers of `ClipPipeline.run`: `with clock("verify"):` adds the interval's milliseconds to ms["verify"], the
+    context synchronised before the clock starts and before it stops.  `with clock.paused("poses"), clock("degeneracy"):`
+    bills what it encloses to "degeneracy" and not to the open "poses" interval around it."""
+
+    def __init__(self, ctx, ms, now=time.perf_counter):
+        self.ctx, self.ms, self.now, self.since = ctx, ms, now, {}
+
+    def _start(self, name):
+        self.ctx.sync()
+        self.since[name] = self.now()
+
+    def _stop(self, name):
+        self.ctx.sync()
+        self.ms[name] = self.ms.get(name, 0.0) + (self.now() - self.since.pop(name)) * 1e3
+
+    @contextmanager
+    def __call__(self, name):
+        self._start(name)
+        yield
+        self._stop(name)
+
+    @contextmanager
+    def paused(self, name):
+        self._stop(name)
+        yield
+        self._start(name)
+
+
+def _only(options, keys):
+    return {k: v for k, v in options.items() if k in keys}
+
+
+class _Front(namedtuple("_Front", "det xy n pairs m verify degeneracy guided is_deg pairs_local frames_local")):
+    """What `ClipPipeline._front` hands on: this rank's `detect` result (None without frames) with its xy and n tables, the
+    matches that go to the linker, the `verify` / `degeneracy` / `guided` entries of the result (None: stage off), the
+    HOMOG_DEGENERATE mask of the pairs (with `degeneracy`), and how many pairs and frames the rank owns."""
+    __slots__ = ()
 
 
 class ClipPipeline:
@@ -196,13 +307,16 @@ class ClipPipeline:
                                 **params)
 
     # ------------------------------------------------------------------------------------------- poses
-    def recover_poses(self, det, pairs, m, F, K, E0=None, min_common=8, **params):
+    def recover_poses(self, det, pairs, m, F, K, E0=None, min_common=8, override=None, **params):
         """Camera poses from what `verify` returned for the frames in `det`: a relative pose per pair (ops.recover_poses,
         `params` as it takes them), chained into one scale and one frame (ops.chain_poses; E0 = the first frame's extrinsic,
-        [I | 0] by default).  -> dict(extrinsics [n+1, 3, 4] f64, R, t, sigma, info, depth, scale, rho, chain_info), device
-        tensors.  The first baseline is the unit of length."""
+        [I | 0] by default).  override: a function (R, t, depth, info) -> the same four, called between the two -- how `run`
+        gives the degenerate pairs the homography's pose.  -> dict(extrinsics [n+1, 3, 4] f64, R, t, sigma, info, depth, scale,
+        rho, chain_info), device tensors.  The first baseline is the unit of length."""
         n = pairs.shape[0]
         R, t, sigma, depth, info = ops.recover_poses(det["xy"][:n + 1], pairs, m, F, K, ctx=self.ctx, **params)
+        if override is not None:
+            R, t, depth, info = override(R, t, depth, info)
         ext, scale, rho, cinfo = ops.chain_poses(pairs, m, depth, R, t, info, E0=E0, min_common=min_common, ctx=self.ctx)
         return dict(extrinsics=ext, R=R, t=t, sigma=sigma, info=info, depth=depth, scale=scale, rho=rho, chain_info=cinfo)
 
@@ -588,330 +702,233 @@ class ClipPipeline:
     def run(self, frames, K, extrinsics=None, ba=True, ftol=1e-4, verbose=0, dist=None, timers=None, max_nfev=None,
             force_collectives=False, triangulation="two_view", cull=None, verify=None, poses=None, resect=None, degeneracy=None,
             guided=None, align=None, refine=None):
-        """frames [F,H,W] u8 (device).  With `dist` = torch.distributed (initialised), frames are the FULL clip on
-        every rank (synthetic input is generated locally) and the work is sharded as described in parallel.py.
-        `max_nfev`: evaluation budget of the adjustment (None = SciPy's default, as adjustPoints).
-        `force_collectives`: take the gather / all-reduce path even in a one-rank group (the collectives are trivial
-        but travel the real backend: how backend "nccl" is exercised on a single GPU).
+        """frames [F,H,W] u8 (device), K [3,3], extrinsics [F, 3|4, 4] (None with `poses`).  With `dist` = torch.distributed
+        (initialised), frames are the FULL clip on every rank (synthetic input is generated locally) and the work is sharded as
+        described in parallel.py; `cull`, `poses`, `resect`, `align` and `refine` need one rank (`run_plan` says why).
+        `force_collectives`: take the gather / all-reduce path even in a one-rank group (the collectives are trivial but travel
+        the real backend: how backend "nccl" is exercised on a single GPU).  `ba`, `ftol`, `max_nfev`: whether the adjustment
+        runs, its tolerance and its evaluation budget (None = SciPy's default, as adjustPoints).  `timers`: a dict the stages'
+        milliseconds are added to (detect, match, verify, degeneracy, guided, link, poses, align, triangulate, resect, ba,
+        ba_solve, refine).
         `triangulation`: "two_view" (default) triangulates a track from its first and last observation, as the reference
-        does; "multi_view" from all its observations (`triangulate_multi_view`), and the result gains `track_quality`
-        [T,4] and `track_flags` [T].  `points0` is [T,3] over all tracks either way.
-        `cull` (needs "multi_view"; one rank only -- the track partition of the sharded adjustment works on contiguous
-        ranges): dict of the thresholds of ops.triangulate_tracks (max_reproj_px, min_angle_deg, min_depth, refine_iters).
-        The adjustment then takes only the tracks no test flagged, `kept_tracks` (indices in track order), and its
-        points are aligned with that list.
-        `verify`: None (default: every Lowe-ratio survivor goes to the linker, as in the reference) or a dict of the
-        parameters of ops.verify_matches ({} for the defaults): each rank verifies its own pairs against a RANSAC
-        fundamental matrix between `match` and the gather / `link`, and only the inliers are linked.  The result gains
-        `verify` = dict(info [n,4], cost [n], F [n,9], matches_in [n]) over this rank's pairs; timer "verify".
-        `poses`: None (default: `extrinsics` holds one [3,4] per frame) or a dict of the parameters of ops.recover_poses and
-        ops.chain_poses ({} for the defaults; needs `verify`, which supplies each pair's F; one rank only -- the chain needs the
-        neighbouring pair's depths across every rank boundary): the extrinsics are recovered from the verified matches and
-        K, `extrinsics` may be None, and the result gains `poses` = dict(extrinsics [F,3,4], R, t, sigma, info, scale, rho,
-        chain_info); timer "poses".  The first baseline is the unit of length.
-        `degeneracy`: None (default: nothing below runs) or a dict of the parameters of ops.verify_homography and the
-        fractions / rotation_tol of ops.recover_poses_homography ({} for the defaults; needs `verify`): every rank fits a
-        homography per pair on the matches `verify` read, and a pair the homography explains as well as the fundamental matrix
-        (HOMOG_DEGENERATE: a planar scene or a camera that only turns) is linked by the homography's inliers; with
-        `poses` its relative pose comes from the homography -- a pure rotation is chained with t = 0 and the scale carried --
-        before the one chain call.  The selection is a torch.where on the device, no host read.  The result gains `degeneracy`
-        = dict(H [n,9], cost [n], info [n,6], and with `poses` pose_info [n,8], sigma [n,3], normal [n,3]); timer "degeneracy".
-        `guided`: None (default: nothing below runs) or a dict of the parameters of ops.guided_match ({} for the defaults; needs
-        `verify`): after `verify` and `degeneracy` and before the gather / `link`, every rank matches the key points its pairs'
-        matches leave unused once more, among the candidates within threshold_px of the pair's model: F of
-        `verify`, no model where it flagged TOO_FEW, NO_MODEL or WEAK, and with `degeneracy` the homography where the pair is
-        HOMOG_DEGENERATE -- a torch.where on the device, no host read.  The enlarged set replaces the matches: the linker reads
-        it, `poses` and the chain read the linked matches as before.  The result gains `guided` = dict(info [n,4],
-        is_new [n,cap]); timer "guided".
-        `resect`: None (default) or a dict of the parameters of ops.resect_cameras ({} for the defaults; one rank only): after
-        the triangulation every frame is resected against `points0` (under "multi_view" only against the tracks no test
-        flagged), with the extrinsics in use -- given or recovered -- as the prior, so no frame ends with a higher MSAC cost
-        than it came in with; the tracks are then triangulated again with the new poses and the adjustment starts from those.
-        Its key `planar` ("auto" / "only", with planar_tol and collinear_tol) sends frames whose points are coplanar through
-        the homography branch; without it exactly the one call of 6f is launched.  The result gains `resect` = dict(extrinsics [F,3,4], cost [F], info [F,6], inliers_per_frame [F]); timer "resect".
-        `align`: None (default: nothing below runs) or the dict of `align_options` (frames, their target extrinsics or centres,
-        optional tau / tau_rel, n_hyp, seed, refit_iters, with_scale, min_inliers; one rank only): once the extrinsics are
-        settled -- given or recovered -- and before the first triangulation, the centres of the cameras `frames` are registered
-        to the targets by a robust similarity and the extrinsics are replaced by their image, so triangulation,
-        `resect` and the adjustment run in the target frame and scale; with `poses`, `poses["extrinsics"]` holds the image.
-        The result gains `align` = dict(sim [13], cost, info [4], inlier [n]); timer "align".  If the adjustment runs, its
-        cameras are registered to the same targets once more: `ba_aligned` = dict(extrinsics [F,3,4], points, sim, info);
-        `ba` itself is left as it is.  ALIGN_TOO_FEW or ALIGN_NO_MODEL: nothing is transformed, the flags say so.
-        `refine`: None (default: nothing below runs) or the dict of `refine_options` ({} for the defaults; one rank only): after
-        the adjustment every observation is judged at the adjusted cameras and points and every point by the observations it
-        has left (ops.filter_observations); if anything is flagged, what survives is adjusted again from the same
-        cameras and the surviving points, up to `rounds` times.  The result gains `refine` = dict(ba = the last result,
-        point_map / obs_map into the rows of the first adjustment, rounds = [dict(max_reproj_px, n_obs, n_points, removed_obs,
-        removed_points, cost_in, cost_out, nfev, status)], obs_flags / pt_flags of the first round, filters = each round's
-        filter output, results = the result of each re-solve); timer "refine".  `ba` itself is left as it is; with `align`, `ba_aligned` is computed from the refined
-        result, so its points are those of `refine["point_map"]`."""
-        verify = verify_options(verify)
-        poses = pose_options(poses)
-        resect = resect_options(resect)
-        degeneracy = degeneracy_options(degeneracy)
-        guided = guided_options(guided)
-        align = align_options(align)
-        refine = refine_options(refine)
-        if guided is not None and verify is None:
-            raise ValueError("guided needs verify (it supplies each pair's fundamental matrix, the model the search is gated by): "
-                             "pass verify={} for the defaults")
-        if degeneracy is not None and verify is None:
-            raise ValueError("degeneracy needs verify (the verdict compares the homography with each pair's fundamental matrix): "
-                             "pass verify={} for the defaults")
-        if poses is not None and verify is None:
-            raise ValueError("poses needs verify (it supplies each pair's fundamental matrix): pass verify={} for the defaults")
-        if poses is None and extrinsics is None:
-            raise ValueError("extrinsics is required unless poses is set")
-        if triangulation not in ("two_view", "multi_view"):
-            raise ValueError("triangulation must be 'two_view' or 'multi_view'")
-        F = frames.shape[0]
-        if align is not None and align["frames"].max() >= F:
-            raise ValueError("align: frames must be at least 3 distinct indices in [0, F)")
-        world = dist.get_world_size() if dist is not None else 1
+        does; "multi_view" from all its observations (`triangulate_multi_view`).  `points0` is [T,3] over all tracks either way.
+        `cull` (needs "multi_view"): dict of the thresholds of ops.triangulate_tracks (max_reproj_px, min_angle_deg, min_depth,
+        refine_iters).  The adjustment then takes only the tracks no test flagged, `kept_tracks` (indices in track order), and
+        its points are aligned with that list.
+        The stages that are off by default, each None or a dict ({} for the defaults) described where it is judged: `verify`
+        (verify_options), `degeneracy` (degeneracy_options), `guided` (guided_options), `poses` (pose_options), `align`
+        (align_options), `resect` (resect_options), `refine` (refine_options).  A stage that is None launches nothing.
+
+        -> dict(det (`detect` of this rank's frames), n_tracks, n_obs, points0, track_ptr_dev, obs_frame_dev, obs_kp_dev, xy_dev,
+        match_count, kp_count, pairs_local, frames_local); under "multi_view" also track_quality [T,4], track_flags [T] and with
+        cull kept_tracks; after the adjustment ba (its result), n_obs_local, cam_span, n_pairs; and one entry per stage that is
+        on, over this rank's n pairs: verify = dict(info [n,4], cost [n], F [n,9], matches_in [n]); degeneracy = dict(H [n,9],
+        cost [n], info [n,6], and with poses pose_info [n,8], sigma [n,3], normal [n,3]); guided = dict(info [n,4], is_new
+        [n,cap]); poses = what `recover_poses` returns, without depth; align = what `align` returns, and after the adjustment
+        ba_aligned = dict(extrinsics [F,3,4], points, sim, info); resect = what `resect` returns, without inlier; refine = what
+        bundleAdjuster.refine_rounds returns."""
+        plan = run_plan(lambda: frames.shape[0], lambda: None if dist is None else dist.get_world_size(), extrinsics is not None,
+                        force_collectives, triangulation, cull, verify, poses, resect, degeneracy, guided, align, refine)
         rank = dist.get_rank() if dist is not None else 0
-        if cull is not None and triangulation != "multi_view":
-            raise ValueError("cull needs triangulation='multi_view' (the two-view path has no per-track verdict)")
-        if cull is not None and world > 1:
-            raise ValueError("cull is not supported with more than one rank: the track partition takes contiguous ranges")
-        if poses is not None and world > 1:
-            raise ValueError("poses is not supported with more than one rank: the chain needs the neighbouring pair's depths "
-                             "across every rank boundary")
-        if resect is not None and world > 1:
-            raise ValueError("resect is not supported with more than one rank: every frame needs the whole point table")
-        if align is not None and world > 1:
-            raise ValueError("align is not supported with more than one rank: the cameras of `frames` live on different ranks")
-        if refine is not None and world > 1:
-            raise ValueError("refine is not supported with more than one rank: the compaction renumbers the points of one shard")
-        if cull is not None:
-            tests = {"max_reproj_px", "min_angle_deg", "min_depth"}
-            unknown = set(cull) - tests - {"refine_iters"}
-            if unknown or not tests & set(cull):
-                raise ValueError("cull takes max_reproj_px, min_angle_deg, min_depth (at least one) and refine_iters"
-                                 + (f"; not {sorted(unknown)}" if unknown else ""))
-        sharded = world > 1 or (dist is not None and force_collectives)
-        T = timers if timers is not None else {}
+        clock = StageClock(self.ctx, timers if timers is not None else {})
+        front = self._front(frames, plan, rank, clock)
+        tracks, m_h, n_h = self._link(front, plan, rank, dist, clock)
+        ext, recovered = self._poses(front, plan, K, extrinsics, clock)
+        ext, X, quality, flags, aligned, resected = self._structure(plan, K, ext, recovered, tracks, clock)
+        track_ptr, obs_frame, obs_kp, xy_dev = tracks
+        out = dict(det=front.det, n_tracks=track_ptr.shape[0] - 1, n_obs=obs_frame.shape[0], points0=X, track_ptr_dev=track_ptr,
+                   obs_frame_dev=obs_frame, obs_kp_dev=obs_kp, xy_dev=xy_dev, match_count=m_h, kp_count=n_h,
+                   pairs_local=front.pairs_local, frames_local=front.frames_local)
+        for name, value in (("verify", front.verify), ("poses", recovered), ("degeneracy", front.degeneracy),
+                            ("guided", front.guided), ("resect", resected), ("align", aligned)):
+            if value is not None:
+                out[name] = value
+        kept = None
+        if plan.triangulation == "multi_view":
+            out.update(track_quality=quality, track_flags=flags)
+            if plan.cull is not None:
+                kept = torch.nonzero(flags == 0).reshape(-1)
+                out["kept_tracks"] = kept
+        if ba and out["n_obs"] > 0 and (kept is None or kept.numel() > 0):
+            out.update(self._adjust(plan, K, ext, X, kept, tracks, rank, ftol, max_nfev, verbose, clock))
+        return out
 
-        def tic(name):
-            self.ctx.sync()
-            T.setdefault("_open", {})[name] = time.perf_counter()
-
-        def toc(name):
-            self.ctx.sync()
-            T[name] = T.get(name, 0.0) + (time.perf_counter() - T["_open"].pop(name)) * 1e3
-
-        (p_lo, p_hi), (f_lo, f_hi) = parallel.pair_block(F, rank, world)
-        tic("detect")
-        det = self.detect(frames[f_lo:f_hi]) if f_hi > f_lo else None
-        toc("detect")
-        tic("match")
-        if det is not None:
+    def _front(self, frames, plan, rank, clock):
+        """This rank's frames and pairs: detect, match, and the pair stages that are on (verify, degeneracy, guided) -> _Front."""
+        (p_lo, p_hi), (f_lo, f_hi) = parallel.pair_block(plan.n_frames, rank, plan.world)
+        if f_hi <= f_lo:
+            for name in ("detect", "match", "verify", "degeneracy", "guided"):      # (its timers still open and close)
+                if getattr(plan, name, True) is not None:
+                    with clock(name):
+                        pass
+            return self._empty_front(plan)
+        with clock("detect"):
+            det = self.detect(frames[f_lo:f_hi])
+        with clock("match"):
             pairs, m = self.match(det)
-        else:
-            pairs = torch.zeros((0, self.cap, 2), dtype=torch.int32, device=self.device)
-            m = torch.zeros(0, dtype=torch.int32, device=self.device)
-        toc("match")
-        verified = None
-        if verify is not None:
-            tic("verify")
-            pairs_in, matches_in = pairs, m
-            if det is not None:
-                pairs, m, F_v, cost_v, info_v = self.verify(det, pairs, m, pair_lo=p_lo, **verify)
-            else:
-                F_v = torch.zeros((0, 9), dtype=torch.float64, device=self.device)
-                cost_v = torch.zeros(0, dtype=torch.float64, device=self.device)
-                info_v = torch.zeros((0, 4), dtype=torch.int32, device=self.device)
-            verified = dict(info=info_v, cost=cost_v, F=F_v, matches_in=matches_in)
-            toc("verify")
-        degenerate = None
-        if degeneracy is not None:
-            tic("degeneracy")
-            if det is not None:
-                hparams = {k: v for k, v in degeneracy.items() if k in DEGENERACY_HOMOGRAPHY_KEYS}
+        verified = degenerate = guided_out = is_deg = None
+        if plan.verify is not None:
+            with clock("verify"):
+                pairs_in, matches_in = pairs, m
+                pairs, m, F_v, cost_v, info_v = self.verify(det, pairs, m, pair_lo=p_lo, **plan.verify)
+                verified = dict(info=info_v, cost=cost_v, F=F_v, matches_in=matches_in)
+        if plan.degeneracy is not None:
+            with clock("degeneracy"):
                 pairs_h, m_hg, H_d, cost_d, info_d = self.homography(det, pairs_in, matches_in, verify_info=info_v, pair_lo=p_lo,
-                                                                     **hparams)
+                                                                     **_only(plan.degeneracy, DEGENERACY_HOMOGRAPHY_KEYS))
                 is_deg = (info_d[:, 0] & ops.HOMOG_DEGENERATE) != 0
                 pairs = torch.where(is_deg[:, None, None], pairs_h, pairs)
                 m = torch.where(is_deg, m_hg, m)
-            else:
-                H_d = torch.zeros((0, 9), dtype=torch.float64, device=self.device)
-                cost_d = torch.zeros(0, dtype=torch.float64, device=self.device)
-                info_d = torch.zeros((0, 6), dtype=torch.int32, device=self.device)
-            degenerate = dict(H=H_d, cost=cost_d, info=info_d)
-            toc("degeneracy")
-        guided_out = None
-        if guided is not None:
-            tic("guided")
-            if det is not None:
+                degenerate = dict(H=H_d, cost=cost_d, info=info_d)
+        if plan.guided is not None:
+            with clock("guided"):
                 failed = (info_v[:, 0] & (ops.VERIFY_TOO_FEW | ops.VERIFY_NO_MODEL | ops.VERIFY_WEAK)) != 0
                 kind_g = torch.where(failed, -1, 0).to(torch.int32)
                 model_g = F_v
                 if degenerate is not None:
                     kind_g = torch.where(is_deg, 1, kind_g).to(torch.int32)
                     model_g = torch.where(is_deg[:, None], H_d, F_v)
-                pairs, m, new_g, info_g = self.guided(det, pairs, m, model_g, kind=kind_g, **guided)
+                pairs, m, new_g, info_g = self.guided(det, pairs, m, model_g, kind=kind_g, **plan.guided)
+                guided_out = dict(info=info_g, is_new=new_g)
+        return _Front(det, det["xy"], det["n"], pairs, m, verified, degenerate, guided_out, is_deg, int(p_hi - p_lo), int(f_hi - f_lo))
+
+    def _empty_front(self, plan):
+        """The `_front` of a rank that owns no frames: det = None and zero rows of everything else, for the gather."""
+        def rows(dtype, *shape):
+            return torch.zeros((0,) + shape, dtype=dtype, device=self.device)
+
+        f64, i32 = torch.float64, torch.int32
+        m = rows(i32)
+        verified = dict(info=rows(i32, 4), cost=rows(f64), F=rows(f64, 9), matches_in=m) if plan.verify is not None else None
+        degenerate = dict(H=rows(f64, 9), cost=rows(f64), info=rows(i32, 6)) if plan.degeneracy is not None else None
+        guided_out = dict(info=rows(i32, 4), is_new=rows(torch.uint8, self.cap)) if plan.guided is not None else None
+        return _Front(None, rows(torch.float32, self.cap, 2), rows(i32), rows(i32, self.cap, 2), m, verified, degenerate, guided_out,
+                      None, 0, 0)
+
+    def _link(self, front, plan, rank, dist, clock):
+        """Every rank's key points and matches (gathered when the run is sharded) linked into tracks
+        -> ((track_ptr, obs_frame, obs_kp, xy_dev), device tensors in the order the track consumers take them, m_h, n_h: the
+        match and key point counts of the whole clip on the host)."""
+        with clock("link"):
+            if plan.sharded:
+                # every rank needs every frame's key points and every pair's matches to link identical tracks.  The block
+                # partition is arithmetic on (F, world), so every rank knows every rank's row counts: fixed-shape device
+                # all-gathers (RCCL over xGMI under "nccl"), nothing goes through host memory.
+                blocks = [parallel.pair_block(plan.n_frames, r, plan.world) for r in range(plan.world)]
+                pair_counts = [b[0][1] - b[0][0] for b in blocks]
+                last_rank_with_pairs = max(r for r in range(plan.world) if pair_counts[r] > 0)
+                # frames f_lo .. f_lo+own-1 are owned; the halo frame belongs to the next rank (the last one keeps it)
+                frame_counts = [pair_counts[r] + (1 if r == last_rank_with_pairs else 0) for r in range(plan.world)]
+                keep = frame_counts[rank]
+                xy_dev = parallel.gather_blocks(front.xy[:keep].contiguous(), frame_counts, dist)
+                n_d = parallel.gather_blocks(front.n[:keep].contiguous(), frame_counts, dist)
+                m_d = parallel.gather_blocks(front.m.contiguous(), pair_counts, dist)
+                pairs_d = parallel.gather_blocks(front.pairs.contiguous(), pair_counts, dist)
             else:
-                new_g = torch.zeros((0, self.cap), dtype=torch.uint8, device=self.device)
-                info_g = torch.zeros((0, 4), dtype=torch.int32, device=self.device)
-            guided_out = dict(info=info_g, is_new=new_g)
-            toc("guided")
-        tic("link")
-        if sharded:
-            # every rank needs every frame's key points and every pair's matches to link identical tracks.  The block
-            # partition is arithmetic on (F, world), so every rank knows every rank's row counts: fixed-shape device
-            # all-gathers (RCCL over xGMI under "nccl"), nothing goes through host memory.
-            blocks = [parallel.pair_block(F, r, world) for r in range(world)]
-            pair_counts = [b[0][1] - b[0][0] for b in blocks]
-            last_rank_with_pairs = max(r for r in range(world) if pair_counts[r] > 0)
-            # frames f_lo .. f_lo+own-1 are owned; the halo frame belongs to the next rank (the last one keeps it)
-            frame_counts = [pair_counts[r] + (1 if r == last_rank_with_pairs else 0) for r in range(world)]
-            keep = frame_counts[rank]
-            d = self.device
-            if det is not None:
-                xy_l, n_l = det["xy"][:keep], det["n"][:keep]
-            else:
-                xy_l = torch.zeros((0, self.cap, 2), dtype=torch.float32, device=d)
-                n_l = torch.zeros(0, dtype=torch.int32, device=d)
-            xy_dev = parallel.gather_blocks(xy_l.contiguous(), frame_counts, dist)
-            n_d = parallel.gather_blocks(n_l.contiguous(), frame_counts, dist)
-            m_d = parallel.gather_blocks(m.contiguous(), pair_counts, dist)
-            pairs_d = parallel.gather_blocks(pairs.contiguous(), pair_counts, dist)
-        else:
-            xy_dev, n_d, m_d, pairs_d = det["xy"], det["n"], m, pairs
-        m_h = m_d.cpu().numpy()
-        n_h = n_d.cpu().numpy()
-        track_ptr, obs_frame, obs_kp, bad = ops.link_tracks_device(n_d, xy_dev, m_d, pairs_d, self.ctx)
-        if bad:
-            raise MMError("link: match index outside the key point tables")
-        toc("link")
-        recovered = None
-        if poses is not None:
-            tic("poses")
-            if degenerate is None:
-                recovered = self.recover_poses(det, pairs, m, F_v, K, **poses)
-            else:
-                # both pose calls on the linked matches, the homography's rows where the verdict says so, then one chain
-                kw = {k: v for k, v in poses.items() if k not in ("E0", "min_common")}
-                R_p, t_p, sigma_p, depth_p, info_p = ops.recover_poses(det["xy"], pairs, m, F_v, K, ctx=self.ctx, **kw)
-                toc("poses")
-                tic("degeneracy")
-                hkw = {k: v for k, v in degeneracy.items() if k in DEGENERACY_POSE_KEYS}
-                if "min_matches" in kw:
-                    hkw["min_matches"] = kw["min_matches"]
-                R_h, t_h, sigma_h, normal_h, depth_h, info_h = ops.recover_poses_homography(det["xy"], pairs, m, H_d, K,
-                                                                                            ctx=self.ctx, **hkw)
-                R_p = torch.where(is_deg[:, None], R_h, R_p)
-                t_p = torch.where(is_deg[:, None], t_h, t_p)
-                depth_p = torch.where(is_deg[:, None, None], depth_h, depth_p)
-                info_p = torch.where(is_deg[:, None], info_h, info_p)
-                degenerate.update(pose_info=info_h, sigma=sigma_h, normal=normal_h)
-                toc("degeneracy")
-                tic("poses")
-                ext_d, scale_d, rho_d, cinfo_d = ops.chain_poses(pairs, m, depth_p, R_p, t_p, info_p, E0=poses.get("E0"),
-                                                                 min_common=poses.get("min_common", 8), ctx=self.ctx)
-                recovered = dict(extrinsics=ext_d, R=R_p, t=t_p, sigma=sigma_p, info=info_p, depth=depth_p, scale=scale_d,
-                                 rho=rho_d, chain_info=cinfo_d)
+                xy_dev, n_d, m_d, pairs_d = front.xy, front.n, front.m, front.pairs
+            m_h = m_d.cpu().numpy()
+            n_h = n_d.cpu().numpy()
+            track_ptr, obs_frame, obs_kp, bad = ops.link_tracks_device(n_d, xy_dev, m_d, pairs_d, self.ctx)
+            if bad:
+                raise MMError("link: match index outside the key point tables")
+        return (track_ptr, obs_frame, obs_kp, xy_dev), m_h, n_h
+
+    def _poses(self, front, plan, K, extrinsics, clock):
+        """The extrinsics in use -> (ext [F,3,4] on the host, the `poses` entry of the result or None): the given ones, or the
+        ones `recover_poses` chains from the linked matches -- with `degeneracy`, the homography's pose in the rows of the
+        degenerate pairs, that call billed to "degeneracy"."""
+        if plan.poses is None:
+            return np.asarray(extrinsics, float)[:, :3, :], None
+        det, pairs, m, is_deg = front.det, front.pairs, front.m, front.is_deg
+
+        def homography_rows(R, t, depth, info):
+            with clock.paused("poses"), clock("degeneracy"):
+                hkw = _only(plan.degeneracy, DEGENERACY_POSE_KEYS)
+                if "min_matches" in plan.poses:
+                    hkw["min_matches"] = plan.poses["min_matches"]
+                R_h, t_h, sigma_h, normal_h, depth_h, info_h = ops.recover_poses_homography(det["xy"], pairs, m, front.degeneracy["H"],
+                                                                                            K, ctx=self.ctx, **hkw)
+                R = torch.where(is_deg[:, None], R_h, R)
+                t = torch.where(is_deg[:, None], t_h, t)
+                depth = torch.where(is_deg[:, None, None], depth_h, depth)
+                info = torch.where(is_deg[:, None], info_h, info)
+                front.degeneracy.update(pose_info=info_h, sigma=sigma_h, normal=normal_h)
+            return R, t, depth, info
+
+        with clock("poses"):
+            recovered = self.recover_poses(det, pairs, m, front.verify["F"], K,
+                                           override=homography_rows if plan.degeneracy is not None else None, **plan.poses)
             recovered.pop("depth")
             ext = recovered["extrinsics"].cpu().numpy()
-            toc("poses")
-        else:
-            ext = np.asarray(extrinsics, float)[:, :3, :]
-        aligned = None
-        if align is not None:
-            tic("align")
-            ext_d = torch.as_tensor(np.ascontiguousarray(ext, dtype=np.float64)).to(self.device)
-            aligned = self.align(ext_d, align)
-            ops.apply_similarity(aligned["sim"], None, ext_d, ctx=self.ctx)      # (a NaN sim -- no model -- changes nothing)
-            if recovered is not None:
-                recovered["extrinsics"] = ext_d
-            ext = ext_d.cpu().numpy()
-            toc("align")
+        return ext, recovered
 
-        def triangulated(ext):
-            """(points, quality, flags) of the linked tracks under the extrinsics `ext`; two-view has no quality or flags."""
-            proj = np.einsum("ij,fjk->fik", np.asarray(K, float), ext)   # K [R|t], processor.py:184,448
-            tic("triangulate")
-            if triangulation == "multi_view":
-                res = self.triangulate_multi_view(track_ptr, obs_frame, obs_kp, xy_dev, proj, **(cull or {}))
-            else:
-                res = self.triangulate(track_ptr, obs_frame, obs_kp, xy_dev, proj), None, None
-            toc("triangulate")
-            return res
+    def _triangulated(self, plan, K, ext, tracks, clock):
+        """(points, quality, flags) of the linked tracks under the extrinsics `ext`; two-view has no quality or flags."""
+        proj = np.einsum("ij,fjk->fik", np.asarray(K, float), ext)   # K [R|t], processor.py:184,448
+        with clock("triangulate"):
+            if plan.triangulation == "multi_view":
+                return self.triangulate_multi_view(*tracks, proj, **(plan.cull or {}))
+            return self.triangulate(*tracks, proj), None, None
 
-        X, quality, flags = triangulated(ext)
-        resected = None
-        if resect is not None and track_ptr.shape[0] > 1:
-            tic("resect")
-            resected = self.resect(K, X, track_ptr, obs_frame, obs_kp, xy_dev, F,
-                                   pt_ok=(flags == 0) if triangulation == "multi_view" else None, prior=ext, **resect)
-            resected.pop("inlier")
-            ext = resected["extrinsics"].cpu().numpy()
-            toc("resect")
-            X, quality, flags = triangulated(ext)
-        P, O = track_ptr.shape[0] - 1, obs_frame.shape[0]
-        out = dict(det=det, n_tracks=P, n_obs=O, points0=X, track_ptr_dev=track_ptr, obs_frame_dev=obs_frame,
-                   obs_kp_dev=obs_kp, xy_dev=xy_dev, match_count=m_h, kp_count=n_h, pairs_local=int(p_hi - p_lo),
-                   frames_local=int(f_hi - f_lo))
-        if verified is not None:
-            out["verify"] = verified
-        if recovered is not None:
-            out["poses"] = recovered
-        if degenerate is not None:
-            out["degeneracy"] = degenerate
-        if guided_out is not None:
-            out["guided"] = guided_out
-        if resected is not None:
-            out["resect"] = resected
-        if aligned is not None:
-            out["align"] = aligned
-        kept = None
-        if triangulation == "multi_view":
-            out.update(track_quality=quality, track_flags=flags)
-            if cull is not None:
-                kept = torch.nonzero(flags == 0).reshape(-1)
-                out["kept_tracks"] = kept
-        if not ba or O == 0 or (kept is not None and kept.numel() == 0):
-            T.pop("_open", None)
-            return out
-        tic("ba")
-        with np.errstate(all="ignore"):
-            cams0 = frameParameters(ext).reshape(F, 6)
-        # managePoints order (point-major, insertion order inside a track), assembled on the device
-        d = self.device
-        if kept is not None:
-            # (mm_flatten_offsets + mm_flatten_tracks: the kept tracks, in track order)
-            coords_d, of_d, pi_d = ops.flatten_tracks(track_ptr, obs_frame, obs_kp, xy_dev, sel=kept, ctx=self.ctx)
-            pb = ops.BADevice(K, of_d, pi_d, coords_d, F, int(kept.numel()), d, self.ctx)
-            pts0 = X[kept].contiguous()
-        else:
-            if world > 1:
-                lo, hi, o_lo, o_hi = parallel.partition_tracks(track_ptr, rank, world)
+    def _structure(self, plan, K, ext, recovered, tracks, clock):
+        """align, triangulate, and with `resect` every frame registered against the points and the tracks triangulated again
+        -> (ext in use [F,3,4] on the host, X, quality, flags, the `align` and `resect` entries of the result or None)."""
+        aligned = resected = None
+        if plan.align is not None:
+            with clock("align"):
+                ext_d = torch.as_tensor(np.ascontiguousarray(ext, dtype=np.float64)).to(self.device)
+                aligned = self.align(ext_d, plan.align)
+                ops.apply_similarity(aligned["sim"], None, ext_d, ctx=self.ctx)      # (a NaN sim -- no model -- changes nothing)
+                if recovered is not None:
+                    recovered["extrinsics"] = ext_d
+                ext = ext_d.cpu().numpy()
+        X, quality, flags = self._triangulated(plan, K, ext, tracks, clock)
+        if plan.resect is not None and tracks[0].shape[0] > 1:
+            with clock("resect"):
+                resected = self.resect(K, X, *tracks, plan.n_frames, pt_ok=(flags == 0) if plan.triangulation == "multi_view" else None,
+                                       prior=ext, **plan.resect)
+                resected.pop("inlier")
+                ext = resected["extrinsics"].cpu().numpy()
+            X, quality, flags = self._triangulated(plan, K, ext, tracks, clock)
+        return ext, X, quality, flags, aligned, resected
+
+    def _adjust(self, plan, K, ext, X, kept, tracks, rank, ftol, max_nfev, verbose, clock):
+        """The global adjustment of the kept tracks (all of them without cull; this rank's share when sharded), then `refine`
+        and the second registration of `align` -> what the result gains: ba, n_obs_local, cam_span, n_pairs, refine, ba_aligned."""
+        F, d = plan.n_frames, self.device
+        with clock("ba"):
+            with np.errstate(all="ignore"):
+                cams0 = frameParameters(ext).reshape(F, 6)
+            # managePoints order (point-major, insertion order inside a track), assembled on the device
+            if kept is not None:
+                # (mm_flatten_offsets + mm_flatten_tracks: the kept tracks, in track order)
+                coords_d, of_d, pi_d = ops.flatten_tracks(*tracks, sel=kept, ctx=self.ctx)
+                pb = ops.BADevice(K, of_d, pi_d, coords_d, F, int(kept.numel()), d, self.ctx)
+                pts0 = X[kept].contiguous()
             else:
-                lo, hi, o_lo, o_hi = 0, P, 0, O
-            # (mm_flatten_tracks: this rank's tracks lo .. hi - 1)
-            coords_d, of_d, pi_d = ops.flatten_tracks(track_ptr, obs_frame, obs_kp, xy_dev, t_lo=lo, n_sel=hi - lo, ctx=self.ctx)
-            pb = ops.BADevice(K, of_d, pi_d, coords_d, F, hi - lo, d, self.ctx)
-            pts0 = X[lo:hi].contiguous()
-        solver = SchurTRF(pb, allreduce=parallel.AllReduce(force=force_collectives) if sharded else None)
-        cams_d = torch.as_tensor(cams0).to(self.device)
-        tic("ba_solve")
-        res = solver.solve(cams_d, pts0, ftol=ftol, max_nfev=max_nfev, verbose=verbose if rank == 0 else 0)
-        toc("ba_solve")
-        toc("ba")
-        out.update(ba=res, n_obs_local=pb.O, cam_span=pb.cam_span, n_pairs=pb.n_pairs)
-        if refine is not None:
-            tic("refine")
-            out["refine"] = refine_rounds(pb, res, K, refine, verbose=verbose)
-            res = out["refine"]["ba"]
-            toc("refine")
-        if align is not None:
-            tic("align")
-            cams_h = res.cams.reshape(F, 6).cpu().numpy()
-            ext_b = np.stack([np.concatenate([_rodrigues_matrix(c[:3]), c[3:, None]], axis=1) for c in cams_h])
-            ext_b = torch.as_tensor(np.ascontiguousarray(ext_b)).to(self.device)
-            again = self.align(ext_b, align)
-            pts_b = res.pts.reshape(-1, 3).clone().contiguous()
-            ops.apply_similarity(again["sim"], pts_b, ext_b, ctx=self.ctx)
-            out["ba_aligned"] = dict(extrinsics=ext_b, points=pts_b, sim=again["sim"], info=again["info"])
-            toc("align")
-        T.pop("_open", None)
+                lo, hi = 0, tracks[0].shape[0] - 1
+                if plan.world > 1:
+                    lo, hi, _, _ = parallel.partition_tracks(tracks[0], rank, plan.world)
+                # (mm_flatten_tracks: this rank's tracks lo .. hi - 1)
+                coords_d, of_d, pi_d = ops.flatten_tracks(*tracks, t_lo=lo, n_sel=hi - lo, ctx=self.ctx)
+                pb = ops.BADevice(K, of_d, pi_d, coords_d, F, hi - lo, d, self.ctx)
+                pts0 = X[lo:hi].contiguous()
+            solver = SchurTRF(pb, allreduce=parallel.AllReduce(force=plan.force_collectives) if plan.sharded else None)
+            cams_d = torch.as_tensor(cams0).to(d)
+            with clock("ba_solve"):
+                res = solver.solve(cams_d, pts0, ftol=ftol, max_nfev=max_nfev, verbose=verbose if rank == 0 else 0)
+        out = dict(ba=res, n_obs_local=pb.O, cam_span=pb.cam_span, n_pairs=pb.n_pairs)
+        if plan.refine is not None:
+            with clock("refine"):
+                out["refine"] = refine_rounds(pb, res, K, plan.refine, verbose=verbose)
+                res = out["refine"]["ba"]
+        if plan.align is not None:
+            with clock("align"):
+                cams_h = res.cams.reshape(F, 6).cpu().numpy()
+                ext_b = np.stack([np.concatenate([_rodrigues_matrix(c[:3]), c[3:, None]], axis=1) for c in cams_h])
+                ext_b = torch.as_tensor(np.ascontiguousarray(ext_b)).to(d)
+                again = self.align(ext_b, plan.align)
+                pts_b = res.pts.reshape(-1, 3).clone().contiguous()
+                ops.apply_similarity(again["sim"], pts_b, ext_b, ctx=self.ctx)
+                out["ba_aligned"] = dict(extrinsics=ext_b, points=pts_b, sim=again["sim"], info=again["info"])
         return out
