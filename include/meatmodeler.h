@@ -810,6 +810,92 @@ int mm_filter_observations(mm_ctx *ctx, const double *cams /*[F,6]*/, int F, con
                            double *cos_parallax /*[P]*/, int32_t *fi_out /*[O]*/, int32_t *pi_out /*[O]*/, double *obs_out /*[O,2]*/,
                            int32_t *obs_map /*[O]*/, int32_t *point_map /*[P]*/, int64_t *counts /*[4]*/, void *ws, size_t ws_bytes);
 
+/* ---- a-9c: dense depth: a plane-sweep depth map per view, the maps fused into a cloud ---------------------------------------------
+ * No reference counterpart: the reference ends with the adjusted corner points.  Every reference view gets a depth map by
+ * sweeping D fronto-parallel planes through its depth range and scoring each against up to S source frames by zero-mean
+ * normalised cross-correlation over a (2r+1)^2 window (mm_depth_sweep); the maps are then checked against each other and the
+ * pixels enough other views agree with become a point cloud (mm_depth_fuse).  Only + - * / sqrt floor rint and conversions
+ * occur, each correctly rounded and none contracted, so a restatement that follows this text gives the same bits.
+ *
+ * mm_depth_sweep.  img [F, H, W] u8; ref [V] i32, the frame of each view; src [V, S] i32, its source frames, -1: none (the
+ * caller checks 0 <= ref < F and -1 <= src < F); AB [V, S, 12] f64, w0, dw [V] f64 -- DEVICE pointers, as are the outputs; K [9]
+ * row-major and prm are HOST.
+ *   Host tables (the caller's: ops.sweep_tables writes every product out).  With [R_r | t_r] the reference and [R_s | t_s] the
+ *   source extrinsic: R = R_s R_r^T, R_ij = (Rs_i0 Rr_j0 + Rs_i1 Rr_j1) + Rs_i2 Rr_j2; t_i = ts_i - ((R_i0 tr_0 + R_i1 tr_1) +
+ *   R_i2 tr_2); M = K R, M_ij = (K_i0 R_0j + K_i1 R_1j) + K_i2 R_2j; with K = (fx s cx; 0 fy cy; 0 0 1), A = M K^-1:
+ *   A_i0 = M_i0 / fx, A_i1 = (M_i1 - s A_i0) / fy, A_i2 = (M_i2 - cx A_i0) - cy A_i1; b_i = (K_i0 t_0 + K_i1 t_1) + K_i2 t_2.
+ *   AB = (A row-major, b).  The view's planes have inverse depths w_k = w0 + k dw, k = 0 .. D-1, with w0 = 1 / dmin and
+ *   dw = (1 / dmax - 1 / dmin) / (D - 1) (0 for D = 1).  K^-1 has the last row (0, 0, 1), so the homography of plane k is A with
+ *   w_k b added to its third column -- the premise K is judged for (the check of mm_resect_cameras); the kernels read AB alone.
+ *   Warp, f64, per reference pixel (u, v), plane k, source s: c_i = A_i2 + w_k b_i; p_i = (A_i0 u + A_i1 v) + c_i; xs = p_0 /
+ *   p_2, ys = p_1 / p_2.  Valid iff p_2 > 0, 0 <= xs <= W-1 and 0 <= ys <= H-1 (a comparison with NaN is false).
+ *   x0 = min(floor(xs), W-2), fx = (float)(xs - x0); y0, fy likewise.
+ *   Sample, f32, with s00 = img[src, y0, x0], s01 at x0+1, s10 at y0+1, s11 at both: top = s00 + fx (s01 - s00), bot = s10 +
+ *   fx (s11 - s10), val = top + fy (bot - top).  The reference's value at a pixel is its u8 as f32.
+ *   Cost, f32.  A pixel with r <= u < W-r and r <= v < H-r has a window, n = (2r+1)^2 pixels, walked row-major (dv outer, du
+ *   inner); every sum below starts at 0 and adds its terms one by one in that order.  mean_a = (sum of the reference values) /
+ *   (float)n, ca = value - mean_a, saa = sum ca ca.  For a source all of whose n window pixels warp validly: mean_b, cb and
+ *   sbb = sum cb cb likewise from the samples, sab = sum ca cb.  The source counts iff those n are valid, saa > thr and sbb > thr,
+ *   thr = (float)var_min (float)n; then cost_s = 1 - sab / sqrt(saa sbb).  Over the sources that count, in list order: acc +=
+ *   cost_s, cnt += 1; cost_k = acc / (float)cnt, valid iff cnt >= min_sources.
+ *   Winner: the lowest valid cost_k, the lowest k among equals.  Sub-plane step, f64 from the f32 costs: if 0 < k < D-1, both
+ *   neighbouring planes are valid and den = (c- - 2 c0) + c+ > 0, delta = (c- - c+) / (2 den) clamped to [-1/2, 1/2]; otherwise 0.
+ *   depth = (float)(1 / (w0 + (k + delta) dw)).
+ *   depth, cost [V, H, W] f32 and plane [V, H, W] i32: NaN, NaN and -1 where a pixel has no window or no valid plane.
+ * A view's map depends on that view's rows alone, one thread computes each number from its own inputs, and a call repeats bit
+ * for bit.  ws holds mm_depth_sweep_workspace_bytes(V, S, D) bytes, 8-byte aligned (c_i per view, source and plane).
+ * planes outside 1 .. MM_SWEEP_MAX_PLANES, radius outside 1 .. MM_SWEEP_MAX_RADIUS, S outside 1 .. MM_SWEEP_MAX_SOURCES,
+ * min_sources outside 1 .. S, a var_min that is negative or not finite, a K that mm_resect_cameras would refuse, null pointers,
+ * non-positive F, H, W, more than 2^31 - 1 pixels: MM_ERR_ARG; a workspace that is too small: MM_ERR_WORKSPACE -- returned before
+ * the device is touched.  V = 0 returns MM_OK and writes nothing.  MM_SWEEP_TILE is the side of the tile of pixels a workgroup
+ * owns (tiles start at (r, r)); no result depends on it.
+ *
+ * mm_depth_fuse.  depth, cost [V, H, W] f32 as the sweep wrote them; ext [V, 3, 4] f64, the views' [R | t]; nbr [V, Q] i32,
+ * per view the other views of this call it is checked against, -1: none (the caller checks -1 <= nbr < V); grey [V, H, W] u8, the
+ * views' images -- DEVICE pointers, as are the outputs; K [9] and prm are HOST.  f64 throughout, sums left to right.
+ *   Candidate: pixel (u, v) of view i with d = (double)depth finite and (double)cost <= max_cost.
+ *   Lift(e, u, v, d): yn = (v - cy) / fy, xn = ((u - cx) - s yn) / fx, a = (d xn - t_0, d yn - t_1, d - t_2),
+ *   X_j = (R_0j a_0 + R_1j a_1) + R_2j a_2.  Project(e, X): Y_i = ((R_i0 X_0 + R_i1 X_1) + R_i2 X_2) + t_i,
+ *   px = ((fx Y_0 + s Y_1) + cx Y_2) / Y_2, py = (fy Y_1 + cy Y_2) / Y_2.
+ *   X_w = Lift(i, u, v, d).  View q of nbr[i] agrees iff: (Y, px, py) = Project(q, X_w) has Y_2 > 0; xi = rint(px), yi =
+ *   rint(py) lie in 0 .. W-1, 0 .. H-1; pixel (xi, yi) of q is a candidate, with depth dq; |dq - Y_2| <= eps_depth Y_2;
+ *   (Z, bx, by) = Project(i, Lift(q, xi, yi, dq)) has Z_2 > 0 and sqrt((bx - u)^2 + (by - v)^2) <= tau_px.
+ *   The pixel is kept iff at least min_consistent views agree.
+ *   Kept pixels are compacted in (view, row, column) order: points [cap, 3] f64 = X_w, grey_out [cap] u8, origin [cap, 2] i32 =
+ *   (view, v W + u), n_consistent [cap] i32 = the views that agreed; keep [V, H, W] u8; counts [2] i64 = (kept, candidates).
+ *   Rows beyond cap are not written; counts[0] still counts them.  The positions are an exclusive scan in chunks of
+ *   MM_FILTER_CHUNK pixels -- sums per chunk, one scan of the sums, then each chunk places its rows: separate launches.
+ *   A surface point seen by several views appears once per view that keeps it: duplicates are NOT merged.
+ * No atomics, no float sum across threads: a call repeats bit for bit.  ws holds mm_depth_fuse_workspace_bytes(V, H, W) bytes,
+ * 8-byte aligned.  A NaN max_cost, a negative or NaN eps_depth or tau_px, min_consistent < 0, Q outside 0 ..
+ * MM_FUSE_MAX_NEIGHBOURS, cap < 0, a K as above, null pointers (nbr may be null with Q = 0, the four row outputs with cap = 0),
+ * more than 2^31 - 1 pixels: MM_ERR_ARG; a workspace that is too small: MM_ERR_WORKSPACE -- before the device is touched.
+ * V = 0 returns MM_OK with counts = 0. */
+#define MM_SWEEP_TILE 16
+#define MM_SWEEP_MAX_RADIUS 4
+#define MM_SWEEP_MAX_PLANES 4096
+#define MM_SWEEP_MAX_SOURCES 16
+#define MM_FUSE_MAX_NEIGHBOURS 64
+typedef struct mm_sweep_params {
+    int32_t planes, radius, min_sources, reserved;
+    double var_min;
+} mm_sweep_params;
+typedef struct mm_fuse_params {
+    int32_t min_consistent, reserved;
+    double max_cost, eps_depth, tau_px;
+} mm_fuse_params;
+size_t mm_depth_sweep_workspace_bytes(int V, int S, int D);
+int mm_depth_sweep(mm_ctx *ctx, const uint8_t *img /*[F,H,W]*/, int F, int H, int W, const double *K /*host [9]*/,
+                   const int32_t *ref /*[V]*/, const int32_t *src /*[V,S]*/, const double *AB /*[V,S,12]*/, const double *w0 /*[V]*/,
+                   const double *dw /*[V]*/, int V, int S, const mm_sweep_params *prm, float *depth /*[V,H,W]*/,
+                   float *cost /*[V,H,W]*/, int32_t *plane /*[V,H,W]*/, void *ws, size_t ws_bytes);
+size_t mm_depth_fuse_workspace_bytes(int V, int H, int W);
+int mm_depth_fuse(mm_ctx *ctx, const float *depth /*[V,H,W]*/, const float *cost /*[V,H,W]*/, int V, int H, int W,
+                  const double *ext /*[V,3,4]*/, const double *K /*host [9]*/, const int32_t *nbr /*[V,Q]*/, int Q,
+                  const uint8_t *grey /*[V,H,W]*/, const mm_fuse_params *prm, int64_t cap, double *points /*[cap,3]*/,
+                  uint8_t *grey_out /*[cap]*/, int32_t *origin /*[cap,2]*/, int32_t *n_consistent /*[cap]*/, uint8_t *keep /*[V,H,W]*/,
+                  int64_t *counts /*[2]*/, void *ws, size_t ws_bytes);
+
 /* ---- a-7..a-9: bundle adjustment sweeps -----------------------------------------------------------
  * Cost model of bundleAdjuster.py:7-52,81-102 (Rodrigues rotate, translate, full 3x3 K, divide, minus obs),
  * f64 throughout.  The LM/trust-region driver (the reference's scipy least_squares TRF loop,

@@ -126,6 +126,18 @@ class FilterParams(C.Structure):
                 ("max_cos_parallax", C.c_double)]
 
 
+class SweepParams(C.Structure):
+    """mm_sweep_params: planes, window radius, source floor and the texture floor of mm_depth_sweep."""
+    _fields_ = [("planes", C.c_int32), ("radius", C.c_int32), ("min_sources", C.c_int32), ("reserved", C.c_int32),
+                ("var_min", C.c_double)]
+
+
+class FuseParams(C.Structure):
+    """mm_fuse_params: the view floor and the three thresholds of mm_depth_fuse."""
+    _fields_ = [("min_consistent", C.c_int32), ("reserved", C.c_int32), ("max_cost", C.c_double), ("eps_depth", C.c_double),
+                ("tau_px", C.c_double)]
+
+
 ALLREDUCE_FN =C.CFUNCTYPE(C.c_int, vp, vp, C.c_int64)
 
 
@@ -205,6 +217,12 @@ SIGNATURES = {
     "mm_filter_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int64]),
     "mm_filter_observations": (C.c_int, [vp, vp, C.c_int, vp, C.c_int64, c_f64p, vp, vp, vp, C.c_int64, vp, C.POINTER(FilterParams),
                                          vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]),
+    "mm_depth_sweep_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "mm_depth_sweep": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, c_f64p, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(SweepParams),
+                                 vp, vp, vp, vp, C.c_size_t]),
+    "mm_depth_fuse_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "mm_depth_fuse": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, c_f64p, vp, C.c_int, vp, C.POINTER(FuseParams), C.c_int64,
+                                vp, vp, vp, vp, vp, vp, vp, C.c_size_t]),
     "mm_ba_residual": (C.c_int, [vp, C.POINTER(BAProblem), vp, vp, vp, vp, vp, C.c_size_t]),
     "mm_ba_jacobian": (C.c_int, [vp, C.POINTER(BAProblem), vp, vp, vp, vp]),
     "mm_ba_normal_eq": (C.c_int, [vp, C.POINTER(BAProblem), vp, vp, vp, vp, vp, vp]),

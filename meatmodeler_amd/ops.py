@@ -1312,6 +1312,180 @@ def filter_observations(cams, pts, K, fi, pi=None, obs=None, pt_ptr=None, max_re
                 err=err, depth=depth, cos_parallax=cosp)
 
 
+SWEEP_TILE = 16                                         # MM_SWEEP_TILE: side of the tile of pixels one workgroup of the sweep owns
+SWEEP_MAX_RADIUS, SWEEP_MAX_PLANES, SWEEP_MAX_SOURCES, FUSE_MAX_NEIGHBOURS = 4, 4096, 16, 64      # MM_SWEEP_MAX_*, MM_FUSE_MAX_*
+
+
+def _dense_K(K, name):
+    Kh = _host_f64(K, 9, f"{name}: K")
+    if not np.isfinite(Kh).all() or Kh[3] != 0 or Kh[6] != 0 or Kh[7] != 0 or Kh[8] != 1 or Kh[0] == 0 or Kh[4] == 0:
+        raise ValueError(f"{name}: K must be finite, upper triangular with K[2, 2] = 1 and non-zero focal lengths")
+    return Kh
+
+
+def _dense_ext(ext, name):
+    e = np.asarray(ext, np.float64)
+    if e.ndim != 3 or e.shape[1] not in (3, 4) or e.shape[2] != 4:
+        raise ValueError(f"{name}: extrinsics [n, 3|4, 4] expected")
+    return np.ascontiguousarray(e[:, :3, :])
+
+
+def sweep_tables(K, extrinsics, ref, src, ranges, planes):
+    """The host tables of depth_sweep, NumPy f64 with every product written out as include/meatmodeler.h states it (no BLAS, so
+    the bits do not depend on the library NumPy was built with): K 3 x 3, extrinsics [F, 3|4, 4], ref [V] and src [V, S] frame
+    indices (-1: no source; its row of AB is zero), ranges [V, 2] = (dmin, dmax) per view, planes = D
+    -> (AB [V, S, 12] = (A row-major, b), w0 [V], dw [V])."""
+    name = "sweep_tables"
+    Kh = _dense_K(K, name)
+    E = _dense_ext(extrinsics, name)
+    ref, src = np.asarray(ref, np.int64).reshape(-1), np.asarray(src, np.int64)
+    rng = np.asarray(ranges, np.float64)
+    V = ref.size
+    if src.ndim != 2 or src.shape[0] != V or rng.shape != (V, 2):
+        raise ValueError(f"{name}: ref [V], src [V, S] and ranges [V, 2] expected")
+    if V and (ref.min() < 0 or ref.max() >= len(E) or src.min() < -1 or src.max() >= len(E)):
+        raise ValueError(f"{name}: frame index out of range")
+    if not (np.isfinite(rng).all() and (rng[:, 0] > 0).all() and (rng[:, 1] >= rng[:, 0]).all()):
+        raise ValueError(f"{name}: 0 < dmin <= dmax expected")
+    D = int(planes)
+    if D < 1:
+        raise ValueError(f"{name}: planes must be at least 1")
+    S = src.shape[1]
+    Er = E[ref][:, None]                                         # [V, 1, 3, 4]
+    Es = E[np.where(src < 0, 0, src)]                            # [V, S, 3, 4]
+    Rr, tr, Rs, ts = Er[..., :3], Er[..., 3], Es[..., :3], Es[..., 3]
+    R = np.empty((V, S, 3, 3))
+    for i in range(3):
+        for j in range(3):
+            R[..., i, j] = (Rs[..., i, 0] * Rr[..., j, 0] + Rs[..., i, 1] * Rr[..., j, 1]) + Rs[..., i, 2] * Rr[..., j, 2]
+    t = np.empty((V, S, 3))
+    for i in range(3):
+        t[..., i] = ts[..., i] - ((R[..., i, 0] * tr[..., 0] + R[..., i, 1] * tr[..., 1]) + R[..., i, 2] * tr[..., 2])
+    fx, sk, cx, fy, cy = Kh[0], Kh[1], Kh[2], Kh[4], Kh[5]
+    AB = np.empty((V, S, 12))
+    for i in range(3):
+        M = [(Kh[3 * i] * R[..., 0, j] + Kh[3 * i + 1] * R[..., 1, j]) + Kh[3 * i + 2] * R[..., 2, j] for j in range(3)]
+        a0 = M[0] / fx
+        a1 = (M[1] - sk * a0) / fy
+        AB[..., 3 * i], AB[..., 3 * i + 1], AB[..., 3 * i + 2] = a0, a1, (M[2] - cx * a0) - cy * a1
+        AB[..., 9 + i] = (Kh[3 * i] * t[..., 0] + Kh[3 * i + 1] * t[..., 1]) + Kh[3 * i + 2] * t[..., 2]
+    AB[src < 0] = 0.0
+    w0 = 1.0 / rng[:, 0]
+    dw = (1.0 / rng[:, 1] - 1.0 / rng[:, 0]) / float(D - 1) if D > 1 else np.zeros(V)
+    return AB, w0, dw
+
+
+def depth_sweep(img, K, extrinsics, ref, src, ranges, planes=64, radius=3, var_min=4.0, min_sources=1, ctx=None):
+    """A plane-sweep depth map per reference view (mm_depth_sweep): img [F, H, W] u8 on the device; K 3 x 3, extrinsics
+    [F, 3|4, 4], ref [V] (the frame of each view), src [V, S] (its source frames, -1: none) and ranges [V, 2] = (dmin, dmax) on
+    the host.  Every pixel with a (2 radius + 1)^2 window is scored on `planes` planes, evenly spaced in inverse depth, by
+    zero-mean normalised cross-correlation against every source that sees the whole window and is textured there (variance
+    above var_min in both images), the mean over at least min_sources of them; the lowest cost wins and is refined between its
+    neighbouring planes.  -> dict(depth, cost [V, H, W] f32, NaN where there is none; plane [V, H, W] i32, -1 there; AB, w0, dw:
+    the host tables of `sweep_tables`).  Bad shapes, dtypes, indices or parameters raise ValueError before the library is
+    called."""
+    name = "depth_sweep"
+    if not torch.is_tensor(img) or img.dtype != torch.uint8 or img.dim() != 3:
+        raise ValueError(f"{name}: img [F, H, W] u8 expected")
+    F, H, W = img.shape
+    try:
+        D, r, ms, vm = int(planes), int(radius), int(min_sources), float(var_min)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: planes, radius and min_sources must be integers and var_min a number") from None
+    if D != planes or r != radius or ms != min_sources:
+        raise ValueError(f"{name}: planes, radius and min_sources must be integers")
+    E = _dense_ext(extrinsics, name)
+    if len(E) != F:
+        raise ValueError(f"{name}: one extrinsic per frame of img expected")
+    src_h = np.asarray(src, np.int64)
+    S = src_h.shape[1] if src_h.ndim == 2 else 0
+    if not 1 <= D <= SWEEP_MAX_PLANES or not 1 <= r <= SWEEP_MAX_RADIUS or not 1 <= S <= SWEEP_MAX_SOURCES or not 1 <= ms <= S:
+        raise ValueError(f"{name}: planes in 1 .. {SWEEP_MAX_PLANES}, radius in 1 .. {SWEEP_MAX_RADIUS}, 1 .. {SWEEP_MAX_SOURCES} "
+                         "sources and min_sources in 1 .. S expected")
+    if not (vm >= 0 and math.isfinite(vm)):
+        raise ValueError(f"{name}: var_min must be finite and >= 0")
+    AB, w0, dw = sweep_tables(K, E, ref, src_h, ranges, D)
+    Kh = _dense_K(K, name)
+    V = w0.size
+    if F == 0 or H == 0 or W == 0 or max(F, V) * H * W > 2 ** 31 - 1 or V > 65535:
+        raise ValueError(f"{name}: an empty image, more than 2^31 - 1 pixels or more than 65535 views")
+    d = img.device
+    ctx = ctx or default_context()
+    f32 = dict(dtype=torch.float32, device=d)
+    depth, cost = torch.empty((V, H, W), **f32), torch.empty((V, H, W), **f32)
+    plane = torch.empty((V, H, W), dtype=torch.int32, device=d)
+    out = dict(depth=depth, cost=cost, plane=plane, AB=AB, w0=w0, dw=dw)
+    if V == 0:
+        return out
+    up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dt)).to(d)
+    ref_d, src_d = up(np.asarray(ref).reshape(-1), np.int32), up(src_h, np.int32)
+    AB_d, w0_d, dw_d = up(AB, np.float64), up(w0, np.float64), up(dw, np.float64)
+    prm = _lib.SweepParams(D, r, ms, 0, vm)
+    ws = torch.empty(max(lib.mm_depth_sweep_workspace_bytes(V, S, D), 256), dtype=torch.uint8, device=d)
+    img = img.contiguous()
+    ctx.check(lib.mm_depth_sweep(ctx.h, ptr(img), F, H, W, Kh.ctypes.data_as(_lib.c_f64p), ptr(ref_d), ptr(src_d), ptr(AB_d), ptr(w0_d),
+                                 ptr(dw_d), V, S, C.byref(prm), ptr(depth), ptr(cost), ptr(plane), ptr(ws), ws.numel()), "mm_depth_sweep")
+    return out
+
+
+def depth_fuse(depth, cost, K, extrinsics, nbr, grey, max_cost=0.4, eps_depth=0.01, tau_px=1.0, min_consistent=2, cap=None, ctx=None):
+    """The depth maps of V views checked against each other and the consistent pixels compacted into a cloud (mm_depth_fuse):
+    depth, cost [V, H, W] f32 as depth_sweep returns them and grey [V, H, W] u8, the views' images, on the device; K 3 x 3,
+    extrinsics [V, 3|4, 4] (the views' own) and nbr [V, Q] (per view the other views it is checked against, -1: none) on the
+    host.  A pixel with a finite depth and cost <= max_cost is a candidate; a neighbour agrees when the pixel's point falls on a
+    candidate of it whose depth is within eps_depth (relative) and whose own point comes back within tau_px; a candidate at
+    least min_consistent neighbours agree with is kept.  cap: rows of the outputs (default: every pixel).
+    -> dict(points [n, 3] f64, grey [n] u8, origin [n, 2] i32 = (view, v W + u), n_consistent [n] i32 -- views of the buffers,
+    sized after one host read of the counts, in (view, row, column) order --, keep [V, H, W] u8, counts = (kept, candidates), n =
+    min(kept, cap)).  A surface point that several views keep appears once per view: duplicates are not merged."""
+    name = "depth_fuse"
+    for what, t, dt in (("depth [V, H, W] f32", depth, torch.float32), ("cost [V, H, W] f32", cost, torch.float32),
+                        ("grey [V, H, W] u8", grey, torch.uint8)):
+        if not torch.is_tensor(t) or t.dtype != dt or t.dim() != 3 or t.shape != depth.shape or t.device != depth.device:
+            raise ValueError(f"{name}: {what} expected, all of one shape on one device")
+    V, H, W = depth.shape
+    Kh = _dense_K(K, name)
+    E = _dense_ext(extrinsics, name)
+    nb = np.asarray(nbr, np.int64)
+    if len(E) != V or nb.ndim != 2 or nb.shape[0] != V or nb.shape[1] > FUSE_MAX_NEIGHBOURS:
+        raise ValueError(f"{name}: one extrinsic per view and nbr [V, Q <= {FUSE_MAX_NEIGHBOURS}] expected")
+    Q = nb.shape[1]
+    if nb.size and (nb.min() < -1 or nb.max() >= V or (nb == np.arange(V)[:, None]).any()):
+        raise ValueError(f"{name}: nbr must name other views of this call (or -1)")
+    try:
+        mc, ed, tp, mk = float(max_cost), float(eps_depth), float(tau_px), int(min_consistent)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: max_cost, eps_depth and tau_px must be numbers and min_consistent an integer") from None
+    if math.isnan(mc) or not ed >= 0 or not tp >= 0 or mk < 0 or mk != min_consistent:
+        raise ValueError(f"{name}: max_cost must be a number, eps_depth and tau_px >= 0 and min_consistent an integer >= 0")
+    N = V * H * W
+    if H == 0 or W == 0 or N > 2 ** 31 - 1:
+        raise ValueError(f"{name}: an empty image or more than 2^31 - 1 pixels")
+    cap = N if cap is None else int(cap)
+    if cap < 0:
+        raise ValueError(f"{name}: cap must not be negative")
+    d = depth.device
+    ctx = ctx or default_context()
+    rows = max(min(cap, N), 1)
+    points = torch.empty((rows, 3), dtype=torch.float64, device=d)
+    grey_out = torch.empty(rows, dtype=torch.uint8, device=d)
+    origin = torch.empty((rows, 2), dtype=torch.int32, device=d)
+    n_cons = torch.empty(rows, dtype=torch.int32, device=d)
+    keep = torch.zeros((V, H, W), dtype=torch.uint8, device=d)
+    counts = torch.zeros(2, dtype=torch.int64, device=d)
+    up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dt)).to(d)
+    ext_d, nbr_d = up(E, np.float64), up(nb if Q else np.zeros((max(V, 1), 1)), np.int32)
+    prm = _lib.FuseParams(mk, 0, mc, ed, tp)
+    ws = torch.empty(max(lib.mm_depth_fuse_workspace_bytes(V, H, W), 256), dtype=torch.uint8, device=d)
+    depth, cost, grey = depth.contiguous(), cost.contiguous(), grey.contiguous()
+    ctx.check(lib.mm_depth_fuse(ctx.h, ptr(depth), ptr(cost), V, H, W, ptr(ext_d), Kh.ctypes.data_as(_lib.c_f64p), ptr(nbr_d), Q, ptr(grey),
+                                C.byref(prm), min(cap, N), ptr(points), ptr(grey_out), ptr(origin), ptr(n_cons), ptr(keep), ptr(counts),
+                                ptr(ws), ws.numel()), "mm_depth_fuse")
+    kept, cand = counts.tolist()      # (the one host read: it sizes the views)
+    n = min(kept, cap)
+    return dict(points=points[:n], grey=grey_out[:n], origin=origin[:n], n_consistent=n_cons[:n], keep=keep, counts=(kept, cand), n=n)
+
+
 class MultiDot:
     """[<a, b> for (a, b) in pairs] in one launch (mm_multi_dot): returns a device tensor [k, 3] =
     (sum over i < split, sum over i >= split, total).  Holds the zero-initialised workspace."""

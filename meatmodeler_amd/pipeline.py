@@ -10,6 +10,7 @@ default and is described by its `*_options` function below; `run_plan` judges al
 the device, and `run` is then one call per phase: `_front`, `_link`, `_poses`, `_structure`, `_adjust`.
 """
 import ctypes as C
+import math
 import queue
 import time
 from concurrent.futures import ThreadPoolExecutor
@@ -36,6 +37,10 @@ RESECT_KEYS = ("n_hyp", "threshold_px", "min_rows", "min_inliers", "refit_iters"
                "collinear_tol")
 ALIGN_KEYS = ("frames", "extrinsics", "centres", "tau", "tau_rel", "n_hyp", "seed", "refit_iters", "with_scale", "min_inliers")
 ALIGN_FRAMES = "align: frames must be at least 3 distinct indices in [0, F)"
+DENSE_DEFAULTS = dict(every=4, sources=4, gap=2, neighbours=4, planes=64, radius=3, downscale=1, depth_margin=0.1, min_points=16,
+                      var_min=4.0, min_sources=1, max_cost=0.4, eps_depth=0.01, tau_px=1.0, min_consistent=2, max_points=None)
+DENSE_KEYS = tuple(DENSE_DEFAULTS)
+DENSE_FEW_POINTS = 1      # flag of a reference view that observes fewer than min_points points: it is not swept
 
 
 def _stage_options(stage, value, keys):
@@ -145,21 +150,124 @@ def refine_options(refine):
     return None if refine is None else refine_schedule(**refine)
 
 
+def dense_options(dense):
+    """`run(..., dense=)`: None (no dense stage) or a dict ({} for the defaults, DENSE_DEFAULTS): `every` (every every-th frame
+    is a reference view), `sources` (source slots per view: the frames at -gap, +gap, -2 gap, +2 gap, ... that exist), `gap`,
+    `neighbours` (the views before and after it in the view list a view is checked against, same pattern), `planes`, `radius`,
+    `var_min`, `min_sources` (ops.depth_sweep), `downscale` (1, 2 or 4: the frames are reduced by integer 2 x 2 means and K
+    scaled), `depth_margin` (a view's depth range is the min / max depth of the adjusted points it observes, divided /
+    multiplied by 1 + depth_margin), `min_points` (a view that observes fewer is skipped and flagged DENSE_FEW_POINTS),
+    `max_cost`, `eps_depth`, `tau_px`, `min_consistent` (ops.depth_fuse) and `max_points` (rows of the cloud; None: every
+    pixel).  After the adjustment -- or, with ba=False, after the triangulation -- every reference view gets a depth map by
+    plane sweep and the maps are fused into a point cloud (DESIGN.md 6m).  Returns the options with the defaults filled in;
+    anything else raises ValueError."""
+    dense = _stage_options("dense", dense, DENSE_KEYS)
+    if dense is None:
+        return None
+    d = dict(DENSE_DEFAULTS, **dense)
+
+    def whole(key, lo, hi=None):
+        v = d[key]
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
+            raise ValueError(f"dense: {key} must be an integer of at least {lo}" + (f" and at most {hi}" if hi is not None else ""))
+        d[key] = int(v)
+
+    def number(key, lo):
+        v = d[key]
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not (v >= lo) or v == np.inf:
+            raise ValueError(f"dense: {key} must be a finite number of at least {lo}")
+        d[key] = float(v)
+
+    whole("every", 1), whole("gap", 1), whole("sources", 1, ops.SWEEP_MAX_SOURCES), whole("neighbours", 0, ops.FUSE_MAX_NEIGHBOURS)
+    whole("planes", 1, ops.SWEEP_MAX_PLANES), whole("radius", 1, ops.SWEEP_MAX_RADIUS), whole("min_points", 1)
+    whole("min_sources", 1, d["sources"]), whole("min_consistent", 0)
+    if d["downscale"] not in (1, 2, 4) or isinstance(d["downscale"], bool):
+        raise ValueError("dense: downscale must be 1, 2 or 4")
+    d["downscale"] = int(d["downscale"])
+    number("depth_margin", 0.0), number("var_min", 0.0), number("eps_depth", 0.0), number("tau_px", 0.0)
+    if isinstance(d["max_cost"], bool) or not isinstance(d["max_cost"], (int, float, np.integer, np.floating)) or d["max_cost"] != d["max_cost"]:
+        raise ValueError("dense: max_cost must be a number")
+    d["max_cost"] = float(d["max_cost"])
+    if d["max_points"] is not None:
+        whole("max_points", 0)
+    return d
+
+
+def dense_views(n_frames, every, sources, gap, neighbours):
+    """The view tables of the dense stage on the host -> (ref [V] i32: frames 0, every, 2 every, ...; src [V, sources] i32: the
+    frames at -gap, +gap, -2 gap, +2 gap, ... of each, -1 where the clip has none; nbr [V, neighbours] i32: the views at -1, +1,
+    -2, +2, ... in the view list, -1 where there is none)."""
+    ref = np.arange(0, n_frames, every, dtype=np.int32)
+    step = np.array([(j // 2 + 1) * (-1 if j % 2 == 0 else 1) for j in range(max(sources, neighbours))], np.int64)
+    src = ref[:, None].astype(np.int64) + gap * step[None, :sources]
+    src = np.where((src >= 0) & (src < n_frames), src, -1).astype(np.int32)
+    nbr = np.arange(ref.size, dtype=np.int64)[:, None] + step[None, :neighbours]
+    nbr = np.where((nbr >= 0) & (nbr < ref.size), nbr, -1).astype(np.int32)
+    return ref, src, nbr
+
+
+def downscale_frames(frames, K, factor):
+    """frames [F, H, W] u8 reduced by `factor` (1, 2 or 4) with the integer 2 x 2 mean (a + b + c + d + 2) >> 2, once per
+    halving (an odd last row or column is dropped), in torch, and K for the reduced grid: a reduced pixel's centre lies half an
+    input pixel beyond the first of the two it covers, so fx, s, fy halve and c -> (c - 1/2) / 2.  -> (frames, K 3 x 3)."""
+    K = np.array(np.asarray(K, np.float64).reshape(3, 3))
+    while factor > 1:
+        H2, W2 = frames.shape[1] // 2 * 2, frames.shape[2] // 2 * 2
+        f = frames[:, :H2, :W2].to(torch.int32)
+        frames = ((f[:, 0::2, 0::2] + f[:, 0::2, 1::2] + f[:, 1::2, 0::2] + f[:, 1::2, 1::2] + 2) >> 2).to(torch.uint8)
+        K[0, :] = K[0, :] * 0.5
+        K[1, :] = K[1, :] * 0.5
+        K[0, 2], K[1, 2] = K[0, 2] - 0.25, K[1, 2] - 0.25
+        factor //= 2
+    return frames.contiguous(), K
+
+
+def dense_cloud(frames, K, extrinsics, ranges, ctx=None, **options):
+    """Depth maps and the fused cloud of a clip with known cameras (ops.depth_sweep, ops.depth_fuse; `options` as
+    `dense_options` takes them): frames [F, H, W] u8 on the device, K 3 x 3, extrinsics [F, 3|4, 4] and ranges [F, 2] =
+    (dmin, dmax) per frame on the host.  The reference views are every `every`-th frame; one whose range is not 0 < dmin
+    <= dmax (NaN: how `run` marks a frame that observes fewer than min_points points) is flagged DENSE_FEW_POINTS and not
+    swept: its maps hold no depth.  -> dict(views [V] the views' frames, range [V, 2] (NaN where flagged), flags [V] on the
+    host; depth, cost [V, h, w] f32, plane [V, h, w] i32, keep [V, h, w] u8, points [n, 3] f64, grey [n] u8, origin [n, 2]
+    i32 = (index into views, pixel v w + u of the reduced grid), n_consistent [n] i32 on the device; counts = (kept,
+    candidates); K: the intrinsics of the reduced grid).  Duplicate surface points from neighbouring views are not merged."""
+    opt = dense_options(options)
+    E = np.ascontiguousarray(np.asarray(extrinsics, np.float64)[:, :3, :])
+    F = frames.shape[0]
+    rng = np.asarray(ranges, np.float64)
+    if E.shape != (F, 3, 4) or rng.shape != (F, 2):
+        raise ValueError("dense: one extrinsic [3|4, 4] and one range (dmin, dmax) per frame expected")
+    ref, src, nbr = dense_views(F, opt["every"], opt["sources"], opt["gap"], opt["neighbours"])
+    r = rng[ref]
+    with np.errstate(invalid="ignore"):
+        ok = np.isfinite(r).all(1) & (r[:, 0] > 0) & (r[:, 1] >= r[:, 0])
+    src = np.where(ok[:, None], src, -1).astype(np.int32)      # (a view without sources has no valid plane anywhere)
+    small, Ks = downscale_frames(frames, K, opt["downscale"])
+    sw = ops.depth_sweep(small, Ks, E, ref, src, np.where(ok[:, None], r, 1.0), planes=opt["planes"], radius=opt["radius"],
+                         var_min=opt["var_min"], min_sources=opt["min_sources"], ctx=ctx)
+    grey = small.index_select(0, torch.as_tensor(ref.astype(np.int64)).to(small.device))
+    fu = ops.depth_fuse(sw["depth"], sw["cost"], Ks, E[ref], nbr, grey, max_cost=opt["max_cost"], eps_depth=opt["eps_depth"],
+                        tau_px=opt["tau_px"], min_consistent=opt["min_consistent"], cap=opt["max_points"], ctx=ctx)
+    return dict(views=ref, range=np.where(ok[:, None], r, np.nan), flags=np.where(ok, 0, DENSE_FEW_POINTS).astype(np.int32),
+                depth=sw["depth"], cost=sw["cost"], plane=sw["plane"], keep=fu["keep"], points=fu["points"], grey=fu["grey"],
+                origin=fu["origin"], n_consistent=fu["n_consistent"], counts=fu["counts"], K=Ks)
+
+
 class RunPlan(namedtuple("RunPlan", "n_frames world sharded force_collectives triangulation cull verify poses resect degeneracy "
-                                    "guided align refine")):
+                                    "guided align refine dense", defaults=(None,))):
     """What `run_plan` makes of the options of `ClipPipeline.run`: every stage as its `*_options` function returns it (None: the
     stage is off), the clip's frame count, the ranks it is spread over, and whether the gather / all-reduce path is taken."""
     __slots__ = ()
 
 
 def run_plan(n_frames, world=None, has_extrinsics=True, force_collectives=False, triangulation="two_view", cull=None,
-             verify=None, poses=None, resect=None, degeneracy=None, guided=None, align=None, refine=None):
+             verify=None, poses=None, resect=None, degeneracy=None, guided=None, align=None, refine=None, dense=None):
     """Every check of `ClipPipeline.run` on its options, without a device -> RunPlan; a broken rule raises ValueError.  world:
     the ranks of the process group, None without one (one rank, and force_collectives has nothing to force).  n_frames and
     world may each be a function without arguments that gives the value: it is called only after the rules that need neither
     have passed -- the order the rules are reported in."""
     verify, poses, resect, degeneracy = verify_options(verify), pose_options(poses), resect_options(resect), degeneracy_options(degeneracy)
-    guided, align, refine = guided_options(guided), align_options(align), refine_options(refine)
+    guided, align, refine, dense = guided_options(guided), align_options(align), refine_options(refine), dense_options(dense)
     for stage, on, why in (("guided", guided, "it supplies each pair's fundamental matrix, the model the search is gated by"),
                            ("degeneracy", degeneracy, "the verdict compares the homography with each pair's fundamental matrix"),
                            ("poses", poses, "it supplies each pair's fundamental matrix")):
@@ -180,7 +288,8 @@ def run_plan(n_frames, world=None, has_extrinsics=True, force_collectives=False,
                            ("poses", poses, "the chain needs the neighbouring pair's depths across every rank boundary"),
                            ("resect", resect, "every frame needs the whole point table"),
                            ("align", align, "the cameras of `frames` live on different ranks"),
-                           ("refine", refine, "the compaction renumbers the points of one shard")):
+                           ("refine", refine, "the compaction renumbers the points of one shard"),
+                           ("dense", dense, "a view's depth range needs every point it observes and its sources' frames")):
         if on is not None and ranks > 1:
             raise ValueError(f"{stage} is not supported with more than one rank: {why}")
     if cull is not None:
@@ -190,7 +299,7 @@ def run_plan(n_frames, world=None, has_extrinsics=True, force_collectives=False,
             raise ValueError("cull takes max_reproj_px, min_angle_deg, min_depth (at least one) and refine_iters"
                              + (f"; not {sorted(unknown)}" if unknown else ""))
     return RunPlan(n_frames, ranks, ranks > 1 or (world is not None and bool(force_collectives)), force_collectives, triangulation,
-                   cull, verify, poses, resect, degeneracy, guided, align, refine)
+                   cull, verify, poses, resect, degeneracy, guided, align, refine, dense)
 
 
 class StageClock:
@@ -698,18 +807,73 @@ class ClipPipeline:
         sim, cost, inlier, info = ops.align_similarity(src, dst, ctx=self.ctx, **align["params"])
         return dict(sim=sim[0].contiguous(), cost=cost[0], info=info[0], inlier=inlier)
 
+    # ------------------------------------------------------------------------------------------- dense
+    def depth_ranges(self, extrinsics, points, fi, pi, depth_margin=0.1, min_points=16):
+        """The depth range of every frame from the points it observes: extrinsics [F, 3, 4] on the host, points [P, 3] f64 and
+        the observations' frame / point indices fi, pi [O] on the device.  z = R_2 . X + t_2 per observation; a frame's range is
+        (min z / (1 + depth_margin), max z (1 + depth_margin)) over its finite, positive depths (torch scatter_reduce amin /
+        amax: no float sum, so it does not depend on the order) -> ranges [F, 2] f64 on the host, NaN for a frame with fewer
+        than min_points such observations."""
+        d = self.device
+        E = torch.as_tensor(np.ascontiguousarray(np.asarray(extrinsics, np.float64)[:, :3, :])).to(d)
+        F = E.shape[0]
+        fl, pl = fi.long(), pi.long()
+        X = points.reshape(-1, 3)[pl]
+        z = (E[fl, 2, 0] * X[:, 0] + E[fl, 2, 1] * X[:, 1]) + E[fl, 2, 2] * X[:, 2] + E[fl, 2, 3]
+        ok = torch.isfinite(z) & (z > 0)
+        inf = torch.full_like(z, math.inf)
+        zmin = torch.full((F,), math.inf, dtype=torch.float64, device=d).scatter_reduce(0, fl, torch.where(ok, z, inf), "amin")
+        zmax = torch.full((F,), -math.inf, dtype=torch.float64, device=d).scatter_reduce(0, fl, torch.where(ok, z, -inf), "amax")
+        cnt = torch.zeros(F, dtype=torch.int64, device=d).index_add_(0, fl, ok.long())
+        zmin, zmax, cnt = (t.cpu().numpy() for t in (zmin, zmax, cnt))      # (one synchronisation: the sweep's tables are the host's)
+        rng = np.stack([zmin / (1.0 + depth_margin), zmax * (1.0 + depth_margin)], 1)
+        rng[cnt < min_points] = np.nan
+        return rng
+
+    def dense(self, frames, K, extrinsics, ranges, **options):
+        """`dense_cloud` on this pipeline's context."""
+        return dense_cloud(frames, K, extrinsics, ranges, ctx=self.ctx, **options)
+
+    def _dense(self, plan, frames, K, ext, X, kept, tracks, out, clock):
+        """The dense stage of `run` at the final cameras and points: the refined ones if `refine` ran, the adjusted ones after
+        the adjustment, the initial ones with ba=False -> the `dense` entry of the result."""
+        with clock("dense"):
+            F, T = plan.n_frames, tracks[0].shape[0] - 1
+            if kept is not None:
+                _, fi, pi = ops.flatten_tracks(*tracks, sel=kept, ctx=self.ctx)
+                pts = X[kept]
+            else:
+                _, fi, pi = ops.flatten_tracks(*tracks, t_lo=0, n_sel=T, ctx=self.ctx)
+                pts = X
+            if "ba" in out:
+                res = out["ba"]
+                if "refine" in out:
+                    # the refined points are rows point_map of the adjusted ones, their observations rows obs_map
+                    res, pm, om = out["refine"]["ba"], out["refine"]["point_map"].long(), out["refine"]["obs_map"].long()
+                    new = torch.full((pts.shape[0],), -1, dtype=torch.int64, device=self.device)
+                    new[pm] = torch.arange(pm.shape[0], device=self.device)
+                    fi, pi = fi[om], new[pi.long()[om]]
+                pts = res.pts.reshape(-1, 3)
+                if pi.numel() and int(pi.max()) >= pts.shape[0]:      # (a last round that kept nothing: no solve followed it)
+                    fi, pi = fi[:0], pi[:0]
+                cams_h = res.cams.reshape(F, 6).cpu().numpy()
+                ext = np.stack([np.concatenate([_rodrigues_matrix(c[:3]), c[3:, None]], axis=1) for c in cams_h])
+            opt = plan.dense
+            ranges = self.depth_ranges(ext, pts, fi, pi, opt["depth_margin"], opt["min_points"])
+            return self.dense(frames, K, ext, ranges, **opt)
+
     # ------------------------------------------------------------------------------------------- whole clip
     def run(self, frames, K, extrinsics=None, ba=True, ftol=1e-4, verbose=0, dist=None, timers=None, max_nfev=None,
             force_collectives=False, triangulation="two_view", cull=None, verify=None, poses=None, resect=None, degeneracy=None,
-            guided=None, align=None, refine=None):
+            guided=None, align=None, refine=None, dense=None):
         """frames [F,H,W] u8 (device), K [3,3], extrinsics [F, 3|4, 4] (None with `poses`).  With `dist` = torch.distributed
         (initialised), frames are the FULL clip on every rank (synthetic input is generated locally) and the work is sharded as
-        described in parallel.py; `cull`, `poses`, `resect`, `align` and `refine` need one rank (`run_plan` says why).
+        described in parallel.py; `cull`, `poses`, `resect`, `align`, `refine` and `dense` need one rank (`run_plan` says why).
         `force_collectives`: take the gather / all-reduce path even in a one-rank group (the collectives are trivial but travel
         the real backend: how backend "nccl" is exercised on a single GPU).  `ba`, `ftol`, `max_nfev`: whether the adjustment
         runs, its tolerance and its evaluation budget (None = SciPy's default, as adjustPoints).  `timers`: a dict the stages'
         milliseconds are added to (detect, match, verify, degeneracy, guided, link, poses, align, triangulate, resect, ba,
-        ba_solve, refine).
+        ba_solve, refine, dense).
         `triangulation`: "two_view" (default) triangulates a track from its first and last observation, as the reference
         does; "multi_view" from all its observations (`triangulate_multi_view`).  `points0` is [T,3] over all tracks either way.
         `cull` (needs "multi_view"): dict of the thresholds of ops.triangulate_tracks (max_reproj_px, min_angle_deg, min_depth,
@@ -717,7 +881,8 @@ class ClipPipeline:
         its points are aligned with that list.
         The stages that are off by default, each None or a dict ({} for the defaults) described where it is judged: `verify`
         (verify_options), `degeneracy` (degeneracy_options), `guided` (guided_options), `poses` (pose_options), `align`
-        (align_options), `resect` (resect_options), `refine` (refine_options).  A stage that is None launches nothing.
+        (align_options), `resect` (resect_options), `refine` (refine_options), `dense` (dense_options).  A stage that is None
+        launches nothing.
 
         -> dict(det (`detect` of this rank's frames), n_tracks, n_obs, points0, track_ptr_dev, obs_frame_dev, obs_kp_dev, xy_dev,
         match_count, kp_count, pairs_local, frames_local); under "multi_view" also track_quality [T,4], track_flags [T] and with
@@ -726,9 +891,9 @@ class ClipPipeline:
         cost [n], info [n,6], and with poses pose_info [n,8], sigma [n,3], normal [n,3]); guided = dict(info [n,4], is_new
         [n,cap]); poses = what `recover_poses` returns, without depth; align = what `align` returns, and after the adjustment
         ba_aligned = dict(extrinsics [F,3,4], points, sim, info); resect = what `resect` returns, without inlier; refine = what
-        bundleAdjuster.refine_rounds returns."""
+        bundleAdjuster.refine_rounds returns; dense = what `dense` returns (at the final cameras and points)."""
         plan = run_plan(lambda: frames.shape[0], lambda: None if dist is None else dist.get_world_size(), extrinsics is not None,
-                        force_collectives, triangulation, cull, verify, poses, resect, degeneracy, guided, align, refine)
+                        force_collectives, triangulation, cull, verify, poses, resect, degeneracy, guided, align, refine, dense)
         rank = dist.get_rank() if dist is not None else 0
         clock = StageClock(self.ctx, timers if timers is not None else {})
         front = self._front(frames, plan, rank, clock)
@@ -751,6 +916,8 @@ class ClipPipeline:
                 out["kept_tracks"] = kept
         if ba and out["n_obs"] > 0 and (kept is None or kept.numel() > 0):
             out.update(self._adjust(plan, K, ext, X, kept, tracks, rank, ftol, max_nfev, verbose, clock))
+        if plan.dense is not None:
+            out["dense"] = self._dense(plan, frames, K, ext, X, kept, tracks, out, clock)
         return out
 
     def _front(self, frames, plan, rank, clock):

@@ -14,6 +14,7 @@ return order, HIP kernels underneath (no CPU fallback: a missing extension or GP
     keyframeTracking               processor.py:61   keyframeTracking    (mm-LK + mm-GFTT: calcOpticalFlowPyrLK / goodFeaturesToTrack)
     increaseContrast               processor.py:12   increaseContrast    (fixed-point L*a*b* + CLAHE), cvtColorBGR2GRAY
     PLY tail                       processor.py:480  savePointCloud      (mm_write_ply)
+    (no counterpart)                                 densePointCloud     (mm_depth_sweep + mm_depth_fuse: plane-sweep depth maps, fused)
 
 Video decode, calibration (chessboard / calibrateCamera) and PnP stay outside (SURVEY.md §8 "out of scope").
 """
@@ -501,6 +502,22 @@ def applySimilarity(sim, points=None, extrinsics=None):
         ed = torch.as_tensor(np.ascontiguousarray(e.reshape(-1, e.shape[-2], 4)[:, :3, :])).to(dev)
     ops.apply_similarity(sd, pd, ed)
     return (None if pd is None else pd.cpu().numpy()), (None if ed is None else ed.cpu().numpy())
+
+
+def densePointCloud(frames, K, extrinsics, ranges, **params):
+    """A dense point cloud from grey frames with known cameras (the reference stops at the adjusted corner points, though it
+    was written to model an item and estimate its volume): frames [F, H, W] u8 (host array or device tensor), K 3 x 3,
+    extrinsics [F, 3|4, 4] and ranges [F, 2] = (dmin, dmax), the depth range each frame sees.  Every `every`-th frame gets a
+    plane-sweep depth map against its neighbouring frames and the maps are checked against each other (pipeline.dense_cloud;
+    `params` as pipeline.dense_options takes them) -> (points [n, 3] f64, grey [n] u8) as NumPy arrays, in (view, row, column)
+    order, ready for savePointCloud.  Duplicate surface points from neighbouring views are not merged."""
+    from .pipeline import dense_cloud
+    ctx = default_context()
+    f = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames, np.uint8))
+    if f.dtype != torch.uint8 or f.dim() != 3:
+        raise ValueError("densePointCloud: frames [F, H, W] u8 expected")
+    out = dense_cloud(f.to(ctx.device), K, extrinsics, ranges, ctx=ctx, **params)
+    return out["points"].cpu().numpy(), out["grey"].cpu().numpy()
 
 
 def rotation_vector(R):

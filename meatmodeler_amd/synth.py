@@ -8,6 +8,7 @@ oracle and the HIP path see byte-identical inputs.
 * ``make_ba_problem``    – tracks of L consecutive frames over an orbit (BA micro workload).
 * ``random_descriptors`` – planted-match descriptor pairs for the matcher (C2 recipe).
 * ``make_texture`` / ``render_orbit_frames`` – procedural textured scene rendered to u8 grey frames.
+* ``render_depth``       – the analytic depth map of that scene for one camera.
 """
 import numpy as np
 
@@ -127,13 +128,10 @@ def make_texture(size=2048, n_shapes=6000, seed=7):
     return tex
 
 
-def render_frame(tex, ext, K, width, height, radii=(2.0, 1.4, 2.0), ground_y=1.4, xp=np):
-    """Render one grey frame: ray-cast an ellipsoid (centre origin) and the plane y=ground_y.
-
-    World y points down (camera convention of look_at_extrinsic), so the ground is at +y.
-    `xp` is numpy or torch-like (only numpy is used in tests; bench renders with torch on device
-    through `render_orbit_frames_torch`).
-    """
+def _ray_cast(ext, K, width, height, radii, ground_y):
+    """The rays of every pixel against the ellipsoid and the ground -> (C, d [H,W,3] world directions, inv = 1 / radii, tt
+    [H,W] the ray parameter of the first hit -- the depth along the optical axis, the camera-frame direction having z = 1 --,
+    valid, use_e: the hit is on the ellipsoid)."""
     R = ext[:, :3]
     t = ext[:, 3]
     C = -R.T @ t
@@ -155,6 +153,24 @@ def render_frame(tex, ext, K, width, height, radii=(2.0, 1.4, 2.0), ground_y=1.4
     use_e = te <= tg
     tt = np.minimum(te, tg)
     valid = np.isfinite(tt)
+    return C, d, inv, tt, valid, use_e
+
+
+def render_depth(ext, K, width, height, radii=(2.0, 1.4, 2.0), ground_y=1.4):
+    """The analytic depth map [height, width] f64 of the scene `render_frame` draws, from the same ray-cast: the camera-frame z
+    of the surface point behind every pixel, NaN where the ray hits nothing."""
+    _, _, _, tt, valid, _ = _ray_cast(np.asarray(ext, float)[:3], K, width, height, radii, ground_y)
+    return np.where(valid, tt, np.nan)
+
+
+def render_frame(tex, ext, K, width, height, radii=(2.0, 1.4, 2.0), ground_y=1.4, xp=np):
+    """Render one grey frame: ray-cast an ellipsoid (centre origin) and the plane y=ground_y.
+
+    World y points down (camera convention of look_at_extrinsic), so the ground is at +y.
+    `xp` is numpy or torch-like (only numpy is used in tests; bench renders with torch on device
+    through `render_orbit_frames_torch`).
+    """
+    C, d, inv, tt, valid, use_e = _ray_cast(ext, K, width, height, radii, ground_y)
     X = C + d * np.where(valid, tt, 0.0)[..., None]
     S = tex.shape[0]
     # texture coordinates: ellipsoid by (azimuth, polar), ground by (x, z)
