@@ -1367,11 +1367,10 @@ int mm_orb_detect_compute(mm_ctx *ctx, const uint8_t *imgs, int batch, int heigh
     const int segs = batch * g.nlevels;
     MM_LAUNCH(ctx, "orb_select_kernel", orb_select_kernel, dim3(segs), dim3(256), 0, g, w8);
     MM_LAUNCH(ctx, "orb_harris_kernel", orb_harris_kernel, dim3(32, segs), dim3(256), 0, g, imgs, w8);
-    // MM_ORB_RANK=count: the O(m^2) counting kernel (kept as the cross-check; also what larger capacities fall back to)
-    static const bool rank_by_count = [] {
-        const char *e = getenv("MM_ORB_RANK");
-        return e && e[0] == 'c';
-    }();
+    // MM_ORB_RANK=count: the O(m^2) counting kernel (kept as the cross-check; also what larger capacities fall back to).
+    // Read on every call, like MM_ORB_PYRAMID above: a test can switch kernels in a process that has already run ORB.
+    const char *rank_env = getenv("MM_ORB_RANK");
+    const bool rank_by_count = rank_env && rank_env[0] == 'c';
     if (g.kcap <= RK_MAX && !rank_by_count)
         MM_LAUNCH(ctx, "orb_rank_kernel", orb_rank_sort_kernel, dim3(segs), dim3(RK_THREADS), 0, g, w8, kp_xy, kp_meta, kp_resp, n_out);
     else
